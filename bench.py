@@ -22,12 +22,16 @@ torch.distributed.run, before this process has touched the GPU) and relays rank 
 `--scaling strong` fixes the job instead of the per-rank load: `in_flight x rounds` samples per pixel of the WHOLE image per
 step whatever N is, every rank tracing its 1/N of the pixels (time-to-image; the line says which mode ran).
 
-Secondary objects of the N = 1 line (each its own short measurement on the same box, none inside the timed region of `value`):
+A plain run (`--gpus 1 --steps K --warmup W`) does only what the headline needs: set-up, warm-up, the K timed steps, the result line.
+`--full` adds everything else the line has carried since round 1 -- the secondary objects, `roofline`, `cpu_baseline`, `frame` -- as below.
+`--dump-outputs DIR` writes what the timed path computed after its last step as DIR/*.npy (see dump_outputs).
+
+Secondary objects of the N = 1 line with `--full` (each its own short measurement on the same box, none inside the timed region of `value`):
 `two_level` -- the same scene with every instance ENTERED instead of copied to world space (PT_FLAG_NO_BAKED_INSTANCES; and with
 only the single-leaf meshes copied, PT_FLAG_TWO_LEVEL_ONLY), `dynamic` -- host and device time of one pt_upload_dynamic_async
 per frame tick, `configs` -- BASELINE configs 2, 3 and 5 on this GPU, `frame` -- the 1-spp interactive frame.
 
-Prints ONE JSON line (rank 0).  `roofline` is measured live with HIP events on the render stream in a separate,
+Prints ONE JSON line (rank 0).  With `--full`, `roofline` is measured live with HIP events on the render stream in a separate,
 profiled pass, for every kernel of the path (`roofline.kernels`); its top-level fields are those of the kernel
 with the largest share of device time (k_trace<true>, the any-hit traversal of the shadow rays);
 `cpu_baseline` times the oracle (our CPU restatement of the reference's path -- the reference has no CPU
@@ -802,6 +806,25 @@ def secondary_measurements(D, H, L, scenes, bundle, args, device, in_flight):
     return out
 
 
+DUMP_BUDGET_BYTES = 56_000_000  # accumulator (+ pixel indices) of a dump: well inside the 64 MB it may take with counters.npy
+
+
+def dump_outputs(out_dir, accum, counts):
+    """What a caller of the timed path receives after the last timed step, for comparing two builds output for output:
+    accum.npy -- the (reduced) HDR accumulator, float32 [pixels, 4] (radiance sums in rgb), every pixel up to 1080p; a larger frame
+    keeps a fixed, seeded sample of pixels, whose indices go to accum_pixels.npy (float64);
+    counters.npy -- float64 [samples per pixel, extension rays, shadow rays, primary rays, shaded hits, deposits] of the timed steps."""
+    os.makedirs(out_dir, exist_ok=True)
+    accum = np.ascontiguousarray(accum, dtype=np.float32)
+    if accum.nbytes > DUMP_BUDGET_BYTES:
+        keep = DUMP_BUDGET_BYTES // (accum.nbytes // len(accum) + 8)  # (+ 8 B of float64 index per kept pixel)
+        pixels = np.sort(np.random.default_rng(0).choice(len(accum), size=keep, replace=False))
+        accum = accum[pixels]
+        np.save(os.path.join(out_dir, "accum_pixels.npy"), pixels.astype(np.float64))
+    np.save(os.path.join(out_dir, "accum.npy"), accum)
+    np.save(os.path.join(out_dir, "counters.npy"), np.asarray(counts, dtype=np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -835,7 +858,13 @@ def main():
     ap.add_argument("--shadow-queue-fraction", type=float, default=SHADOW_QUEUE_FRACTION, help="pt_config.shadow_queue_fraction of the headline's context")
     ap.add_argument("--flags", type=int, default=0, help="pt_config.flags of the render context (2 = PT_FLAG_NO_BAKED_INSTANCES: two-level traversal)")
     ap.add_argument("--dump-accum", default=None, help="rank 0 saves the (reduced) HDR accumulator as .npy (tests)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="rank 0 writes what the timed steps computed as DIR/<name>.npy (dump_outputs)")
+    ap.add_argument("--full", action="store_true", help="also the secondary figures: roofline, cpu_baseline, frame, two_level / dynamic / configs "
+                                                         "(without it: the headline alone; the --no-* switches still prune a --full run)")
     args = ap.parse_args()
+    if not args.full:  # a plain run measures the headline and nothing else
+        args.no_cpu_baseline = args.no_roofline = args.no_frame = args.no_secondary = True
+        args.frame_after = False
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # Not under a launcher: start the ranks ourselves, as fresh child processes (this process has not touched the GPU -- torch
@@ -983,6 +1012,8 @@ def main():
         image_mean = float(accum[:, :3].mean().item()) / max(total_spp, 1) if rank == 0 else 0.0
         if rank == 0 and args.dump_accum:
             np.save(args.dump_accum, accum.cpu().numpy())
+        if rank == 0 and args.dump_outputs:
+            dump_outputs(args.dump_outputs, accum.cpu().numpy(), [total_spp, ext, shadow, gen, hits, deposits])
 
         roofline = None
         if not args.no_roofline:

@@ -14,6 +14,7 @@ sys.path.insert(0, os.path.join(ROOT, "opencl-path-tracer_amd"))
 sys.path.insert(0, os.path.join(ROOT, "oracle"))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import orclib as O  # noqa: E402
+import golden_io  # noqa: E402
 import gpu_util as U  # noqa: E402
 from ptamd import host as H, layout as L, scenes  # noqa: E402
 
@@ -21,14 +22,14 @@ PLY = "/root/reference/assets/3dmodels/stanford/bunny/bun_zipper.ply"
 W, Hh, SPP, NRAYS = 64, 36, 256, 4096
 
 
-def bunny_room(builder, material):
+def bunny_room(builder, material, ply=PLY):
     """configs 2 / 3: the bunny (bounding box ~0.16 x 0.15 x 0.12 m around (-0.02, 0.11, 0)) scaled to ~0.95 m and set on the floor of the room"""
     mats = scenes._room_materials()
     mb = scenes._MeshBuilder()
     scenes._room(mb, mats)
     scene = H.Scene()
     scene.add_node(mb.build(mats, H.BVH_BINNED_SAH))
-    bunny = H.Mesh.from_ply(PLY, material, builder=builder)
+    bunny = H.Mesh.from_ply(ply, material, builder=builder)
     s = 6.0
     scene.add_node(bunny, location=(0.1, -0.033 * s, 0.1), scale=(s, s, s))
     cam = scenes._camera(W, Hh, (0.0, 1.0, -3.9), (0.0, 0.7, 0.0), min(40.0 * (W / Hh) ** 0.5, 75.0))
@@ -71,8 +72,8 @@ def main():
         print(name, st, "hit fraction", float((h["prim"] >= 0).mean()), "on the bunny", float((h["inst"] == 1).mean()), "occluded", float(occ.mean()),
               "image mean", float(ref[:, :3].mean()) / SPP, cnt)
     path = os.path.join(HERE, "bunny_flat.npz")
-    np.savez_compressed(path, **out)
-    print(path, os.path.getsize(path) / 1e6, "MB")
+    size = golden_io.save_npz_split(path, **out)  # bunny_flat.npz.partNN
+    print(path, size / 1e6, "MB")
 
 
 if __name__ == "__main__":

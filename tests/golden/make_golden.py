@@ -12,7 +12,9 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.abspath(os.path.join(HERE, "..", ".."))
 sys.path.insert(0, os.path.join(ROOT, "opencl-path-tracer_amd"))
 sys.path.insert(0, os.path.join(ROOT, "oracle"))
+sys.path.insert(0, os.path.join(ROOT, "tests"))
 import ctypes as C  # noqa: E402
+import golden_io  # noqa: E402
 import orclib as O  # noqa: E402
 from ptamd import host as H, layout as L, scenes  # noqa: E402
 
@@ -236,8 +238,8 @@ def main():
         else:
             packed[k] = v
     out = os.path.join(HERE, "golden_v1.npz")
-    np.savez_compressed(out, **packed)
-    print("wrote", out, os.path.getsize(out) // 1024, "KiB,", len(G), "arrays")
+    size = golden_io.save_npz_split(out, **packed)  # golden_v1.npz.partNN
+    print("wrote", out, size // 1024, "KiB,", len(G), "arrays")
 
 
 if __name__ == "__main__":

@@ -1,7 +1,7 @@
 """BASELINE configs 2 / 3 on the REAL Stanford bunny.  The reference's bun_zipper.ply does not travel to the GPU box; what travels is
 tests/golden/bunny_flat.npz -- the typed arrays the host library flattens it to (binned-SAH tree / diffuse: config 2; SBVH / rough glass: config 3; in the
 five-wall room) and what the oracle finds on them (tests/golden/make_bunny_golden.py, build container only).  CPU: the oracle reproduces the fixture from
-the stored arrays (and, where /root/reference exists, the host library still flattens the PLY to the very same arrays).  GPU: the HIP path uploads the
+the stored arrays (and the host library still flattens the PLY, tests/golden/reference_assets, to the very same arrays).  GPU: the HIP path uploads the
 arrays through the C-ABI and is held against the stored hits, occlusion verdicts and 256-spp image."""
 import os
 import sys
@@ -12,6 +12,7 @@ import pytest
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(HERE, "..", "opencl-path-tracer_amd"))
 sys.path.insert(0, os.path.join(HERE, "..", "oracle"))
+import golden_io  # noqa: E402
 import gpu_util as U  # noqa: E402
 import orclib as O  # noqa: E402
 from ptamd import layout as L  # noqa: E402
@@ -21,7 +22,7 @@ W, Hh, SPP = 64, 36, 256
 
 
 def _load():
-    z = np.load(os.path.join(HERE, "golden", "bunny_flat.npz"))
+    z = golden_io.load_npz("bunny_flat.npz")
     out = {}
     for k in z.files:
         if "@" in k:
@@ -56,14 +57,17 @@ def test_the_oracle_reproduces_the_bunny_fixture(name):
     assert abs(ref[:, :3].mean() / 16 - g[name + "_accum"].mean() / SPP) < 0.05 * g[name + "_accum"].mean() / SPP
 
 
-@pytest.mark.skipif(not os.path.exists("/root/reference/assets/3dmodels/stanford/bunny/bun_zipper.ply"), reason="the reference's assets are only in the build container")
-def test_the_host_library_still_flattens_the_ply_to_the_fixture():
+def test_the_host_library_still_flattens_the_ply_to_the_fixture(tmp_path):
+    import lzma
     sys.path.insert(0, os.path.join(HERE, "golden"))
     import make_bunny_golden as M
     from ptamd import host as H
+    ply = tmp_path / "bun_zipper.ply"  # the reference's file, kept xz-compressed under tests/golden/reference_assets
+    with lzma.open(os.path.join(HERE, "golden", "reference_assets", "bun_zipper.ply.xz")) as f:
+        ply.write_bytes(f.read())
     g = _load()
     for name, builder, material in (("binned", H.BVH_BINNED_SAH, L.material_diffuse((0.8, 0.8, 0.8))), ("sbvh", H.BVH_SPATIAL_SPLIT, L.material_refractive(0.9, 1.5, (1.0, 0.6, 0.6), 5.0))):
-        b, _ = M.bunny_room(builder, material)
+        b, _ = M.bunny_room(builder, material, ply=str(ply))
         for k in ("vertices", "triangles", "sub_nodes", "top_nodes"):
             assert getattr(b.flat, k).tobytes() == g[f"{name}_{k}"].tobytes(), (name, k)
 

@@ -470,12 +470,22 @@ def test_material_texture_layers_are_prepared_like_the_reference_texture_array(t
     assert np.array_equal(small * 255.0, np.round(small * 255.0)) and abs(small[..., :3].mean() - lin[..., :3].mean()) < 0.03
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/assets"), reason="the reference's assets are only present in the build container")
+ASSETS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_assets")  # data files the reference ships (README.md there)
+
+
 def test_every_png_the_reference_ships_decodes_like_pil():
+    """One texture of every PNG kind among the reference's 51 (tests/golden/reference_assets/png: 1-bit grey, 8-bit grey, grey + alpha, RGB, RGBA;
+    none interlaced), decoded as PIL decodes it."""
     from PIL import Image
     import glob
-    files = sorted(glob.glob("/root/reference/assets/**/*.png", recursive=True))
-    assert len(files) >= 40
+    files = sorted(glob.glob(os.path.join(ASSETS, "png", "*.png")))
+    kinds = set()
+    for f in files:
+        with open(f, "rb") as fh:
+            head = fh.read(29)
+        kinds.add((head[24], head[25]))  # IHDR bit depth, colour type
+        assert head[28] == 0, f
+    assert kinds == {(1, 0), (8, 0), (8, 4), (8, 2), (8, 6)}, kinds
     for f in files:
         want = np.asarray(Image.open(f).convert("RGBA"))
         assert np.array_equal(H.load_png(f), want), f
@@ -519,11 +529,10 @@ def test_obj_diffuse_maps_register_texture_files_like_the_reference(tmp_path):
     assert (H.Mesh.from_obj(tmp_path / "m.obj", builder=H.BVH_BINNED_SAH).geometry()[1]["textureId"][:4] == -1).all()
 
 
-@pytest.mark.skipif(not os.path.isfile("/root/reference/assets/3dmodels/plane/plane.obj"), reason="the reference's assets are only present in the build container")
 def test_the_reference_light_plane_imports_as_main_cpp_uses_it():
     """main.cpp:131: Mesh(assets/3dmodels/plane/plane.obj, Material::Emissive(5500 K, 1000 lm), textureArray) -- two
     emissive triangles; without the override its `usemtl Material.001` is not in plane.mtl, i.e. the default grey."""
-    f = "/root/reference/assets/3dmodels/plane/plane.obj"
+    f = os.path.join(ASSETS, "plane", "plane.obj")
     m = H.Mesh.from_obj(f, material=L.material_emissive((1.0, 0.9, 0.8), 1000.0), builder=H.BVH_BINNED_SAH)
     st = m.stats()
     assert st["num_input_triangles"] == 2 and st["num_vertices"] == 4 and st["all_triangles_referenced"]
@@ -539,17 +548,23 @@ def test_the_reference_light_plane_imports_as_main_cpp_uses_it():
     assert plain[0]["type"] == L.MAT_DIFFUSE and np.allclose(plain[0]["colour"][:3], 0.6) and tf.files() == []
 
 
-BUNNY = "/root/reference/assets/3dmodels/stanford/bunny/bun_zipper.ply"
+@pytest.fixture(scope="module")
+def bunny_ply(tmp_path_factory):
+    """bun_zipper.ply as the reference ships it (kept xz-compressed under tests/golden/reference_assets)."""
+    import lzma
+    path = tmp_path_factory.mktemp("bunny") / "bun_zipper.ply"
+    with lzma.open(os.path.join(ASSETS, "bun_zipper.ply.xz")) as f:
+        path.write_bytes(f.read())
+    return str(path)
 
 
-@pytest.mark.skipif(not os.path.isfile(BUNNY), reason="the reference's assets are only present in the build container")
 @pytest.mark.parametrize("builder", [H.BVH_BINNED_SAH, H.BVH_SPATIAL_SPLIT])
-def test_the_stanford_bunny_ply_loads_and_builds(builder):
+def test_the_stanford_bunny_ply_loads_and_builds(builder, bunny_ply):
     """The mesh BASELINE configs 2-5 are quoted on (bun_zipper.ply: 35 947 vertices, 69 451 faces, no normals) through the
     PLY reader, the area-weighted smooth normals and both builders the configs name, with the reference's BvhTester
     checks (src/bvh/bvh_test.cpp:117-139; SBVH leaves hold clipped boxes, so 'triangles inside leaves' is exact for the
     object-split tree only)."""
-    m = H.Mesh.from_ply(BUNNY, L.material_diffuse((0.8, 0.8, 0.8)), builder=builder)
+    m = H.Mesh.from_ply(bunny_ply, L.material_diffuse((0.8, 0.8, 0.8)), builder=builder)
     verts, mats = m.geometry()
     nodes, tris, orig = m.bvh()
     v, n = verts["vertex"][:, :3], verts["normal"][:, :3]

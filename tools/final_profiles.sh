@@ -8,7 +8,7 @@ SETS=("FETCH_SIZE" "WRITE_SIZE" "TCC_HIT_sum TCC_MISS_sum TCC_EA0_RDREQ_sum TCC_
 run_set() { # <out dir> <extra bench flags...>
   out=$1; shift
   rm -rf $out && mkdir -p $out
-  timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats -- python3 bench.py --no-cpu-baseline --no-frame --no-secondary --steps 2 --warmup 1 "$@" > $out/stats_bench.json 2> $out/stats.log
+  timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats -- python3 bench.py --full --no-cpu-baseline --no-frame --no-secondary --steps 2 --warmup 1 "$@" > $out/stats_bench.json 2> $out/stats.log
   echo "$out: stats done"
   for set in "${SETS[@]}"; do
     name=$(echo $set | cut -d' ' -f1)
@@ -21,17 +21,18 @@ run_set() { # <out dir> <extra bench flags...>
 }
 run_set gpurun_out/final
 if [ -z "$PMC_ONLY" ]; then
-timeout -k 10 600 python bench.py > gpurun_out/final/bench.json 2> gpurun_out/final/bench.log
+# the bench lines below go into the folder the run_set before them filled ($out)
+timeout -k 10 600 python bench.py --full > $out/bench.json 2> $out/bench.log
 echo "bench done"
 fi
 run_set gpurun_out/final_tl --flags 2
-[ -z "$PMC_ONLY" ] && timeout -k 10 300 python bench.py --no-cpu-baseline --no-frame --no-secondary --flags 2 > gpurun_out/final_tl/bench.json 2> gpurun_out/final_tl/bench.log
+[ -z "$PMC_ONLY" ] && timeout -k 10 300 python bench.py --full --no-cpu-baseline --no-frame --no-secondary --flags 2 > $out/bench.json 2> $out/bench.log
 # round 6: the same scene, every instance entered through the GENERAL route (pt_trace.h LEVELS 2; PTAMD_GENERAL_ROUTE=1 forces it on a scene the fold table
 # would serve): kernel stats + the instruction and issue counters
 SETS=("SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_VMEM_RD SQ_INSTS_LDS SQ_INSTS_BRANCH" "GRBM_GUI_ACTIVE TA_BUSY_avr SQ_ACTIVE_INST_VALU SQ_THREAD_CYCLES_VALU" "FETCH_SIZE")
 export PTAMD_GENERAL_ROUTE=1
 run_set gpurun_out/final_gen --flags 2
-[ -z "$PMC_ONLY" ] && timeout -k 10 300 python bench.py --no-cpu-baseline --no-frame --no-secondary --flags 2 > gpurun_out/final_gen/bench.json 2> gpurun_out/final_gen/bench.log
+[ -z "$PMC_ONLY" ] && timeout -k 10 300 python bench.py --full --no-cpu-baseline --no-frame --no-secondary --flags 2 > $out/bench.json 2> $out/bench.log
 unset PTAMD_GENERAL_ROUTE
 # (the rank-by-rank emulation of the N = 1 .. 8 jobs is a session of its own: tools/rank_emul.py)
 rm -rf gpurun_out/final*/stats/*/*_agent_info.csv
