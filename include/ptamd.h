@@ -136,11 +136,14 @@ typedef struct {
                                    Only with max_active_rays == 0 and PT_RNG_COUNTER. */
     /* Round 6: queues SMALLER than a batch (0 = 1: one slot per entry, as the reference allocates, src/raytracer.cpp:760-787).  A batch of B entries needs B hit
      * records and B camera-ray directions, but its second extension queue only holds the paths that go on after the first hit and its shadow queue the shadow
-     * rays of the first hits -- 26 % and 58 % of B on BASELINE config 4.  With fractions f_ext, f_shadow in (0, 1) those queues hold f x (owned pixels x
-     * samples_in_flight) entries: 36 + 80 f_ext + 48 f_shadow bytes per entry instead of 164 (pinhole; a thin lens keeps its camera-ray origins: 68 + 48 f_ext +
-     * 48 f_shadow).  pt_render then sizes every batch so that what its first pass emits fits -- from the counts of earlier batches of the same camera, scene
-     * and tiles; a short probe batch first -- i.e. a scene that emits more than the fractions allow renders in smaller batches, never wrongly; a guess that
-     * turns out wrong all the same is cut at the queue's end on the device and REPORTED: pt_synchronize and the image reads fail (PT_ERR_STATE).
+     * rays of one pass -- 26 % and 58 % of B on BASELINE config 4 (the first pass emits most there).  With fractions f_ext, f_shadow in (0, 1) those queues hold
+     * f x (owned pixels x samples_in_flight) entries: 36 + 80 f_ext + 48 f_shadow bytes per entry instead of 164 (pinhole; a thin lens keeps its camera-ray
+     * origins: 68 + 48 f_ext + 48 f_shadow).  pt_render then sizes every batch so that the extension rays of its first pass and the shadow rays of its busiest
+     * pass fit, from the counts of earlier batches of the same camera, scene state, textures and tiles (a short probe batch first; again after pt_clear has
+     * cleared a reported overflow).  A scene that emits more than the fractions allow renders in smaller batches.  A batch that emits more than its queues hold
+     * all the same (a guess from earlier batches that turned out wrong) has every pass's counts cut at the queues' ends on the device -- nothing is read or
+     * written past them -- and is REPORTED: pt_synchronize, pt_render and the image reads fail (PT_ERR_STATE) until pt_clear.  So an image read that succeeds
+     * holds every path; an incomplete one is never returned.
      * Fixed schedule only (max_active_rays == 0, PT_RNG_COUNTER, samples_in_flight >= 16). */
     float ext_queue_fraction;
     float shadow_queue_fraction;

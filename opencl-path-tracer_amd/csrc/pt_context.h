@@ -202,11 +202,13 @@ struct pt_ctx {
     uint32_t capacity = 0;
     // Queues smaller than a batch (pt_config.ext_queue_fraction / shadow_queue_fraction, round 6): entries the second extension queue (and, for batches of a
     // pinhole's bundles, the origin / throughput planes of the first) and the shadow queue hold; == capacity without fractions.  A batch is sized so that what its
-    // FIRST pass emits fits (every later pass emits at most what it was handed): from the largest ratios seen in this epoch (camera, scene state, tiling).
+    // passes emit fits, from the largest ratios seen in this epoch (camera, scene state, textures, tiling): extension rays of the FIRST pass (every later pass emits
+    // at most what it was handed), shadow rays of ANY pass (a later pass can emit more of them than the first: glass in front of diffuse walls).
     uint32_t capExt = 0, capShadow = 0;
     bool q0Small = false; // the first queue's origin / throughput planes hold capExt entries (camera rays queued as directions only)
     bool ratiosKnown = false;
-    double ratioExt = 0, ratioShadow = 0; // (rays emitted by pass 0) / (entries of the batch), the largest of this epoch
+    double ratioExt = 0, ratioShadow = 0; // (extension rays emitted by pass 0, shadow rays emitted by the pass that emitted most) / (entries of the batch), the largest of this epoch
+    double ratioShadowFirst = 0; // (shadow rays emitted by pass 0) / (entries of the batch), the largest of this epoch: pt_stats.first_pass_shadow_ratio
     uint32_t* overflowPinned = nullptr; // set by k_clamp_counts when a batch emitted more than a queue holds after all: sticky, reported by pt_synchronize and the image reads
     uint32_t batchSamples = 0, probeBatches = 0;
     uint32_t epoch = 0, passCountsEpoch = 0; // camera / scene state / tiling the ratios belong to; ... the report in flight was launched in

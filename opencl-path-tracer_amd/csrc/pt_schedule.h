@@ -59,12 +59,12 @@ inline bool splitShadowAccum(const pt_ctx* c, uint64_t cap)
 }
 
 bool derivedPrimariesCapable(const pt_ctx* c); // (defined with renderSampleFixed's choice of kernels, below)
-// a new camera, scene state or tiling: what a batch's first pass emits is no longer known
+// a new camera, scene state, texture or tiling (or ratios learned from counts cut at a queue's end): what a batch emits is no longer known
 inline void newEpoch(pt_ctx* c)
 {
     c->epoch++;
     c->ratiosKnown = false;
-    c->ratioExt = c->ratioShadow = 0;
+    c->ratioExt = c->ratioShadow = c->ratioShadowFirst = 0;
 }
 inline bool smallQueues(const pt_ctx* c) { return c->capExt < c->capacity || c->capShadow < c->capacity; }
 inline int checkOverflow(pt_ctx* c)
@@ -74,19 +74,26 @@ inline int checkOverflow(pt_ctx* c)
                                     "running batch?): the rays beyond were dropped, the image since the last pt_clear is incomplete -- pt_clear and render again");
     return PT_OK;
 }
-// adopt a pass-counter report that has landed (renderSampleFixed); the ratios of this epoch only ever grow
+// adopt a pass-counter report that has landed (renderSampleFixed); the ratios of this epoch only ever grow.  Extension rays: pass 0's (a later pass emits at most
+// what it was handed, and hands on into queues of capExt entries).  Shadow rays: the largest count of any pass -- every pass writes the one shadow queue, and a pass
+// b >= 1 may emit more of them than pass 0 did (camera rays that hit glass send none, the walls behind it do): sized by pass 0 alone, pass 1 outgrew capShadow
 inline void adoptPassCounts(pt_ctx* c)
 {
     std::memcpy(c->passCountsHint, c->passCountsPinned, sizeof(c->passCountsHint));
     c->passCountsEntries = c->passCountsPending;
     c->passCountsPending = 0;
     if (c->passCountsEpoch == c->epoch && c->passCountsEntries) {
-        c->ratioExt = std::max(c->ratioExt, (double)c->passCountsHint[1] / (double)c->passCountsEntries);
-        c->ratioShadow = std::max(c->ratioShadow, (double)c->passCountsHint[kMaxPasses + 1] / (double)c->passCountsEntries);
+        const double entries = (double)c->passCountsEntries;
+        uint32_t shadowMost = 0;
+        for (int b = 0; b <= kMaxPasses; b++)
+            shadowMost = std::max(shadowMost, c->passCountsHint[kMaxPasses + 1 + b]);
+        c->ratioExt = std::max(c->ratioExt, (double)c->passCountsHint[1] / entries);
+        c->ratioShadow = std::max(c->ratioShadow, (double)shadowMost / entries);
+        c->ratioShadowFirst = std::max(c->ratioShadowFirst, (double)c->passCountsHint[kMaxPasses + 1] / entries);
         c->ratiosKnown = true;
     }
 }
-// the largest batch (samples per pixel) whose first pass fits the queues, by the ratios seen so far + 3 % + 64 K entries (a 64th of a small queue)
+// the largest batch (samples per pixel) whose passes fit the queues, by the ratios seen so far + 3 % + 64 K entries (a 64th of a small queue)
 inline uint32_t safeBatch(const pt_ctx* c)
 {
     auto limit = [&](uint32_t cap, double ratio) -> double {
@@ -708,8 +715,13 @@ int renderSampleFixed(pt_ctx* c, uint32_t sample, uint32_t batch, Prof& prof)
             HIPCHK(c, hipStreamWaitEvent(c->stream, c->evShadowed[b - 1], 0)); // the deposits of bounce b - 1's shadow rays come first
         prof.begin(2);
         launchShade(c, fp, in, out, b, entries, split ? &c->shadowQ[b] : nullptr, derived && b == 0);
-        if (b == 0 && (c->capExt < c->capacity || c->capShadow < c->capacity)) // (later passes emit at most what they were handed: only the first can outgrow a queue)
-            hipLaunchKernelGGL(k_clamp_counts, dim3(1), dim3(64), 0, c->stream, c->control.p, 0u, c->capExt, c->capShadow, c->overflowPinned);
+        // A pass emits at most one extension and one shadow ray per entry it was handed.  Pass 0 is handed the whole batch: the only pass that can outgrow the
+        // extension queues, and it may outgrow the shadow queue.  A later pass is handed at most capExt entries: where the shadow queue is the smaller one, it may
+        // outgrow that too (the batch was sized by the counts of earlier batches: a guess).  k_trace<true> reads as many shadow entries as the count says -- cut it.
+        if (b == 0 ? smallQueues(c) : c->capShadow < c->capExt) {
+            const uint32_t outCap = out == 1 ? c->capExt : (c->q0Small ? c->capExt : c->capacity); // (the queue pass b writes: launchShade's a.outCap)
+            hipLaunchKernelGGL(k_clamp_counts, dim3(1), dim3(64), 0, c->stream, c->control.p, b, outCap, c->capShadow, c->overflowPinned);
+        }
         prof.end();
         prof.begin(3);
         if (overlap && b + 1u == bounces && PT_LAST_SHADOW_ON_MAIN) {

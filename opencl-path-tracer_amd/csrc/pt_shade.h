@@ -717,7 +717,7 @@ struct ShadeArgs {
     uint32_t* activeFlag;
     uint32_t firstTile; // first 512-entry tile this launch is responsible for
     uint32_t derivedPrimaries; // pass 0 behind k_trace_multi (pinhole): the queue holds (direction, pixel) only -- origin = the eye, sample from the entry index
-    // entries the out queue / the shadow queue hold (round 6: they may be smaller than the batch -- ptamd.hip sizes a batch so that what its first pass emits
+    // entries the out queue / the shadow queue hold (round 6: they may be smaller than the batch -- ptamd.hip sizes a batch so that what its passes emit
     // fits, from the counts of earlier batches; the guard below and k_clamp_counts turn a wrong guess into a reported error instead of a write past the end)
     uint32_t outCap, shadowCap;
 };

@@ -692,6 +692,7 @@ int pt_upload_texture_array(pt_ctx* c, int kind, uint32_t width, uint32_t height
     t.layers = (int)layers;
     t.format = format;
     refreshSceneView(c);
+    newEpoch(c); // (an albedo map's alpha decides how many paths go on after a hit: the ratios the batches are sized by are measured again)
     return PT_OK;
     });
 }
@@ -804,6 +805,7 @@ int pt_clear(pt_ctx* c)
     if (c->overflowPinned && *c->overflowPinned) { // a reported overflow is cleared with the image it spoiled (whatever set it has run: the word is only read after a synchronisation)
         HIPCHK(c, hipStreamSynchronize(c->stream));
         *c->overflowPinned = 0u;
+        newEpoch(c); // the ratios learned since were measured on cut counts: the next render probes again
     }
     if (c->accumShadow.p) // (zero between pt_render calls unless one failed half-way)
         HIPCHK(c, hipMemsetAsync(c->accumShadow.p, 0, c->accumShadow.n * sizeof(float4), c->stream));
@@ -1013,7 +1015,7 @@ int pt_stats_get(pt_ctx* c, pt_stats* out)
     out->entered_instances = c->dyn[c->active].enteredInstances;
     out->batch_samples = c->batchSamples;
     out->probe_batches = c->probeBatches;
-    out->first_pass_ext_ratio = (float)c->ratioExt, out->first_pass_shadow_ratio = (float)c->ratioShadow;
+    out->first_pass_ext_ratio = (float)c->ratioExt, out->first_pass_shadow_ratio = (float)c->ratioShadowFirst;
     out->general_route = c->dyn[c->active].generalRoute ? 1u : 0u;
     out->team_launches = c->teamLaunches;
     return PT_OK;

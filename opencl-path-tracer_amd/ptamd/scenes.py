@@ -195,6 +195,20 @@ def cornell_box(width=512, height=512, builder=H.BVH_BINNED_SAH, box_materials=N
     return SceneBundle(scene, cam, width, height, name="cornell")
 
 
+def glass_first(width=160, height=90, builder=H.BVH_BINNED_SAH, smoothness=0.95, ior=1.5):
+    """The room of config 1 seen from just inside its opening through a pane of rough glass that fills the whole view.  Refractive materials send no shadow
+    ray (next-event estimation is skipped on them), so a batch's first pass emits none -- and its second pass, on the diffuse walls behind the pane, emits one
+    for most paths: the scene where a later pass sends more shadow rays than the first (queue sizing, pt_config.shadow_queue_fraction)."""
+    mats = _room_materials() + [L.material_refractive(smoothness, ior)]
+    mb = _MeshBuilder()
+    _room(mb, mats)
+    mb.add_quad((-1, 0, -0.6), (-1, 2, -0.6), (1, 2, -0.6), (1, 0, -0.6), 4)  # n = -z: towards the camera
+    scene = H.Scene()
+    scene.add_node(mb.build(mats, builder))
+    cam = _camera(width, height, (0.0, 1.0, -0.95), (0.0, 1.0, 1.0), 40.0)
+    return SceneBundle(scene, cam, width, height, name="glass_first")
+
+
 def blob_room(width=1920, height=1080, material=None, builder=H.BVH_BINNED_SAH, level=6, textured_floor=False):
     """Configs 2/3: the ~70k-triangle mesh (scale as main.cpp:146 would give a ~0.6 m bunny) inside the
     5-wall room with one 2-triangle area light."""

@@ -82,36 +82,52 @@ def test_config4_as_a_5x3_grid_against_the_oracle(gpu):
 
 @pytest.mark.parametrize("flags_name", ["copied", "entered", "thin_lens"])
 def test_the_timed_configuration_against_the_oracle_directly(gpu, bundle, flags_name):
-    """What bench.py times -- config 4 with bench.IN_FLIGHT (512 since round 4: ~200 GB of queues and planes) samples in flight: ONE batch whose primary
-    rays are generated and traced by the bundle kernel (k_trace_multi: beam test, four rays per lane, no k_gen launch), 1.06 G queue entries -- held against
-    the oracle directly: 4 096 sampled pixels at the full sample count, at north_star's gate (mean bias < 1e-3, tone-mapped RMSE < 1e-3; measured 2e-5 /
-    2e-6 at 256 in flight, profiles/round4/parity_margins.json).  `entered`: the same with every instance entered at traversal
+    """What bench.py times -- config 4 with bench.IN_FLIGHT (512 since round 4) samples in flight and the queue fractions of its headline context
+    (bench.EXT_QUEUE_FRACTION / SHADOW_QUEUE_FRACTION, round 6: ~90 instead of ~164 B per entry): a first render that probes and learns what a batch emits, then,
+    as bench.py's timed steps after `clear` and `reset_stats`, ONE batch whose primary rays are generated and traced by the bundle kernel (k_trace_multi: beam
+    test, four rays per lane, no k_gen launch), 1.06 G entries -- held against the oracle directly: 4 096 sampled pixels at the full sample count, at
+    north_star's gate (mean bias < 1e-3, tone-mapped RMSE < 1e-3).  `entered`: the same with every instance entered at traversal
     (PT_FLAG_NO_BAKED_INSTANCES), the `two_level` object of the bench line; `thin_lens`: config 5's camera (f/2 focused on the grid centre) -- the packets
-    are converging bundles walked around their waist on the focal plane."""
+    are converging bundles walked around their waist on the focal plane, and the first queue keeps its camera-ray origins (bench.bytes_per_entry)."""
     import bench
     import torch
-    # bench.IN_FLIGHT where the card has the ~200 GB free that it wants; otherwise the largest multiple of 256 that fits, as bench.py itself falls
-    # back (the note goes on the record with the margins: a box with another tenant must not turn a PARITY test red)
+    fe, fs = bench.EXT_QUEUE_FRACTION, bench.SHADOW_QUEUE_FRACTION
+    thin_lens = flags_name == "thin_lens"
+    # bench.IN_FLIGHT where the card has the memory free that it wants; otherwise the largest batch that fits, as bench.py itself falls back (the note goes
+    # on the record with the margins: a box with another tenant must not turn a PARITY test red)
     free_b, _ = torch.cuda.mem_get_info(0)
-    n = bench.fit_in_flight(bench.IN_FLIGHT, W * H, free_b)
+    n = bench.fit_in_flight(bench.IN_FLIGHT, W * H, free_b, per_entry=bench.bytes_per_entry(fe, fs, thin_lens))
     assert n >= 256, f"{free_b / 1e9:.0f} GB free: not even 256 samples in flight fit"
     flags = gpu.FLAG_NO_BAKED_INSTANCES if flags_name == "entered" else 0
-    if flags_name == "thin_lens":
+    if thin_lens:
         bundle = scenes.instanced_grid(W, H, level=6, thin_lens=True)
         assert bundle.camera["thinLensEnabled"]
-    ctx = U.make_ctx(gpu, bundle, W, H, seed=1, samples_in_flight=n, flags=flags)
-    ctx.render(n)
+    # the headline context of bench.py, argument for argument
+    ctx = gpu.Context(W, H, seed=1, device=0, samples_in_flight=n, flags=flags, ext_queue_fraction=fe, shadow_queue_fraction=fs)
+    ctx.upload_scene(bundle.flat, sky=bundle.sky, material_textures=bundle.material_textures)
+    ctx.set_camera(bundle.camera)
+    ctx.render(n)  # bench.py's first batch: the probe and the rest
+    probes = ctx.stats()["probe_batches"]
+    assert probes == 1
+    ctx.clear()
+    ctx.reset_stats()
+    ctx.render(n, sync=False)
+    ctx.synchronize()  # (no overflow reported)
     st = ctx.stats()
+    assert st["probe_batches"] == probes, "the ratios of the first render serve: no new probe batch"
+    assert st["batch_samples"] == n, "the timed batch is whole: what it emits fits the fractions"
     assert st["packet_launches"] == 1 and st["gen_launches"] == 0, "the batch must take the path the benchmark times"
     assert st["bundle_launches"] == 1  # bundles of 4 x 64 (k_trace_multi): around the eye of a pinhole, around the waist of a thin lens's converging bundle (round 6)
     assert st["rays_generated"] == W * H * n and ctx.samples_per_pixel == n
+    assert 0 < st["first_pass_ext_ratio"] < fe and 0 < st["first_pass_shadow_ratio"] < fs, st
     a = ctx.read_accum()[:, :3]
     ctx.close()
     px = np.random.default_rng(4).choice(W * H, 4096, replace=False).astype(np.uint32)
     ref, _ = O.render(U.oracle_scene(bundle), bundle.camera, W, H, n, seed=1, pixels=px, threads=16)
     got, want = a[px], ref[px, :3]
     U.image_margins(f"config4 as timed ({n} in flight), {n} spp, {flags_name}", got, want, n, bundle.camera, 1e-3, 1e-3,
-                    in_flight_wanted=bench.IN_FLIGHT, device_free_gb=round(free_b / 1e9, 1),
+                    in_flight_wanted=bench.IN_FLIGHT, device_free_gb=round(free_b / 1e9, 1), ext_queue_fraction=fe, shadow_queue_fraction=fs,
+                    first_pass_ext_ratio=st["first_pass_ext_ratio"], first_pass_shadow_ratio=st["first_pass_shadow_ratio"],
                     note="" if n == bench.IN_FLIGHT else f"fell back from {bench.IN_FLIGHT} to {n} samples in flight: {free_b / 1e9:.0f} GB of device memory free")
     # path by path most pixels agree to round-off (a pixel holds hundreds of paths here; one fp32 decision flip per pixel is common)
     close = np.isclose(got, want, rtol=2e-3, atol=2e-3 * want.max()).all(axis=1)
