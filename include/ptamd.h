@@ -349,6 +349,12 @@ int pt_shade_batch(pt_ctx* ctx, pt_shade_batch_io* io);
  * to the access shape MI355X_MICROARCH.md measures 6.29 TB/s with (the reference has no counterpart). */
 int pt_debug_copy_bandwidth(pt_ctx* ctx, size_t bytes, uint32_t repeat, float* gbps_out);
 int pt_debug_quantise_node(const float* lo12, const float* hi12, const uint32_t* refs4, const uint8_t* empty4, uint32_t empty_ref, void* out64);
+/* test hook, no device needed: what pt_upload_static (records made on the host) and -- given a top level (n_top > 0) -- pt_upload_dynamic make of these
+ * arrays under cfg's flags and RNG mode, as one line into `line` (line_bytes with its terminating zero): hashes of every array of the static part, then
+ * after ' | ' of every array of the dynamic state and the figures of its instance route.  Refusals as the uploads give them, through pt_last_error(NULL). */
+int pt_debug_convert(const pt_config* cfg, const pt_vertex* verts, uint32_t n_verts, const pt_triangle* tris, uint32_t n_tris, const pt_material* mats,
+                     uint32_t n_mats, const pt_sub_bvh_node* nodes, uint32_t n_nodes, const pt_emissive_triangle* lights, uint32_t n_lights,
+                     const pt_top_bvh_node* top_nodes, uint32_t n_top, uint32_t top_root, char* line, size_t line_bytes);
 const char* pt_version(void);
 
 #ifdef __cplusplus

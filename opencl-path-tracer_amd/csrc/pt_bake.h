@@ -9,78 +9,9 @@
 // thread per (instance, triangle reference) transforms a triangle.  Round 2 did all of this on the host, single-threaded, and
 // copied the result (110 MB for the benchmark scene) through pinned staging: 240 ms per tick.
 #pragma once
-#include "pt_device.h"
-#include <cmath>
+#include "pt_hostdev.h" // (quantiseWideNode: the host packs nodes with the same routine)
 
 namespace ptd {
-
-// Quantise up to four child boxes into a WideNode (pt_device.h): origin = min corner of their union, per-axis power-of-two scale
-// with (extent / scale) <= 255, planes rounded OUTWARDS and then verified with the exact expression the traversal kernels evaluate
-// (origin + scale * q).  An empty slot gets an inverted box and `emptyRef`.  Shared by the host (collapse of the caller's binary
-// trees) and the device (world-space copies), so that both produce the same bytes from the same boxes.
-__host__ __device__ inline void quantiseWideNode(const float (*lo)[3], const float (*hi)[3], const uint32_t* refs, const bool* empty, uint32_t emptyRef, WideNode* out)
-{
-    float nlo[3] = { 3.402823466e+38f, 3.402823466e+38f, 3.402823466e+38f }, nhi[3] = { -3.402823466e+38f, -3.402823466e+38f, -3.402823466e+38f };
-    for (int k = 0; k < 4; k++)
-        for (int a = 0; a < 3; a++)
-            if (!empty[k] && lo[k][a] <= hi[k][a]) {
-                nlo[a] = fminf(nlo[a], lo[k][a]);
-                nhi[a] = fmaxf(nhi[a], hi[k][a]);
-            }
-    WideNode w {};
-    float scale[3];
-    for (int a = 0; a < 3; a++) {
-        if (!(nlo[a] <= nhi[a]))
-            nlo[a] = nhi[a] = 0.f;
-        // smallest power of two s with (hi - lo) / s <= 255, evaluated in float like the kernel does
-        int e = 0;
-        const float extent = nhi[a] - nlo[a];
-        (void)frexpf(extent / 255.0f, &e); // extent/255 = m * 2^e, m in [0.5,1)  =>  2^e >= extent/255
-        e = e < -126 ? -126 : (e > 127 ? 127 : e);
-        scale[a] = ldexpf(1.0f, e);
-        while (extent > 0.f && nlo[a] + scale[a] * 255.0f < nhi[a] && e < 127) // guard float round-off
-            scale[a] = ldexpf(1.0f, ++e);
-    }
-    w.ox = nlo[0], w.oy = nlo[1], w.oz = nlo[2];
-    w.scaleX = scale[0], w.scaleY = scale[1], w.scaleZ = scale[2];
-    uint32_t q[6] = { 0, 0, 0, 0, 0, 0 }; // qlox, qhix, qloy, qhiy, qloz, qhiz
-    for (int k = 0; k < 4; k++) {
-        w.child[k] = empty[k] ? emptyRef : refs[k];
-        for (int a = 0; a < 3; a++) {
-            uint32_t ql = 255, qh = 0;
-            if (!empty[k]) {
-                const float fl = floorf((lo[k][a] - nlo[a]) / scale[a]);
-                const float fh = ceilf((hi[k][a] - nlo[a]) / scale[a]);
-                ql = (uint32_t)fmaxf(0.f, fminf(255.f, fl));
-                qh = (uint32_t)fmaxf(0.f, fminf(255.f, fh));
-                while (ql > 0 && nlo[a] + scale[a] * (float)ql > lo[k][a])
-                    ql--;
-                while (qh < 255 && nlo[a] + scale[a] * (float)qh < hi[k][a])
-                    qh++;
-            }
-            q[a * 2] |= ql << (8 * k);
-            q[a * 2 + 1] |= qh << (8 * k);
-        }
-    }
-    w.qlox = q[0], w.qhix = q[1], w.qloy = q[2], w.qhiy = q[3], w.qloz = q[4], w.qhiz = q[5];
-    *out = w;
-}
-
-// What a world-space copy of one instance needs (built on the host per tick, a few dozen bytes per instance).
-struct BakeJob {
-    double m[12]; // rows 0..2 of the WORLD transform (inverse of the top-level leaf's invTransform), row-major 3 x 4
-    uint32_t srcNode, numNodes; // the mesh's run of packed bottom-level nodes (0 nodes: the mesh is a single leaf)
-    uint32_t dstNode; // where the copy's nodes go (same order)
-    uint32_t srcRef, numRefs; // the mesh's run in the table of triangle references (leaf order; an SBVH references a triangle more than once)
-    uint32_t dstTri; // where the copy's triangles go
-    uint32_t instance; // instance index reported for hits on the copy
-    uint32_t _pad;
-};
-
-// exact boxes of a packed node's (up to) four children, object space -- the quantised planes of the node itself are already rounded
-struct WideBoxes {
-    float lo[4][3], hi[4][3];
-};
 
 struct BakeArgs {
     const BakeJob* jobs;

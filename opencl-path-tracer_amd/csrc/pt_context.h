@@ -1,5 +1,5 @@
 // The context of the C-ABI (include/ptamd.h): device buffers, the two static scenes and the two dynamic sets a context holds, error reporting.
-// Included by ptamd.hip alone (one translation unit: pt_context.h, pt_convert.h, pt_schedule.h, then the C-ABI shell).
+// Included by ptamd.hip alone (one translation unit: pt_context.h, pt_schedule.h, then the C-ABI shell; the conversion is pt_convert.cpp).
 #pragma once
 
 namespace {
@@ -38,82 +38,35 @@ struct ShadowQueueBuf {
 
 } // namespace
 
-// Everything pt_upload_static derives from the caller's static arrays -- the host's mirrors and the device's master copies.  A context holds TWO
-// (like the dynamic sets, like the reference's double-buffered cl::Buffers): renders and refits work on the current one while
-// pt_upload_static_async converts a rebuilt scene into the other; pt_frame_tick adopts it together with the dynamic state built on it.
+// Everything pt_upload_static derives from the caller's static arrays -- the host half (ptconv::StaticHost, pt_convert.h: what the conversion makes) and the
+// device's master copies.  A context holds TWO (like the dynamic sets, like the reference's double-buffered cl::Buffers): renders and refits work on the
+// current one while pt_upload_static_async converts a rebuilt scene into the other; pt_frame_tick adopts it together with the dynamic state built on it.
 struct StaticScene {
-    // The static part: the bottom-level trees as packed 4-wide nodes, object-space triangles and shading records.  Converted on the
-    // host once per pt_upload_static / pt_update_geometry (buildStaticGeom); one master copy on the device, from which a dynamic
-    // set refreshes its own copy (device to device) when its version is stale.
-    struct StaticGeom {
-        std::vector<WideNode> wide; // packed, object space
-        std::vector<WideBoxes> boxes; // exact child boxes of every packed node
-        std::vector<uint32_t> leafOfs; // [node][child]: offset of a leaf child's first triangle reference in its mesh's run
-        std::vector<uint32_t> refTri; // triangle references in leaf order, mesh by mesh -> caller's triangle index
-        std::vector<uint32_t> stackNeed; // per packed node
-        // what a REFIT needs of the conversion and cannot change: which pair-node child the box of every packed child slot is, which
-        // slots are unused (the collapse's split choices and the packing order stay as they are)
-        std::vector<uint32_t> kidSrc; // [node][child]: (pair node << 1) | side
-        std::vector<uint8_t> kidEmpty; // [node][child]
-        std::vector<uint32_t> kidBoxNode; // [node][child]: the same as a caller's node index (k_refit_nodes, pt_bake.h), 0x80000000 | i: extra box i, ~0: unused
-        std::vector<TriFat> fat;
-        struct Root {
-            uint32_t ref; // device reference of the mesh root (a packed node, or a leaf)
-            uint32_t nodeBase, numNodes, refBase, numRefs;
-            bool bakeable; // its nodes are one run of their own
-        };
-        std::vector<Root> roots;
-        std::vector<int32_t> rootOfNode; // caller's node index -> roots[] slot, -1: not a root
-        std::vector<uint32_t> extraRoots; // interior nodes a top-level leaf has named
-        uint32_t emptyRef = 0;
-        uint64_t version = 0;
-        bool onDevice = false;
-        // pt_upload_static_async (a rebuilt tree per frame): the host makes the topology only -- child references, the slots' box sources, the triangle
-        // references -- and the device makes the records from the caller's own arrays, as after a refit (k_refit_nodes: exact boxes and quantised planes;
-        // k_refit_tris: intersection and shading records).  The host's `wide` planes, `boxes` and `fat` are then not filled in (nothing reads them: a
-        // conversion that runs again makes everything anew, refitWideOnHost / buildFat re-make them from the pair boxes where a host-side refit needs them).
-        bool deviceMakesRecords = false;
-        DevBuf<WideNode> dWide;
-        DevBuf<WideBoxes> dBoxes;
-        DevBuf<uint32_t> dLeafOfs, dRefTri;
-        DevBuf<TriIsect> dTris;
-        DevBuf<TriFat> dFat;
-        // refit (pt_update_geometry): the caller's vertices on the device (the triangles' intersection and shading records are re-made
-        // from them by k_refit_tris), pinned staging for them and for the re-quantised nodes, guarded by an event of its own
-        DevBuf<pt_vertex> dVerts;
-        DevBuf<pt_sub_bvh_node> dNodes; // the caller's nodes as last handed in
-        DevBuf<uint32_t> dKidBoxNode;
-        DevBuf<float> dExtra;
-        // refit on the device alone (pt_refit_vertices): who a packed node reports to and how many arrivals complete it (k_refit_tree, pt_bake.h)
-        DevBuf<uint32_t> dParent, dNeed, dArrived;
-        uint64_t refitTablesFor = 0; // topology the tables were made for (0: none)
-        bool refitTablesOk = false; // false: a node has two parents (roots that share a subtree): the caller refits on the host (pt_update_geometry)
-        uint64_t topology = 0; // bumped by every buildStaticGeom
-        bool latestInStage = false; // the caller's latest vertices and nodes live in `stage` (vertices first), not in rawVerts / hostSubNodes
-        void* stage = nullptr;
-        size_t stageBytes = 0;
-        hipEvent_t stageRead = nullptr;
-        bool stageBusy = false;
-    } sg;
+    ptconv::StaticHost host;
+    // one master copy of the converted arrays on the device, from which a dynamic set refreshes its own copy (device to device) when its version is stale
+    DevBuf<WideNode> dWide;
+    DevBuf<WideBoxes> dBoxes;
+    DevBuf<uint32_t> dLeafOfs, dRefTri;
+    DevBuf<TriIsect> dTris;
+    DevBuf<TriFat> dFat;
+    uint64_t onDeviceTopology = 0; // the host.topology the master copy was made from (a conversion that runs again makes a new one)
+    // refit (pt_update_geometry): the caller's vertices on the device (the triangles' intersection and shading records are re-made
+    // from them by k_refit_tris), pinned staging for them and for the re-quantised nodes, guarded by an event of its own
+    DevBuf<pt_vertex> dVerts;
+    DevBuf<pt_sub_bvh_node> dNodes; // the caller's nodes as last handed in
+    DevBuf<uint32_t> dKidBoxNode;
+    DevBuf<float> dExtra;
+    // refit on the device alone (pt_refit_vertices): who a packed node reports to and how many arrivals complete it (k_refit_tree, pt_bake.h)
+    DevBuf<uint32_t> dParent, dNeed, dArrived;
+    uint64_t refitTablesFor = 0; // topology the tables were made for (0: none)
+    bool refitTablesOk = false; // false: a node has two parents (roots that share a subtree): the caller refits on the host (pt_update_geometry)
+    bool latestInStage = false; // the caller's latest vertices and nodes live in `stage` (vertices first), not in host.rawVerts / host.hostSubNodes
+    void* stage = nullptr;
+    size_t stageBytes = 0;
+    hipEvent_t stageRead = nullptr;
+    bool stageBusy = false;
     DevBuf<TriShade> triShade;
     DevBuf<Material> materials;
-    std::vector<VertexShade> hostVerts;
-    std::vector<pt_vertex> rawVerts; // the caller's vertices as last handed in (pt_upload_static / pt_update_geometry)
-    std::vector<uint32_t> denseOfNode; // caller's sub-BVH node -> pair node (0xFFFFFFFF: a leaf or a pad)
-    uint32_t numDensePairs = 0; // pair nodes [0, numDensePairs) mirror the caller's inner nodes; the rest split leaves of more than kMaxLeafTris
-    std::vector<TriIsect> hostTris; // object-space intersection triangles (world-space copies of tiny instances are appended per pt_upload_dynamic)
-    std::vector<PairNode> hostBottomNodes; // bottom-level pair nodes (the top level is appended per pt_upload_dynamic)
-    std::vector<uint32_t> nodeRef; // reference sub-BVH node index -> device child reference
-    std::vector<uint32_t> subtreeDepth; // per reference node (roots queried)
-    std::vector<TriShade> hostTriShade; // vertex indices + material of every triangle (kept for pt_update_geometry)
-    std::vector<pt_material> hostMaterials;
-    std::vector<pt_sub_bvh_node> hostSubNodes; // the caller's sub-BVH as uploaded (topology; boxes are replaced by pt_update_geometry)
-    uint32_t numVerts = 0;
-    uint32_t numRefNodes = 0, numTris = 0;
-    bool hostNodeBoxesStale = false; // the boxes in hostSubNodes are older than rawVerts (pt_refit_vertices: the device refitted its own tree, nobody handed nodes in)
-    bool hostGeomStale = false; // hostTris / hostVerts / hostBottomNodes' boxes / sg.wide / sg.boxes / sg.fat are older than the caller's latest arrays (a refit
-                                // re-makes the device's copies on the device only; the host's are refreshed if the whole conversion ever runs again)
-    bool materialBins = false; // the surfaces are of more than one material type: k_shade shades its tiles in material order
     bool have = false; // holds a converted scene
 };
 
@@ -317,7 +270,7 @@ void refreshSceneView(pt_ctx* c)
     s.numInstRoots = d.numInstRoots;
     s.materialTex.texels = c->texMaterial.p;
     s.sky.texels = c->texSky.p;
-    s.numTriangles = c->haveDynamic ? d.numTris : c->st->numTris;
+    s.numTriangles = c->haveDynamic ? d.numTris : c->st->host.numTris;
 }
 
 template <typename T>

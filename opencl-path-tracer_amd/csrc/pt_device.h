@@ -100,11 +100,28 @@ struct Material { // the reference's 48-byte record, read as 3 x float4
     float4 params; // bits: x = textureId | smoothness | iorBasic ; y = f0NonMetal | iorRough ; z = metallic byte
     float4 typeAndPad; // bits x = type
 };
+enum : int { MAT_DIFFUSE = 0, MAT_PBR = 1, MAT_REFRACTIVE = 2, MAT_BASIC_REFRACTIVE = 3, MAT_EMISSIVE = 4 };
 
 struct Light { // EmissiveTriangle (light.cl:5-9) pre-digested: 80 B
     float4 v0, v1, v2; // world space; v0.w = area (Heron), v1.w.. unused
     float4 normal; // normalize(cross(v1-v0, v2-v0))
     float4 colour;
+};
+
+// What a world-space copy of one instance needs (built on the host per tick, a few dozen bytes per instance).
+struct BakeJob {
+    double m[12]; // rows 0..2 of the WORLD transform (inverse of the top-level leaf's invTransform), row-major 3 x 4
+    uint32_t srcNode, numNodes; // the mesh's run of packed bottom-level nodes (0 nodes: the mesh is a single leaf)
+    uint32_t dstNode; // where the copy's nodes go (same order)
+    uint32_t srcRef, numRefs; // the mesh's run in the table of triangle references (leaf order; an SBVH references a triangle more than once)
+    uint32_t dstTri; // where the copy's triangles go
+    uint32_t instance; // instance index reported for hits on the copy
+    uint32_t _pad;
+};
+
+// exact boxes of a packed node's (up to) four children, object space -- the quantised planes of the node itself are already rounded
+struct WideBoxes {
+    float lo[4][3], hi[4][3];
 };
 
 struct Texture {

@@ -1,30 +1,10 @@
 // Device vector helpers and the two PRNGs of the path.
 #pragma once
-#include "pt_device.h"
+#include "pt_hostdev.h" // (V3 and its operators)
 #include <cfloat>
 
 namespace ptd {
 
-struct V3 {
-    float x, y, z;
-};
-__host__ __device__ inline V3 mk(float x, float y, float z) { return { x, y, z }; }
-__host__ __device__ inline V3 mk(float s) { return { s, s, s }; }
-__host__ __device__ inline V3 xyz(float4 f) { return { f.x, f.y, f.z }; }
-__host__ __device__ inline V3 operator+(V3 a, V3 b) { return { a.x + b.x, a.y + b.y, a.z + b.z }; }
-__host__ __device__ inline V3 operator-(V3 a, V3 b) { return { a.x - b.x, a.y - b.y, a.z - b.z }; }
-__host__ __device__ inline V3 operator-(V3 a) { return { -a.x, -a.y, -a.z }; }
-__host__ __device__ inline V3 operator*(V3 a, V3 b) { return { a.x * b.x, a.y * b.y, a.z * b.z }; }
-__host__ __device__ inline V3 operator*(V3 a, float s) { return { a.x * s, a.y * s, a.z * s }; }
-__host__ __device__ inline V3 operator*(float s, V3 a) { return { s * a.x, s * a.y, s * a.z }; }
-__host__ __device__ inline V3 operator/(V3 a, float s) { return { a.x / s, a.y / s, a.z / s }; }
-__host__ __device__ inline float dot(V3 a, V3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
-__host__ __device__ inline V3 cross(V3 a, V3 b) { return { a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x }; }
-__host__ __device__ inline V3 normalize(V3 a)
-{
-    float len = sqrtf(dot(a, a));
-    return { a.x / len, a.y / len, a.z / len };
-}
 __device__ inline float saturate(float a) { return fminf(fmaxf(a, 0.0f), 1.0f); }
 __device__ inline float asF(uint32_t u) { return __uint_as_float(u); }
 __device__ inline uint32_t asU(float f) { return __float_as_uint(f); }

@@ -16,7 +16,6 @@ constexpr float kINVPI = 0.31830988618f; // shading_helper.cl:9
 constexpr float kEPS = 0.0001f; // shading_helper.cl:15
 constexpr float kMaxSmoothness = 0.94f; // shading.cl:9
 constexpr float kAirIor = 1.000277f; // scene.cl:46
-enum : int { MAT_DIFFUSE = 0, MAT_PBR = 1, MAT_REFRACTIVE = 2, MAT_BASIC_REFRACTIVE = 3, MAT_EMISSIVE = 4 };
 
 // ---- texture fetch: NORMALIZED_COORDS | ADDRESS_REPEAT | FILTER_LINEAR on a 2D array ----------
 // (sampler of shading_helper.cl:19-22 / skydome.cl:4-7; OpenCL 1.2 s8.2 linear filter, s8.3 repeat)

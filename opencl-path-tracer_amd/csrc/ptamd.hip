@@ -2,7 +2,6 @@
 // conversion into the HBM layouts of pt_device.h, the launch schedule that replaces the reference's
 // RayTracer::traceRays (src/raytracer.cpp:289-430), and the kernel-granular test hooks.
 #include "../../include/ptamd.h"
-#include "../host/parallel.h" // (header only: the worker threads the host library uses, here for the conversion of an upload)
 #include "pt_shade.h"
 #include "pt_trace.h"
 #include "pt_packet.h"
@@ -31,9 +30,194 @@
 
 using namespace ptd;
 
-#include "pt_context.h"
 #include "pt_convert.h"
+#include "pt_context.h"
 #include "pt_schedule.h"
+
+namespace {
+
+// The conversion's options for one upload call: pt_config, the diagnostic variables of tools/README.md and EXPERIMENTS.md, the kernels' limits
+// (pt_convert.cpp reads no environment).  `async`: pt_upload_static_async, whose records the device makes unless PTAMD_HOST_RECORDS is set.
+static ptconv::ConvertOptions convertOptions(const pt_config& cfg, bool async = false)
+{
+    ptconv::ConvertOptions o;
+    o.flags = cfg.flags;
+    o.parity = cfg.rng_mode == PT_RNG_LFSR113_PARITY;
+    if (const char* e = getenv("PTAMD_LEAF_FORMATION")) {
+        unsigned cap = o.costs.cap;
+        if (sscanf(e, "%u,%lf,%lf,%lf,%lf", &cap, &o.costs.inner, &o.costs.leaf0, &o.costs.tri, &o.costs.alpha) >= 1)
+            o.costs.cap = std::min(cap, kMaxLeafTris);
+    }
+    if (const char* e = getenv("PTAMD_MAX_LEAF"))
+        o.maxLeaf = std::max(1u, std::min((uint32_t)atoi(e), kMaxLeafTris));
+    if (const char* e = getenv("PTAMD_BAKE_BUDGET_GB")) // diagnostics (bench.py, two_level_general: the copied scene as the yardstick of the entered one)
+        o.bakeBudgetBytes = (uint64_t)std::max(0.0, atof(e) * (double)(1ull << 30));
+    o.noFoldedInstances = getenv("PTAMD_NO_FOLDED_INSTANCES") != nullptr;
+    if (const char* e = getenv("PTAMD_GENERAL_ROUTE"))
+        o.generalRoute = atoi(e) != 0 ? 1 : 0;
+    const char* seq = getenv("PTAMD_BUILD_THREADS"); // (1: everything on the calling thread, as the host library's builders read it)
+    o.sequential = seq && atoi(seq) == 1;
+    o.hostRecords = !async || getenv("PTAMD_HOST_RECORDS"); // (PTAMD_HOST_RECORDS=1: the records of a rebuilt scene on the host too -- A / B)
+    o.timing = getenv("PTAMD_UPLOAD_TIMING") != nullptr;
+    o.collapseReport = getenv("PTAMD_COLLAPSE_REPORT") != nullptr;
+    o.stackMax = (uint32_t)kTraversalStackMax, o.packetStack = kPacketStack, o.foldTable = kInstFoldTable;
+    return o;
+}
+
+// the caller's latest arrays where the conversion cannot find them in the host vectors: in the staging memory after a refit on the device (pt_update_geometry)
+static ptconv::Latest latestOf(const StaticScene& s)
+{
+    if (!s.latestInStage)
+        return {};
+    return { (const pt_vertex*)s.stage, (const pt_sub_bvh_node*)((const unsigned char*)s.stage + (size_t)s.host.numVerts * sizeof(pt_vertex)) };
+}
+
+// the host's mirrors brought up to the caller's latest arrays (the host vectors take them over from the staging memory)
+static void refreshHost(StaticScene& s)
+{
+    ptconv::refreshHostGeometry(s.host, latestOf(s));
+    s.latestInStage = false;
+}
+
+// the static arrays' master copy in device memory (the two dynamic sets take theirs from it, device to device)
+static int uploadStaticGeom(pt_ctx* c, const ptconv::ConvertOptions& o)
+{
+    StaticScene& g = *c->st;
+    if (g.onDeviceTopology == g.host.topology)
+        return PT_OK;
+    ptconv::StageTimer tm("uploadStaticGeom", o.timing);
+    // the copy stream may still be reading the old master (a set being refreshed from it)
+    HIPCHK(c, hipStreamSynchronize(c->copyStream));
+    tm.lap("syncCopyStream");
+    if (g.host.hostGeomStale) { // refitted before the master copy ever reached the device
+        refreshHost(g);
+        ptconv::buildFat(g.host);
+    }
+    int rc;
+    if (g.host.deviceMakesRecords) {
+        // the topology and the caller's arrays as they are; the records on the device (what pt_update_geometry does after a refit: the same kernels from the same
+        // boxes with the same routines -- a context that adopts this scene holds the bytes a fresh one makes on the host, tests/test_gpu_dynamic.py)
+        const std::vector<float> extra = ptconv::extraBoxes(g.host); // (boxes of the pair nodes that cut a leaf of more than two triangles)
+        const size_t nT = c->st->host.numTris;
+        if ((rc = uploadVec(c, g.dWide, g.host.wide)) || (rc = uploadVec(c, g.dLeafOfs, g.host.leafOfs)) || (rc = uploadVec(c, g.dRefTri, g.host.refTri))
+            || (rc = uploadVec(c, g.dVerts, c->st->host.rawVerts)) || (rc = uploadVec(c, c->st->triShade, c->st->host.hostTriShade))
+            || (rc = uploadVec(c, g.dNodes, c->st->host.hostSubNodes)) || (rc = uploadVec(c, g.dKidBoxNode, g.host.kidBoxNode)) || (rc = uploadVec(c, g.dExtra, extra)))
+            return rc;
+        if (g.dBoxes.n < std::max<size_t>(g.host.wide.size(), 1))
+            HIPCHK(c, g.dBoxes.alloc(g.host.wide.size() + g.host.wide.size() / 8 + 1));
+        if (g.dTris.n < nT + 1)
+            HIPCHK(c, g.dTris.alloc(nT + nT / 8 + 1));
+        if (g.dFat.n < std::max<size_t>(nT, 1))
+            HIPCHK(c, g.dFat.alloc(nT + nT / 8 + 1));
+        tm.lap("uploads");
+        static_assert(sizeof(VertexIn) == sizeof(pt_vertex) && sizeof(SubNodeIn) == sizeof(pt_sub_bvh_node), "the refit kernels read the caller's records as they are");
+        HIPCHK(c, hipMemsetAsync(g.dTris.p + nT, 0, sizeof(TriIsect), c->copyStream)); // what an unused child slot refers to
+        if (!g.host.wide.empty()) {
+            RefitNodeArgs rn {};
+            rn.nodes = (const SubNodeIn*)g.dNodes.p, rn.kidBoxNode = g.dKidBoxNode.p, rn.extra = g.dExtra.p, rn.wide = g.dWide.p, rn.boxes = g.dBoxes.p;
+            rn.emptyRef = g.host.emptyRef, rn.n = (uint32_t)g.host.wide.size();
+            hipLaunchKernelGGL(k_refit_nodes, dim3((rn.n + 127u) / 128u), dim3(128), 0, c->copyStream, rn);
+        }
+        RefitArgs ra {};
+        ra.verts = (const VertexIn*)g.dVerts.p, ra.tri = c->st->triShade.p, ra.mats = c->st->materials.p, ra.tris = g.dTris.p, ra.fat = g.dFat.p, ra.n = (uint32_t)nT;
+        hipLaunchKernelGGL(k_refit_tris, dim3(((uint32_t)nT + 255u) / 256u), dim3(256), 0, c->copyStream, ra);
+        HIPCHK(c, hipGetLastError());
+        tm.lap("kernels");
+        g.onDeviceTopology = g.host.topology;
+        return PT_OK;
+    }
+    std::vector<TriIsect> tris = c->st->host.hostTris;
+    tris.push_back(TriIsect { make_float4(0, 0, 0, 0), make_float4(0, 0, 0, 0), make_float4(0, 0, 0, 0) }); // what an unused child slot refers to
+    if ((rc = uploadVec(c, g.dWide, g.host.wide)) || (rc = uploadVec(c, g.dBoxes, g.host.boxes)) || (rc = uploadVec(c, g.dLeafOfs, g.host.leafOfs))
+        || (rc = uploadVec(c, g.dRefTri, g.host.refTri)) || (rc = uploadVec(c, g.dTris, tris)) || (rc = uploadVec(c, g.dFat, g.host.fat))
+        || (rc = uploadVec(c, g.dVerts, c->st->host.rawVerts)) || (rc = uploadVec(c, c->st->triShade, c->st->host.hostTriShade))
+        || (rc = uploadVec(c, g.dNodes, c->st->host.hostSubNodes)) || (rc = uploadVec(c, g.dKidBoxNode, g.host.kidBoxNode)))
+        return rc;
+    tm.lap("uploads");
+    g.onDeviceTopology = g.host.topology;
+    return PT_OK;
+}
+
+// `async`: into c->st without touching the render stream or the dynamic state (pt_upload_static_async: c->st is the scene that is not current)
+static int uploadStaticImpl(pt_ctx* c, const pt_vertex* verts, uint32_t nV, const pt_triangle* tris, uint32_t nT, const pt_material* mats,
+    uint32_t nM, const pt_sub_bvh_node* nodes, uint32_t nN, bool async = false)
+{
+    if (!c)
+        return PT_ERR_INVALID;
+    const ptconv::ConvertOptions o = convertOptions(c->cfg, async);
+    ptconv::StageTimer tm("uploadStatic", o.timing);
+    std::string why;
+    if (const int rc = ptconv::convertStatic(c->st->host, o, c->staticVersions, verts, nV, tris, nT, mats, nM, nodes, nN, tm, why))
+        return fail(c, rc, "%s", why.c_str());
+    c->st->latestInStage = false;
+    c->st->have = true;
+    HIPCHK(c, hipSetDevice(c->device));
+    if (!async) {
+        HIPCHK(c, hipStreamSynchronize(c->stream)); // renders in flight read these buffers
+        c->haveStatic = true;
+        c->haveDynamic = false; // top-level leaves reference sub-BVH roots: must be re-uploaded
+        c->pending = -1;
+        c->statPending = -1; // (a rebuilt scene that was waiting for its frame tick is dropped with the dynamic state)
+    }
+    // (pt_upload_static_async: the materials go last.  A blocking copy issued while a frame of the current scene holds every compute unit with its persistent
+    // waves waited for most of that frame -- 0.43 ms of a 1080p frame, tools/rebuild_timing.py --1080p -- and the conversion above is host work the frame can hide)
+    std::vector<Material> hMats(nM);
+    static_assert(sizeof(Material) == sizeof(pt_material), "material record is copied verbatim");
+    std::memcpy(hMats.data(), mats, (size_t)nM * sizeof(pt_material));
+    if (const int rc = uploadVec(c, c->st->materials, hMats))
+        return rc;
+    tm.lap("materials");
+    if (!async)
+        refreshSceneView(c);
+    return PT_OK;
+}
+
+// Who a packed node reports to in a bottom-up pass, and how many arrivals complete it (k_refit_tree).  Made once per topology.
+static int ensureRefitTables(pt_ctx* c)
+{
+    StaticScene& g = *c->st;
+    if (g.refitTablesFor == g.host.topology)
+        return PT_OK;
+    const size_t n = g.host.wide.size();
+    std::vector<uint32_t> parent(n, 0xFFFFFFFFu), need(n, 1u);
+    bool ok = true;
+    for (size_t q = 0; q < n; q++)
+        for (int k = 0; k < 4; k++) {
+            const uint32_t r = g.host.wide[q].child[k];
+            if (r == g.host.emptyRef || refCount(r) != 0u)
+                continue;
+            const uint32_t ch = refIndex(r);
+            if (ch >= n || ch == q || parent[ch] != 0xFFFFFFFFu) { // (two parents: roots that share a subtree -- the bottom-up pass would complete the child once and leave one parent waiting)
+                ok = false;
+                continue;
+            }
+            parent[ch] = ((uint32_t)q << 2) | (uint32_t)k;
+            need[q]++;
+        }
+    g.refitTablesOk = ok;
+    g.refitTablesFor = g.host.topology;
+    if (!ok)
+        return PT_OK;
+    HIPCHK(c, hipStreamSynchronize(c->copyStream)); // (an earlier refit may still be walking the old tables)
+    int rc;
+    if ((rc = uploadVec(c, g.dParent, parent)) || (rc = uploadVec(c, g.dNeed, need)))
+        return rc;
+    if (!g.dArrived.p || g.dArrived.n < std::max<size_t>(n, 1))
+        HIPCHK(c, g.dArrived.alloc(std::max<size_t>(n + n / 8, 1)));
+    HIPCHK(c, hipMemset(g.dArrived.p, 0, g.dArrived.n * sizeof(uint32_t)));
+    return PT_OK;
+}
+
+template <typename T>
+int growTo(pt_ctx* c, DevBuf<T>& buf, size_t count)
+{
+    if (buf.n >= std::max<size_t>(count, 1))
+        return PT_OK;
+    HIPCHK(c, buf.alloc(std::max<size_t>(count + count / 8, 1))); // some headroom: the number of world-space copies varies from state to state
+    return PT_OK;
+}
+
+} // namespace
 
 
 // =================================================================================================
@@ -89,7 +273,7 @@ int pt_debug_copy_bandwidth(pt_ctx* c, size_t bytes, uint32_t repeat, float* gbp
 
 const char* pt_last_error(const pt_ctx* ctx) { return ctx ? ctx->error.c_str() : g_createError.c_str(); }
 
-// Test hook, no device needed: the host side of quantiseWideNode (pt_bake.h) -- up to four child boxes (lo / hi: 4 x 3 floats; empty[k] != 0:
+// Test hook, no device needed: the host side of quantiseWideNode (pt_hostdev.h) -- up to four child boxes (lo / hi: 4 x 3 floats; empty[k] != 0:
 // unused slot) into the 64-byte node the traversal kernels read.  tests/test_abi_and_layout.py checks the planes it makes against the
 // expression the kernels evaluate (origin + 2^exp * q): every child box must lie inside its quantised box.
 int pt_debug_quantise_node(const float* lo12, const float* hi12, const uint32_t* refs4, const uint8_t* empty4, uint32_t emptyRef, void* out64)
@@ -107,6 +291,54 @@ int pt_debug_quantise_node(const float* lo12, const float* hi12, const uint32_t*
     quantiseWideNode(lo, hi, refs4, empty, emptyRef, &w);
     std::memcpy(out64, &w, sizeof(w));
     return PT_OK;
+}
+
+// Test hook, no device needed: what pt_upload_static (the records made on the host) and, given a top level, pt_upload_dynamic make of these arrays, as one line
+// -- FNV-1a hashes of every array of the static part | of every array of the dynamic state, and the figures of its instance route (tests/test_convert.py).
+int pt_debug_convert(const pt_config* cfg, const pt_vertex* verts, uint32_t nV, const pt_triangle* tris, uint32_t nT, const pt_material* mats, uint32_t nM,
+    const pt_sub_bvh_node* nodes, uint32_t nN, const pt_emissive_triangle* lights, uint32_t nL, const pt_top_bvh_node* topNodes, uint32_t nTop, uint32_t topRoot,
+    char* line, size_t lineBytes)
+{
+    return guarded(nullptr, "pt_debug_convert", [&]() -> int {
+        if (!cfg || !line)
+            return fail(nullptr, PT_ERR_INVALID, "pt_debug_convert: null argument");
+        const ptconv::ConvertOptions o = convertOptions(*cfg);
+        ptconv::StaticHost s;
+        ptconv::DynamicHost d;
+        uint64_t versions = 0;
+        std::string why;
+        ptconv::StageTimer tm("convert", o.timing);
+        int rc = ptconv::convertStatic(s, o, versions, verts, nV, tris, nT, mats, nM, nodes, nN, tm, why);
+        if (rc == PT_OK && nTop)
+            rc = ptconv::convertDynamic(s, o, versions, {}, lights, nL, topNodes, nTop, topRoot, d, why);
+        if (rc)
+            return fail(nullptr, rc, "%s", why.c_str());
+        auto fnv = [](const void* p, size_t n) {
+            uint64_t h = 1469598103934665603ull;
+            for (size_t i = 0; i < n; i++)
+                h = (h ^ ((const uint8_t*)p)[i]) * 1099511628211ull;
+            return (unsigned long long)h;
+        };
+        char buf[1024];
+        int n = snprintf(buf, sizeof buf, "wide %zu %016llx boxes %016llx leafOfs %016llx refTri %zu %016llx kidSrc %016llx kidBoxNode %016llx stackNeed %016llx fat %016llx pairs %zu %016llx",
+            s.wide.size(), fnv(s.wide.data(), s.wide.size() * sizeof(WideNode)), fnv(s.boxes.data(), s.boxes.size() * sizeof(s.boxes[0])),
+            fnv(s.leafOfs.data(), s.leafOfs.size() * 4), s.refTri.size(), fnv(s.refTri.data(), s.refTri.size() * 4), fnv(s.kidSrc.data(), s.kidSrc.size() * 4),
+            fnv(s.kidBoxNode.data(), s.kidBoxNode.size() * 4), fnv(s.stackNeed.data(), s.stackNeed.size() * 4), fnv(s.fat.data(), s.fat.size() * sizeof(s.fat[0])),
+            s.hostBottomNodes.size(), fnv(s.hostBottomNodes.data(), s.hostBottomNodes.size() * sizeof(PairNode)));
+        if (nTop)
+            n += snprintf(buf + n, sizeof buf - n, " | topWide %zu %016llx instances %zu %016llx lights %zu %016llx jobs %zu %016llx instanceTopNode %016llx instRoots %zu %016llx "
+                "instRootSrc %016llx instFold %zu %016llx hasInstances %d enteredInstances %u enteredGeneral %u foldedInstances %u generalRoute %d bakedNodes %u bakedTris %u "
+                "stackNeed %u rootRef %08x rootRefFolded %08x",
+                d.topWide.size(), fnv(d.topWide.data(), d.topWide.size() * sizeof(WideNode)), d.instances.size(), fnv(d.instances.data(), d.instances.size() * sizeof(Instance)),
+                d.lights.size(), fnv(d.lights.data(), d.lights.size() * sizeof(Light)), d.jobs.size(), fnv(d.jobs.data(), d.jobs.size() * sizeof(BakeJob)),
+                fnv(d.instanceTopNode.data(), d.instanceTopNode.size() * 4), d.instRoots.size(), fnv(d.instRoots.data(), d.instRoots.size() * sizeof(WideNode)),
+                fnv(d.instRootSrc.data(), d.instRootSrc.size() * 4), d.instFold.size(), fnv(d.instFold.data(), d.instFold.size() * sizeof(float4)), (int)d.hasInstances,
+                d.enteredInstances, d.enteredGeneral, d.foldedInstances, (int)d.generalRoute, d.bakedNodes, d.bakedTris, d.stackNeed, d.rootRef, d.rootRefFolded);
+        if ((size_t)n >= lineBytes)
+            return fail(nullptr, PT_ERR_INVALID, "pt_debug_convert: the line takes %d bytes", n + 1);
+        std::memcpy(line, buf, (size_t)n + 1);
+        return PT_OK;
+    });
 }
 
 int pt_create(const pt_config* cfg, pt_ctx** out)
@@ -215,7 +447,7 @@ void pt_destroy(pt_ctx* c)
     c->texMaterial.release(), c->texSky.release();
     c->nodes.release();
     for (StaticScene& sc : c->stat) {
-        StaticScene::StaticGeom& g = sc.sg;
+        StaticScene& g = sc;
         sc.materials.release(), sc.triShade.release();
         g.dWide.release(), g.dBoxes.release(), g.dLeafOfs.release(), g.dRefTri.release(), g.dTris.release(), g.dFat.release();
         g.dVerts.release(), g.dNodes.release(), g.dKidBoxNode.release(), g.dExtra.release(), g.dParent.release(), g.dNeed.release(), g.dArrived.release();
@@ -293,7 +525,7 @@ int pt_upload_static_async(pt_ctx* c, const pt_vertex* verts, uint32_t nV, const
         c->st = &c->stat[target];
         int rc = uploadStaticImpl(c, verts, nV, tris, nT, mats, nM, nodes, nN, true);
         if (rc == PT_OK)
-            rc = uploadStaticGeom(c);
+            rc = uploadStaticGeom(c, convertOptions(c->cfg));
         if (rc != PT_OK)
             c->st->have = false;
         c->st = cur;
@@ -316,7 +548,7 @@ int pt_upload_static(pt_ctx* c, const pt_vertex* verts, uint32_t nV, const pt_tr
 //
 // A refit cannot change what the conversion of pt_upload_static decided -- which descendants of a binary node became the children of
 // its 4-wide node (the collapse's split choices), the breadth-first packing, the leaves' triangle references, the stack bound -- so all
-// of that is kept (StaticScene::StaticGeom::kidSrc / kidBoxNode / kidEmpty / leafOfs / refTri / stackNeed) and only what moves is re-made, ON THE
+// of that is kept (ptconv::StaticHost::kidSrc / kidBoxNode / kidEmpty / leafOfs / refTri / stackNeed) and only what moves is re-made, ON THE
 // DEVICE: the caller's vertex and node arrays travel as they are through pinned staging on the copy stream (an event of its own guards
 // the staging memory: no stream is synchronised), k_refit_nodes gathers every packed node's child boxes from the caller's nodes and
 // re-quantises it (quantiseWideNode: the host's routine), k_refit_tris re-makes the triangles' intersection and shading records.  The
@@ -333,23 +565,23 @@ int pt_update_geometry(pt_ctx* c, const pt_vertex* verts, uint32_t nV, const pt_
             return fail(c, PT_ERR_STATE, "pt_update_geometry: call pt_upload_static first");
         if (c->statPending >= 0) // (the caller's offsets and counts are those of the rebuilt scene already; the scene that still renders is the old one)
             return fail(c, PT_ERR_STATE, "pt_update_geometry: a rebuilt scene (pt_upload_static_async) is waiting for pt_frame_tick: refit after the tick");
-        if (!verts || !nodes || nV != c->st->numVerts || nN != c->st->numRefNodes)
-            return fail(c, PT_ERR_INVALID, "pt_update_geometry: the vertex and node counts must be the uploaded ones (%u, %u)", c->st->numVerts, c->st->numRefNodes);
+        if (!verts || !nodes || nV != c->st->host.numVerts || nN != c->st->host.numRefNodes)
+            return fail(c, PT_ERR_INVALID, "pt_update_geometry: the vertex and node counts must be the uploaded ones (%u, %u)", c->st->host.numVerts, c->st->host.numRefNodes);
         for (uint32_t i = 0; i < nN; i++)
-            if (nodes[i].leftChildOrFirstTriangle != c->st->hostSubNodes[i].leftChildOrFirstTriangle || nodes[i].triangleCount != c->st->hostSubNodes[i].triangleCount)
+            if (nodes[i].leftChildOrFirstTriangle != c->st->host.hostSubNodes[i].leftChildOrFirstTriangle || nodes[i].triangleCount != c->st->host.hostSubNodes[i].triangleCount)
                 return fail(c, PT_ERR_INVALID, "pt_update_geometry: node %u changed its links: a refit keeps the topology (use pt_upload_static for a rebuilt tree)", i);
         HIPCHK(c, hipSetDevice(c->device));
-        StaticScene::StaticGeom& g = c->st->sg;
-        if (!g.onDevice) {
+        StaticScene& g = *c->st;
+        if (g.onDeviceTopology != g.host.topology) {
             // nothing of the old geometry is on the device yet: everything on the host, the first upload takes it from the host arrays
-            refreshHostGeometry(c); // (an earlier device-side refit may have left the host mirrors behind)
-            refitPairBoxes(c, verts, nodes, false);
-            refitWideOnHost(c);
-            c->st->rawVerts.assign(verts, verts + nV);
-            c->st->hostSubNodes.assign(nodes, nodes + nN);
+            refreshHost(g); // (an earlier device-side refit may have left the host mirrors behind)
+            ptconv::refitPairBoxes(g.host, verts, nodes, false);
+            ptconv::refitWideOnHost(g.host);
+            c->st->host.rawVerts.assign(verts, verts + nV);
+            c->st->host.hostSubNodes.assign(nodes, nodes + nN);
             g.latestInStage = false;
-            c->st->hostGeomStale = true; // hostTris / hostVerts / sg.fat follow at the upload
-            g.version = ++c->staticVersions;
+            c->st->host.hostGeomStale = true; // hostTris / hostVerts / sg.host.fat follow at the upload
+            g.host.version = ++c->staticVersions;
             return PT_OK;
         }
         // ---- the device's master copy: the caller's vertices and nodes AS THEY ARE through pinned staging on the copy stream; the packed nodes
@@ -357,15 +589,8 @@ int pt_update_geometry(pt_ctx* c, const pt_vertex* verts, uint32_t nV, const pt_
         // caller's latest arrays (refreshHostGeometry reads it if the whole conversion ever runs again).
         static_assert(sizeof(VertexIn) == sizeof(pt_vertex), "k_refit_tris reads the caller's vertex records as they are");
         static_assert(sizeof(SubNodeIn) == sizeof(pt_sub_bvh_node), "k_refit_nodes reads the caller's node records as they are");
-        std::vector<float> extra; // boxes of the pair nodes that split an oversized leaf (rare): recomputed here
-        if (c->st->hostBottomNodes.size() > c->st->numDensePairs) {
-            refitPairBoxes(c, verts, nodes, true);
-            for (size_t j = c->st->numDensePairs; j < c->st->hostBottomNodes.size(); j++) {
-                const PairNode& n = c->st->hostBottomNodes[j];
-                const float b[12] = { n.bx.x, n.by.x, n.bz.x, n.bx.y, n.by.y, n.bz.y, n.bx.z, n.by.z, n.bz.z, n.bx.w, n.by.w, n.bz.w };
-                extra.insert(extra.end(), b, b + 12);
-            }
-        }
+        ptconv::refitPairBoxes(g.host, verts, nodes, true); // the boxes of the pair nodes that split an oversized leaf (rare): recomputed here
+        const std::vector<float> extra = ptconv::extraBoxes(g.host);
         const size_t bytesV = (size_t)nV * sizeof(pt_vertex), bytesN = (size_t)nN * sizeof(pt_sub_bvh_node), bytesE = extra.size() * sizeof(float);
         const size_t total = bytesV + bytesN + bytesE;
         if (!g.stageRead)
@@ -376,7 +601,7 @@ int pt_update_geometry(pt_ctx* c, const pt_vertex* verts, uint32_t nV, const pt_
         }
         if (g.stageBytes < total) {
             if (g.latestInStage)
-                refreshHostGeometry(c); // (the staging memory holds the host's only copy of the latest arrays: take it over before it goes)
+                refreshHost(g); // (the staging memory holds the host's only copy of the latest arrays: take it over before it goes)
             if (g.stage)
                 (void)hipHostFree(g.stage);
             g.stage = nullptr;
@@ -387,8 +612,8 @@ int pt_update_geometry(pt_ctx* c, const pt_vertex* verts, uint32_t nV, const pt_
         std::memcpy(st, verts, bytesV);
         std::memcpy(st + bytesV, nodes, bytesN);
         g.latestInStage = true;
-        c->st->hostGeomStale = true;
-        g.version = ++c->staticVersions;
+        c->st->host.hostGeomStale = true;
+        g.host.version = ++c->staticVersions;
         HIPCHK(c, hipMemcpyAsync(g.dVerts.p, st, bytesV, hipMemcpyHostToDevice, c->copyStream));
         HIPCHK(c, hipMemcpyAsync(g.dNodes.p, st + bytesV, bytesN, hipMemcpyHostToDevice, c->copyStream));
         if (bytesE) {
@@ -399,15 +624,15 @@ int pt_update_geometry(pt_ctx* c, const pt_vertex* verts, uint32_t nV, const pt_
         }
         HIPCHK(c, hipEventRecord(g.stageRead, c->copyStream));
         g.stageBusy = true;
-        if (!g.wide.empty()) {
+        if (!g.host.wide.empty()) {
             RefitNodeArgs rn {};
             rn.nodes = (const SubNodeIn*)g.dNodes.p, rn.kidBoxNode = g.dKidBoxNode.p, rn.extra = g.dExtra.p, rn.wide = g.dWide.p, rn.boxes = g.dBoxes.p;
-            rn.emptyRef = g.emptyRef, rn.n = (uint32_t)g.wide.size();
+            rn.emptyRef = g.host.emptyRef, rn.n = (uint32_t)g.host.wide.size();
             hipLaunchKernelGGL(k_refit_nodes, dim3((rn.n + 127u) / 128u), dim3(128), 0, c->copyStream, rn);
         }
         RefitArgs ra {};
-        ra.verts = (const VertexIn*)g.dVerts.p, ra.tri = c->st->triShade.p, ra.mats = c->st->materials.p, ra.tris = g.dTris.p, ra.fat = g.dFat.p, ra.n = c->st->numTris;
-        hipLaunchKernelGGL(k_refit_tris, dim3((c->st->numTris + 255u) / 256u), dim3(256), 0, c->copyStream, ra);
+        ra.verts = (const VertexIn*)g.dVerts.p, ra.tri = c->st->triShade.p, ra.mats = c->st->materials.p, ra.tris = g.dTris.p, ra.fat = g.dFat.p, ra.n = c->st->host.numTris;
+        hipLaunchKernelGGL(k_refit_tris, dim3((c->st->host.numTris + 255u) / 256u), dim3(256), 0, c->copyStream, ra);
         HIPCHK(c, hipGetLastError());
         return PT_OK;
     });
@@ -428,12 +653,12 @@ int pt_refit_vertices(pt_ctx* c, uint32_t firstVertex, const pt_vertex* verts, u
             return fail(c, PT_ERR_STATE, "pt_refit_vertices: call pt_upload_static first");
         if (c->statPending >= 0) // (a refit between a rebuild and its tick addressed the OLD scene with the NEW scene's offsets)
             return fail(c, PT_ERR_STATE, "pt_refit_vertices: a rebuilt scene (pt_upload_static_async) is waiting for pt_frame_tick: refit after the tick");
-        if (!verts || nV == 0 || (uint64_t)firstVertex + nV > c->st->numVerts)
-            return fail(c, PT_ERR_INVALID, "pt_refit_vertices: [%u, %u + %u) is not a range of the %u uploaded vertices", firstVertex, firstVertex, nV, c->st->numVerts);
+        if (!verts || nV == 0 || (uint64_t)firstVertex + nV > c->st->host.numVerts)
+            return fail(c, PT_ERR_INVALID, "pt_refit_vertices: [%u, %u + %u) is not a range of the %u uploaded vertices", firstVertex, firstVertex, nV, c->st->host.numVerts);
         HIPCHK(c, hipSetDevice(c->device));
-        StaticScene::StaticGeom& g = c->st->sg;
+        StaticScene& g = *c->st;
         int rc;
-        if ((rc = uploadStaticGeom(c)) || (rc = ensureRefitTables(c))) // (the master copy reaches the device with the first dynamic upload at the latest)
+        if ((rc = uploadStaticGeom(c, convertOptions(c->cfg))) || (rc = ensureRefitTables(c))) // (the master copy reaches the device with the first dynamic upload at the latest)
             return rc;
         if (!g.refitTablesOk)
             return fail(c, PT_ERR_UNSUPPORTED, "pt_refit_vertices: two roots of the sub-BVH array share a subtree: refit on the host and use pt_update_geometry");
@@ -444,15 +669,14 @@ int pt_refit_vertices(pt_ctx* c, uint32_t firstVertex, const pt_vertex* verts, u
                 HIPCHK(c, hipEventSynchronize(g.stageRead));
                 g.stageBusy = false;
             }
-            const pt_vertex* sv = latestVerts(c);
-            const pt_sub_bvh_node* sn = latestNodes(c);
-            c->st->rawVerts.assign(sv, sv + c->st->numVerts);
-            c->st->hostSubNodes.assign(sn, sn + c->st->numRefNodes);
+            const ptconv::Latest l = latestOf(g);
+            g.host.rawVerts.assign(l.verts, l.verts + g.host.numVerts);
+            g.host.hostSubNodes.assign(l.nodes, l.nodes + g.host.numRefNodes);
             g.latestInStage = false;
         }
-        std::memcpy(c->st->rawVerts.data() + firstVertex, verts, (size_t)nV * sizeof(pt_vertex));
-        c->st->hostNodeBoxesStale = true;
-        c->st->hostGeomStale = true;
+        std::memcpy(c->st->host.rawVerts.data() + firstVertex, verts, (size_t)nV * sizeof(pt_vertex));
+        c->st->host.hostNodeBoxesStale = true;
+        c->st->host.hostGeomStale = true;
         const size_t bytesV = (size_t)nV * sizeof(pt_vertex);
         if (!g.stageRead)
             HIPCHK(c, hipEventCreateWithFlags(&g.stageRead, hipEventDisableTiming));
@@ -468,20 +692,20 @@ int pt_refit_vertices(pt_ctx* c, uint32_t firstVertex, const pt_vertex* verts, u
             HIPCHK(c, hipHostMalloc(&g.stage, g.stageBytes, hipHostMallocDefault));
         }
         std::memcpy(g.stage, verts, bytesV);
-        g.version = ++c->staticVersions;
+        g.host.version = ++c->staticVersions;
         HIPCHK(c, hipMemcpyAsync(g.dVerts.p + firstVertex, g.stage, bytesV, hipMemcpyHostToDevice, c->copyStream));
         HIPCHK(c, hipEventRecord(g.stageRead, c->copyStream));
         g.stageBusy = true;
         static_assert(sizeof(VertexIn) == sizeof(pt_vertex), "the refit kernels read the caller's vertex records as they are");
-        if (!g.wide.empty()) {
+        if (!g.host.wide.empty()) {
             RefitTreeArgs rt {};
             rt.verts = (const VertexIn*)g.dVerts.p, rt.tri = c->st->triShade.p, rt.wide = g.dWide.p, rt.boxes = g.dBoxes.p;
-            rt.parent = g.dParent.p, rt.need = g.dNeed.p, rt.arrived = g.dArrived.p, rt.emptyRef = g.emptyRef, rt.n = (uint32_t)g.wide.size();
+            rt.parent = g.dParent.p, rt.need = g.dNeed.p, rt.arrived = g.dArrived.p, rt.emptyRef = g.host.emptyRef, rt.n = (uint32_t)g.host.wide.size();
             hipLaunchKernelGGL(k_refit_tree, dim3((rt.n + 127u) / 128u), dim3(128), 0, c->copyStream, rt);
         }
         RefitArgs ra {};
-        ra.verts = (const VertexIn*)g.dVerts.p, ra.tri = c->st->triShade.p, ra.mats = c->st->materials.p, ra.tris = g.dTris.p, ra.fat = g.dFat.p, ra.n = c->st->numTris;
-        hipLaunchKernelGGL(k_refit_tris, dim3((c->st->numTris + 255u) / 256u), dim3(256), 0, c->copyStream, ra);
+        ra.verts = (const VertexIn*)g.dVerts.p, ra.tri = c->st->triShade.p, ra.mats = c->st->materials.p, ra.tris = g.dTris.p, ra.fat = g.dFat.p, ra.n = c->st->host.numTris;
+        hipLaunchKernelGGL(k_refit_tris, dim3((c->st->host.numTris + 255u) / 256u), dim3(256), 0, c->copyStream, ra);
         HIPCHK(c, hipGetLastError());
         return PT_OK;
     });
@@ -503,10 +727,6 @@ int pt_upload_dynamic_async(pt_ctx* c, const pt_emissive_triangle* lights, uint3
         return PT_ERR_INVALID;
     if (!c->haveStatic)
         return fail(c, PT_ERR_STATE, "pt_upload_dynamic: call pt_upload_static first");
-    if (!topNodes || nTop == 0 || topRoot >= nTop)
-        return fail(c, PT_ERR_INVALID, "pt_upload_dynamic: bad top-level BVH");
-    if (nL > 0 && !lights)
-        return fail(c, PT_ERR_INVALID, "pt_upload_dynamic: null light array");
     HIPCHK(c, hipSetDevice(c->device));
     // a rebuilt scene is waiting (pt_upload_static_async): this state is built on IT -- its top-level leaves name the new sub-BVH roots
     struct UseScene {
@@ -516,21 +736,27 @@ int pt_upload_dynamic_async(pt_ctx* c, const pt_emissive_triangle* lights, uint3
     } useScene { c, c->st };
     if (c->statPending >= 0)
         c->st = &c->stat[c->statPending];
-    StageTimer tm("uploadDynamicAsync");
-    DynamicHost h;
-    int rc = convertDynamic(c, lights, nL, topNodes, nTop, topRoot, h);
+    const ptconv::ConvertOptions o = convertOptions(c->cfg);
+    ptconv::StageTimer tm("uploadDynamicAsync", o.timing);
+    ptconv::DynamicHost h;
+    std::string why;
+    int rc = ptconv::convertDynamic(c->st->host, o, c->staticVersions, latestOf(*c->st), lights, nL, topNodes, nTop, topRoot, h, why);
+    if (!c->st->host.hostGeomStale) // (a conversion of the static part ran again and took the latest arrays over)
+        c->st->latestInStage = false;
     tm.lap("convertDynamic");
-    if (rc || (rc = uploadStaticGeom(c)))
+    if (rc)
+        return fail(c, rc, "%s", why.c_str());
+    if ((rc = uploadStaticGeom(c, o)))
         return rc;
     tm.lap("uploadStaticGeom");
-    StaticScene::StaticGeom& sg = c->st->sg;
+    StaticScene& sg = *c->st;
     const int target = c->haveDynamic ? 1 - c->active : c->active; // nothing active yet: fill the active set itself
     pt_ctx::DynamicSet& d = c->dyn[target];
     // the copies may not start before the renders that still read this set are done (it was the active set until the last tick),
     // nor before an earlier, never-adopted upload into it has finished (same stream: ordered)
     if (d.used)
         HIPCHK(c, hipStreamWaitEvent(c->copyStream, d.lastUse, 0));
-    const size_t staticNodes = sg.wide.size(), staticTris = (size_t)c->st->numTris + 1;
+    const size_t staticNodes = sg.host.wide.size(), staticTris = (size_t)c->st->host.numTris + 1;
     // (+ 1: the SMALL traversal instantiations fetch 96 bytes from wherever a lane stands -- 32 beyond a node, 48 beyond a one-triangle leaf)
     const size_t needWide = staticNodes + h.topSlots + h.bakedNodes + h.instRoots.size() + 1, needTris = staticTris + h.bakedTris + 1;
     // the traversal kernels address nodes and triangle records by base + 32-bit byte offset (pt_trace.h, PT_OFFSET32)
@@ -543,7 +769,7 @@ int pt_upload_dynamic_async(pt_ctx* c, const pt_emissive_triangle* lights, uint3
     const size_t bytes[7] = { h.topWide.size() * sizeof(WideNode), h.instances.size() * sizeof(Instance), h.lights.size() * sizeof(Light),
         h.jobs.size() * sizeof(BakeJob), h.instRoots.size() * sizeof(WideNode), h.instFold.size() * sizeof(float4), h.instRootSrc.size() * sizeof(uint32_t) };
     const size_t total = bytes[0] + bytes[1] + bytes[2] + bytes[3] + bytes[4] + bytes[5] + bytes[6];
-    if (d.wide.n < needWide || d.tris.n < needTris || d.fat.n < sg.fat.size() || d.instances.n < std::max<size_t>(h.instances.size(), 1)
+    if (d.wide.n < needWide || d.tris.n < needTris || d.fat.n < sg.host.fat.size() || d.instances.n < std::max<size_t>(h.instances.size(), 1)
         || d.lights.n < std::max<size_t>(h.lights.size(), 1) || d.jobs.n < std::max<size_t>(h.jobs.size(), 1) || d.instFold.n < std::max<size_t>(h.instFold.size(), 1)
         || d.instRootSrc.n < std::max<size_t>(h.instRootSrc.size(), 1) || d.stageBytes < std::max<size_t>(total, 1)) {
         // growing frees device memory, which the runtime only does once nothing uses it: wait for both streams (rare: the first
@@ -551,8 +777,8 @@ int pt_upload_dynamic_async(pt_ctx* c, const pt_emissive_triangle* lights, uint3
         HIPCHK(c, hipStreamSynchronize(c->copyStream));
         if (d.used)
             HIPCHK(c, hipEventSynchronize(d.lastUse));
-        const bool regrown = d.wide.n < needWide || d.tris.n < needTris || d.fat.n < sg.fat.size();
-        if ((rc = growTo(c, d.wide, needWide)) || (rc = growTo(c, d.tris, needTris)) || (rc = growTo(c, d.fat, sg.fat.size()))
+        const bool regrown = d.wide.n < needWide || d.tris.n < needTris || d.fat.n < sg.host.fat.size();
+        if ((rc = growTo(c, d.wide, needWide)) || (rc = growTo(c, d.tris, needTris)) || (rc = growTo(c, d.fat, sg.host.fat.size()))
             || (rc = growTo(c, d.instances, h.instances.size())) || (rc = growTo(c, d.lights, h.lights.size())) || (rc = growTo(c, d.jobs, h.jobs.size()))
             || (rc = growTo(c, d.instFold, h.instFold.size())) || (rc = growTo(c, d.instRootSrc, h.instRootSrc.size())))
             return rc;
@@ -572,13 +798,13 @@ int pt_upload_dynamic_async(pt_ctx* c, const pt_emissive_triangle* lights, uint3
         d.stageBusy = false;
     }
     tm.lap("grow");
-    if (d.staticVersion != sg.version) { // device to device, from the master copy
+    if (d.staticVersion != sg.host.version) { // device to device, from the master copy
         if (staticNodes)
             HIPCHK(c, hipMemcpyAsync(d.wide.p, sg.dWide.p, staticNodes * sizeof(WideNode), hipMemcpyDeviceToDevice, c->copyStream));
         HIPCHK(c, hipMemcpyAsync(d.tris.p, sg.dTris.p, staticTris * sizeof(TriIsect), hipMemcpyDeviceToDevice, c->copyStream));
-        if (!sg.fat.empty())
-            HIPCHK(c, hipMemcpyAsync(d.fat.p, sg.dFat.p, sg.fat.size() * sizeof(TriFat), hipMemcpyDeviceToDevice, c->copyStream));
-        d.staticVersion = sg.version;
+        if (!sg.host.fat.empty())
+            HIPCHK(c, hipMemcpyAsync(d.fat.p, sg.dFat.p, sg.host.fat.size() * sizeof(TriFat), hipMemcpyDeviceToDevice, c->copyStream));
+        d.staticVersion = sg.host.version;
     }
     unsigned char* st = (unsigned char*)d.stage;
     const void* src[7] = { h.topWide.data(), h.instances.data(), h.lights.data(), h.jobs.data(), h.instRoots.data(), h.instFold.data(), h.instRootSrc.data() };
@@ -601,7 +827,7 @@ int pt_upload_dynamic_async(pt_ctx* c, const pt_emissive_triangle* lights, uint3
     if (!h.jobs.empty()) { // the world-space copies: one thread per (copy, node) and per (copy, triangle reference)
         BakeArgs ba {};
         ba.srcWide = sg.dWide.p, ba.srcBoxes = sg.dBoxes.p, ba.srcLeafOfs = sg.dLeafOfs.p, ba.refTri = sg.dRefTri.p, ba.srcTris = sg.dTris.p;
-        ba.dstWide = d.wide.p, ba.dstTris = d.tris.p, ba.emptyRef = sg.emptyRef;
+        ba.dstWide = d.wide.p, ba.dstTris = d.tris.p, ba.emptyRef = sg.host.emptyRef;
         for (size_t first = 0; first < h.jobs.size(); first += 32768) {
             const uint32_t n = (uint32_t)std::min<size_t>(32768, h.jobs.size() - first);
             uint32_t maxNodes = 0, maxRefs = 0;
@@ -620,7 +846,7 @@ int pt_upload_dynamic_async(pt_ctx* c, const pt_emissive_triangle* lights, uint3
     d.numLights = h.numLights;
     d.rootRef = h.rootRef;
     d.staticIndex = (int)(c->st - c->stat);
-    d.numTris = c->st->numTris, d.firstWorldNode = (uint32_t)sg.wide.size();
+    d.numTris = c->st->host.numTris, d.firstWorldNode = (uint32_t)sg.host.wide.size();
     d.rootRefFolded = h.rootRefFolded;
     d.foldedInstances = h.foldedInstances;
     d.instRootBase = h.instRootBase, d.numInstRoots = (uint32_t)h.instRoots.size(), d.instFoldCount = h.generalRoute ? h.enteredGeneral : (uint32_t)h.instFold.size(); // (the general route: how many entered instances want their 3 x 4 rows)
@@ -1299,7 +1525,7 @@ int pt_shade_batch(pt_ctx* c, pt_shade_batch_io* io)
         hH[i] = make_float4(prim >= 0 ? io->t[i] : INFINITY, io->u[i], io->v[i], fprim);
         int32_t ti = io->inst[i];
         hI[i] = (ti >= 0 && (size_t)ti < topToInst.size()) ? topToInst[ti] : -1;
-        if (prim >= 0 && (hI[i] < 0 || (uint32_t)prim >= c->st->numTris))
+        if (prim >= 0 && (hI[i] < 0 || (uint32_t)prim >= c->st->host.numTris))
             return fail(c, PT_ERR_INVALID, "pt_shade_batch: entry %u has an invalid prim/inst", i);
     }
     RayQueueBuf in, out, stagedDummy;

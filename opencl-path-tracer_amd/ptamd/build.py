@@ -1,4 +1,4 @@
-"""In-tree builds: libptamd_host.so (g++) and libptamd.so (hipcc, gfx950 code objects, no JIT)."""
+"""In-tree builds: libptamd_host.so (g++) and libptamd.so (hipcc, gfx950 code objects, no JIT; the host-only conversion unit by clang++)."""
 import os
 import subprocess
 
@@ -66,13 +66,20 @@ DEVICE_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared"
                 "-Xarch_host", "-msse4.1"]  # (host side: floorf / ceilf of the node quantiser inline -- it is most of a conversion's packing pass)
 
 
+# The scene conversion (csrc/pt_convert.cpp) is host code alone: the compiler of hipcc's host pass with the host flags of DEVICE_FLAGS, into the same library.
+ROCM_PATH = os.environ.get("ROCM_PATH", "/opt/rocm")
+CONVERT_FLAGS = ["-O3", "-std=c++17", "-fPIC", "-msse4.1", "-pthread"]
+CSRC_EXTS = (".hip", ".h", ".cpp")
+
+
 def csrc_fingerprint(csrc_dir=None):
-    """sha256 over the device library's sources (csrc/*.hip, *.h: names and bytes, sorted) and its compiler flags: what a set of hardware counters
-    (profiles/roundN/traffic*.json) was taken on, and what bench.py holds them against before it quotes them (roofline.traffic_stale)."""
+    """sha256 over the device library's sources (csrc/*.hip, *.h, *.cpp: names and bytes, sorted) and its compiler flags: what a set of hardware counters
+    (profiles/roundN/traffic*.json) was taken on -- the conversion decides the trees they were measured on -- and what bench.py holds them against before
+    it quotes them (roofline.traffic_stale)."""
     import hashlib
     d = csrc_dir or CSRC_DIR
-    h = hashlib.sha256(" ".join(DEVICE_FLAGS).encode())
-    for name in sorted(f for f in os.listdir(d) if f.endswith((".hip", ".h"))):
+    h = hashlib.sha256(" ".join(DEVICE_FLAGS + CONVERT_FLAGS).encode())
+    for name in sorted(f for f in os.listdir(d) if f.endswith(CSRC_EXTS)):
         h.update(name.encode() + b"\0")
         with open(os.path.join(d, name), "rb") as f:
             h.update(f.read())
@@ -81,10 +88,12 @@ def csrc_fingerprint(csrc_dir=None):
 
 def build_device(force=False):
     out = os.path.join(CSRC_DIR, "libptamd.so")
-    deps = _all_files(CSRC_DIR, (".hip", ".h")) + _all_files(os.path.join(ROOT, "..", "include"), (".h",))
+    deps = _all_files(CSRC_DIR, CSRC_EXTS) + _all_files(os.path.join(ROOT, "..", "include"), (".h",))
     if force or _newer(out, deps):
+        subprocess.run([os.path.join(ROCM_PATH, "llvm", "bin", "clang++")] + CONVERT_FLAGS + ["-D__HIP_PLATFORM_AMD__", "-I" + os.path.join(ROCM_PATH, "include"),
+                        "-c", "pt_convert.cpp", "-o", "pt_convert.o"], cwd=CSRC_DIR, check=True)
         hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-        subprocess.run([hipcc] + DEVICE_FLAGS + ["ptamd.hip", "-o", out], cwd=CSRC_DIR, check=True)
+        subprocess.run([hipcc] + DEVICE_FLAGS + ["ptamd.hip", "-x", "none", "pt_convert.o", "-o", out], cwd=CSRC_DIR, check=True)
     return out
 
 

@@ -67,7 +67,7 @@ EXPORTS = ["pt_create", "pt_destroy", "pt_last_error", "pt_set_stream", "pt_uplo
            "pt_upload_texture_array", "pt_set_camera", "pt_set_tiles", "pt_set_accum_buffer", "pt_clear", "pt_render",
            "pt_synchronize", "pt_resolve", "pt_resolve_device", "pt_resolve_device_ptr", "pt_read_accum", "pt_write_accum", "pt_accum_device_ptr",
            "pt_samples_per_pixel", "pt_stats_get", "pt_stats_reset", "pt_profile_kernels", "pt_reduce_accum",
-           "pt_intersect", "pt_gen_rays", "pt_primary_pass", "pt_shade_batch", "pt_debug_quantise_node", "pt_debug_copy_bandwidth", "pt_version"]
+           "pt_intersect", "pt_gen_rays", "pt_primary_pass", "pt_shade_batch", "pt_debug_quantise_node", "pt_debug_convert", "pt_debug_copy_bandwidth", "pt_version"]
 
 _lib = None
 
@@ -125,6 +125,7 @@ def lib():
         l.pt_gen_rays.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32] + [C.c_void_p] * 7
         l.pt_primary_pass.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32] + [C.c_void_p] * 8
         l.pt_shade_batch.argtypes = [C.c_void_p, C.POINTER(ShadeBatchIO)]
+        l.pt_debug_convert.argtypes = [C.POINTER(Config)] + [C.c_void_p, C.c_uint32] * 6 + [C.c_uint32, C.c_void_p, C.c_size_t]
         _lib = l
     return _lib
 
@@ -135,6 +136,18 @@ class PtError(RuntimeError):
 
 def _p(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+def debug_convert(flat, flags=0, rng_mode=RNG_COUNTER):
+    """pt_debug_convert: the line of digests of what pt_upload_static (records made on the host) and pt_upload_dynamic make of `flat` -- no device needed."""
+    cfg = Config(64, 64, 0, 0, rng_mode, 1, 0, flags, 0, 0.0, 0.0)
+    line = C.create_string_buffer(2048)
+    rc = lib().pt_debug_convert(C.byref(cfg), _p(flat.vertices), len(flat.vertices), _p(flat.triangles), len(flat.triangles), _p(flat.materials),
+                                len(flat.materials), _p(flat.sub_nodes), len(flat.sub_nodes), _p(flat.lights), len(flat.lights), _p(flat.top_nodes),
+                                len(flat.top_nodes), flat.top_root, line, len(line))
+    if rc != 0:
+        raise PtError(f"pt_debug_convert failed ({rc}): {lib().pt_last_error(None).decode()}")
+    return line.value.decode()
 
 
 class Context:

@@ -35,9 +35,16 @@ def test_a_doctored_byte_of_csrc_flips_traffic_stale(tmp_path):
     assert k["traffic"] == 100000 and "valu_busy" not in k and "valu_active_lanes" not in k
     # a json that does not say which build it was taken on (rounds 1-5) is stale by definition; no json at all is not "stale", it is absent
     assert bench.traffic_is_stale({"kernels": {}}, fp) and not bench.traffic_is_stale(None, fp)
+    # ... and so does one of the host-only conversion unit (it decides the trees the counters were taken on)
+    src = copy / "pt_convert.cpp"
+    data = bytearray(src.read_bytes())
+    data[len(data) // 2] ^= 1
+    src.write_bytes(bytes(data))
+    fp3 = B.csrc_fingerprint(str(copy))
+    assert fp3 not in (fp, fp2) and bench.traffic_is_stale(tj, fp3)
     # a new file in csrc/ counts too
     (copy / "pt_new.h").write_text("// nothing\n")
-    assert B.csrc_fingerprint(str(copy)) not in (fp, fp2)
+    assert B.csrc_fingerprint(str(copy)) not in (fp, fp2, fp3)
 
 
 def test_committed_traffic_files_name_their_build_or_are_flagged():
