@@ -298,6 +298,68 @@ int pt_profile_kernels(pt_ctx* ctx, int enable); /* per-kernel hipEvent timing i
 /* Sum the accumulator over ranks onto `root` with RCCL (ncclReduce, float sum). comm: ncclComm_t. */
 int pt_reduce_accum(pt_ctx* ctx, void* nccl_comm, int root);
 
+/* ---- guides and denoiser: first-hit feature buffers and an edge-avoiding a-trous wavelet filter (Dammertz et al. 2010) ------
+ * The reference has no counterpart: what pt_resolve returns at 1-8 spp is raw Monte-Carlo noise.  Nothing below touches the render
+ * path: the guides come from a cheap pass of their own, the filter reads the accumulator and writes an image of its own.
+ *
+ * GUIDE PASS.  Two width*height float4 images, SUMS over guide samples:
+ *   albedo_hits  = (sum albedo.rgb, number of samples that hit geometry)
+ *   normal_depth = (sum world-space shading normal.xyz, sum hit distance t)
+ * Guide sample s traces the camera ray pt_render traces for sample index s (same counter-PRNG keying, pinhole and thin lens); guide
+ * indices continue from pt_guide_samples.  Closest hit only, per OWNED pixel (tiles are honoured; pixels of other ranks stay zero, so the
+ * images of complementary tilings add up to the whole one bit for bit).  Deposits per sample:
+ *   albedo   DIFFUSE: diffuseColour -- where textured, the bilinear-repeat texture fetch shading makes, an alpha-0 texel giving (1,1,1);
+ *            PBR: baseColour; REFRACTIVE, BASIC_REFRACTIVE, EMISSIVE and misses: (1,1,1), so that demodulation leaves them alone
+ *   normal   the interpolated shading normal taken to world space with the instance's normal transform, normalised, flipped to face the
+ *            ray; a miss deposits -D
+ *   distance t of the hit; a miss deposits PT_GUIDE_SKY_DEPTH, so that sky against geometry is an edge and sky against sky is not
+ *   hits     1 or 0
+ *   (a thin lens traces un-normalised directions: its deposits use D / |D| and t * |D|)
+ * The sums are bit-reproducible run to run and independent of samples_in_flight and of the queue fractions: no float atomics, a pixel's
+ * samples are added in sample order (pt_render_guides(2) then (3) is pt_render_guides(5)).  Fixed schedule with PT_RNG_COUNTER only:
+ * PT_ERR_UNSUPPORTED in parity / refill mode, PT_ERR_STATE before scene and camera are set.  The pass never touches the accumulator,
+ * pt_samples_per_pixel, the pt_stats counters or the batch sizing of pt_render; its scratch queue (one sample of the owned pixels, 52 bytes
+ * each) is allocated at first use.  pt_clear zeroes the guides and their count with the image they describe; pt_set_camera does not
+ * (the caller decides, as for the accumulator). */
+#define PT_GUIDE_SKY_DEPTH 1e6f
+int pt_render_guides(pt_ctx* ctx, uint32_t spp); /* asynchronous, like pt_render */
+uint32_t pt_guide_samples(const pt_ctx* ctx);
+int pt_read_guides(pt_ctx* ctx, float* albedo_hits, float* normal_depth); /* host, width*height*4 floats each; either may be NULL */
+int pt_write_guides(pt_ctx* ctx, const float* albedo_hits, const float* normal_depth, uint32_t spp); /* checkpoint restore, mirrors pt_write_accum */
+void* pt_guides_device_ptr(pt_ctx* ctx, int which); /* 0 albedo_hits, 1 normal_depth; NULL before the first guide call */
+
+/* FILTER.  Per pixel  c = accum.rgb / spp,  a = albedo sum / gspp,  n = normal sum normalised (zero stays zero),  z = t sum / gspp.
+ * The filtered signal is the demodulated colour d0 = c / max(a, 1e-3), per component.  Iteration i = 0 .. iterations-1 uses step s = 2^i:
+ *   d_{i+1}(p) = sum_q k(q-p) w_i(p,q) d_i(q) / sum_q k(q-p) w_i(p,q),   q = p + s (dx, dy), dx, dy in [-2, 2], taps outside the image skipped,
+ *   k = outer product of (1/16, 1/4, 3/8, 1/4, 1/16)  (the 5 x 5 B3 spline),   w_i = exp(-(e_n + e_z + e_l)):
+ *   e_n = k_normal max(0, 1 - n(p).n(q))
+ *   e_z = |z(p) - z(q)| / (sigma_depth (min(z(p), z(q)) + 1e-6))
+ *   e_l = |L(d_i(p)) - L(d_i(q))| / (sigma_lum 2^-i (max(L(d_i(p)), L(d_i(q))) + 1e-3)),   L = Rec.709 luminance
+ * (the centre tap has weight k(0), so the denominator is at least 9/64).  Output: d_N max(a, 1e-3) as it is (PT_DENOISE_HDR: linear mean
+ * radiance, w = 1) or through exactly pt_resolve's exposure / Reinhard / sRGB arithmetic (PT_DENOISE_TONEMAPPED).  iterations == 0: no
+ * filtering and no demodulation -- the tone-mapped output IS pt_resolve's image, bit for bit.
+ * Refusals: PT_ERR_INVALID for iterations > 6; PT_ERR_UNSUPPORTED while tiles are set (a filter needs every pixel's neighbours: a multi-GPU
+ * caller denoises after its reduce, on a context that owns the frame); PT_ERR_STATE when pt_samples_per_pixel or pt_guide_samples is 0, and
+ * when the tone-mapped output is asked for before a camera was set.
+ * Defaults (a parameter of 0 selects them), chosen on the 64 x 64 Cornell box at 4 spp against 256 spp (tests/test_denoise_ref.py; the scan is in
+ * EXPERIMENTS.md).  e_l is a RELATIVE luminance difference, at most 1 / (sigma_lum 2^-i): an edge that only the colour shows -- a light against the
+ * ceiling it hangs from: same normal, same depth, albedo 1 against 0.73 -- is kept by a sigma_lum below 1 alone. */
+#define PT_DENOISE_DEFAULT_K_NORMAL 64.0f
+#define PT_DENOISE_DEFAULT_SIGMA_DEPTH 0.05f
+#define PT_DENOISE_DEFAULT_SIGMA_LUM 0.7f
+enum { PT_DENOISE_TONEMAPPED = 0, PT_DENOISE_HDR = 1 };
+typedef struct {
+    uint32_t iterations; /* 0..6; 0 = no filtering at all */
+    uint32_t output; /* PT_DENOISE_TONEMAPPED (as pt_resolve) | PT_DENOISE_HDR (linear mean radiance) */
+    float k_normal, sigma_depth, sigma_lum; /* 0 = the documented default */
+    uint32_t _reserved[3];
+} pt_denoise_params;
+/* host image out (width*height*4 floats); ms_out (optional): device ms of the filter's kernels (hipEvents), the copy to the host not included */
+int pt_denoise(pt_ctx* ctx, const pt_denoise_params* params, float* rgba_out, float* ms_out);
+/* the same, output left in DEVICE memory (width*height float4), asynchronous on the context's stream; NULL: the context-owned image
+ * pt_resolve_device_ptr returns (shared with pt_resolve_device) */
+int pt_denoise_device(pt_ctx* ctx, const pt_denoise_params* params, void* device_rgba);
+
 /* ---- kernel-granular entry points (parity tests and micro-benchmarks) ------------------
  * Host SoA arrays in, host SoA arrays out; the scene must have been uploaded. */
 typedef struct {

@@ -203,6 +203,17 @@ struct pt_ctx {
     uint32_t foldPlanes = 0; // extra accumulator planes written since the last fold (folded at the end of pt_render)
     bool queuesReady = false;
 
+    // first-hit guide buffers and the denoiser (pt_denoise.h): two width * height float4 sums over `guideSpp` guide samples, the scratch queue of the guide
+    // pass (one sample of the owned pixels; allocated at first use, whatever the render queues look like), the filter's two ping-pong images and its
+    // normalised guide image
+    DevBuf<float4> guideAlbedoHits, guideNormalDepth;
+    uint32_t guideSpp = 0;
+    DevBuf<float4> guideRayO, guideRayD, guideHit;
+    DevBuf<int32_t> guideHitInst;
+    DevBuf<Control> guideCtl;
+    DevBuf<float4> denoiseColour[2], denoiseGuide;
+    hipEvent_t evDenoise[2] = { nullptr, nullptr };
+
     double msLastRender = 0, msIntersect = 0, msShade = 0, msShadow = 0, msGen = 0, msPacket = 0;
 };
 

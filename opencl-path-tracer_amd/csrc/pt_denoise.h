@@ -1,0 +1,223 @@
+// First-hit guide buffers and the edge-avoiding a-trous wavelet denoiser (Dammertz et al. 2010) -- include/ptamd.h, "guides and denoiser"; DESIGN.md
+// section 9.  Nothing here is on the render path: the guides come from a pass of their own (camera rays into a scratch queue, the per-ray closest-hit
+// kernel over it, k_guides), the filter reads the accumulator and the guide sums and writes an image of its own.
+#pragma once
+#include "pt_shade.h"
+
+namespace ptd {
+
+constexpr float kGuideSkyDepth = 1e6f; // PT_GUIDE_SKY_DEPTH
+constexpr float kAlbedoFloor = 1e-3f; // demodulation divides by max(albedo, this)
+
+// ---- guide pass ---------------------------------------------------------------------------------
+// Camera rays of guide sample fp.sample for the first n owned pixels, one entry per pixel in the order of the pixel list -- the ray pt_render traces
+// for that sample index (primaryRay: same keying of the counter PRNG, pinhole and thin lens).  Thread 0 arms the scratch control block's pass 0.
+__global__ void __launch_bounds__(256) k_guide_gen(FrameParams fp, float4* __restrict__ qO, float4* __restrict__ qD, const uint32_t* __restrict__ pixelList,
+    uint32_t n, Control* __restrict__ ctl)
+{
+    const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k == 0u) {
+        ctl->extCount[0] = n;
+        ctl->extCursor[0] = 0u;
+    }
+    if (k >= n)
+        return;
+    const uint32_t pixel = pixelList ? pixelList[k] : k;
+    V3 o, d;
+    primaryRay(fp, pixel, 0u, &o, &d);
+    qO[k] = make_float4(o.x, o.y, o.z, asF(pixel));
+    qD[k] = make_float4(d.x, d.y, d.z, asF(packState(0u, 0u, 0u)));
+}
+
+// One thread owns one pixel: it adds the deposits of this sample's first hit to the pixel's two sums (plain read-modify-write: the launches of
+// consecutive samples are ordered on the stream, so a pixel's samples are summed in sample order and the sums are bit-reproducible).
+//   albedoHits  += (albedo.rgb, 1)   DIFFUSE: diffuseColour, or the texture fetch shadeHit makes (alpha-0 texel: 1,1,1); PBR: baseColour;
+//                                    REFRACTIVE / BASIC_REFRACTIVE / EMISSIVE: (1,1,1).  A miss: (1,1,1, 0).
+//   normalDepth += (N.xyz, t)        N: interpolated shading normal, to world space with the instance's normal transform, normalised, turned to face
+//                                    the ray.  A miss: (-D, PT_GUIDE_SKY_DEPTH).
+// A thin lens traces un-normalised directions (camera.cl:71-75): its deposits use D / |D| and t * |D|, so that normal and distance mean the same
+// for both cameras.
+__global__ void __launch_bounds__(256) k_guides(SceneDev sc, const float4* __restrict__ qO, const float4* __restrict__ qD, const float4* __restrict__ hit,
+    const int32_t* __restrict__ hitInst, uint32_t n, uint32_t thinLens, float4* __restrict__ albedoHits, float4* __restrict__ normalDepth)
+{
+    const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n)
+        return;
+    const uint32_t pixel = asU(qO[k].w);
+    const float4 rd = qD[k], h = hit[k];
+    V3 D = xyz(rd);
+    float scale = 1.0f;
+    if (thinLens) {
+        scale = sqrtf(dot(D, D));
+        D = D / scale;
+    }
+    const int32_t prim = (int32_t)asU(h.w);
+    V3 albedo = mk(1.0f), N = D * -1.0f;
+    float t = kGuideSkyDepth, hits = 0.0f;
+    if (prim >= 0) {
+        const TriFat* fp = &sc.triFat[prim];
+        const float4 f0 = fp->n0u, f1 = fp->n1u, f2 = fp->n2u, f3 = fp->vvvm, f6 = fp->v0c, f7 = fp->mat;
+        const float u = h.y, v = h.z;
+        const Instance in = sc.instances[hitInst[k]];
+        const V3 n0 = xyz(f0), n1 = xyz(f1), n2 = xyz(f2);
+        const V3 shadingNormal = normalize(n0 + (n1 - n0) * u + (n2 - n0) * v); // object space (shadeHit)
+        N = normalize(normalTransform(in, shadingNormal));
+        if (dot(N, D) > 0.0f)
+            N = N * -1.0f;
+        const MatView mat = loadMaterial(f6, f7);
+        if (mat.type == MAT_PBR) {
+            albedo = mat.colour;
+        } else if (mat.type == MAT_DIFFUSE) {
+            albedo = mat.colour;
+            if (mat.texId != -1) {
+                albedo = diffuseColourTextured(sc, mat, f0, f1, f2, f3, u, v);
+                if (albedo.x == -1.0f) // alpha-0 texel
+                    albedo = mk(1.0f);
+            }
+        }
+        t = h.x * scale;
+        hits = 1.0f;
+    }
+    float4 a = albedoHits[pixel], g = normalDepth[pixel];
+    a.x += albedo.x, a.y += albedo.y, a.z += albedo.z, a.w += hits;
+    g.x += N.x, g.y += N.y, g.z += N.z, g.w += t;
+    albedoHits[pixel] = a;
+    normalDepth[pixel] = g;
+}
+
+// ---- filter -------------------------------------------------------------------------------------
+__device__ inline float luminance709(float r, float g, float b) { return 0.2126f * r + 0.7152f * g + 0.0722f * b; }
+__device__ inline float albedoOf(float sum, float gspp) { return fmaxf(sum / gspp, kAlbedoFloor); }
+
+// mean, demodulation and guide normalisation in one pass over the three inputs:
+//   colour = (c / max(a, 1e-3), luminance of that)   c = accum.rgb / spp, a = albedo sum / gspp
+//   guide  = (n, z)                                   n = normal sum normalised (zero stays zero), z = distance sum / gspp
+// so that a tap of the filter costs two 16-byte loads.
+__global__ void __launch_bounds__(256) k_denoise_prepare(const float4* __restrict__ accum, const float4* __restrict__ albedoHits,
+    const float4* __restrict__ normalDepth, float4* __restrict__ colour, float4* __restrict__ guide, uint32_t n, float spp, float gspp)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n)
+        return;
+    const float4 s = accum[i], a = albedoHits[i], g = normalDepth[i];
+    const float r = s.x / spp / albedoOf(a.x, gspp), gr = s.y / spp / albedoOf(a.y, gspp), b = s.z / spp / albedoOf(a.z, gspp);
+    colour[i] = make_float4(r, gr, b, luminance709(r, gr, b));
+    const float len = sqrtf(g.x * g.x + g.y * g.y + g.z * g.z);
+    const float inv = len > 0.0f ? 1.0f / len : 0.0f;
+    guide[i] = make_float4(g.x * inv, g.y * inv, g.z * inv, g.w / gspp);
+}
+
+// iterations == 0, linear output: the mean radiance as it is
+__global__ void __launch_bounds__(256) k_denoise_mean(const float4* __restrict__ accum, float4* __restrict__ out, uint32_t n, float spp)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n)
+        return;
+    const float4 s = accum[i];
+    out[i] = make_float4(s.x / spp, s.y / spp, s.z / spp, 1.0f);
+}
+
+enum : uint32_t { ATROUS_MORE = 0, ATROUS_LAST_HDR = 1, ATROUS_LAST_TONEMAPPED = 2 };
+struct AtrousArgs {
+    const float4* colour; // d_i.rgb, luminance
+    const float4* guide; // n.xyz, z
+    float4* out; // d_{i+1} in the same form, or the final image
+    const float4* albedoHits; // last iteration: re-modulation
+    uint32_t width, height;
+    int32_t step; // 2^i
+    float kNormal, invSigmaDepth, invSigmaLum; // invSigmaLum = 1 / (sigma_lum * 2^-i)
+    uint32_t mode; // ATROUS_*
+    float gspp;
+    float relativeAperture, shutterTime, ISO; // ATROUS_LAST_TONEMAPPED
+};
+
+constexpr int kAtrousTileW = 32, kAtrousTileH = 8; // 256 threads; a wave is two rows of 32 pixels
+constexpr int kAtrousMaxHalo = 4; // 2 * step for the steps staged in LDS (1 and 2)
+constexpr int kAtrousLdsW = kAtrousTileW + 2 * kAtrousMaxHalo, kAtrousLdsH = kAtrousTileH + 2 * kAtrousMaxHalo;
+
+// One iteration: d_{i+1}(p) = sum_q k(q - p) w_i(p, q) d_i(q) / sum_q k w_i over the 5 x 5 taps q = p + step * (dx, dy) inside the image, k the outer
+// product of (1/16, 1/4, 3/8, 1/4, 1/16), w_i = exp(-(e_n + e_z + e_l)) -- one exp per tap (include/ptamd.h has the three terms).
+// STEP_IN_LDS (steps 1 and 2): the tile and its halo of 2 * step pixels are staged in LDS, both images as float4.  Every tap is two 16-byte LDS reads
+// (ds_read_b128) at [row][x + const]: the 16 lanes such a read serves together (MI355X_MICROARCH.md, LDS: {0-3, 12-15, 20-27} and its three
+// translates) lie in ONE row of 32 consecutive float4, i.e. on 16 different 16-byte slots of the 256-byte bank row whatever the pitch -- no conflicts,
+// no padding.  Steps >= 4 would need a halo larger than the tile: their taps are global loads (strided gathers over two images of 15-33 MB, served
+// by L2 / the memory-side cache).
+template <bool STEP_IN_LDS>
+__global__ void __launch_bounds__(256) k_atrous(AtrousArgs a)
+{
+    const int tx = threadIdx.x, ty = threadIdx.y;
+    const int x = blockIdx.x * kAtrousTileW + tx, y = blockIdx.y * kAtrousTileH + ty;
+    const int W = (int)a.width, H = (int)a.height;
+    __shared__ float4 ldsC[STEP_IN_LDS ? kAtrousLdsH * kAtrousLdsW : 1];
+    __shared__ float4 ldsG[STEP_IN_LDS ? kAtrousLdsH * kAtrousLdsW : 1];
+    const int halo = 2 * a.step, pitch = kAtrousTileW + 2 * halo;
+    if constexpr (STEP_IN_LDS) {
+        const int rows = kAtrousTileH + 2 * halo, x0 = (int)blockIdx.x * kAtrousTileW - halo, y0 = (int)blockIdx.y * kAtrousTileH - halo;
+        for (int e = ty * kAtrousTileW + tx; e < rows * pitch; e += kAtrousTileW * kAtrousTileH) {
+            const int ly = e / pitch, lx = e - ly * pitch;
+            const int gx = x0 + lx, gy = y0 + ly;
+            float4 c = make_float4(0.f, 0.f, 0.f, 0.f), g = c; // outside the image: never read (the tap loop skips those)
+            if (gx >= 0 && gx < W && gy >= 0 && gy < H) {
+                c = a.colour[(size_t)gy * W + gx];
+                g = a.guide[(size_t)gy * W + gx];
+            }
+            ldsC[e] = c;
+            ldsG[e] = g;
+        }
+        __syncthreads();
+    }
+    if (x >= W || y >= H)
+        return;
+    const size_t p = (size_t)y * W + x;
+    float4 cp, gp;
+    if constexpr (STEP_IN_LDS) {
+        cp = ldsC[(ty + halo) * pitch + tx + halo];
+        gp = ldsG[(ty + halo) * pitch + tx + halo];
+    } else {
+        cp = a.colour[p];
+        gp = a.guide[p];
+    }
+    const float kern[5] = { 1.0f / 16.0f, 1.0f / 4.0f, 3.0f / 8.0f, 1.0f / 4.0f, 1.0f / 16.0f };
+    float sr = 0.f, sg = 0.f, sb = 0.f, sw = 0.f;
+#pragma unroll
+    for (int dy = -2; dy <= 2; dy++) {
+        const int qy = y + dy * a.step;
+        if (qy < 0 || qy >= H)
+            continue;
+#pragma unroll
+        for (int dx = -2; dx <= 2; dx++) {
+            const int qx = x + dx * a.step;
+            if (qx < 0 || qx >= W)
+                continue;
+            float4 cq, gq;
+            if constexpr (STEP_IN_LDS) {
+                const int e = (ty + halo + dy * a.step) * pitch + tx + halo + dx * a.step;
+                cq = ldsC[e];
+                gq = ldsG[e];
+            } else {
+                cq = a.colour[(size_t)qy * W + qx];
+                gq = a.guide[(size_t)qy * W + qx];
+            }
+            const float en = a.kNormal * fmaxf(0.0f, 1.0f - (gp.x * gq.x + gp.y * gq.y + gp.z * gq.z));
+            const float ez = fabsf(gp.w - gq.w) * a.invSigmaDepth / (fminf(gp.w, gq.w) + 1e-6f);
+            const float el = fabsf(cp.w - cq.w) * a.invSigmaLum / (fmaxf(cp.w, cq.w) + 1e-3f);
+            const float w = kern[dy + 2] * kern[dx + 2] * __expf(-(en + ez + el));
+            sr += w * cq.x, sg += w * cq.y, sb += w * cq.z, sw += w;
+        }
+    }
+    // (the centre tap has w = k(0): sw >= 9/64)
+    float r = sr / sw, g = sg / sw, b = sb / sw;
+    if (a.mode == ATROUS_MORE) {
+        a.out[p] = make_float4(r, g, b, luminance709(r, g, b));
+        return;
+    }
+    const float4 al = a.albedoHits[p];
+    r *= albedoOf(al.x, a.gspp), g *= albedoOf(al.y, a.gspp), b *= albedoOf(al.z, a.gspp);
+    if (a.mode == ATROUS_LAST_TONEMAPPED) {
+        const float exposure = resolveExposure(a.relativeAperture, a.shutterTime, a.ISO);
+        r = resolveChannel(r * exposure), g = resolveChannel(g * exposure), b = resolveChannel(b * exposure);
+    }
+    a.out[p] = make_float4(r, g, b, 1.0f);
+}
+
+} // namespace ptd

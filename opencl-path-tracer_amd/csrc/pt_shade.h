@@ -1039,20 +1039,29 @@ __global__ void __launch_bounds__(1024) k_compact_stable(CompactArgs a)
 
 // accumulate, accumulate.cl:6-34: mean -> exposure (exposure.cl:7-41) -> Reinhard (tonemapping.cl:7-10)
 // -> sRGB (gamma.cl:4-13)
+// The two halves of that arithmetic, shared with the denoiser's last iteration (pt_denoise.h): the exposure scale of the camera, and Reinhard + sRGB of
+// one exposed channel.
+__device__ inline float resolveExposure(float relativeAperture, float shutterTime, float ISO)
+{
+    const float EV100 = log2f(relativeAperture * relativeAperture / shutterTime * 100 / ISO);
+    return 1.0f / (1.2f * powf(2.0f, EV100));
+}
+__device__ inline float resolveChannel(float exposed)
+{
+    const float col = exposed / (1.0f + exposed);
+    return (col <= 0.0031308f) ? col * 12.92f : (powf(fabsf(col), 1.0f / 2.4f) * 1.055f) - 0.055f;
+}
 __global__ void __launch_bounds__(256) k_resolve(const float4* __restrict__ accum, float4* __restrict__ out, uint32_t n, float spp,
     float relativeAperture, float shutterTime, float ISO)
 {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n)
         return;
-    const float EV100 = log2f(relativeAperture * relativeAperture / shutterTime * 100 / ISO);
-    const float exposure = 1.0f / (1.2f * powf(2.0f, EV100));
+    const float exposure = resolveExposure(relativeAperture, shutterTime, ISO);
     const float4 s = accum[i];
     float c[3] = { s.x / spp * exposure, s.y / spp * exposure, s.z / spp * exposure };
-    for (int k = 0; k < 3; k++) {
-        const float col = c[k] / (1.0f + c[k]);
-        c[k] = (col <= 0.0031308f) ? col * 12.92f : (powf(fabsf(col), 1.0f / 2.4f) * 1.055f) - 0.055f;
-    }
+    for (int k = 0; k < 3; k++)
+        c[k] = resolveChannel(c[k]);
     out[i] = make_float4(c[0], c[1], c[2], 1.0f);
 }
 

@@ -8,6 +8,7 @@
 #include "pt_packet_multi.h"
 #include "pt_bake.h"
 #include "pt_team.h"
+#include "pt_denoise.h"
 #ifndef PT_PACK_WIDE
 #define PT_PACK_WIDE 1
 #endif
@@ -463,6 +464,10 @@ void pt_destroy(pt_ctx* c)
     }
     if (c->copyStream) (void)hipStreamDestroy(c->copyStream);
     c->pixelList.release(), c->hitInst.release();
+    c->guideAlbedoHits.release(), c->guideNormalDepth.release(), c->guideRayO.release(), c->guideRayD.release(), c->guideHit.release(), c->guideHitInst.release();
+    c->guideCtl.release(), c->denoiseColour[0].release(), c->denoiseColour[1].release(), c->denoiseGuide.release();
+    for (hipEvent_t ev : c->evDenoise)
+        if (ev) (void)hipEventDestroy(ev);
     c->accumPlanes.release(), c->pixelOrdinal.release(), c->resolveTmp.release(), c->activeFlag.release(), c->streams.release(), c->control.release(), c->totals.release(), c->spill.release();
     for (hipEvent_t ev : c->profEvents)
         (void)hipEventDestroy(ev);
@@ -1028,6 +1033,11 @@ int pt_clear(pt_ctx* c)
         HIPCHK(c, hipMemsetAsync(c->accumPlanes.p, 0, c->accumPlanes.n * sizeof(float4), c->stream));
     c->foldPlanes = 0;
     c->spp = 0;
+    if (c->guideAlbedoHits.p) { // the guide sums belong to the image they describe
+        HIPCHK(c, hipMemsetAsync(c->guideAlbedoHits.p, 0, c->guideAlbedoHits.n * sizeof(float4), c->stream));
+        HIPCHK(c, hipMemsetAsync(c->guideNormalDepth.p, 0, c->guideNormalDepth.n * sizeof(float4), c->stream));
+    }
+    c->guideSpp = 0;
     if (c->overflowPinned && *c->overflowPinned) { // a reported overflow is cleared with the image it spoiled (whatever set it has run: the word is only read after a synchronisation)
         HIPCHK(c, hipStreamSynchronize(c->stream));
         *c->overflowPinned = 0u;
@@ -1205,6 +1215,211 @@ int pt_write_accum(pt_ctx* c, const float* in, uint32_t spp)
 void* pt_accum_device_ptr(pt_ctx* c) { return c ? (void*)c->accum : nullptr; }
 
 uint32_t pt_samples_per_pixel(const pt_ctx* c) { return c ? c->spp : 0; }
+
+// ---- first-hit guide buffers and the denoiser (pt_denoise.h) -----------------------------------
+
+namespace {
+
+// the two guide sums: allocated (zeroed) at first use
+int ensureGuides(pt_ctx* c)
+{
+    const size_t n = (size_t)c->cfg.width * c->cfg.height;
+    if (c->guideAlbedoHits.p)
+        return PT_OK;
+    HIPCHK(c, c->guideAlbedoHits.alloc(n));
+    HIPCHK(c, c->guideNormalDepth.alloc(n));
+    HIPCHK(c, hipMemsetAsync(c->guideAlbedoHits.p, 0, n * sizeof(float4), c->stream));
+    HIPCHK(c, hipMemsetAsync(c->guideNormalDepth.p, 0, n * sizeof(float4), c->stream));
+    return PT_OK;
+}
+
+bool tilesSet(const pt_ctx* c) { return (uint64_t)c->numOwned != (uint64_t)c->cfg.width * c->cfg.height; }
+
+} // namespace
+
+int pt_render_guides(pt_ctx* c, uint32_t spp)
+{
+    return guarded(c, "pt_render_guides", [&]() -> int {
+    if (!c)
+        return PT_ERR_INVALID;
+    if (!c->haveStatic || !c->haveDynamic || !c->haveCamera)
+        return fail(c, PT_ERR_STATE, "pt_render_guides: scene (static + dynamic) and camera must be set first");
+    if (parityMode(c) || c->cfg.max_active_rays != 0)
+        return fail(c, PT_ERR_UNSUPPORTED, "pt_render_guides: the fixed schedule with PT_RNG_COUNTER only (not in parity / refill mode)");
+    HIPCHK(c, hipSetDevice(c->device));
+    int rc;
+    if ((rc = ensureSpill(c)) || (rc = ensureGuides(c)))
+        return rc;
+    const uint32_t n = c->numOwned;
+    if (c->guideRayO.n < n) { // a scratch queue of its own: one sample of the owned pixels (the render queues may be smaller than that, or hold directions only)
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        HIPCHK(c, c->guideRayO.alloc(n));
+        HIPCHK(c, c->guideRayD.alloc(n));
+        HIPCHK(c, c->guideHit.alloc(n));
+        HIPCHK(c, c->guideHitInst.alloc(n));
+    }
+    if (!c->guideCtl.p) {
+        HIPCHK(c, c->guideCtl.alloc(1));
+        HIPCHK(c, hipMemsetAsync(c->guideCtl.p, 0, sizeof(Control), c->stream));
+    }
+    // always the per-ray kernel: which kernel traces a launch must not depend on what the last render left in the context (the team kernel is chosen
+    // by the previous batch's counters), and the launch is none of pt_stats' business
+    const uint32_t batchEntries = c->batchEntries;
+    const uint64_t teamLaunches = c->teamLaunches;
+    c->batchEntries = 0;
+    for (uint32_t s = 0; s < spp; s++) {
+        const FrameParams fp = frameParams(c, c->guideSpp + s);
+        hipLaunchKernelGGL(k_guide_gen, dim3((n + 255u) / 256u), dim3(256), 0, c->stream, fp, c->guideRayO.p, c->guideRayD.p,
+            c->identityPixels ? nullptr : c->pixelList.p, n, c->guideCtl.p);
+        TraceArgs a = traceArgsBase(c);
+        a.parityShadow = 0;
+        a.rayO = c->guideRayO.p, a.rayD = c->guideRayD.p, a.rayC = nullptr;
+        a.hit = c->guideHit.p, a.inst = c->guideHitInst.p, a.accum = AccumView { nullptr, nullptr, nullptr, 0u }, a.occluded = nullptr;
+        a.ctl = c->guideCtl.p, a.pass = 0;
+        launchTrace(c, false, a);
+        hipLaunchKernelGGL(k_guides, dim3((n + 255u) / 256u), dim3(256), 0, c->stream, c->scene, c->guideRayO.p, c->guideRayD.p, c->guideHit.p,
+            c->guideHitInst.p, n, c->camera.thinLens, c->guideAlbedoHits.p, c->guideNormalDepth.p);
+    }
+    c->batchEntries = batchEntries;
+    c->teamLaunches = teamLaunches;
+    HIPCHK(c, hipGetLastError());
+    c->guideSpp += spp;
+    return PT_OK;
+    });
+}
+
+uint32_t pt_guide_samples(const pt_ctx* c) { return c ? c->guideSpp : 0; }
+
+int pt_read_guides(pt_ctx* c, float* albedo_hits, float* normal_depth)
+{
+    if (!c)
+        return PT_ERR_INVALID;
+    HIPCHK(c, hipSetDevice(c->device));
+    int rc = ensureGuides(c);
+    if (rc)
+        return rc;
+    const size_t bytes = (size_t)c->cfg.width * c->cfg.height * sizeof(float4);
+    if (albedo_hits)
+        HIPCHK(c, hipMemcpyAsync(albedo_hits, c->guideAlbedoHits.p, bytes, hipMemcpyDeviceToHost, c->stream));
+    if (normal_depth)
+        HIPCHK(c, hipMemcpyAsync(normal_depth, c->guideNormalDepth.p, bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return PT_OK;
+}
+
+int pt_write_guides(pt_ctx* c, const float* albedo_hits, const float* normal_depth, uint32_t spp)
+{
+    if (!c || !albedo_hits || !normal_depth)
+        return PT_ERR_INVALID;
+    HIPCHK(c, hipSetDevice(c->device));
+    int rc = ensureGuides(c);
+    if (rc)
+        return rc;
+    const size_t bytes = (size_t)c->cfg.width * c->cfg.height * sizeof(float4);
+    HIPCHK(c, hipMemcpyAsync(c->guideAlbedoHits.p, albedo_hits, bytes, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->guideNormalDepth.p, normal_depth, bytes, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->guideSpp = spp;
+    return PT_OK;
+}
+
+void* pt_guides_device_ptr(pt_ctx* c, int which)
+{
+    if (!c || which < 0 || which > 1)
+        return nullptr;
+    return which == 0 ? (void*)c->guideAlbedoHits.p : (void*)c->guideNormalDepth.p;
+}
+
+int pt_denoise_device(pt_ctx* c, const pt_denoise_params* prm, void* device_rgba)
+{
+    return guarded(c, "pt_denoise_device", [&]() -> int {
+    if (!c || !prm)
+        return PT_ERR_INVALID;
+    if (prm->iterations > 6u)
+        return fail(c, PT_ERR_INVALID, "pt_denoise: iterations = %u (0..6)", prm->iterations);
+    if (prm->output != PT_DENOISE_TONEMAPPED && prm->output != PT_DENOISE_HDR)
+        return fail(c, PT_ERR_INVALID, "pt_denoise: output = %u (PT_DENOISE_TONEMAPPED or PT_DENOISE_HDR)", prm->output);
+    if (prm->k_normal < 0.f || prm->sigma_depth < 0.f || prm->sigma_lum < 0.f)
+        return fail(c, PT_ERR_INVALID, "pt_denoise: negative filter parameter");
+    if (tilesSet(c))
+        return fail(c, PT_ERR_UNSUPPORTED, "pt_denoise: tiles are set -- the filter needs every pixel's neighbours; denoise after the reduce, on a context that owns the frame");
+    if (c->spp == 0)
+        return fail(c, PT_ERR_STATE, "pt_denoise: no colour samples yet (pt_render)");
+    if (c->guideSpp == 0)
+        return fail(c, PT_ERR_STATE, "pt_denoise: no guide samples yet (pt_render_guides)");
+    const bool tonemapped = prm->output == PT_DENOISE_TONEMAPPED;
+    if (tonemapped && !c->haveCamera)
+        return fail(c, PT_ERR_STATE, "pt_denoise: the tone-mapped output needs the camera's exposure (pt_set_camera)");
+    HIPCHK(c, hipSetDevice(c->device));
+    const uint32_t W = c->cfg.width, H = c->cfg.height, n = W * H;
+    if (!device_rgba) { // the context's own image (pt_resolve_device_ptr)
+        if (c->resolveTmp.n != n)
+            HIPCHK(c, c->resolveTmp.alloc(n));
+        device_rgba = c->resolveTmp.p;
+    }
+    const dim3 lin((n + 255u) / 256u);
+    if (prm->iterations == 0u) { // no filtering, no demodulation: pt_resolve's image, or the mean
+        if (tonemapped)
+            hipLaunchKernelGGL(k_resolve, lin, dim3(256), 0, c->stream, c->accum, (float4*)device_rgba, n, (float)c->spp, c->camera.relativeAperture,
+                c->camera.shutterTime, c->camera.ISO);
+        else
+            hipLaunchKernelGGL(k_denoise_mean, lin, dim3(256), 0, c->stream, c->accum, (float4*)device_rgba, n, (float)c->spp);
+        HIPCHK(c, hipGetLastError());
+        return PT_OK;
+    }
+    if (c->denoiseGuide.n != n) {
+        HIPCHK(c, c->denoiseColour[0].alloc(n));
+        HIPCHK(c, c->denoiseColour[1].alloc(n));
+        HIPCHK(c, c->denoiseGuide.alloc(n));
+    }
+    hipLaunchKernelGGL(k_denoise_prepare, lin, dim3(256), 0, c->stream, c->accum, c->guideAlbedoHits.p, c->guideNormalDepth.p, c->denoiseColour[0].p,
+        c->denoiseGuide.p, n, (float)c->spp, (float)c->guideSpp);
+    AtrousArgs a {};
+    a.guide = c->denoiseGuide.p;
+    a.albedoHits = c->guideAlbedoHits.p;
+    a.width = W, a.height = H;
+    a.kNormal = prm->k_normal > 0.f ? prm->k_normal : PT_DENOISE_DEFAULT_K_NORMAL;
+    a.invSigmaDepth = 1.0f / (prm->sigma_depth > 0.f ? prm->sigma_depth : PT_DENOISE_DEFAULT_SIGMA_DEPTH);
+    const float sigmaLum = prm->sigma_lum > 0.f ? prm->sigma_lum : PT_DENOISE_DEFAULT_SIGMA_LUM;
+    a.gspp = (float)c->guideSpp;
+    a.relativeAperture = c->camera.relativeAperture, a.shutterTime = c->camera.shutterTime, a.ISO = c->camera.ISO;
+    const dim3 grid((W + kAtrousTileW - 1) / kAtrousTileW, (H + kAtrousTileH - 1) / kAtrousTileH), block(kAtrousTileW, kAtrousTileH);
+    for (uint32_t i = 0; i < prm->iterations; i++) {
+        const bool last = i + 1u == prm->iterations;
+        a.colour = c->denoiseColour[i & 1u].p;
+        a.out = last ? (float4*)device_rgba : c->denoiseColour[(i + 1u) & 1u].p;
+        a.step = 1 << i;
+        a.invSigmaLum = 1.0f / (sigmaLum * std::ldexp(1.0f, -(int)i));
+        a.mode = !last ? ATROUS_MORE : (tonemapped ? ATROUS_LAST_TONEMAPPED : ATROUS_LAST_HDR);
+        if (2 * a.step <= kAtrousMaxHalo)
+            hipLaunchKernelGGL(k_atrous<true>, grid, block, 0, c->stream, a);
+        else
+            hipLaunchKernelGGL(k_atrous<false>, grid, block, 0, c->stream, a);
+    }
+    HIPCHK(c, hipGetLastError());
+    return PT_OK;
+    });
+}
+
+int pt_denoise(pt_ctx* c, const pt_denoise_params* prm, float* rgba_out, float* ms_out)
+{
+    if (!c || !prm || !rgba_out)
+        return PT_ERR_INVALID;
+    HIPCHK(c, hipSetDevice(c->device));
+    for (hipEvent_t& ev : c->evDenoise)
+        if (!ev)
+            HIPCHK(c, hipEventCreate(&ev));
+    HIPCHK(c, hipEventRecord(c->evDenoise[0], c->stream));
+    int rc = pt_denoise_device(c, prm, nullptr);
+    if (rc)
+        return rc;
+    HIPCHK(c, hipEventRecord(c->evDenoise[1], c->stream));
+    HIPCHK(c, hipMemcpyAsync(rgba_out, c->resolveTmp.p, (size_t)c->cfg.width * c->cfg.height * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (ms_out)
+        HIPCHK(c, hipEventElapsedTime(ms_out, c->evDenoise[0], c->evDenoise[1]));
+    return checkOverflow(c);
+}
 
 int pt_stats_get(pt_ctx* c, pt_stats* out)
 {

@@ -145,6 +145,35 @@ std::vector<float> RayTracer::getAccumulator()
     return out;
 }
 
+void RayTracer::renderMissingGuides()
+{
+    const uint32_t want = pt_samples_per_pixel(m_ctx), have = pt_guide_samples(m_ctx);
+    if (have < want)
+        check(pt_render_guides(m_ctx, want - have), "pt_render_guides");
+}
+
+std::vector<float> RayTracer::getDenoisedOutput(int iterations)
+{
+    renderMissingGuides();
+    pt_denoise_params prm {};
+    prm.iterations = (uint32_t)iterations;
+    prm.output = PT_DENOISE_TONEMAPPED;
+    std::vector<float> out((size_t)m_width * m_height * 4);
+    check(pt_denoise(m_ctx, &prm, out.data(), nullptr), "pt_denoise");
+    return out;
+}
+
+RayTracer::Guides RayTracer::getGuides()
+{
+    renderMissingGuides();
+    Guides g;
+    g.albedoHits.resize((size_t)m_width * m_height * 4);
+    g.normalDepth.resize((size_t)m_width * m_height * 4);
+    check(pt_read_guides(m_ctx, g.albedoHits.data(), g.normalDepth.data()), "pt_read_guides");
+    g.samples = (int)pt_guide_samples(m_ctx);
+    return g;
+}
+
 pt_stats RayTracer::getStats()
 {
     pt_stats s;

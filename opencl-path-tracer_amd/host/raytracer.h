@@ -86,11 +86,20 @@ public:
 
     std::vector<float> getOutput(); // width*height RGBA in [0,1]: the `accumulate` kernel's image
     std::vector<float> getAccumulator(); // width*height float4 HDR sums
+    // the image of getOutput() through the edge-avoiding a-trous filter (include/ptamd.h, "guides and denoiser"): renders as many guide samples as are
+    // missing to match getSamplesPerPixel(), then filters `iterations` times (0..6; 0: getOutput())
+    std::vector<float> getDenoisedOutput(int iterations = 5);
+    struct Guides {
+        std::vector<float> albedoHits, normalDepth; // width*height float4 sums over `samples` guide samples
+        int samples = 0;
+    };
+    Guides getGuides(); // what the filter is guided by (rendered up to getSamplesPerPixel() like getDenoisedOutput does)
     pt_stats getStats();
     pt_ctx* context() { return m_ctx; }
 
 private:
     void check(int rc, const char* what);
+    void renderMissingGuides();
     void upload(const TextureArray& materialTextures, const TextureArray& skydomeTextures); // constructor body proper
     pt_ctx* m_ctx = nullptr;
     std::shared_ptr<Scene> m_scene;

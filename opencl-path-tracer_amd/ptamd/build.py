@@ -122,6 +122,10 @@ def build_raytracer(force=False):
     if force or _newer(exe4, [os.path.join(ex_dir, "rebuild_loop.cpp"), out]):
         subprocess.run(["g++", "-std=c++17", "-O2", "-Wall", "rebuild_loop.cpp", "-o", "rebuild_loop", "-L" + HOST_DIR, "-lptamd_raytracer",
                         "-lptamd_host", "-L" + CSRC_DIR, "-lptamd", "-Wl,-rpath," + HOST_DIR, "-Wl,-rpath," + CSRC_DIR], cwd=ex_dir, check=True)
+    exe5 = os.path.join(ex_dir, "denoise_cornell")
+    if force or _newer(exe5, [os.path.join(ex_dir, "denoise_cornell.cpp"), out]):
+        subprocess.run(["g++", "-std=c++17", "-O2", "-Wall", "denoise_cornell.cpp", "-o", "denoise_cornell", "-L" + HOST_DIR, "-lptamd_raytracer",
+                        "-lptamd_host", "-L" + CSRC_DIR, "-lptamd", "-Wl,-rpath," + HOST_DIR, "-Wl,-rpath," + CSRC_DIR], cwd=ex_dir, check=True)
     return out, exe
 
 

@@ -62,11 +62,22 @@ class ShadeBatchIO(C.Structure):
                                              "soz", "sdx", "sdy", "sdz", "slen", "sc_r", "sc_g", "sc_b")])
 
 
+DENOISE_TONEMAPPED, DENOISE_HDR = 0, 1
+GUIDE_SKY_DEPTH = 1e6
+
+
+class DenoiseParams(C.Structure):
+    """pt_denoise_params (32 bytes); a filter parameter of 0 selects the default documented in include/ptamd.h"""
+    _fields_ = [("iterations", C.c_uint32), ("output", C.c_uint32), ("k_normal", C.c_float), ("sigma_depth", C.c_float),
+                ("sigma_lum", C.c_float), ("_reserved", C.c_uint32 * 3)]
+
+
 EXPORTS = ["pt_create", "pt_destroy", "pt_last_error", "pt_set_stream", "pt_upload_static", "pt_upload_static_async", "pt_upload_dynamic",
            "pt_upload_dynamic_async", "pt_frame_tick", "pt_update_geometry", "pt_refit_vertices",
            "pt_upload_texture_array", "pt_set_camera", "pt_set_tiles", "pt_set_accum_buffer", "pt_clear", "pt_render",
            "pt_synchronize", "pt_resolve", "pt_resolve_device", "pt_resolve_device_ptr", "pt_read_accum", "pt_write_accum", "pt_accum_device_ptr",
-           "pt_samples_per_pixel", "pt_stats_get", "pt_stats_reset", "pt_profile_kernels", "pt_reduce_accum",
+           "pt_samples_per_pixel", "pt_render_guides", "pt_guide_samples", "pt_read_guides", "pt_write_guides", "pt_guides_device_ptr",
+           "pt_denoise", "pt_denoise_device", "pt_stats_get", "pt_stats_reset", "pt_profile_kernels", "pt_reduce_accum",
            "pt_intersect", "pt_gen_rays", "pt_primary_pass", "pt_shade_batch", "pt_debug_quantise_node", "pt_debug_convert", "pt_debug_copy_bandwidth", "pt_version"]
 
 _lib = None
@@ -116,6 +127,15 @@ def lib():
         l.pt_accum_device_ptr.argtypes = [C.c_void_p]
         l.pt_samples_per_pixel.restype = C.c_uint32
         l.pt_samples_per_pixel.argtypes = [C.c_void_p]
+        l.pt_render_guides.argtypes = [C.c_void_p, C.c_uint32]
+        l.pt_guide_samples.restype = C.c_uint32
+        l.pt_guide_samples.argtypes = [C.c_void_p]
+        l.pt_read_guides.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        l.pt_write_guides.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]
+        l.pt_guides_device_ptr.restype = C.c_void_p
+        l.pt_guides_device_ptr.argtypes = [C.c_void_p, C.c_int]
+        l.pt_denoise.argtypes = [C.c_void_p, C.POINTER(DenoiseParams), C.c_void_p, C.POINTER(C.c_float)]
+        l.pt_denoise_device.argtypes = [C.c_void_p, C.POINTER(DenoiseParams), C.c_void_p]
         l.pt_stats_get.argtypes = [C.c_void_p, C.POINTER(Stats)]
         l.pt_stats_reset.argtypes = [C.c_void_p]
         l.pt_profile_kernels.argtypes = [C.c_void_p, C.c_int]
@@ -293,6 +313,48 @@ class Context:
     @property
     def accum_device_ptr(self):
         return lib().pt_accum_device_ptr(self._h)
+
+    # ---- first-hit guide buffers and the a-trous denoiser
+    def render_guides(self, spp=1, sync=True):
+        """`spp` more guide samples (albedo, world-space normal, hit distance, coverage of the camera rays' first hits)."""
+        self._chk(lib().pt_render_guides(self._h, spp), "pt_render_guides")
+        if sync:
+            self.synchronize()
+
+    @property
+    def guide_samples(self):
+        return int(lib().pt_guide_samples(self._h))
+
+    def read_guides(self):
+        """(albedo_hits, normal_depth): two (width*height, 4) arrays of sums over the guide samples"""
+        a = np.zeros((self.height * self.width, 4), np.float32)
+        g = np.zeros((self.height * self.width, 4), np.float32)
+        self._chk(lib().pt_read_guides(self._h, _p(a), _p(g)), "pt_read_guides")
+        return a, g
+
+    def write_guides(self, albedo_hits, normal_depth, spp):
+        a = np.ascontiguousarray(albedo_hits, np.float32)
+        g = np.ascontiguousarray(normal_depth, np.float32)
+        assert a.size == g.size == self.width * self.height * 4
+        self._chk(lib().pt_write_guides(self._h, _p(a), _p(g), spp), "pt_write_guides")
+
+    def guides_device_ptr(self, which):
+        """Device address of the albedo_hits (0) / normal_depth (1) image (0 before the first guide call)."""
+        return lib().pt_guides_device_ptr(self._h, which) or 0
+
+    def denoise(self, iterations=5, hdr=False, k_normal=0.0, sigma_depth=0.0, sigma_lum=0.0, with_ms=False):
+        """The edge-avoiding a-trous filter over the accumulator under the guides: (height, width, 4) tone-mapped like resolve(), or linear
+        mean radiance (hdr=True); with_ms: also the device ms of the filter's kernels."""
+        prm = DenoiseParams(iterations, DENOISE_HDR if hdr else DENOISE_TONEMAPPED, k_normal, sigma_depth, sigma_lum)
+        out = np.zeros((self.height, self.width, 4), np.float32)
+        ms = C.c_float(0)
+        self._chk(lib().pt_denoise(self._h, C.byref(prm), _p(out), C.byref(ms)), "pt_denoise")
+        return (out, float(ms.value)) if with_ms else out
+
+    def denoise_device(self, iterations=5, hdr=False, k_normal=0.0, sigma_depth=0.0, sigma_lum=0.0, device_ptr=None):
+        """The same into device memory (None: the context-owned image, resolve_device_ptr); asynchronous."""
+        prm = DenoiseParams(iterations, DENOISE_HDR if hdr else DENOISE_TONEMAPPED, k_normal, sigma_depth, sigma_lum)
+        self._chk(lib().pt_denoise_device(self._h, C.byref(prm), C.c_void_p(device_ptr) if device_ptr else None), "pt_denoise_device")
 
     def stats(self):
         s = Stats()
