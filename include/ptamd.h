@@ -410,6 +410,10 @@ int pt_shade_batch(pt_ctx* ctx, pt_shade_batch_io* io);
 /* Diagnostic (bench.py, roofline.peak_measured_copy): GB/s, read + written, of a float4 grid-stride device copy of `bytes` bytes -- what the HBM of the box at hand delivers
  * to the access shape MI355X_MICROARCH.md measures 6.29 TB/s with (the reference has no counterpart). */
 int pt_debug_copy_bandwidth(pt_ctx* ctx, size_t bytes, uint32_t repeat, float* gbps_out);
+/* Test hook: the contract of the shading kernel's division / square-root helpers (csrc/pt_math.h), evaluated on the device for n pairs (a[i], b[i]).  `out`
+ * receives ten planes of n floats: a / b, fastDiv(a, b), sqrtf(|a|), fastSqrt(|a|), normalize((a, b, a + b)).xyz, fastNormalize((a, b, a + b)).xyz -- the
+ * plain forms as the library's build compiles them. */
+int pt_debug_math_probe(pt_ctx* ctx, const float* a, const float* b, uint32_t n, float* out);
 int pt_debug_quantise_node(const float* lo12, const float* hi12, const uint32_t* refs4, const uint8_t* empty4, uint32_t empty_ref, void* out64);
 /* test hook, no device needed: what pt_upload_static (records made on the host) and -- given a top level (n_top > 0) -- pt_upload_dynamic make of these
  * arrays under cfg's flags and RNG mode, as one line into `line` (line_bytes with its terminating zero): hashes of every array of the static part, then

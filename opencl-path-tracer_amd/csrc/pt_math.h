@@ -9,6 +9,59 @@ __device__ inline float saturate(float a) { return fminf(fmaxf(a, 0.0f), 1.0f); 
 __device__ inline float asF(uint32_t u) { return __uint_as_float(u); }
 __device__ inline uint32_t asU(float f) { return __float_as_uint(f); }
 
+// ---- division, square root and normalize of the shading kernel without the compiler's range scaling --------------------------
+// The device pass is built with -fno-hip-fp32-correctly-rounded-divide-sqrt (ptamd/build.py), and what the compiler makes of the plain
+// operators under it is v_rcp_f32 / v_sqrt_f32 wrapped in a rescaling: `a / b` = ldexp(frexp_mant(a) * rcp(frexp_mant(b)), frexp_exp(a) -
+// frexp_exp(b)), 8 vector instructions; sqrtf(x) = x < 2^-96 ? ldexp(sqrt(ldexp(x, 32)), -16) : sqrt(x), 6.  frexp and ldexp move powers
+// of two, which is exact, and the two hardware instructions see the same mantissa either way; the wrapping only serves operands they flush
+// (denormals) and reciprocals that would be denormal.  The helpers below are the bare instructions.
+// CONTRACT: fastDiv(a, b), fastSqrt(x), fastDiv(V3, s) and fastNormalize(v) return the bits of `a / b`, sqrtf(x), `v / s` and normalize(v)
+// as this build compiles them whenever every operand and every result is a normal float, +-0, +-inf or NaN.  They differ only for a denormal
+// denominator or one with |b| > 2^126 (its reciprocal is denormal: flushed to zero), a denormal x under the root (taken as zero), and a
+// denormal quotient (flushed).  k_shade's denominators are cosines, lengths of scene-scale vectors, material parameters and constants, and
+// where one of them reaches zero the plain operator divides by zero just the same.  v_rsq_f32 is NOT used for normalize: it rounds
+// differently from rcp(sqrt(x)) and would change bits.  The product is kept out of fused multiply-adds (contract off): the rescaled form it
+// replaces ends in an ldexp, which no neighbouring addition could ever be fused with.
+// PT_SHADE_RANGE_SAFE = 1: the helpers are the plain operators and sqrtf -- the code before they existed, for A / B and equality checks
+// (tests/test_gpu_fastmath.py, k_math_probe).  fastRcp is the bare instruction in either build (the traversal kernels use it).
+#ifndef PT_SHADE_RANGE_SAFE
+#define PT_SHADE_RANGE_SAFE 0
+#endif
+__device__ inline float fastRcp(float x) { return __builtin_amdgcn_rcpf(x); } // v_rcp_f32, 1 ulp
+#if PT_SHADE_RANGE_SAFE
+__device__ inline float fastDiv(float a, float b) { return a / b; }
+__device__ inline float fastSqrt(float x) { return sqrtf(x); }
+__device__ inline V3 fastDiv(V3 a, float s) { return a / s; }
+__device__ inline V3 fastNormalize(V3 a) { return normalize(a); }
+#else
+__device__ inline float fastDiv(float a, float b)
+{
+#pragma clang fp contract(off)
+    return a * fastRcp(b);
+}
+__device__ inline float fastSqrt(float x) // v_sqrt_f32, 1 ulp
+{
+    float r = __builtin_amdgcn_sqrtf(x);
+    asm("" : "+v"(r)); // opaque to the optimiser, which would merge a reciprocal taken of this root into one v_rsq_f32 (see above); no instruction
+    return r;
+}
+__device__ inline V3 fastDiv(V3 a, float s) // one reciprocal, three products
+{
+#pragma clang fp contract(off)
+    const float r = fastRcp(s);
+    return { a.x * r, a.y * r, a.z * r };
+}
+__device__ inline V3 fastNormalize(V3 a) // one root, one reciprocal, three products
+{
+    const float len2 = dot(a, a); // (contracted as normalize's is: pt_hostdev.h)
+    const float r = fastRcp(fastSqrt(len2));
+    {
+#pragma clang fp contract(off)
+        return { a.x * r, a.y * r, a.z * r };
+    }
+}
+#endif
+
 // ---- production PRNG: counter-based, stateless (replaces clRNG; DESIGN.md "PRNG") ------------
 // The stream of a path is named by 64 bits -- k0 = mix32(pixel ^ mix32(seed ^ phi)), k1 = mix32(sample ^ c), both
 // bijections, so distinct (pixel, sample) pairs never share a stream (a 32-bit key would: a batch holds ~2^32 pairs) --

@@ -265,7 +265,7 @@ __global__ void __launch_bounds__(kPacketBlock, LENS ? (TWO_LEVEL ? PT_MULTI_MIN
 #pragma unroll
                             for (int r = 0; r < R; r++)
                                 cd[r] = mk(r0.x * cd[r].x, r1.y * cd[r].y, r2.z * cd[r].z);
-                            const float scl = rcpFast(r0.x);
+                            const float scl = fastRcp(r0.x);
                             if constexpr (LENS) { // the waist moves with the rays (t is shared between the spaces: it stays at t = 1); a little outwards for the round-off of the map
                                 const float wA = axis == 0u ? r0.w : (axis == 1u ? r1.w : r2.w);
                                 const float c = fmaf(r0.x, corner, wA);

@@ -46,9 +46,9 @@ __device__ inline V3 readSkydome(const SceneDev& sc, V3 dir) // skydome.cl:12-26
 {
     if (!sc.sky.texels)
         return mk(0.0f);
-    float u = 1 + atan2f(dir.x, -dir.z) / kPI;
-    const float v = acosf(dir.y) / kPI;
-    u /= 2;
+    float u = 1 + fastDiv(atan2f(dir.x, -dir.z), kPI);
+    const float v = fastDiv(acosf(dir.y), kPI);
+    u *= 0.5f;
     return xyz(sampleLinearRepeat(sc.sky, u, 1.0f - v, 0.0f));
 }
 
@@ -149,25 +149,25 @@ __device__ inline V3 F_Schlick(V3 f0, float f90, float u) { return f0 + (mk(f90)
 __device__ inline float G_SmithBeckmannCorrelated(float VdotM, float NdotV, float alpha)
 {
     // 1 / (alpha * tan(acos(NdotV))) with tan(acos c) = sqrt(1 - c^2) / c: same value and the same signs / infinities
-    const float a = NdotV / (alpha * sqrtf(1.0f - NdotV * NdotV));
+    const float a = fastDiv(NdotV, alpha * fastSqrt(1.0f - NdotV * NdotV));
     const float chi = a > 0 ? 1.0f : 0.0f;
     float approx = 1.0f;
     if (a < 1.6f)
-        approx = (3.535f * a + 2.181f * a * a) / (1 + 2.276f * a + 2.577f * a * a);
-    return chi * VdotM / NdotV * approx;
+        approx = fastDiv(3.535f * a + 2.181f * a * a, 1 + 2.276f * a + 2.577f * a * a);
+    return fastDiv(chi * VdotM, NdotV) * approx;
 }
 __device__ inline float G_SmithGGX_IncludeFraction(float NdotL, float NdotV, float alphaG)
 {
     const float a2 = alphaG * alphaG;
-    const float lv = NdotL * sqrtf((-NdotV * a2 + NdotV) * NdotV + a2);
-    const float ll = NdotV * sqrtf((-NdotL * a2 + NdotL) * NdotL + a2);
-    return 0.5f / (lv + ll);
+    const float lv = NdotL * fastSqrt((-NdotV * a2 + NdotV) * NdotV + a2);
+    const float ll = NdotV * fastSqrt((-NdotL * a2 + NdotL) * NdotL + a2);
+    return fastDiv(0.5f, lv + ll);
 }
 __device__ inline float D_GGX(float NdotH, float alpha)
 {
     const float a2 = alpha * alpha;
     const float f = (NdotH * NdotH) * (a2 - 1) + 1;
-    return f > kEPS ? a2 / (kPI * f * f) : 1.0f;
+    return f > kEPS ? fastDiv(a2, kPI * f * f) : 1.0f;
 }
 __device__ inline float Fr_DisneyDiffuse(float NdotV, float NdotL, float LdotH, float linearRoughness)
 {
@@ -204,9 +204,9 @@ __device__ inline V3 pbrBrdfWithDiffuse(V3 V, V3 L, V3 N, const MatView& m, bool
 {
     const V3 f0 = pbrF0(m);
     const float roughness = 1.0f - m.p0;
-    const float linearRoughness = sqrtf(roughness);
+    const float linearRoughness = fastSqrt(roughness);
     const float NdotV = fabsf(dot(N, V)) + 1e-5f;
-    const V3 H = normalize(V + L);
+    const V3 H = fastNormalize(V + L);
     const float LdotH = saturate(dot(L, H));
     const float NdotH = saturate(dot(N, H));
     const float NdotL = saturate(dot(N, L));
@@ -214,7 +214,7 @@ __device__ inline V3 pbrBrdfWithDiffuse(V3 V, V3 L, V3 N, const MatView& m, bool
     const float G = G_SmithGGX_IncludeFraction(NdotL, NdotV, roughness);
     const float D = D_GGX(NdotH, roughness);
     const V3 Fr = D * G * F;
-    const float Fd = Fr_DisneyDiffuse(NdotV, NdotL, LdotH, linearRoughness) / kPI;
+    const float Fd = fastDiv(Fr_DisneyDiffuse(NdotV, NdotL, LdotH, linearRoughness), kPI);
     const V3 diffuseColour = m.metallic ? mk(0.0f) : m.colour;
     const V3 diffuse = (mk(1.0f) - F) * (Fd * diffuseColour);
     return nospecular ? diffuse : Fr + diffuse;
@@ -227,7 +227,7 @@ __device__ inline float calcWeight(V3 I, V3 N, V3 M, float smoothness, V3 O) // 
     const float roughness = 1.0f - smoothness;
     float G = G_SmithBeckmannCorrelated(IdotM, NdotI, roughness) * G_SmithBeckmannCorrelated(MdotO, NdotO, roughness);
     G = fmaxf(fminf(G, 4.0f), 0.f);
-    const float weight = (IdotM * G) / (NdotI * MdotN);
+    const float weight = fastDiv(IdotM * G, NdotI * MdotN);
     return fminf(weight, 4.0f);
 }
 
@@ -242,17 +242,17 @@ __device__ inline V3 normalTransform(const Instance& in, V3 v)
 }
 __device__ inline V3 orient(V3 sample, V3 normal, V3 tangentSeed, const Instance& in)
 {
-    const V3 tangent = normalize(cross(normal, tangentSeed));
+    const V3 tangent = fastNormalize(cross(normal, tangentSeed));
     const V3 bitangent = cross(normal, tangent);
     const V3 os = sample.x * tangent + sample.y * bitangent + sample.z * normal;
-    return normalize(normalTransform(in, os));
+    return fastNormalize(normalTransform(in, os));
 }
 __device__ inline V3 cosineWeightedDiffuseReflection(V3 normal, V3 edge1, const Instance& in, Rng& rng) // shading_helper.cl:62-90
 {
     const float r0 = rng.u01(), r1 = rng.u01();
-    const float r = sqrtf(r0);
+    const float r = fastSqrt(r0);
     const float theta = 2 * kPI * r1;
-    return normalize(orient(mk(r * cosf(theta), r * sinf(theta), sqrtf(1 - r0)), normal, edge1, in));
+    return fastNormalize(orient(mk(r * cosf(theta), r * sinf(theta), fastSqrt(1 - r0)), normal, edge1, in));
 }
 
 struct ShadeResult {
@@ -294,11 +294,11 @@ __device__ inline V3 diffuseColourTextured(const SceneDev& sc, const MatView& ma
 // twice (same arithmetic, same values) so that no per-lane array is needed.
 __device__ inline float lightWeight(const Light& lt, V3 X)
 {
-    const V3 centroid = (xyz(lt.v2) + xyz(lt.v1) + xyz(lt.v0)) / 3.0f;
+    const V3 centroid = fastDiv(xyz(lt.v2) + xyz(lt.v1) + xyz(lt.v0), 3.0f);
     V3 L = centroid - X;
     const float dist2 = dot(L, L);
-    L = L / sqrtf(dist2);
-    const float solidAngle = (dot(xyz(lt.normal), -L) * lt.v0.w) / dist2;
+    L = fastDiv(L, fastSqrt(dist2));
+    const float solidAngle = fastDiv(dot(xyz(lt.normal), -L) * lt.v0.w, dist2);
     return 2 * kPI < solidAngle ? 2 * kPI : solidAngle; // OpenCL min(2 pi, x)
 }
 __device__ inline int pickWeightedLight(const SceneDev& sc, V3 X, Rng& rng, float* weightTotalOut)
@@ -330,9 +330,9 @@ __device__ inline void shadeHit(const SceneDev& sc, V3 X, V3 D, float t, float u
     const float4 f0 = fp->n0u, f1 = fp->n1u, f2 = fp->n2u, f3 = fp->vvvm, f4 = fp->e1e, f5 = fp->e2v, f6 = fp->v0c, f7 = fp->mat;
     const V3 edge1 = xyz(f4), edge2 = mk(f4.w, f5.x, f5.y);
     const Instance in = sc.instances[instIdx];
-    const V3 realNormal = normalize(normalTransform(in, cross(edge1, edge2)));
+    const V3 realNormal = fastNormalize(normalTransform(in, cross(edge1, edge2)));
     const V3 n0 = xyz(f0), n1 = xyz(f1), n2 = xyz(f2);
-    const V3 shadingNormal = normalize(n0 + (n1 - n0) * u + (n2 - n0) * v); // object space, not instance-transformed (shading.cl:378)
+    const V3 shadingNormal = fastNormalize(n0 + (n1 - n0) * u + (n2 - n0) * v); // object space, not instance-transformed (shading.cl:378)
     V3 raySideNormal = shadingNormal;
     if (dot(raySideNormal, -D) < 0.0f)
         raySideNormal = raySideNormal * -1.0f;
@@ -349,16 +349,16 @@ __device__ inline void shadeHit(const SceneDev& sc, V3 X, V3 D, float t, float u
         } else if (MIS) { // shading.cl:69-90: a BSDF-sampled direction found the light: balance heuristic against NEE's density
             const V3 v0 = mk(f5.z, f5.w, f6.x), v1 = v0 + edge1, v2 = v0 + edge2; // object space, as the reference
             const V3 A = v1 - v0, B = v2 - v1, C = v0 - v2;
-            const float la = sqrtf(dot(A, A)), lb = sqrtf(dot(B, B)), lc = sqrtf(dot(C, C));
-            const float hs = (la + lb + lc) / 2.0f;
-            const float lightArea = sqrtf(hs * (hs - la) * (hs - lb) * (hs - lc));
+            const float la = fastSqrt(dot(A, A)), lb = fastSqrt(dot(B, B)), lc = fastSqrt(dot(C, C));
+            const float hs = (la + lb + lc) * 0.5f;
+            const float lightArea = fastSqrt(hs * (hs - la) * (hs - lb) * (hs - lc));
             const V3 distV = X - opt.rayOrigin;
-            float solidAngle = (dot(realNormal, -D) * lightArea) / dot(distV, distV);
+            float solidAngle = fastDiv(dot(realNormal, -D) * lightArea, dot(distV, distV));
             solidAngle = 2 * kPI < solidAngle ? 2 * kPI : solidAngle;
             const float pdf2 = opt.inPdf;
             if (solidAngle > kEPS && !(pdf2 < kEPS)) {
-                const float pdf1 = 1 / solidAngle;
-                out.radiance = throughput * mat.colour * (pdf2 / (pdf1 + pdf2));
+                const float pdf1 = fastDiv(1.0f, solidAngle);
+                out.radiance = throughput * mat.colour * fastDiv(pdf2, pdf1 + pdf2);
             }
         }
         return;
@@ -381,7 +381,7 @@ __device__ inline void shadeHit(const SceneDev& sc, V3 X, V3 D, float t, float u
         if (GENERAL && opt.weightedLights) {
             float weightTotal;
             li = pickWeightedLight(sc, X, rng, &weightTotal);
-            colourScale = weightTotal / (float)sc.numLights;
+            colourScale = fastDiv(weightTotal, (float)sc.numLights);
         } else {
             li = rng.randomInteger(0, (int)sc.numLights - 1);
         }
@@ -389,43 +389,44 @@ __device__ inline void shadeHit(const SceneDev& sc, V3 X, V3 D, float t, float u
         if (GENERAL && li >= (int)sc.numLights) // past the end (see pickWeightedLight): a zero-area, black light
             lt.colour = lt.v0 = lt.v1 = lt.v2 = make_float4(0.f, 0.f, 0.f, 0.f), lt.normal = make_float4(NAN, NAN, NAN, 0.f);
         const float u1 = rng.u01(), u2 = rng.u01();
-        const V3 lightPos = (1 - sqrtf(u1)) * xyz(lt.v0) + (sqrtf(u1) * (1 - u2)) * xyz(lt.v1) + (sqrtf(u1) * u2) * xyz(lt.v2);
+        const float su1 = fastSqrt(u1);
+        const V3 lightPos = (1 - su1) * xyz(lt.v0) + (su1 * (1 - u2)) * xyz(lt.v1) + (su1 * u2) * xyz(lt.v2);
         const V3 lightNormal = xyz(lt.normal);
         const V3 lightColour = GENERAL ? xyz(lt.colour) * colourScale : xyz(lt.colour);
         V3 L = lightPos - X;
         const float dist2 = dot(L, L);
-        const float dist = sqrtf(dist2);
-        L = L / dist;
+        const float dist = fastSqrt(dist2);
+        L = fastDiv(L, dist);
         if (dot(shadingNormal, L) > kEPS && dot(realNormal, L) > kEPS && dot(lightNormal, -L) > kEPS) {
             float pdf2 = 0.0f; // MIS: density with which the BSDF sampling below would have produced L
             if (mat.type == MAT_PBR && MIS) { // shading.cl:116-146
-                const V3 halfway = normalize(-D + L);
+                const V3 halfway = fastNormalize(-D + L);
                 const V3 F = F_Schlick(pbrF0(mat), 1.0f, saturate(dot(L, halfway)));
                 const float rand01 = rng.u01();
                 if (!mat.metallic && rand01 > F.x)
-                    pdf2 = dot(shadingNormal, L) / kPI; // cosine weighted PDF
+                    pdf2 = fastDiv(dot(shadingNormal, L), kPI); // cosine weighted PDF
                 else
                     pdf2 = D_GGX(dot(shadingNormal, halfway), 1.0f - mat.p0);
                 // sic: diffuseColour() of a PBR record -- tex_id is the bit pattern of `smoothness`, never -1, so this is a
                 // material-texture fetch at a clamped layer (pbrBrdf's value, shading.cl:117, is overwritten there)
                 const V3 c = diffuseColourTextured(sc, mat, f0, f1, f2, f3, u, v);
-                BRDF = (c.x == -1.0f) ? mk(0.0f) : c / kPI;
+                BRDF = (c.x == -1.0f) ? mk(0.0f) : fastDiv(c, kPI);
             } else if (mat.type == MAT_PBR) {
                 BRDF = pbrBrdfWithDiffuse(-D, L, shadingNormal, mat, mat.p0 > kMaxSmoothness);
             } else if (mat.type == MAT_DIFFUSE && MIS) { // shading.cl:148-152
-                BRDF = albedo / kPI; // sic: no alpha-0 check in this variant
-                pdf2 = dot(realNormal, L) / kPI;
+                BRDF = fastDiv(albedo, kPI); // sic: no alpha-0 check in this variant
+                pdf2 = fastDiv(dot(realNormal, L), kPI);
             } else if (mat.type == MAT_DIFFUSE) {
-                BRDF = (albedo.x == -1.0f) ? mk(0.0f) : albedo / kPI;
+                BRDF = (albedo.x == -1.0f) ? mk(0.0f) : fastDiv(albedo, kPI);
             }
             float solidAngle = 2 * kPI;
             if (dist2 > kEPS) {
-                solidAngle = (dot(lightNormal, -L) * lt.v0.w) / dist2;
+                solidAngle = fastDiv(dot(lightNormal, -L) * lt.v0.w, dist2);
                 solidAngle = fminf(fmaxf(solidAngle, 0.0f), 2 * kPI);
             }
             V3 Ld;
             if (MIS) // shading.cl:153-163
-                Ld = (float)sc.numLights * lightColour * BRDF * dot(realNormal, L) / (1 / solidAngle + pdf2);
+                Ld = fastDiv((float)sc.numLights * lightColour * BRDF * dot(realNormal, L), fastDiv(1.0f, solidAngle) + pdf2);
             else
                 Ld = (float)sc.numLights * lightColour * BRDF * solidAngle * dot(shadingNormal, L);
             out.shadowFlags = 0;
@@ -455,10 +456,10 @@ __device__ inline void shadeHit(const SceneDev& sc, V3 X, V3 D, float t, float u
         const float phi = 2.0f * kPI * r0;
         const float r1 = rng.u01();
         // theta = acos(c); the reference then takes cos(pi/2 - theta) = sin(theta) and sin(pi/2 - theta) = cos(theta) = c
-        const float cosTheta = sqrtf((1.0f - r1) / ((alpha * alpha - 1.0f) * r1 + 1.0f));
-        const float sinTheta = sqrtf(fmaxf(0.0f, 1.0f - cosTheta * cosTheta));
+        const float cosTheta = fastSqrt(fastDiv(1.0f - r1, (alpha * alpha - 1.0f) * r1 + 1.0f));
+        const float sinTheta = fastSqrt(fmaxf(0.0f, 1.0f - cosTheta * cosTheta));
         const V3 halfway = orient(mk(cosf(phi) * sinTheta, sinf(phi) * sinTheta, cosTheta), shadingNormal, mk(1.0f, 0.0f, 0.0f), in);
-        reflection = normalize(2 * dot(halfway, V) * halfway - V);
+        reflection = fastNormalize(2 * dot(halfway, V) * halfway - V);
         if (MIS) // the density ggxWeightedImportanceDirection reports (shading_helper.cl:162-175); "MIS needs real PDF", shading.cl:210
             out.pdf = D_GGX(dot(halfway, shadingNormal), alpha);
         cosineTerm = dot(shadingNormal, reflection);
@@ -478,8 +479,8 @@ __device__ inline void shadeHit(const SceneDev& sc, V3 X, V3 D, float t, float u
                 out.pdf = dot(shadingNormal, reflection) * kINVPI; // MIS needs the real unsimplified PDF (shading.cl:205)
             // diffuseOnly, pbr_brdf.cl:217-237
             const float NdotV = fabsf(dot(shadingNormal, V)) + 1e-5f;
-            const float Fd = Fr_DisneyDiffuse(NdotV, saturate(dot(shadingNormal, reflection)), saturate(dot(reflection, halfway)), sqrtf(roughness));
-            BRDF = Fd * mat.colour / kPI;
+            const float Fd = Fr_DisneyDiffuse(NdotV, saturate(dot(shadingNormal, reflection)), saturate(dot(reflection, halfway)), fastSqrt(roughness));
+            BRDF = fastDiv(Fd * mat.colour, kPI);
         } else {
             PDF = 1.0f;
             // brdfOnlyNoFresnelNoNDF, pbr_brdf.cl:194-213
@@ -504,27 +505,29 @@ __device__ inline void shadeHit(const SceneDev& sc, V3 X, V3 D, float t, float u
             absorptionFactor = mk(expf(e.x), expf(e.y), expf(e.z));
         }
         const float cos1 = dot(raySideNormal, -D);
-        const float n1n2 = n1 / n2;
+        const float n1n2 = fastDiv(n1, n2);
         const float K = 1 - (n1n2 * n1n2) * (1 - cos1 * cos1);
         if (K > kEPS) {
             const float rand01 = rng.u01();
-            const float f0 = ((n1 - n2) / (n1 + n2)) * ((n1 - n2) / (n1 + n2));
+            const float f0 = fastDiv(n1 - n2, n1 + n2) * fastDiv(n1 - n2, n1 + n2);
             const V3 F = F_Schlick(mk(f0), 1.0f, dot(raySideNormal, -D));
             if (rand01 < F.x)
-                reflection = normalize(-D - 2 * dot(-D, raySideNormal) * raySideNormal); // sic (shading.cl:522)
+                reflection = fastNormalize(-D - 2 * dot(-D, raySideNormal) * raySideNormal); // sic (shading.cl:522)
             else
-                reflection = normalize(n1n2 * D + raySideNormal * (n1n2 * cos1 - sqrtf(K)));
+                reflection = fastNormalize(n1n2 * D + raySideNormal * (n1n2 * cos1 - fastSqrt(K)));
         } else {
-            reflection = normalize(-D - 2 * dot(-D, raySideNormal) * raySideNormal);
+            reflection = fastNormalize(-D - 2 * dot(-D, raySideNormal) * raySideNormal);
         }
         BRDF = absorptionFactor;
     } else if (mat.type == MAT_REFRACTIVE) { // :539-586
         // beckmannWeightedHalfway, shading_helper.cl:127-160
-        const float alpha = (1.2f - 0.2f * sqrtf(fabsf(dot(D, raySideNormal)))) * (1 - mat.p0);
+        const float alpha = (1.2f - 0.2f * fastSqrt(fabsf(dot(D, raySideNormal)))) * (1 - mat.p0);
         const float r0 = rng.u01(), r1 = rng.u01();
         const float phi = 2.0f * kPI * r0;
         // theta = atan(x): cos(theta) = 1 / sqrt(1 + x^2), sin(theta) = x / sqrt(1 + x^2)
         const float tanTheta = -alpha * alpha * log1pf(-r1);
+        // (left on the plain operators: the compiler makes ONE range-scaled v_rsq_f32 of `1 / sqrtf(x)`, which rounds differently from the reciprocal of
+        // a root -- fastDiv(1, fastSqrt(x)) would change bits)
         const float cosTheta = 1.0f / sqrtf(1.0f + tanTheta * tanTheta), sinTheta = tanTheta * cosTheta;
         const V3 halfway = orient(mk(cosf(phi) * sinTheta, sinf(phi) * sinTheta, cosTheta), raySideNormal, mk(1.0f, 0.0f, 0.0f), in);
         V3 absorptionFactor = mk(1.0f);
@@ -538,22 +541,22 @@ __device__ inline void shadeHit(const SceneDev& sc, V3 X, V3 D, float t, float u
             const V3 e = -mat.colour * t;
             absorptionFactor = mk(expf(e.x), expf(e.y), expf(e.z));
         }
-        const float f0 = ((n_i - n_t) / (n_i + n_t)) * ((n_i - n_t) / (n_i + n_t));
+        const float f0 = fastDiv(n_i - n_t, n_i + n_t) * fastDiv(n_i - n_t, n_i + n_t);
         const V3 F = F_Schlick(mk(f0), 1.0f, dot(-D, halfway));
         const float rand01 = rng.u01();
         const V3 I = -D;
         bool refract = false;
         float n1n2 = 0.f, cos1 = 0.f, K = 0.f;
         if (!(rand01 < F.x)) {
-            n1n2 = n_i / n_t;
+            n1n2 = fastDiv(n_i, n_t);
             cos1 = dot(halfway, I);
             K = 1 - (n1n2 * n1n2) * (1 - cos1 * cos1);
             refract = K >= 0;
         }
         if (refract)
-            reflection = normalize(-n1n2 * I + halfway * (n1n2 * cos1 - sqrtf(K))); // evaluateRefract, refract.cl:142-153
+            reflection = fastNormalize(-n1n2 * I + halfway * (n1n2 * cos1 - fastSqrt(K))); // evaluateRefract, refract.cl:142-153
         else
-            reflection = normalize(I - 2 * dot(I, halfway) * halfway); // evaluateReflect, refract.cl:136-140
+            reflection = fastNormalize(I - 2 * dot(I, halfway) * halfway); // evaluateReflect, refract.cl:136-140
         const float w = calcWeight(I, raySideNormal, halfway, mat.p0, reflection);
         BRDF = mk(w) * absorptionFactor;
     } else if (mat.type == MAT_DIFFUSE) { // :587-601
@@ -570,7 +573,7 @@ __device__ inline void shadeHit(const SceneDev& sc, V3 X, V3 D, float t, float u
 
     // Russian roulette + spawn, :606-622
     out.flags = (mat.type == MAT_REFRACTIVE || mat.type == MAT_BASIC_REFRACTIVE || dospecular) ? FLAG_LASTSPECULAR : 0u;
-    const V3 integral = BRDF * cosineTerm / PDF;
+    const V3 integral = fastDiv(BRDF * cosineTerm, PDF);
     const float survive = saturate(fmaxf(fmaxf(integral.x, integral.y), integral.z));
     const float choice = rng.u01();
     if (survive < kEPS || choice > survive) {
@@ -579,7 +582,7 @@ __device__ inline void shadeHit(const SceneDev& sc, V3 X, V3 D, float t, float u
     }
     out.origin = X + reflection * kEPS;
     out.direction = reflection;
-    out.throughput = throughput * integral / survive;
+    out.throughput = fastDiv(throughput * integral, survive);
 }
 
 // =================================================================================================
@@ -876,10 +879,10 @@ __global__ void __launch_bounds__(kShadeBlock, (PARITY || GENERAL || LOOP) ? 4 :
                     opt.inPdf = thr.w; // 0 for primary rays (they carry LASTSPECULAR: never consulted)
                 }
 #if PT_SHADE_PARK
-                shadeHit<GENERAL>(a.sc, X, normalize(d), h.x, h.y, h.z, (uint32_t)prim, (uint32_t)a.hits.inst[i], throughput, fb & 0xFFu, rng, r, opt,
+                shadeHit<GENERAL>(a.sc, X, fastNormalize(d), h.x, h.y, h.z, (uint32_t)prim, (uint32_t)a.hits.inst[i], throughput, fb & 0xFFu, rng, r, opt,
                     PARITY ? nullptr : &sPark[0][threadIdx.x], PARITY ? 0u : (uint32_t)kShadeBlock);
 #else
-                shadeHit<GENERAL>(a.sc, X, normalize(d), h.x, h.y, h.z, (uint32_t)prim, (uint32_t)a.hits.inst[i], throughput, fb & 0xFFu, rng, r, opt);
+                shadeHit<GENERAL>(a.sc, X, fastNormalize(d), h.x, h.y, h.z, (uint32_t)prim, (uint32_t)a.hits.inst[i], throughput, fb & 0xFFu, rng, r, opt);
 #endif
                 if (PARITY)
                     rngLfsrStore(a.streams, i, rng);
@@ -900,7 +903,7 @@ __global__ void __launch_bounds__(kShadeBlock, (PARITY || GENERAL || LOOP) ? 4 :
                 float4* ap = a.accum.at(plane, pixel);
                 float4 px = *ap;
                 asm volatile("" : "+v"(px.x), "+v"(px.y), "+v"(px.z), "+v"(px.w)); // keeps the load where it is written
-                const V3 c = throughput * readSkydome(a.sc, normalize(d));
+                const V3 c = throughput * readSkydome(a.sc, fastNormalize(d));
                 px.x += c.x, px.y += c.y, px.z += c.z;
                 *ap = px;
                 deposited = true;
@@ -1122,6 +1125,25 @@ __global__ void k_set_word(uint32_t* p, uint32_t v)
 {
     if (threadIdx.x == 0 && blockIdx.x == 0)
         *p = v;
+}
+
+// Test hook (pt_debug_math_probe): the contract of the fast helpers (pt_math.h) as this unit, with these flags, compiles both sides.  Ten planes of n floats:
+// a / b, fastDiv(a, b), sqrtf(|a|), fastSqrt(|a|), normalize((a, b, a + b)).xyz, fastNormalize((a, b, a + b)).xyz.
+__global__ void __launch_bounds__(256) k_math_probe(const float* __restrict__ a, const float* __restrict__ b, uint32_t n, float* __restrict__ out)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n)
+        return;
+    const float x = a[i], y = b[i];
+    const V3 v = mk(x, y, x + y);
+    const V3 np = normalize(v), nf = fastNormalize(v);
+    const size_t s = n;
+    out[i] = x / y;
+    out[s + i] = fastDiv(x, y);
+    out[2 * s + i] = sqrtf(fabsf(x));
+    out[3 * s + i] = fastSqrt(fabsf(x));
+    out[4 * s + i] = np.x, out[5 * s + i] = np.y, out[6 * s + i] = np.z;
+    out[7 * s + i] = nf.x, out[8 * s + i] = nf.y, out[9 * s + i] = nf.z;
 }
 
 // end-of-sample bookkeeping: fold the per-pass counters into 64-bit totals and zero the control

@@ -145,7 +145,6 @@ __device__ unsigned long long g_traceStats[64]; // [0..23] closest-hit launches,
 #define PT_TOC(i, t)
 #endif
 
-__device__ inline float rcpFast(float x) { return __builtin_amdgcn_rcpf(x); } // v_rcp_f32, 1 ulp
 // v_fma_f32 that stays a plain v_fma_f32 (the vectoriser would pack two of them into one v_pk_fma_f32: a half-rate instruction that competes with the
 // conversions, compares and selects around it, while a plain FP32 multiply-add next to one of those issues at about half its price -- measured,
 // profiles/round5/r5r_valu_issue_pairs.md: v_cmp / v_cndmask / v_min3 / v_cvt_f32_ubyte + v_fma_f32 pairs take 2.55 units against 2.0 for the half-rate one alone)
@@ -175,7 +174,7 @@ __device__ inline f2 planePair(const f2 q, const float a, const float b)
 // Reciprocal direction for the slab test, clamped to +-1e18: a zero (or FLT_MIN, scene.cl:123-137)
 // component then yields plane distances of +-1e18 * (b - o) -- far beyond any scene, with the correct
 // sign -- instead of the inf - inf = NaN the one-FMA form would produce from an infinite reciprocal.
-__device__ inline float rcpSlab(float x) { return fminf(fmaxf(rcpFast(x), -1e18f), 1e18f); }
+__device__ inline float rcpSlab(float x) { return fminf(fmaxf(fastRcp(x), -1e18f), 1e18f); }
 
 // Moeller-Trumbore (shapes.cl:20-72), operation by operation.  Rounds 1-4 wrote the test as cross / dot expressions and left the choice of fused
 // multiply-adds to the compiler: every kernel then had to happen on the same choice ("the same hits as k_trace, to the bit" is what the tests of the
@@ -209,7 +208,7 @@ __device__ inline void triRayHalf(const V3 d, const V3 e1, const V3 e2, const V3
     const V3 P = crossExact(d, e2);
     const float pz = e1.z * P.z;
     *det = pz + __builtin_fmaf(e1.x, P.x, e1.y * P.y);
-    const float inv = rcpFast(*det);
+    const float inv = fastRcp(*det);
     *u = dotExact(T, P) * inv;
     *v = dotExact(d, Q) * inv;
     *t = e2Q * inv;

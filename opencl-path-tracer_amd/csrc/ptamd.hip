@@ -272,6 +272,28 @@ int pt_debug_copy_bandwidth(pt_ctx* c, size_t bytes, uint32_t repeat, float* gbp
     });
 }
 
+// Test hook (tests/test_gpu_fastmath.py): k_math_probe over n pairs; `out` receives ten planes of n floats (pt_shade.h).
+int pt_debug_math_probe(pt_ctx* c, const float* a, const float* b, uint32_t n, float* out)
+{
+    return guarded(c, "pt_debug_math_probe", [&]() -> int {
+    if (!c || !a || !b || !out || n == 0)
+        return PT_ERR_INVALID;
+    HIPCHK(c, hipSetDevice(c->device));
+    DevBuf<float> dA, dB, dOut;
+    HIPCHK(c, dA.alloc(n));
+    HIPCHK(c, dB.alloc(n));
+    HIPCHK(c, dOut.alloc((size_t)n * 10));
+    HIPCHK(c, hipMemcpy(dA.p, a, (size_t)n * sizeof(float), hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(dB.p, b, (size_t)n * sizeof(float), hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_math_probe, dim3((n + 255u) / 256u), dim3(256), 0, c->stream, dA.p, dB.p, n, dOut.p);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpy(out, dOut.p, (size_t)n * 10 * sizeof(float), hipMemcpyDeviceToHost));
+    dA.release(), dB.release(), dOut.release();
+    return PT_OK;
+    });
+}
+
 const char* pt_last_error(const pt_ctx* ctx) { return ctx ? ctx->error.c_str() : g_createError.c_str(); }
 
 // Test hook, no device needed: the host side of quantiseWideNode (pt_hostdev.h) -- up to four child boxes (lo / hi: 4 x 3 floats; empty[k] != 0:

@@ -55,9 +55,11 @@ def build_sanitized(force=False):
     return out, oout
 
 
-# Division and square root as v_rcp_f32 / v_sqrt_f32 (1 ulp) instead of the correctly rounded expansions (~10
-# instructions each): a quarter of k_shade's instructions were those expansions.  The reference builds its kernels
-# with -cl-fast-relaxed-math (raytracer.cpp:819); every parity test passes either way.
+# -fno-hip-fp32-correctly-rounded-divide-sqrt: `/` and sqrtf built on the 1-ulp v_rcp_f32 / v_sqrt_f32 instead of the correctly rounded expansions.  The
+# reference builds its kernels with -cl-fast-relaxed-math (raytracer.cpp:819); every parity test passes either way.  What the compiler emits under the
+# flag is not the bare instruction: `a / b` is 8 vector instructions (both operands through frexp, v_rcp_f32, a product, an ldexp) and sqrtf 6 -- a
+# rescaling that serves denormal operands only.  k_shade spells the bare forms out (fastDiv / fastSqrt / fastNormalize, csrc/pt_math.h); the other kernels
+# keep the operators.
 # -fno-slp-vectorize (device code only): the vectoriser packs pairs of FP32 multiplies and multiply-adds into v_pk_* instructions, which issue at half
 # rate and compete with the conversions, compares and selects of the traversal kernels; plain FP32 arithmetic next to one of those is nearly free
 # (profiles/round5/r5r_valu_issue_pairs.md).  Benchmark scene: 11 040 -> 11 660 Mrays/s, k_shade 85 -> 75 VGPRs.

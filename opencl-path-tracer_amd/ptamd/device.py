@@ -78,7 +78,7 @@ EXPORTS = ["pt_create", "pt_destroy", "pt_last_error", "pt_set_stream", "pt_uplo
            "pt_synchronize", "pt_resolve", "pt_resolve_device", "pt_resolve_device_ptr", "pt_read_accum", "pt_write_accum", "pt_accum_device_ptr",
            "pt_samples_per_pixel", "pt_render_guides", "pt_guide_samples", "pt_read_guides", "pt_write_guides", "pt_guides_device_ptr",
            "pt_denoise", "pt_denoise_device", "pt_stats_get", "pt_stats_reset", "pt_profile_kernels", "pt_reduce_accum",
-           "pt_intersect", "pt_gen_rays", "pt_primary_pass", "pt_shade_batch", "pt_debug_quantise_node", "pt_debug_convert", "pt_debug_copy_bandwidth", "pt_version"]
+           "pt_intersect", "pt_gen_rays", "pt_primary_pass", "pt_shade_batch", "pt_debug_quantise_node", "pt_debug_convert", "pt_debug_copy_bandwidth", "pt_debug_math_probe", "pt_version"]
 
 _lib = None
 
@@ -367,6 +367,19 @@ class Context:
         g = C.c_float(0)
         self._chk(lib().pt_debug_copy_bandwidth(self._h, nbytes, repeat, C.byref(g)), "pt_debug_copy_bandwidth")
         return float(g.value)
+
+    def debug_math_probe(self, a, b):
+        """The fast division / square-root helpers of k_shade next to the plain operators, on the device (pt_debug_math_probe): a dict of float32
+        arrays div, fast_div, sqrt, fast_sqrt (n) and normalize, fast_normalize (n, 3) of the vectors (a, b, a + b)."""
+        a = np.ascontiguousarray(a, np.float32)
+        b = np.ascontiguousarray(b, np.float32)
+        if a.shape != b.shape or a.ndim != 1:
+            raise ValueError("debug_math_probe: a and b must be one-dimensional and of one length")
+        out = np.zeros((10, len(a)), np.float32)
+        lib().pt_debug_math_probe.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
+        self._chk(lib().pt_debug_math_probe(self._h, _p(a), _p(b), len(a), _p(out)), "pt_debug_math_probe")
+        return {"div": out[0], "fast_div": out[1], "sqrt": out[2], "fast_sqrt": out[3],
+                "normalize": np.ascontiguousarray(out[4:7].T), "fast_normalize": np.ascontiguousarray(out[7:10].T)}
 
     def reset_stats(self):
         self._chk(lib().pt_stats_reset(self._h), "pt_stats_reset")
