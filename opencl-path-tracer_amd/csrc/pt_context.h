@@ -1,5 +1,6 @@
 // The context of the C-ABI (include/ptamd.h): device buffers, the two static scenes and the two dynamic sets a context holds, error reporting.
-// Included by ptamd.hip alone (one translation unit: pt_context.h, pt_schedule.h, then the C-ABI shell; the conversion is pt_convert.cpp).
+// Included by ptamd.hip alone (one translation unit: the kernels -- pt_shade.h, then pt_walk.h, the steps every traversal kernel shares, under pt_trace.h / pt_packet.h /
+// pt_packet_multi.h / pt_team.h --, pt_context.h, pt_schedule.h, then the C-ABI shell; the conversion is pt_convert.cpp).
 #pragma once
 
 namespace {

@@ -20,11 +20,11 @@
 // Reference semantics: traceRay, scene.cl:61-271 (closest hit, and hitAny :181-185); slab accept test bvh.cl:72,114;
 // Moeller-Trumbore shapes.cl:20-72.
 #pragma once
-#include "pt_trace.h"
+#include "pt_walk.h"
 
 #ifndef PT_PACKET_DYNAMIC
-#define PT_PACKET_DYNAMIC 16 // > 0: packets per claim of the queue cursor; 0: static round-robin.  4 / 8 / 16 / 32 / 64 / 128: 27.2 / 25.4 / 25.0 / 25.7 / 26.1 / 28.2 ms of closest-hit traversal per batch (27.3 static)
-#endif
+#define PT_PACKET_DYNAMIC 16 // packets per claim of the queue cursor.  4 / 8 / 16 / 32 / 64 / 128: 27.2 / 25.4 / 25.0 / 25.7 / 26.1 / 28.2 ms of closest-hit traversal per batch
+#endif                       // (27.3 with the packets dealt round-robin, every wave over the whole queue and no cursor)
 #ifndef PT_PACKET_MIN_WAVES
 #define PT_PACKET_MIN_WAVES 8
 #endif
@@ -49,10 +49,8 @@ __device__ inline void lanePush(uint32_t& r, uint32_t& lo, uint32_t& hi, uint32_
 }
 typedef uint32_t u4v_t __attribute__((ext_vector_type(4)));
 constexpr uint32_t kKeyNone = 0x7F800000u; // +inf: no lane sees the child
+__device__ inline float4 asF4(const u4v_t v) { return make_float4(asF(v.x), asF(v.y), asF(v.z), asF(v.w)); }
 
-#ifndef PT_PACKET_BEAM
-#define PT_PACKET_BEAM 1 // 1: packets whose rays all point into one octant test the child boxes against the BEAM (24 lanes, one plane each)
-#endif
 // min of a0, a1, a2 and max of b0, b1, b2 over the 64 lanes, six DPP steps each (row_shr 1 / 2 / 4 / 8 leave a row's result in its
 // lane 15 -- min and max do not mind an element counted twice --, row_bcast 15 / 31 carry it on to lane 63), the six chains
 // interleaved so that no step reads a register the previous instruction wrote (a DPP read needs two wait states after a vector
@@ -142,8 +140,7 @@ __device__ inline void packetIntoInstance(const Instance* instances, uint32_t wh
     typedef const u4v_t __attribute__((address_space(4)))* ScalarU4i;
     const ScalarU4i m = (ScalarU4i)(unsigned long long)&instances[what];
     const u4v_t r0 = m[0], r1 = m[1], r2 = m[2];
-    rayIntoInstance(make_float4(asF(r0.x), asF(r0.y), asF(r0.z), asF(r0.w)), make_float4(asF(r1.x), asF(r1.y), asF(r1.z), asF(r1.w)),
-        make_float4(asF(r2.x), asF(r2.y), asF(r2.z), asF(r2.w)), co, cd, to, td);
+    rayIntoInstance(asF4(r0), asF4(r1), asF4(r2), co, cd, to, td);
     *root = m[3].x;
 }
 template <bool ANY_HIT, bool TWO_LEVEL>
@@ -153,7 +150,6 @@ __global__ void __launch_bounds__(kPacketBlock, TWO_LEVEL ? PT_PACKET_MIN_WAVES_
     const uint32_t pwave = threadIdx.x >> 6;
     typedef uint32_t u4v __attribute__((ext_vector_type(4)));
     typedef const u4v __attribute__((address_space(4)))* ScalarU4; // uniform address + constant space = scalar loads
-    typedef float f2 __attribute__((ext_vector_type(2)));
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t gwave = (blockIdx.x * kPacketBlock + threadIdx.x) >> 6;
     const uint32_t totalWaves = (gridDim.x * kPacketBlock) >> 6;
@@ -164,20 +160,16 @@ __global__ void __launch_bounds__(kPacketBlock, TWO_LEVEL ? PT_PACKET_MIN_WAVES_
     const ScalarU4 wideS = (ScalarU4)(unsigned long long)sc.wide;
     const ScalarU4 trisS = (ScalarU4)(unsigned long long)sc.tris;
 
-#if PT_PACKET_DYNAMIC
     // The first PT_PACKET_DYNAMIC packets of a wave are static (wave w: [w * n, w * n + n)), later spans of the same
-    // size come from the queue cursor: one atomic per span, well under what a device-scope word sustains (pt_trace.h).
+    // size come from the queue cursor: one atomic per span, well under what a device-scope word sustains (pt_trace.h), and guided (kGuidedSpans).
     // Consecutive packets are neighbouring pixels, so a wave keeps finding its nodes in the scalar cache and L2, and
     // no wave is left with a long static tail while others idle.
     constexpr uint32_t kSpan = PT_PACKET_DYNAMIC;
     uint32_t spanBase = uni(gwave) * kSpan, spanLeft = kSpan;
     for (;;) {
         if (spanLeft == 0u) {
-            uint32_t claim = kSpan;
-#if PT_GUIDED_SPANS
             const uint32_t left = packets > spanBase ? packets - spanBase : 0u; // spanBase lags the cursor: an upper bound
-            claim = min(kSpan, max(1u, left / (totalWaves * PT_GUIDED_SPANS)));
-#endif
+            const uint32_t claim = min(kSpan, max(1u, left / (totalWaves * kGuidedSpans)));
             uint32_t b = 0;
             if (lane == 0)
                 b = atomicAdd(ANY_HIT ? &a.ctl->shadowCursor[a.pass] : &a.ctl->extCursor[a.pass], claim);
@@ -189,12 +181,6 @@ __global__ void __launch_bounds__(kPacketBlock, TWO_LEVEL ? PT_PACKET_MIN_WAVES_
         const uint32_t p = spanBase;
         spanBase++;
         spanLeft--;
-        {
-#else
-    // packets are dealt round-robin: every wave sees the whole queue, so the load evens out without a shared cursor
-    for (uint32_t p = uni(gwave); p < packets; p += totalWaves) {
-        {
-#endif
         const uint32_t idx = p * 64u + lane;
         bool active = idx < count;
         float4 ro = make_float4(0, 0, 0, 0), rd = make_float4(0, 0, 0, 1);
@@ -219,14 +205,9 @@ __global__ void __launch_bounds__(kPacketBlock, TWO_LEVEL ? PT_PACKET_MIN_WAVES_
             a.inst[idx] = -1;
             active = false;
         }
-        // zero components are nudged as at k_trace's hand-out (NO_PARALLEL_RAYS, scene.cl:123-137)
-        if (rd.x == 0.0f) rd.x = FLT_MIN;
-        if (rd.y == 0.0f) rd.y = FLT_MIN;
-        if (rd.z == 0.0f) rd.z = FLT_MIN;
-        if (ro.x == 0.0f) ro.x = -FLT_MIN;
-        if (ro.y == 0.0f) ro.y = -FLT_MIN;
-        if (ro.z == 0.0f) ro.z = -FLT_MIN;
-        V3 co = xyz(ro), cd = xyz(rd);
+        float4 no = ro, nd = rd; // (ro / rd stay as queued: rd.w is the pixel of a shadow ray's deposit)
+        nudgeZero(no, nd);
+        V3 co = xyz(no), cd = xyz(nd);
         V3 cid = mk(rcpSlab(cd.x), rcpSlab(cd.y), rcpSlab(cd.z));
         bool nx = cid.x < 0.f, ny = cid.y < 0.f, nz = cid.z < 0.f;
         float hu = 0.f, hv = 0.f;
@@ -252,7 +233,6 @@ __global__ void __launch_bounds__(kPacketBlock, TWO_LEVEL ? PT_PACKET_MIN_WAVES_
         uint32_t statNodes = 0u, statLeaves = 0u; // wave-uniform: per-lane path of this packet
 #endif
         bool viaBeam = false;
-#if PT_PACKET_BEAM
         if (!ANY_HIT) {
             const unsigned long long all = ~0ull;
             const unsigned long long sx = __builtin_amdgcn_ballot_w64(nx), sy = __builtin_amdgcn_ballot_w64(ny), sz = __builtin_amdgcn_ballot_w64(nz);
@@ -377,10 +357,11 @@ __global__ void __launch_bounds__(kPacketBlock, TWO_LEVEL ? PT_PACKET_MIN_WAVES_
                     for (uint32_t k = 0; k < n; k++) {
                         const u4v ta = trisS[(first + k) * 3u + 0u], tb = trisS[(first + k) * 3u + 1u];
                         const uint32_t tcx = trisS[(first + k) * 3u + 2u].x;
-                        const V3 v0 = mk(asF(ta.x), asF(ta.y), asF(ta.z)), e1 = mk(asF(ta.w), asF(tb.x), asF(tb.y)), e2 = mk(asF(tb.z), asF(tb.w), asF(tcx));
+                        V3 v0, e1, e2;
+                        triEdges(asF4(ta), asF4(tb), asF(tcx), &v0, &e1, &e2);
                         float det, u, v, t;
                         triangleTest(co, cd, v0, e1, e2, &det, &u, &v, &t);
-                        const bool hit = !(det > -FLT_MIN && det < FLT_MIN) && !(u < 0.f || u > 1.f) && !(v < 0.f || u + v > 1.f) && t > 0.f && t < tClosest;
+                        const bool hit = PT_TRI_HIT(det, u, v, t, tClosest);
                         if (hit) {
                             tClosest = t;
                             hu = u;
@@ -408,7 +389,6 @@ __global__ void __launch_bounds__(kPacketBlock, TWO_LEVEL ? PT_PACKET_MIN_WAVES_
             }
 #endif
         }
-#endif
         if (ANY_HIT || !viaBeam) {
         if constexpr (TWO_LEVEL && !ANY_HIT) { // (a packet that left the beam walk: its rays are the world-space ones; 1 / direction was not kept)
             cid = mk(rcpSlab(cd.x), rcpSlab(cd.y), rcpSlab(cd.z));
@@ -451,22 +431,14 @@ __global__ void __launch_bounds__(kPacketBlock, TWO_LEVEL ? PT_PACKET_MIN_WAVES_
                     const uint4* wp = (const uint4*)&sc.wide[ni]; // the plane bytes are selected per lane: vector registers
                     const uint4 B = wp[1];
                     const uint2 C = *(const uint2*)&wp[2];
-                    const float ax = asF(A.w) * cid.x, ay = asF(Cs.z) * cid.y, az = asF(Cs.w) * cid.z;
-                    const float bx = (asF(A.x) - co.x) * cid.x, by = (asF(A.y) - co.y) * cid.y, bz = (asF(A.z) - co.z) * cid.z;
-                    const uint32_t qnx = nx ? B.y : B.x, qfx = nx ? B.x : B.y;
-                    const uint32_t qny = ny ? B.w : B.z, qfy = ny ? B.z : B.w;
-                    const uint32_t qnz = nz ? C.y : C.x, qfz = nz ? C.x : C.y;
+                    const SlabSetup slab = slabSetup(make_uint4(A.x, A.y, A.z, A.w), B, make_uint4(C.x, C.y, Cs.z, Cs.w), co, cid, nx, ny, nz);
                     const float tLimit = here ? tClosest : -INFINITY; // a lane that is not in this node sees no child
                     unsigned long long m[4];
                     uint32_t key[4]; // entry distance of the first lane that sees the child (float bits, >= 0: ordered as integers), slot in the low bits
 #pragma unroll
                     for (int k = 0; k < 4; k++) {
-                        const f2 qx = { (float)((qnx >> (8 * k)) & 0xFFu), (float)((qfx >> (8 * k)) & 0xFFu) };
-                        const f2 qy = { (float)((qny >> (8 * k)) & 0xFFu), (float)((qfy >> (8 * k)) & 0xFFu) };
-                        const f2 qz = { (float)((qnz >> (8 * k)) & 0xFFu), (float)((qfz >> (8 * k)) & 0xFFu) };
-                        const f2 tx = planePair(qx, ax, bx), ty = planePair(qy, ay, by), tz = planePair(qz, az, bz);
-                        const float tmin = fmaxf(fmaxf(tx.x, ty.x), tz.x);
-                        const float tmax = fminf(fminf(tx.y, ty.y), tz.y);
+                        const f2 tt = childSlab(slab, k);
+                        const float tmin = tt.x, tmax = tt.y;
                         // tmax >= tmin && tmax >= 0 && tmin < closest (bvh.cl:72,114), the first two folded into one compare
                         const float tlo = fmaxf(tmin, 0.f);
                         const bool vis = tmax >= tlo && tmin < tLimit;
@@ -506,11 +478,11 @@ __global__ void __launch_bounds__(kPacketBlock, TWO_LEVEL ? PT_PACKET_MIN_WAVES_
                     for (uint32_t k = 0; k < n; k++) {
                         const u4v ta = trisS[(first + k) * 3u + 0u], tb = trisS[(first + k) * 3u + 1u];
                         const uint32_t tcx = trisS[(first + k) * 3u + 2u].x;
-                        const V3 v0 = mk(asF(ta.x), asF(ta.y), asF(ta.z)), e1 = mk(asF(ta.w), asF(tb.x), asF(tb.y)), e2 = mk(asF(tb.z), asF(tb.w), asF(tcx));
+                        V3 v0, e1, e2;
+                        triEdges(asF4(ta), asF4(tb), asF(tcx), &v0, &e1, &e2);
                         float det, u, v, t;
                         triangleTest(co, cd, v0, e1, e2, &det, &u, &v, &t);
-                        const bool hit = here && !(det > -FLT_MIN && det < FLT_MIN) && !(u < 0.f || u > 1.f) && !(v < 0.f || u + v > 1.f) && t > 0.f
-                            && t < tClosest;
+                        const bool hit = here && PT_TRI_HIT(det, u, v, t, tClosest);
                         if (hit) {
                             if (ANY_HIT) {
                                 active = false; // occluded: nothing to deposit
@@ -550,22 +522,10 @@ __global__ void __launch_bounds__(kPacketBlock, TWO_LEVEL ? PT_PACKET_MIN_WAVES_
             if (active) {
                 if (a.occluded)
                     a.occluded[idx] = 0u;
-                const float4 contrib = a.rayC[idx];
-                const uint32_t pixel = asU(rd.w);
-                float4* ap = a.accum.at(asU(contrib.w) >> 16, pixel); // one live path per entry: plain RMW
-                float4 px = *ap;
-                px.x += contrib.x, px.y += contrib.y, px.z += contrib.z;
-                *ap = px;
+                depositUnoccluded(a, a.rayC[idx], asU(rd.w));
             }
         } else if (active) {
-            if (hprim >= 0 && hinst < 0) { // a world-space copy of an instance: back to (original triangle, instance)
-                const float4 tc = sc.tris[hprim].c;
-                hprim = (int)asU(tc.y);
-                hinst = (int)asU(tc.z);
-            }
-            a.hit[idx] = make_float4(hprim >= 0 ? tClosest : INFINITY, hu, hv, asF((uint32_t)hprim));
-            a.inst[idx] = hinst;
-        }
+            writeClosestHit(a, sc, idx, tClosest, hu, hv, hprim, hinst);
         }
     }
 }

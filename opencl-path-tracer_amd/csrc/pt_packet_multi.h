@@ -27,7 +27,7 @@
 
 namespace ptd {
 
-// (Moeller-Trumbore in two halves, operation by operation: triOriginHalf / triRayHalf, pt_trace.h)
+// (Moeller-Trumbore in two halves, operation by operation: triOriginHalf / triRayHalf, pt_walk.h)
 
 // Do the R x 64 directions point into one octant?  Per axis: the interval of |1 / direction| over the lane's rays (folded over the wave by
 // bundleBeam) and the common sign.
@@ -125,7 +125,6 @@ __global__ void __launch_bounds__(kPacketBlock, LENS ? (TWO_LEVEL ? PT_MULTI_MIN
     const uint32_t pwave = threadIdx.x >> 6;
     typedef uint32_t u4v __attribute__((ext_vector_type(4)));
     typedef const u4v __attribute__((address_space(4)))* ScalarU4; // uniform address + constant space = scalar loads
-    typedef float f2 __attribute__((ext_vector_type(2)));
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t gwave = (blockIdx.x * kPacketBlock + threadIdx.x) >> 6;
     const uint32_t totalWaves = (gridDim.x * kPacketBlock) >> 6;
@@ -185,13 +184,7 @@ __global__ void __launch_bounds__(kPacketBlock, LENS ? (TWO_LEVEL ? PT_MULTI_MIN
                     ((float4*)a.rayD)[idx] = make_float4(d.x, d.y, d.z, asF(packState(FLAG_LASTSPECULAR, 0u, pl)));
                 }
             }
-            // zero components are nudged as at k_trace's hand-out (NO_PARALLEL_RAYS, scene.cl:123-137)
-            if (d.x == 0.0f) d.x = FLT_MIN;
-            if (d.y == 0.0f) d.y = FLT_MIN;
-            if (d.z == 0.0f) d.z = FLT_MIN;
-            if (o.x == 0.0f) o.x = -FLT_MIN;
-            if (o.y == 0.0f) o.y = -FLT_MIN;
-            if (o.z == 0.0f) o.z = -FLT_MIN;
+            nudgeZero(o, d);
             if (LENS || r == 0)
                 co[LENS ? r : 0] = o;
             cd[r] = d;
@@ -251,8 +244,7 @@ __global__ void __launch_bounds__(kPacketBlock, LENS ? (TWO_LEVEL ? PT_MULTI_MIN
                         typedef const u4v_t __attribute__((address_space(4)))* ScalarU4i;
                         const ScalarU4i mrow = (ScalarU4i)(unsigned long long)&sc.instances[refIndex(cur)];
                         const u4v_t m0 = mrow[0], m1 = mrow[1], m2 = mrow[2];
-                        const float4 r0 = make_float4(asF(m0.x), asF(m0.y), asF(m0.z), asF(m0.w)), r1 = make_float4(asF(m1.x), asF(m1.y), asF(m1.z), asF(m1.w)),
-                                     r2 = make_float4(asF(m2.x), asF(m2.y), asF(m2.z), asF(m2.w));
+                        const float4 r0 = asF4(m0), r1 = asF4(m1), r2 = asF4(m2);
                         if (uni(mrow[3].w) != 0u) {
                             // a translation + uniform scale (Instance::simple; the reference's own scenes, BASELINE configs 4 / 5): x' = x / s + w maps the
                             // beam onto itself -- same octant, the origin moved, every |1 / direction| times s -- so nothing is reduced over the wave
@@ -361,7 +353,8 @@ __global__ void __launch_bounds__(kPacketBlock, LENS ? (TWO_LEVEL ? PT_MULTI_MIN
                     for (uint32_t k = 0; k < n; k++) {
                         const u4v ta = trisS[(first + k) * 3u + 0u], tb = trisS[(first + k) * 3u + 1u];
                         const uint32_t tcx = trisS[(first + k) * 3u + 2u].x;
-                        const V3 v0 = mk(asF(ta.x), asF(ta.y), asF(ta.z)), e1 = mk(asF(ta.w), asF(tb.x), asF(tb.y)), e2 = mk(asF(tb.z), asF(tb.w), asF(tcx));
+                        V3 v0, e1, e2;
+                        triEdges(asF4(ta), asF4(tb), asF(tcx), &v0, &e1, &e2);
                         // the half of Moeller-Trumbore that only knows the origin: once per triangle (LENS: per ray -- every ray has its own)
                         V3 T, Q;
                         float e2Q;
@@ -373,7 +366,7 @@ __global__ void __launch_bounds__(kPacketBlock, LENS ? (TWO_LEVEL ? PT_MULTI_MIN
                             if constexpr (LENS)
                                 triOriginHalf(co[r], v0, e1, e2, &T, &Q, &e2Q);
                             triRayHalf(cd[r], e1, e2, T, Q, e2Q, &det, &u, &v, &t);
-                            const bool hit = !(det > -FLT_MIN && det < FLT_MIN) && !(u < 0.f || u > 1.f) && !(v < 0.f || u + v > 1.f) && t > 0.f && t < tClosest[r];
+                            const bool hit = PT_TRI_HIT(det, u, v, t, tClosest[r]);
                             if (hit) {
                                 tClosest[r] = t;
                                 hu[r] = u;
@@ -423,12 +416,7 @@ __global__ void __launch_bounds__(kPacketBlock, LENS ? (TWO_LEVEL ? PT_MULTI_MIN
                     primaryEntry(a.fp, a.pixelList, idx, &px, &pl);
                     primaryRay(a.fp, px, pl, &o, &d);
                 }
-                if (d.x == 0.0f) d.x = FLT_MIN;
-                if (d.y == 0.0f) d.y = FLT_MIN;
-                if (d.z == 0.0f) d.z = FLT_MIN;
-                if (o.x == 0.0f) o.x = -FLT_MIN;
-                if (o.y == 0.0f) o.y = -FLT_MIN;
-                if (o.z == 0.0f) o.z = -FLT_MIN;
+                nudgeZero(o, d);
                 V3 cid = mk(rcpSlab(d.x), rcpSlab(d.y), rcpSlab(d.z));
                 bool nx = cid.x < 0.f, ny = cid.y < 0.f, nz = cid.z < 0.f;
                 const V3 wo = o, wd = d; // TWO_LEVEL: the world-space ray, for the way back out of an instance
@@ -466,22 +454,14 @@ __global__ void __launch_bounds__(kPacketBlock, LENS ? (TWO_LEVEL ? PT_MULTI_MIN
                             const uint4* wp = (const uint4*)&sc.wide[ni];
                             const uint4 B = wp[1];
                             const uint2 C = *(const uint2*)&wp[2];
-                            const float kx = asF(A.w) * cid.x, ky = asF(Cs.z) * cid.y, kz = asF(Cs.w) * cid.z;
-                            const float bx = (asF(A.x) - o.x) * cid.x, by = (asF(A.y) - o.y) * cid.y, bz = (asF(A.z) - o.z) * cid.z;
-                            const uint32_t qnx = nx ? B.y : B.x, qfx = nx ? B.x : B.y;
-                            const uint32_t qny = ny ? B.w : B.z, qfy = ny ? B.z : B.w;
-                            const uint32_t qnz = nz ? C.y : C.x, qfz = nz ? C.x : C.y;
+                            const SlabSetup slab = slabSetup(make_uint4(A.x, A.y, A.z, A.w), B, make_uint4(C.x, C.y, Cs.z, Cs.w), o, cid, nx, ny, nz);
                             const float tLimit = here ? tC : -INFINITY; // a lane that is not in this node sees no child
                             unsigned long long m[4];
                             uint32_t key[4];
 #pragma unroll
                             for (int k = 0; k < 4; k++) {
-                                const f2 qx = { (float)((qnx >> (8 * k)) & 0xFFu), (float)((qfx >> (8 * k)) & 0xFFu) };
-                                const f2 qy = { (float)((qny >> (8 * k)) & 0xFFu), (float)((qfy >> (8 * k)) & 0xFFu) };
-                                const f2 qz = { (float)((qnz >> (8 * k)) & 0xFFu), (float)((qfz >> (8 * k)) & 0xFFu) };
-                                const f2 tx = planePair(qx, kx, bx), ty = planePair(qy, ky, by), tz = planePair(qz, kz, bz);
-                                const float tmin = fmaxf(fmaxf(tx.x, ty.x), tz.x);
-                                const float tmax = fminf(fminf(tx.y, ty.y), tz.y);
+                                const f2 tt = childSlab(slab, k);
+                                const float tmin = tt.x, tmax = tt.y;
                                 const float tlo = fmaxf(tmin, 0.f);
                                 const bool vis = tmax >= tlo && tmin < tLimit; // bvh.cl:72,114
                                 m[k] = __builtin_amdgcn_ballot_w64(vis);
@@ -512,12 +492,13 @@ __global__ void __launch_bounds__(kPacketBlock, LENS ? (TWO_LEVEL ? PT_MULTI_MIN
                             for (uint32_t k = 0; k < n; k++) {
                                 const u4v ta = trisS[(first + k) * 3u + 0u], tb = trisS[(first + k) * 3u + 1u];
                                 const uint32_t tcx = trisS[(first + k) * 3u + 2u].x;
-                                const V3 v0 = mk(asF(ta.x), asF(ta.y), asF(ta.z)), e1 = mk(asF(ta.w), asF(tb.x), asF(tb.y)), e2 = mk(asF(tb.z), asF(tb.w), asF(tcx));
+                                V3 v0, e1, e2;
+                                triEdges(asF4(ta), asF4(tb), asF(tcx), &v0, &e1, &e2);
                                 V3 T, Q;
                                 float e2Q, det, u, v, t;
                                 triOriginHalf(o, v0, e1, e2, &T, &Q, &e2Q);
                                 triRayHalf(d, e1, e2, T, Q, e2Q, &det, &u, &v, &t);
-                                const bool hit = here && !(det > -FLT_MIN && det < FLT_MIN) && !(u < 0.f || u > 1.f) && !(v < 0.f || u + v > 1.f) && t > 0.f && t < tC;
+                                const bool hit = here && PT_TRI_HIT(det, u, v, t, tC);
                                 if (hit) {
                                     tC = t, u_ = u, v_ = v, hp = (int)(first + k);
                                     if constexpr (TWO_LEVEL)
@@ -543,16 +524,10 @@ __global__ void __launch_bounds__(kPacketBlock, LENS ? (TWO_LEVEL ? PT_MULTI_MIN
         for (int r = 0; r < R; r++) {
             const uint32_t idx = base + 64u * (uint32_t)r + lane;
             if (idx < count) {
-                int hp = hprim[r], hinst = -1;
+                int hinst = -1;
                 if constexpr (TWO_LEVEL)
                     hinst = (int)ldsSave[pwave][kSaveInst + r][lane];
-                if (hp >= 0 && hinst < 0) { // a world-space copy of an instance: back to (original triangle, instance)
-                    const float4 tc = sc.tris[hp].c;
-                    hp = (int)asU(tc.y);
-                    hinst = (int)asU(tc.z);
-                }
-                a.hit[idx] = make_float4(hp >= 0 ? tClosest[r] : INFINITY, hu[r], hv[r], asF((uint32_t)hp));
-                a.inst[idx] = hinst;
+                writeClosestHit(a, sc, idx, tClosest[r], hu[r], hv[r], hprim[r], hinst);
             }
         }
     }

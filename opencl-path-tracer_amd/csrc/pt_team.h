@@ -15,7 +15,7 @@
 // from any state the stack then grows by at most the tree's worst-case depth-first need, which ptamd.hip checks against kTeamStack before it
 // launches this kernel).
 #pragma once
-#include "pt_trace.h"
+#include "pt_walk.h"
 
 namespace ptd {
 
@@ -68,13 +68,7 @@ __global__ void __launch_bounds__(kTeamBlock, PT_TEAM_MIN_WAVES) k_trace_team(Tr
             rayIdx = nextRay;
             nextRay += totalTeams;
             float4 ro = a.rayO[rayIdx], rd = a.rayD[rayIdx];
-            // zero components are nudged as at k_trace's hand-out (NO_PARALLEL_RAYS, scene.cl:123-137)
-            if (rd.x == 0.0f) rd.x = FLT_MIN;
-            if (rd.y == 0.0f) rd.y = FLT_MIN;
-            if (rd.z == 0.0f) rd.z = FLT_MIN;
-            if (ro.x == 0.0f) ro.x = -FLT_MIN;
-            if (ro.y == 0.0f) ro.y = -FLT_MIN;
-            if (ro.z == 0.0f) ro.z = -FLT_MIN;
+            nudgeZero(ro, rd);
             co = xyz(ro), cd = xyz(rd);
             cid = mk(rcpSlab(cd.x), rcpSlab(cd.y), rcpSlab(cd.z));
             tBest = ANY_HIT ? ro.w : INFINITY;
@@ -98,12 +92,9 @@ __global__ void __launch_bounds__(kTeamBlock, PT_TEAM_MIN_WAVES) k_trace_team(Tr
         // leaf (2 x 48 B: leaves hold two at most since round 5; ptamd.hip keeps one record of slack behind both arrays)
         uint4 line[6];
         {
-#if PT_OFFSET32 // base + 32-bit byte offset (pt_trace.h)
+            // base + 32-bit byte offset as in fetchTri (pt_walk.h); its own copy: ONE address, selected between a node and a leaf's first record, serves the 96-byte fetch
             const uint4* at = isLeaf ? (const uint4*)((const char*)sc.tris + (size_t)(uint32_t)(refIndex(cur) * (uint32_t)sizeof(TriIsect)))
                                      : (const uint4*)((const char*)sc.wide + (size_t)(uint32_t)((isInner ? refIndex(cur) : 0u) << 6));
-#else
-            const uint4* at = isLeaf ? (const uint4*)&sc.tris[refIndex(cur)] : (const uint4*)&sc.wide[isInner ? refIndex(cur) : 0u];
-#endif
 #pragma unroll
             for (int q = 0; q < 6; q++)
                 line[q] = at[q];
@@ -117,62 +108,38 @@ __global__ void __launch_bounds__(kTeamBlock, PT_TEAM_MIN_WAVES) k_trace_team(Tr
         uint32_t ref[4] = { kRefFinish, kRefFinish, kRefFinish, kRefFinish };
         uint32_t nPush = 0;
         if (isInner) {
-            // -------- k_trace's inner step (pt_trace.h): four quantised child boxes, entry / exit planes by the sign of the direction ----------
+            // -------- k_trace's inner step (slabSetup / childSlab, pt_walk.h): four quantised child boxes, entry / exit planes by the sign of the direction ----------
             const uint4 A = line[0], B = line[1], D = line[3];
             const uint4 C = line[2];
-            const float ax = asF(A.w) * cid.x, ay = asF(C.z) * cid.y, az = asF(C.w) * cid.z;
-            const float bx = (asF(A.x) - co.x) * cid.x, by = (asF(A.y) - co.y) * cid.y, bz = (asF(A.z) - co.z) * cid.z;
-            const bool nx = cid.x < 0.f, ny = cid.y < 0.f, nz = cid.z < 0.f;
-            const uint32_t qnx = nx ? B.y : B.x, qfx = nx ? B.x : B.y;
-            const uint32_t qny = ny ? B.w : B.z, qfy = ny ? B.z : B.w;
-            const uint32_t qnz = nz ? C.y : C.x, qfz = nz ? C.x : C.y;
+            const SlabSetup slab = slabSetup(A, B, C, co, cid);
             float key[4];
             ref[0] = D.x, ref[1] = D.y, ref[2] = D.z, ref[3] = D.w;
 #pragma unroll
             for (int k = 0; k < 4; k++) {
-                const f2 qx = { (float)((qnx >> (8 * k)) & 0xFFu), (float)((qfx >> (8 * k)) & 0xFFu) };
-                const f2 qy = { (float)((qny >> (8 * k)) & 0xFFu), (float)((qfy >> (8 * k)) & 0xFFu) };
-                const f2 qz = { (float)((qnz >> (8 * k)) & 0xFFu), (float)((qfz >> (8 * k)) & 0xFFu) };
-                const f2 tx = planePair(qx, ax, bx), ty = planePair(qy, ay, by), tz = planePair(qz, az, bz);
-                const float tmin = fmaxf(fmaxf(tx.x, ty.x), tz.x);
-                const float tmax = fminf(fminf(tx.y, ty.y), tz.y);
-                const bool vis = tmax >= tmin && tmax >= 0.f && tmin < tCull; // the accept test of bvh.cl:72,114 on the (slightly larger) quantised box
-                key[k] = vis ? tmin : INFINITY;
+                const f2 tt = childSlab(slab, k);
+                const bool vis = tt.y >= tt.x && tt.y >= 0.f && tt.x < tCull; // the accept test of bvh.cl:72,114 on the (slightly larger) quantised box
+                key[k] = vis ? tt.x : INFINITY;
             }
-#define PT_TSWAP(i, j)                                   \
-    {                                                    \
-        const bool sw = key[j] < key[i];                 \
-        const float tk = sw ? key[j] : key[i];           \
-        key[j] = sw ? key[i] : key[j];                   \
-        key[i] = tk;                                     \
-        const uint32_t tr = sw ? ref[j] : ref[i];        \
-        ref[j] = sw ? ref[i] : ref[j];                   \
-        ref[i] = tr;                                     \
-    }
             // visible children first, nearest first (any hit: any order of the visible ones would do; the network also compacts them)
-            PT_TSWAP(0, 1) PT_TSWAP(2, 3) PT_TSWAP(0, 2) PT_TSWAP(1, 3) PT_TSWAP(1, 2)
-#undef PT_TSWAP
+            sort4Nearest(key, ref);
             nPush = (key[0] < INFINITY ? 1u : 0u) + (key[1] < INFINITY ? 1u : 0u) + (key[2] < INFINITY ? 1u : 0u) + (key[3] < INFINITY ? 1u : 0u);
         }
         bool occluder = false;
         if (isLeaf) {
-            // -------- leaf (scene.cl:168-195), Moeller-Trumbore as k_trace spells it (shapes.cl:20-72) --------------------------------------------
+            // -------- leaf (scene.cl:168-195), Moeller-Trumbore as every kernel spells it (shapes.cl:20-72; pt_walk.h) --------------------------------
             const uint32_t first = refIndex(cur), n = kind;
             for (uint32_t k = 0; k < n; k++) {
-                float4 ta, tb;
-                float tcx;
+                V3 v0, e1, e2;
                 if (k < 2u) {
                     const uint4 la = k == 0u ? line[0] : line[3], lb = k == 0u ? line[1] : line[4];
-                    ta = make_float4(asF(la.x), asF(la.y), asF(la.z), asF(la.w)), tb = make_float4(asF(lb.x), asF(lb.y), asF(lb.z), asF(lb.w));
-                    tcx = asF(k == 0u ? line[2].x : line[5].x);
-                } else { // (leaves of more than two triangles: PTAMD_MAX_LEAF, parity mode never gets here)
+                    triEdges(make_float4(asF(la.x), asF(la.y), asF(la.z), asF(la.w)), make_float4(asF(lb.x), asF(lb.y), asF(lb.z), asF(lb.w)), asF(k == 0u ? line[2].x : line[5].x), &v0, &e1, &e2);
+                } else { // (leaves of more than two triangles: PTAMD_MAX_LEAF, parity mode never gets here; plain indexing, not fetchTri: rare, and as it was compiled)
                     const TriIsect* tp = &sc.tris[first + k];
-                    ta = tp->a, tb = tp->b, tcx = tp->c.x;
+                    triEdges(tp->a, tp->b, tp->c.x, &v0, &e1, &e2);
                 }
-                const V3 v0 = mk(ta.x, ta.y, ta.z), e1 = mk(ta.w, tb.x, tb.y), e2 = mk(tb.z, tb.w, tcx);
                 float det, u, v, t;
                 triangleTest(co, cd, v0, e1, e2, &det, &u, &v, &t);
-                const bool hit = !(det > -FLT_MIN && det < FLT_MIN) && !(u < 0.f || u > 1.f) && !(v < 0.f || u + v > 1.f) && t > 0.f && t < tBest;
+                const bool hit = PT_TRI_HIT(det, u, v, t, tBest);
                 if (hit) {
                     if (ANY_HIT) {
                         occluder = true;
@@ -207,13 +174,8 @@ __global__ void __launch_bounds__(kTeamBlock, PT_TEAM_MIN_WAVES) k_trace_team(Tr
                 if (m == 0u) {
                     if (a.occluded)
                         a.occluded[rayIdx] = teamOccluded ? 1u : 0u;
-                    if (!teamOccluded) { // the deposit of intersectShadows (kernel.cl:132-135): one live path per accumulator entry, plain RMW
-                        const float4 contrib = a.rayC[rayIdx];
-                        const uint32_t pixel = asU(a.rayD[rayIdx].w);
-                        float4* ap = a.accum.at(asU(contrib.w) >> 16, pixel);
-                        float4 px = *ap;
-                        px.x += contrib.x, px.y += contrib.y, px.z += contrib.z;
-                        *ap = px;
+                    if (!teamOccluded) {
+                        depositUnoccluded(a, a.rayC[rayIdx], asU(a.rayD[rayIdx].w));
                         unoccluded++;
                     }
                 }
@@ -230,16 +192,8 @@ __global__ void __launch_bounds__(kTeamBlock, PT_TEAM_MIN_WAVES) k_trace_team(Tr
                     const bool better = op >= 0 && (bp < 0 || ot < bt || (ot == bt && op < bp));
                     bt = better ? ot : bt, bu = better ? ou : bu, bv = better ? ov : bv, bp = better ? op : bp;
                 }
-                if (m == 0u) {
-                    int hinst = -1;
-                    if (bp >= 0) { // a hit on a world-space copy of an instance: back to (original triangle, instance)
-                        const float4 tc = sc.tris[bp].c;
-                        bp = (int)asU(tc.y);
-                        hinst = (int)asU(tc.z);
-                    }
-                    a.hit[rayIdx] = make_float4(bp >= 0 ? bt : INFINITY, bu, bv, asF((uint32_t)bp));
-                    a.inst[rayIdx] = hinst;
-                }
+                if (m == 0u)
+                    writeClosestHit(a, sc, rayIdx, bt, bu, bv, bp, -1); // (one world-space tree: no instance is ever entered)
             }
             active = false;
             sp = 0;

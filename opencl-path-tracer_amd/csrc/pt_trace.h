@@ -20,7 +20,7 @@
 //    below); deeper entries spill to a lane-interleaved region in global memory;
 //  * 4-wide nodes with 8-bit quantised child boxes (WideNode, 64 B = four 16-byte loads for four children) at
 //    both levels, so one code path -- and one slot in the vote below -- serves both; entry/exit plane bytes are
-//    picked per ray-direction sign as whole dwords, planes are one packed FMA per pair
+//    picked per ray-direction sign as whole dwords, planes are one FMA each
 //    (q * (2^e / d) + (origin - o) / d, reciprocal clamped so axis-parallel rays stay NaN-free), the four
 //    (distance, reference) pairs go through a 5-comparator network, pushes are branch-free and the stack top is
 //    prefetched before the node fetch;
@@ -33,12 +33,9 @@
 //    in any order) -- in inner steps / in leaf steps / in both: 43.5 / 41.2 / 42.7 ms of any-hit traversal per batch against
 //    40.4: the near-first descent finds occluders sooner than fuller steps save.
 #pragma once
-#include "pt_shade.h"
-#include <type_traits>
+#include "pt_walk.h"
 
 namespace ptd {
-
-typedef float f2 __attribute__((ext_vector_type(2)));
 
 #ifndef PT_REFILL_IDLE
 #define PT_REFILL_IDLE 8 // hand out new rays once this many lanes are idle; with (PT_PARKED_BREAK, _ANY) = (32, 48): 4 / 8 / 12 / 16 -> 8 810 / 8 865 /
@@ -46,27 +43,12 @@ typedef float f2 __attribute__((ext_vector_type(2)));
 #ifndef PT_TRACE_MIN_WAVES
 #define PT_TRACE_MIN_WAVES 7
 #endif
-#ifndef PT_GUIDED_SPANS
-#define PT_GUIDED_SPANS 1 // > 0: a claim takes at most (entries left) / (waves x this); 0 / 1 / 2 / 4: 8.47 / 8.52 / 8.50 / 8.43 Grays/s
-#endif
 #ifndef PT_PARKED_BREAK
 #define PT_PARKED_BREAK 32 // (this, PT_PARKED_BREAK_ANY) at 8 idle lanes: (16, 24) / (24, 40) / (32, 48) / (40, 56) / (48, 60) -> 8 702 / 8 823 / 8 883 /
 #endif                     // 8 860 / 8 733 Mrays/s: every pass over the parked lanes costs the whole wave
-#ifndef PT_ANYHIT_SORT
-#define PT_ANYHIT_SORT 0
-#endif
 #ifndef PT_VOTE_INNER
 #define PT_VOTE_INNER 2 // an inner step runs when 2 * (lanes wanting one) >= 3 * (lanes wanting a leaf): leaf steps are the
 #define PT_VOTE_LEAF 3 // long ones (sequential triangle fetches), so they are not left waiting for a majority
-#endif
-#ifndef PT_PACKED_FMA
-#define PT_PACKED_FMA 0 // 1: the plane distances as 12 v_pk_fma_f32 instead of 24 v_fma_f32 (rounds 2-4; see fmaPlain: 11 040 -> 11 270 Mrays/s without them)
-#endif
-#ifndef PT_CLOSEST_SORT
-#define PT_CLOSEST_SORT 5
-#endif
-#ifndef PT_OFFSET32
-#define PT_OFFSET32 1
 #endif
 #ifndef PT_LDS_STACK
 #define PT_LDS_STACK 12 // 16 and 10 measure the same on the benchmark scene; deeper entries spill to global memory
@@ -98,144 +80,6 @@ constexpr int kRefillIdleLanes = PT_REFILL_IDLE; // hand out new rays once this 
 #ifndef PT_REFILL_IDLE_TL
 #define PT_REFILL_IDLE_TL 8 // the same in the instantiations that enter instances
 #endif
-
-struct TraceArgs {
-    SceneDev sc;
-    // closest-hit: rays from (rayO, rayD), results to (hit, inst)
-    // any-hit: rays from (shO, shD, shC); unoccluded contributions are added to accum
-    const float4* rayO;
-    const float4* rayD;
-    const float4* rayC;
-    float4* hit;
-    int32_t* inst;
-    AccumView accum;
-    uint32_t* occluded; // optional (test hook): 1/0 per shadow ray
-    // queue words of this launch, all in the sample's control block (one pointer + the pass index instead of three
-    // pointers: the any-hit kernel sits at the scalar-register limit of 7 waves per SIMD):
-    //   entries in the queue  ctl->extCount[pass] / shadowCount[pass]; fetch cursor (zero at launch)  ctl->extCursor[pass] /
-    //   shadowCursor[pass]; any-hit launches add their unoccluded rays (= accumulator updates) to ctl->depositsShadow
-    Control* ctl;
-    uint32_t pass;
-    // packet kernel, first pass of a batch: the camera rays are generated from the entry index instead of read from the queue
-    uint32_t fused;
-    uint32_t noOrigins; // fused bundles of a pinhole camera: only the direction (with the pixel in .w) is queued for k_shade, which knows the eye and derives the rest from the entry index
-    const uint32_t* pixelList;
-    FrameParams fp;
-    uint32_t* spill; // kSpillStack * totalThreads dwords
-    uint32_t totalThreads;
-    uint32_t parityShadow; // any-hit: entries carry a FINISHED flag in rayC.w (reference semantics)
-    // k_trace<., true>: the table of folded instance transforms, entry 1 + k = (1/s, w) of instance k (the identity for instances that take the general
-    // route), entry 0 = the identity; instFoldCount 0: nothing is folded (more instances than the table holds, parity mode, PT_FLAG_PARKED_INSTANCES)
-    // k_trace<., 2> (the general route): the ENTRY records, two float4 per instance -- (1 / s, w) and (root reference, simple flag, s, -); instFoldCount != 0: some
-    // entered instance is NOT a translation + uniform scale (its 3 x 4 rows are wanted)
-    const float4* instFold;
-    uint32_t instFoldCount;
-};
-
-#ifdef PT_TRACE_STATS
-// diagnostic build only (tools/variants.sh ... -DPT_TRACE_STATS): where do the lanes of a wave go?
-// [0] iterations, [1] sum of active lanes, [2..4] iterations per kind, [5..7] lanes served per kind, [8] hand-outs, [9] rays
-__device__ unsigned long long g_traceStats[64]; // [0..23] closest-hit launches, [24..47] any-hit launches, [48..63] packet kernel
-#define PT_STAT(i, v) statAcc[i] += (unsigned long long)(v)
-#define PT_TIC(t) const unsigned long long t = __builtin_readcyclecounter()
-#define PT_TOC(i, t) statAcc[i] += __builtin_readcyclecounter() - t
-#else
-#define PT_STAT(i, v)
-#define PT_TIC(t)
-#define PT_TOC(i, t)
-#endif
-
-// v_fma_f32 that stays a plain v_fma_f32 (the vectoriser would pack two of them into one v_pk_fma_f32: a half-rate instruction that competes with the
-// conversions, compares and selects around it, while a plain FP32 multiply-add next to one of those issues at about half its price -- measured,
-// profiles/round5/r5r_valu_issue_pairs.md: v_cmp / v_cndmask / v_min3 / v_cvt_f32_ubyte + v_fma_f32 pairs take 2.55 units against 2.0 for the half-rate one alone)
-__device__ inline float fmaPlain(float a, float b, float c)
-{
-    float r;
-    asm("v_fma_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
-    return r;
-}
-// 3 * x as one shift-add (the compiler turns "x * 48" and "(x + 2 x) << 4" alike into v_mul_lo_u32: a quarter-rate instruction)
-__device__ inline uint32_t times3(uint32_t x)
-{
-    uint32_t r;
-    asm("v_lshl_add_u32 %0, %1, 1, %1" : "=v"(r) : "v"(x));
-    return r;
-}
-// the distances to a child's entry and exit planes of one axis: q * a + b for both
-__device__ inline f2 planePair(const f2 q, const float a, const float b)
-{
-#if PT_PACKED_FMA
-    const f2 a2 = { a, a }, b2 = { b, b };
-    return __builtin_elementwise_fma(q, a2, b2);
-#else
-    return { fmaPlain(q.x, a, b), fmaPlain(q.y, a, b) };
-#endif
-}
-// Reciprocal direction for the slab test, clamped to +-1e18: a zero (or FLT_MIN, scene.cl:123-137)
-// component then yields plane distances of +-1e18 * (b - o) -- far beyond any scene, with the correct
-// sign -- instead of the inf - inf = NaN the one-FMA form would produce from an infinite reciprocal.
-__device__ inline float rcpSlab(float x) { return fminf(fmaxf(fastRcp(x), -1e18f), 1e18f); }
-
-// Moeller-Trumbore (shapes.cl:20-72), operation by operation.  Rounds 1-4 wrote the test as cross / dot expressions and left the choice of fused
-// multiply-adds to the compiler: every kernel then had to happen on the same choice ("the same hits as k_trace, to the bit" is what the tests of the
-// packet, bundle and team kernels assert), and a build option that changes the choice in one of them (round 5: -fno-slp-vectorize) moves
-// barycentrics in their fifth digit (cancellation in T x e1).  So the sequence those builds emitted is spelled out once, for every kernel:
-//   cross(a, b).x = fma(a.y, b.z, -(a.z * b.y))              dot(a, b) = fma(a.z, b.z, fma(a.x, b.x, a.y * b.y))
-//   det           = e1.z * P.z + fma(e1.x, P.x, e1.y * P.y)  (the last product rounded on its own)
-// The bundle kernel computes the origin half once per triangle and the ray half per ray; the others call triangleTest.
-__device__ inline V3 crossExact(const V3 a, const V3 b)
-{
-#pragma clang fp contract(off)
-    return mk(__builtin_fmaf(a.y, b.z, -(a.z * b.y)), __builtin_fmaf(a.z, b.x, -(a.x * b.z)), __builtin_fmaf(a.x, b.y, -(a.y * b.x)));
-}
-__device__ inline float dotExact(const V3 a, const V3 b)
-{
-#pragma clang fp contract(off)
-    return __builtin_fmaf(a.z, b.z, __builtin_fmaf(a.x, b.x, a.y * b.y));
-}
-// the half that only knows the origin
-__device__ inline void triOriginHalf(const V3 o, const V3 v0, const V3 e1, const V3 e2, V3* T, V3* Q, float* e2Q)
-{
-#pragma clang fp contract(off)
-    *T = mk(o.x - v0.x, o.y - v0.y, o.z - v0.z);
-    *Q = crossExact(*T, e1);
-    *e2Q = dotExact(e2, *Q);
-}
-// the half per ray: det (the caller rejects |det| < FLT_MIN), u, v, t
-__device__ inline void triRayHalf(const V3 d, const V3 e1, const V3 e2, const V3 T, const V3 Q, const float e2Q, float* det, float* u, float* v, float* t)
-{
-#pragma clang fp contract(off)
-    const V3 P = crossExact(d, e2);
-    const float pz = e1.z * P.z;
-    *det = pz + __builtin_fmaf(e1.x, P.x, e1.y * P.y);
-    const float inv = fastRcp(*det);
-    *u = dotExact(T, P) * inv;
-    *v = dotExact(d, Q) * inv;
-    *t = e2Q * inv;
-}
-__device__ inline void triangleTest(const V3 o, const V3 d, const V3 v0, const V3 e1, const V3 e2, float* det, float* u, float* v, float* t)
-{
-    V3 T, Q;
-    float e2Q;
-    triOriginHalf(o, v0, e1, e2, &T, &Q, &e2Q);
-    triRayHalf(d, e1, e2, T, Q, e2Q, det, u, v, t);
-}
-
-// A ray taken into an instance's space (scene.cl:116-139): rows r0..r2 of the inverse transform; the direction is NOT
-// renormalised, so t is shared between the two spaces; exactly-zero components are nudged (NO_PARALLEL_RAYS, scene.cl:123-137).
-// One spelling (explicit FMAs) for every kernel that enters instances, so that they produce the same bits.
-__device__ inline void rayIntoInstance(const float4 r0, const float4 r1, const float4 r2, const V3 o, const V3 d, V3* to, V3* td)
-{
-    *to = mk(fmaf(r0.x, o.x, fmaf(r0.y, o.y, fmaf(r0.z, o.z, r0.w))), fmaf(r1.x, o.x, fmaf(r1.y, o.y, fmaf(r1.z, o.z, r1.w))),
-        fmaf(r2.x, o.x, fmaf(r2.y, o.y, fmaf(r2.z, o.z, r2.w))));
-    *td = mk(fmaf(r0.x, d.x, fmaf(r0.y, d.y, r0.z * d.z)), fmaf(r1.x, d.x, fmaf(r1.y, d.y, r1.z * d.z)), fmaf(r2.x, d.x, fmaf(r2.y, d.y, r2.z * d.z)));
-    if (td->x == 0.0f) td->x = FLT_MIN;
-    if (td->y == 0.0f) td->y = FLT_MIN;
-    if (td->z == 0.0f) td->z = FLT_MIN;
-    if (to->x == 0.0f) to->x = -FLT_MIN;
-    if (to->y == 0.0f) to->y = -FLT_MIN;
-    if (to->z == 0.0f) to->z = -FLT_MIN;
-}
 
 // TWO_LEVEL: the tree holds instance references (instances that were not copied to world space at upload); scenes that are one
 // world-space tree run the instantiation without the instance code.  Entering and leaving an instance are PARKED steps (served in
@@ -298,6 +142,27 @@ __global__ void __launch_bounds__(kTraceBlock, LEVELS == 2 ? PT_TRACE_MIN_WAVES_
     const uint32_t wave = threadIdx.x >> 6;
     const uint32_t gtid = blockIdx.x * kTraceBlock + threadIdx.x;
 #define spill (a.spill + gtid) /* entry e at spill[e * totalThreads]; recomputed where used (rare) to save two registers */
+    // Ray finished: closestT != maxT decides hit/miss (scene.cl:257); a shadow ray only gets here unoccluded (an occluded one retires in its leaf step).
+    // ONE definition for the two special-step schemes below -- as a macro, with the closest hit written in place (writeClosestHit's arithmetic, pt_walk.h, on the
+    // lane's own registers): as a lambda like push / pop it costs k_trace<false, 0> 12 bytes of scratch, as a function, or with the record passed on by value, the
+    // three closest-hit instantiations come out with another schedule
+#define finishRay()                                                                                                  \
+    {                                                                                                                \
+        if (ANY_HIT) {                                                                                               \
+            if (a.occluded)                                                                                          \
+                a.occluded[rayIdx] = 0u;                                                                             \
+            depositUnoccluded(a, a.rayC[rayIdx], asU(a.rayD[rayIdx].w));                                             \
+        } else {                                                                                                     \
+            if (hprim >= 0 && hinst < 0) { /* hit on a world-space copy of an instance: back to (original triangle, instance) */ \
+                const float4 tc = sc.tris[hprim].c;                                                                  \
+                hprim = (int)asU(tc.y);                                                                              \
+                hinst = (int)asU(tc.z);                                                                              \
+            }                                                                                                        \
+            a.hit[rayIdx] = make_float4(hprim >= 0 ? tClosest : INFINITY, hu, hv, asF((uint32_t)hprim));             \
+            a.inst[rayIdx] = hinst;                                                                                  \
+        }                                                                                                            \
+        active = false;                                                                                              \
+    }
     const uint32_t total = a.totalThreads;
     const uint32_t count = ANY_HIT ? a.ctl->shadowCount[a.pass] : a.ctl->extCount[a.pass];
     const SceneDev& sc = a.sc;
@@ -332,14 +197,8 @@ __global__ void __launch_bounds__(kTraceBlock, LEVELS == 2 ? PT_TRACE_MIN_WAVES_
         return v;
     };
 
-#ifdef PT_TRACE_STATS
-    unsigned long long statAcc[24] = {};
+    PT_STAT_BEGIN;
     PT_TIC(tKernel);
-    // round 5, any-hit launches: does an occluded shadow ray die in the leaf that stopped the previous occluded ray of its lane / of its wave?
-    // [19] occluded rays, [20] ... in the leaf of the lane's previous occluded ray, [21] ... in the leaf that last stopped ANY ray of the wave (in an
-    // earlier iteration), [22] ... on the very triangle of the lane's previous one, [23] ... whose leaf is one of the wave's last FOUR occluder leaves
-    uint32_t statLaneLeaf = 0xFFFFFFFFu, statLaneTri = 0xFFFFFFFFu, statWaveLeaf[4] = { 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu };
-#endif
     bool active = false;
     bool exhausted = false; // wave-uniform: queue has no more rays
     uint32_t rayIdx = 0;
@@ -356,8 +215,6 @@ __global__ void __launch_bounds__(kTraceBlock, LEVELS == 2 ? PT_TRACE_MIN_WAVES_
             v = ((const volatile uint32_t*)spill)[(size_t)(sp - 1 - kLdsStack) * total];
         return v;
     };
-
-
     auto setRay = [&](V3 o, V3 d) {
         co = o;
         cd = d;
@@ -379,14 +236,10 @@ __global__ void __launch_bounds__(kTraceBlock, LEVELS == 2 ? PT_TRACE_MIN_WAVES_
     auto requestPacket = [&]() {
         if (spanNext >= spanEnd) {
             uint32_t base = 0xFFFFFFC0u; // "nothing left"
-            uint32_t claim = spanSize;
-#if PT_GUIDED_SPANS
-            // guided self-scheduling: towards the end of the queue claim less, so that no wave is left with a long
-            // span while the others have run dry (`spanEnd`, this wave's previous claim, lags the cursor: an upper
-            // bound of what is left)
+            // guided self-scheduling (kGuidedSpans): towards the end of the queue claim less (`spanEnd`, this wave's previous claim, lags the
+            // cursor: an upper bound of what is left)
             const uint32_t left = count > spanEnd ? count - spanEnd : 0u;
-            claim = min(spanSize, max(64u, (left / (totalWaves * PT_GUIDED_SPANS)) & ~63u));
-#endif
+            const uint32_t claim = min(spanSize, max(64u, (left / (totalWaves * kGuidedSpans)) & ~63u));
             // (small launches -- the passes of a 1-spp frame -- are covered by the static packets: no dynamic part, and no wave asks the
             // cursor just to learn that: 7 168 such atomics were ~80 us of a 100-250 us launch)
             if (gwave * 64u < count && (count + 63u) / 64u > totalWaves) {
@@ -455,16 +308,7 @@ __global__ void __launch_bounds__(kTraceBlock, LEVELS == 2 ? PT_TRACE_MIN_WAVES_
                         }
                         if (live) {
                             rayIdx = idx;
-                            // The reference nudges exactly-zero components of the ray it takes into an instance
-                            // (NO_PARALLEL_RAYS, scene.cl:123-137).  Instances copied to world space are never "entered",
-                            // so the same nudge is applied to the world-space ray: identical for the identity and
-                            // axis-aligned transforms, and the top-level box tests do not notice 1e-38.
-                            if (rd.x == 0.0f) rd.x = FLT_MIN;
-                            if (rd.y == 0.0f) rd.y = FLT_MIN;
-                            if (rd.z == 0.0f) rd.z = FLT_MIN;
-                            if (ro.x == 0.0f) ro.x = -FLT_MIN;
-                            if (ro.y == 0.0f) ro.y = -FLT_MIN;
-                            if (ro.z == 0.0f) ro.z = -FLT_MIN;
+                            nudgeZero(ro, rd);
                             setRay(xyz(ro), xyz(rd));
                             tClosest = tMax;
                             hprim = -1;
@@ -513,37 +357,13 @@ __global__ void __launch_bounds__(kTraceBlock, LEVELS == 2 ? PT_TRACE_MIN_WAVES_
                         ldsDeposits[wave] += nFin;
                 }
                 if (finishing) {
-                    // -------- ray finished: closestT != maxT decides hit/miss (scene.cl:257) ------------
-                    if (ANY_HIT) {
-                        if (a.occluded)
-                            a.occluded[rayIdx] = 0u;
-                        const float4 contrib = a.rayC[rayIdx];
-                        const uint32_t pixel = asU(a.rayD[rayIdx].w);
-                        float4* ap = a.accum.at(asU(contrib.w) >> 16, pixel); // one live path per entry: plain RMW
-                        float4 px = *ap;
-                        px.x += contrib.x, px.y += contrib.y, px.z += contrib.z;
-                        *ap = px;
-                    } else {
-                        if (hprim >= 0 && hinst < 0) { // hit on a world-space copy of an instance: back to (original triangle, instance)
-                            const float4 tc = sc.tris[hprim].c;
-                            hprim = (int)asU(tc.y);
-                            hinst = (int)asU(tc.z);
-                        }
-                        a.hit[rayIdx] = make_float4(hprim >= 0 ? tClosest : INFINITY, hu, hv, asF((uint32_t)hprim));
-                        a.inst[rayIdx] = hinst;
-                    }
-                    active = false;
+                    finishRay()
                 } else if (wantSpecial) {
                     V3 wo = co, wd = cd; // the world-space ray: still in the registers, unless the lane comes out of an instance
-                    if (leaving) {
+                    if (leaving) { // ... then from the queue again, with the hand-out's fix-up (instances are rarely entered: ptamd.hip copies them to world space)
                         const float4 qo = a.rayO[rayIdx], qd = a.rayD[rayIdx];
                         wo = xyz(qo), wd = xyz(qd);
-                        if (wd.x == 0.0f) wd.x = FLT_MIN;
-                        if (wd.y == 0.0f) wd.y = FLT_MIN;
-                        if (wd.z == 0.0f) wd.z = FLT_MIN;
-                        if (wo.x == 0.0f) wo.x = -FLT_MIN;
-                        if (wo.y == 0.0f) wo.y = -FLT_MIN;
-                        if (wo.z == 0.0f) wo.z = -FLT_MIN;
+                        nudgeZero(wo, wd);
                     }
                     if (refCount(cur) == kRefSpecial) {
                         // -------- enter instance refIndex(cur) (scene.cl:116-139); instances are only ever entered from world space
@@ -568,7 +388,8 @@ __global__ void __launch_bounds__(kTraceBlock, LEVELS == 2 ? PT_TRACE_MIN_WAVES_
                 }
             }
         } else {
-            // ---- resolve special references (instance entry / leave, end of traversal) -------------------
+            // ---- resolve special references: in these instantiations the end of a traversal alone (one world-space tree has no instance
+            // references, GENERAL enters them in its leaf steps) -------------------
             // They are kept OUT of the hot loop below: lanes that reach one park until the loop breaks, then all
             // of them are served here at once.  The hot loop thus only ever changes (cur, sp, closest hit) and
             // the ray-space registers stay loop-invariant in it.
@@ -584,57 +405,8 @@ __global__ void __launch_bounds__(kTraceBlock, LEVELS == 2 ? PT_TRACE_MIN_WAVES_
                     if (lane == 0)
                         ldsDeposits[wave] += nFin;
                 }
-                if (wantSpecial) {
-                    const uint32_t what = refIndex(cur);
-                    if (what == kSpecialFinish) {
-                        // -------- ray finished: closestT != maxT decides hit/miss (scene.cl:257) ------------
-                        if (ANY_HIT) {
-                            if (a.occluded)
-                                a.occluded[rayIdx] = 0u;
-                            const float4 contrib = a.rayC[rayIdx];
-                            const uint32_t pixel = asU(a.rayD[rayIdx].w);
-                            float4* ap = a.accum.at(asU(contrib.w) >> 16, pixel); // one live path per entry: plain RMW
-                            float4 px = *ap;
-                            px.x += contrib.x, px.y += contrib.y, px.z += contrib.z;
-                            *ap = px;
-                        } else {
-                            if (hprim >= 0 && hinst < 0) { // hit on a world-space copy of an instance: back to (original triangle, instance)
-                                const float4 tc = sc.tris[hprim].c;
-                                hprim = (int)asU(tc.y);
-                                hinst = (int)asU(tc.z);
-                            }
-                            a.hit[rayIdx] = make_float4(hprim >= 0 ? tClosest : INFINITY, hu, hv, asF((uint32_t)hprim));
-                            a.inst[rayIdx] = hinst;
-                        }
-                        active = false;
-                    } else if (TWO_LEVEL) {
-                        if (what == kSpecialLeaveInstance) {
-                            // -------- back to world space ---------------------------------------------------------
-                            {   // the world-space ray again, from the queue (instances are rarely entered: ptamd.hip copies them to world space)
-                                float4 wo = a.rayO[rayIdx], wd = a.rayD[rayIdx];
-                                if (wd.x == 0.0f) wd.x = FLT_MIN;
-                                if (wd.y == 0.0f) wd.y = FLT_MIN;
-                                if (wd.z == 0.0f) wd.z = FLT_MIN;
-                                if (wo.x == 0.0f) wo.x = -FLT_MIN;
-                                if (wo.y == 0.0f) wo.y = -FLT_MIN;
-                                if (wo.z == 0.0f) wo.z = -FLT_MIN;
-                                setRay(xyz(wo), xyz(wd));
-                            }
-                            curInst = -1;
-                            cur = sp > 0 ? pop(--sp) : kRefFinish;
-                        } else {
-                            // -------- enter instance `what` (scene.cl:116-139); instances are only ever entered from world space
-                            const Instance in = sc.instances[what];
-                            V3 to, td;
-                            rayIntoInstance(in.r0, in.r1, in.r2, co, cd, &to, &td);
-                            setRay(to, td);
-                            curInst = (int)what; // instance index; pt_intersect reports the top-level leaf
-                            push(sp, kRefLeaveInstance);
-                            sp++;
-                            cur = in.rootRef;
-                        }
-                    }
-                }
+                if (wantSpecial && refIndex(cur) == kSpecialFinish)
+                    finishRay()
             }
         }
         PT_TOC(13, tSpec);
@@ -668,9 +440,6 @@ __global__ void __launch_bounds__(kTraceBlock, LEVELS == 2 ? PT_TRACE_MIN_WAVES_
                 PT_STAT(2, 1);
                 PT_STAT(5, nInner);
                 PT_TIC(tInner);
-#ifdef PT_TRACE_STATS
-                bool statInside = false;
-#endif
                 if (wantInner) {
                     // -------- inner step at either level: one 64-byte fetch, FOUR quantised child boxes ----------
                     // TWO_LEVEL: the lane's instance and its table entry, ahead of the node fetch (the LDS read hides under it)
@@ -694,26 +463,11 @@ __global__ void __launch_bounds__(kTraceBlock, LEVELS == 2 ? PT_TRACE_MIN_WAVES_
                         genO = mk(ldsObj[wave][0][slot], ldsObj[wave][1][slot], ldsObj[wave][2][slot]);
                         genI = mk(ldsObj[wave][3][slot], ldsObj[wave][4][slot], ldsObj[wave][5][slot]);
                     }
-#if PT_OFFSET32
-                    // base (scalar registers) + 32-bit byte offset: one shift instead of two 64-bit vector operations per step (nodes < 4 GB: checked at upload)
+                    // base (scalar registers) + 32-bit byte offset: one shift instead of two 64-bit vector operations per step (nodes < 4 GB: refused at upload otherwise)
                     const uint4* wp = (const uint4*)((const char*)sc.wide + (size_t)(uint32_t)(refIndex(cur) << 6));
-#else
-                    const uint4* wp = (const uint4*)&sc.wide[refIndex(cur)];
-#endif
                     const uint4 A = wp[0], B = wp[1];
                     const uint4 C = wp[2];
                     const uint4 D = wp[3];
-#ifdef PT_EXTRA_LOADS // diagnostic: how sensitive is the kernel to vector-memory instruction count?
-                    uint32_t extra = 0;
-                    for (int q = 0; q < PT_EXTRA_LOADS; q++) {
-                        typedef uint32_t u4 __attribute__((ext_vector_type(4)));
-                        const u4 E = __builtin_nontemporal_load((const u4*)wp + (q & 3)); // distinct instruction, not CSE'd with A..D
-                        asm volatile("" : "+v"(extra));
-                        extra ^= E.x;
-                    }
-                    if (extra == 0x12345u) // never true for real nodes; keeps the loads alive
-                        tClosest = 0.f;
-#endif
                     // the ray in the node's space (TWO_LEVEL: object-space nodes are seen through the lane's instance, see the top)
                     V3 no = co, nid = cid;
                     if constexpr (TWO_LEVEL) {
@@ -724,112 +478,57 @@ __global__ void __launch_bounds__(kTraceBlock, LEVELS == 2 ? PT_TRACE_MIN_WAVES_
                         no = mk(fmaf(co.x, genM, genO.x), fmaf(co.y, genM, genO.y), fmaf(co.z, genM, genO.z));
                         nid = mk(fmaf(cid.x, genM, genI.x), fmaf(cid.y, genM, genI.y), fmaf(cid.z, genM, genI.z));
                     }
-                    // box plane = origin + scale * q  =>  t = q * (scale / d) + (origin - o) / d : one FMA per plane
-                    const float ax = asF(A.w) * nid.x, ay = asF(C.z) * nid.y, az = asF(C.w) * nid.z;
-                    // (origin - o) / d from the live registers: keeping -o/d around as well would cost three VGPRs, and 72 is
-                    // what 7 waves per SIMD allow
-                    const float bx = (asF(A.x) - no.x) * nid.x, by = (asF(A.y) - no.y) * nid.y, bz = (asF(A.z) - no.z) * nid.z;
-                    // entry / exit planes chosen by the sign of the ray direction (whole dwords: 4 children at once)
-                    // instead of min/max per plane pair; an empty slot is an inverted box (q 255..0) and can never
-                    // satisfy exit >= entry -- and if round-off ever made it, its reference is a degenerate triangle
-                    const bool nx = nid.x < 0.f, ny = nid.y < 0.f, nz = nid.z < 0.f;
-                    const uint32_t qnx = nx ? B.y : B.x, qfx = nx ? B.x : B.y;
-                    const uint32_t qny = ny ? B.w : B.z, qfy = ny ? B.z : B.w;
-                    const uint32_t qnz = nz ? C.y : C.x, qfz = nz ? C.x : C.y;
+                    const SlabSetup slab = slabSetup(A, B, C, no, nid);
                     float key[4];
                     uint32_t ref[4] = { D.x, D.y, D.z, D.w };
-#ifdef PT_TRACE_STATS
-                    bool inside = false;
-#endif
 #pragma unroll
                     for (int k = 0; k < 4; k++) {
-                        const f2 qx = { (float)((qnx >> (8 * k)) & 0xFFu), (float)((qfx >> (8 * k)) & 0xFFu) };
-                        const f2 qy = { (float)((qny >> (8 * k)) & 0xFFu), (float)((qfy >> (8 * k)) & 0xFFu) };
-                        const f2 qz = { (float)((qnz >> (8 * k)) & 0xFFu), (float)((qfz >> (8 * k)) & 0xFFu) };
-                        const f2 tx = planePair(qx, ax, bx), ty = planePair(qy, ay, by), tz = planePair(qz, az, bz);
-                        const float tmin = fmaxf(fmaxf(tx.x, ty.x), tz.x);
-                        const float tmax = fminf(fminf(tx.y, ty.y), tz.y);
+                        const f2 tt = childSlab(slab, k);
                         // accept test of bvh.cl:72,114 on the (slightly larger) quantised box
-                        const bool vis = tmax >= tmin && tmax >= 0.f && tmin < tClosest;
-                        key[k] = vis ? tmin : INFINITY;
-#ifdef PT_TRACE_STATS
-                        inside = inside || (vis && tmin <= 0.f); // the ray starts inside this child's box
-#endif
+                        const bool vis = tt.y >= tt.x && tt.y >= 0.f && tt.x < tClosest;
+                        key[k] = vis ? tt.x : INFINITY;
                     }
-#ifdef PT_TRACE_STATS
-                    // [18] lane-steps whose node has a child that contains the ray's origin ("re-finding the surface the ray starts on")
-                    statInside = inside;
-#endif
-#define PT_VISIBLE(k) (key[k] < INFINITY ? 1 : 0)
-                    // sort the four (entry distance, reference) pairs: nearest first (5-comparator network)
-#define PT_CSWAP(i, j)                                   \
-    {                                                    \
-        const bool sw = key[j] < key[i];                 \
-        const float tk = sw ? key[j] : key[i];           \
-        key[j] = sw ? key[i] : key[j];                   \
-        key[i] = tk;                                     \
-        const uint32_t tr = sw ? ref[j] : ref[i];        \
-        ref[j] = sw ? ref[i] : ref[j];                   \
-        ref[i] = tr;                                     \
-    }
-#if PT_ANYHIT_SORT == 0
-                    if (ANY_HIT) { // any occluder will do: only move the nearest visible child to the front
-                        PT_CSWAP(0, 1) PT_CSWAP(2, 3) PT_CSWAP(0, 2)
-                    } else
-#endif
-                    {
-#if PT_CLOSEST_SORT == 3 // (experiments: the nearest first, the others as they come / nearest first and farthest last)
-                        PT_CSWAP(0, 1) PT_CSWAP(2, 3) PT_CSWAP(0, 2)
-#elif PT_CLOSEST_SORT == 4
-                        PT_CSWAP(0, 1) PT_CSWAP(2, 3) PT_CSWAP(0, 2) PT_CSWAP(1, 3)
-#else
-                        PT_CSWAP(0, 1) PT_CSWAP(2, 3) PT_CSWAP(0, 2) PT_CSWAP(1, 3) PT_CSWAP(1, 2)
-#endif
-                    }
-#undef PT_CSWAP
+                    auto visible = [&](int k) { return key[k] < INFINITY ? 1 : 0; };
+                    if (ANY_HIT)
+                        sort4NearestToFront(key, ref);
+                    else
+                        sort4Nearest(key, ref);
                     // farthest first onto the stack, continue with the nearest
                     if (sp + 3 <= kLdsStack) {
                         // common case, branch-free: every candidate is stored, the stack pointer only moves past the
                         // ones that are kept (a rejected one is overwritten by the next store)
                         ldsStack[wave][sp][lane] = ref[3];
-                        sp += (int)PT_VISIBLE(3);
+                        sp += visible(3);
                         ldsStack[wave][sp][lane] = ref[2];
-                        sp += (int)PT_VISIBLE(2);
+                        sp += visible(2);
                         ldsStack[wave][sp][lane] = ref[1];
-                        sp += (int)PT_VISIBLE(1);
+                        sp += visible(1);
                     } else {
-                        if (PT_VISIBLE(3)) {
+                        if (visible(3)) {
                             push(sp, ref[3]);
                             sp++;
                         }
-                        if (PT_VISIBLE(2)) {
+                        if (visible(2)) {
                             push(sp, ref[2]);
                             sp++;
                         }
-                        if (PT_VISIBLE(1)) {
+                        if (visible(1)) {
                             push(sp, ref[1]);
                             sp++;
                         }
                     }
                     // no visible child => nothing was pushed => the prefetched stack top is still the top
                     const uint32_t next = popTop(stackTop);
-                    if (PT_VISIBLE(0))
+                    if (visible(0))
                         cur = ref[0];
                     else
                         cur = next, sp = max(sp - 1, 0);
-#undef PT_VISIBLE
                 }
-#ifdef PT_TRACE_STATS
-                PT_STAT(18, __popcll(__ballot(statInside)));
-#endif
                 PT_TOC(11, tInner);
             } else {
                 PT_STAT(3, 1);
                 PT_STAT(6, nLeaf);
                 PT_TIC(tLeaf);
-#ifdef PT_TRACE_STATS
-                bool stOcc = false, stLane = false, stWave = false, stTri = false, stWave4 = false;
-#endif
                 if (GENERAL && wantLeaf && kindBits == kRefSpecial) {
                     // -------- enter instance refIndex(cur) (scene.cl:116-139): a leaf-kind step.  The lane's registers keep the world-space ray; the
                     // instance-space ray goes into the lane's LDS slot, where the steps on the instance's nodes and triangles read it
@@ -885,30 +584,15 @@ __global__ void __launch_bounds__(kTraceBlock, LEVELS == 2 ? PT_TRACE_MIN_WAVES_
                         ld_ = mk(cd.x * is.x, cd.y * is.x, cd.z * is.x);
                     }
                     bool done = false;
-#ifdef PT_TRACE_STATS
-                    uint32_t statTri = 0xFFFFFFFFu;
-#endif
                     for (uint32_t k = 0; k < n; k++) {
-#if PT_OFFSET32
-                        static_assert(sizeof(TriIsect) == 48, "48 = 3 << 4: a shift-add and a shift instead of a quarter-rate 32-bit multiply");
-                        const uint32_t ti = first + k;
-                        const TriIsect* tp = (const TriIsect*)((const char*)sc.tris + (size_t)(uint32_t)(times3(ti) << 4));
-#else
-                        const TriIsect* tp = &sc.tris[first + k];
-#endif
-                        const float4 ta = tp->a, tb = tp->b;
-                        const float tcx = tp->c.x;
-                        const V3 v0 = mk(ta.x, ta.y, ta.z), e1 = mk(ta.w, tb.x, tb.y), e2 = mk(tb.z, tb.w, tcx);
+                        V3 v0, e1, e2;
+                        fetchTri(sc, first + k, &v0, &e1, &e2);
                         float det, u, v, t;
                         triangleTest(lo_, ld_, v0, e1, e2, &det, &u, &v, &t);
-                        const bool hit = !(det > -FLT_MIN && det < FLT_MIN) && !(u < 0.f || u > 1.f) && !(v < 0.f || u + v > 1.f) && t > 0.f
-                            && t < tClosest;
+                        const bool hit = PT_TRI_HIT(det, u, v, t, tClosest);
                         if (hit) {
                             if (ANY_HIT) {
                                 done = true;
-#ifdef PT_TRACE_STATS
-                                statTri = first + k;
-#endif
                                 break;
                             }
                             tClosest = t;
@@ -918,16 +602,6 @@ __global__ void __launch_bounds__(kTraceBlock, LEVELS == 2 ? PT_TRACE_MIN_WAVES_
                             hinst = (TWO_LEVEL || GENERAL) ? (inObject ? curInst : -1) : curInst;
                         }
                     }
-#ifdef PT_TRACE_STATS
-                    if (ANY_HIT && done) {
-                        stOcc = true;
-                        stLane = cur == statLaneLeaf;
-                        stWave = cur == statWaveLeaf[0];
-                        stTri = statTri == statLaneTri;
-                        stWave4 = cur == statWaveLeaf[0] || cur == statWaveLeaf[1] || cur == statWaveLeaf[2] || cur == statWaveLeaf[3];
-                        statLaneLeaf = cur, statLaneTri = statTri;
-                    }
-#endif
                     if (ANY_HIT && done) { // occluded: nothing to deposit
                         if (a.occluded)
                             a.occluded[rayIdx] = 1u;
@@ -938,23 +612,6 @@ __global__ void __launch_bounds__(kTraceBlock, LEVELS == 2 ? PT_TRACE_MIN_WAVES_
                         sp = max(sp - 1, 0);
                     }
                 }
-#ifdef PT_TRACE_STATS
-                if (ANY_HIT) { // the leaves that stopped rays in this step become the wave's most recent occluder leaves (up to four, newest first)
-                    PT_STAT(19, __popcll(__ballot(stOcc)));
-                    PT_STAT(20, __popcll(__ballot(stLane)));
-                    PT_STAT(21, __popcll(__ballot(stWave)));
-                    PT_STAT(22, __popcll(__ballot(stTri)));
-                    PT_STAT(23, __popcll(__ballot(stWave4)));
-                    unsigned long long stopped = __ballot(stOcc);
-                    for (int q = 0; q < 4 && stopped; q++) {
-                        const int src = __builtin_ctzll(stopped);
-                        stopped &= stopped - 1ull;
-                        const uint32_t leaf = (uint32_t)__shfl((int)statLaneLeaf, src);
-                        if (leaf != statWaveLeaf[0] && leaf != statWaveLeaf[1] && leaf != statWaveLeaf[2] && leaf != statWaveLeaf[3])
-                            statWaveLeaf[3] = statWaveLeaf[2], statWaveLeaf[2] = statWaveLeaf[1], statWaveLeaf[1] = statWaveLeaf[0], statWaveLeaf[0] = leaf;
-                    }
-                }
-#endif
                 PT_TOC(12, tLeaf);
             }
         }
@@ -962,13 +619,10 @@ __global__ void __launch_bounds__(kTraceBlock, LEVELS == 2 ? PT_TRACE_MIN_WAVES_
     if (ANY_HIT && lane == 0 && ldsDeposits[wave])
         atomicAdd(&a.ctl->depositsShadow, ldsDeposits[wave]);
     PT_TOC(10, tKernel);
-#ifdef PT_TRACE_STATS
-    if (lane == 0)
-        for (int i = 0; i < 24; i++)
-            atomicAdd(&g_traceStats[i + (ANY_HIT ? 24 : 0)], statAcc[i]);
-#endif
+    PT_STAT_END(ANY_HIT ? 24 : 0);
 }
 
 #undef spill
+#undef finishRay
 
 } // namespace ptd

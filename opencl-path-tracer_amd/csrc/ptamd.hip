@@ -228,7 +228,7 @@ const char* pt_version(void) { return "ptamd 0.1 (gfx950)"; }
 
 #ifdef PT_TRACE_STATS
 // diagnostic builds only: read and clear the traversal-loop counters
-int pt_debug_trace_stats(unsigned long long* out, unsigned int n) // n <= 64 counters (pt_trace.h, g_traceStats)
+int pt_debug_trace_stats(unsigned long long* out, unsigned int n) // n <= 64 counters (pt_walk.h, g_traceStats)
 {
     n = std::min(n, 64u);
     if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_traceStats), sizeof(unsigned long long) * n) != hipSuccess)
@@ -786,7 +786,7 @@ int pt_upload_dynamic_async(pt_ctx* c, const pt_emissive_triangle* lights, uint3
     const size_t staticNodes = sg.host.wide.size(), staticTris = (size_t)c->st->host.numTris + 1;
     // (+ 1: the SMALL traversal instantiations fetch 96 bytes from wherever a lane stands -- 32 beyond a node, 48 beyond a one-triangle leaf)
     const size_t needWide = staticNodes + h.topSlots + h.bakedNodes + h.instRoots.size() + 1, needTris = staticTris + h.bakedTris + 1;
-    // the traversal kernels address nodes and triangle records by base + 32-bit byte offset (pt_trace.h, PT_OFFSET32)
+    // the traversal kernels address nodes and triangle records by base + 32-bit byte offset (fetchTri, pt_walk.h; the node fetches of pt_trace.h and pt_team.h)
     uint64_t offsetLimit = 0xFFFFFFFFull;
     if (const char* e = getenv("PTAMD_OFFSET_LIMIT")) // (tests: the refusal below without a 4 GB scene)
         offsetLimit = std::min<uint64_t>(offsetLimit, strtoull(e, nullptr, 10));
