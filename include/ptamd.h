@@ -372,7 +372,19 @@ typedef struct {
     int32_t* inst; /* top-level LEAF node index of the hit instance, -1 on miss */
 } pt_hits_soa;
 /* traceRay (assets/cl/scene.cl:61-271) over n rays; any_hit selects intersectShadows semantics.
- * repeat > 1 re-runs the launch for timing; ms_out (optional) receives the mean device ms per launch. */
+ * repeat > 1 re-runs the launch for timing; ms_out (optional) receives the mean device ms per launch.
+ * Directions need not be normalised: t (and an any-hit ray's tmax) is in units of |d|, as in the reference, which never renormalises a direction it
+ * takes into an instance.  Instances may carry any invertible transform: mirrors, negative and non-uniform scales, shears.
+ * Guaranteed by tests/test_gpu_transforms.py for every traversal kernel: a scene in units 2^k times smaller (k = -20 ... 20 on scenes a few units across:
+ * coordinates from 1e-9 to 2e7) gives the same triangle, instance and u / v BITS and t times 2^k exactly, and a direction 2^k times longer (k = -12 ... 12)
+ * the same with t times 2^-k.  The kernels hold three absolute constants (csrc/pt_walk.h), none of which acts inside that range: an exactly-zero component
+ * of origin or direction becomes -+FLT_MIN (the reference's NO_PARALLEL_RAYS); the reciprocal of a direction component is clamped at +-1e18 for the slab
+ * test, which changes it for any component below 1e-18 in magnitude, nudged or not; a triangle is rejected where |det| = |e1 . (d x e2)| < FLT_MIN
+ * (1.2e-38: about |d| times twice its area).  Outside the range they do act, and results are no longer equivariant.
+ * One departure from the reference follows from where the nudge is applied: a ray whose origin lies EXACTLY in the plane of a triangle of an instance that
+ * is translated along that plane's normal and was copied to world space meets it at t = 0 and reports no hit (as exact arithmetic does), whether it leaves
+ * the plane or runs in it; the reference, nudging in the instance's space, reports that triangle (at t = FLT_MIN / d for a ray that leaves the plane).
+ * Pinned by test_rays_that_start_in_the_plane_of_a_translated_copied_quad. */
 int pt_intersect(pt_ctx* ctx, const pt_rays_soa* rays, uint32_t n, int any_hit, pt_hits_soa* hits, uint32_t repeat, float* ms_out);
 /* generatePrimaryRays (kernel.cl:24-84) for sample index `sample`: first n owned pixels, SoA out. */
 int pt_gen_rays(pt_ctx* ctx, uint32_t sample, uint32_t n, float* ox, float* oy, float* oz, float* dx, float* dy, float* dz, uint32_t* pixel);

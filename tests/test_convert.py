@@ -10,6 +10,7 @@ import re
 import numpy as np
 import pytest
 
+from gpu_util import parse_digest
 from ptamd import device as D, host as H, scenes
 
 GOLDEN = os.path.join(os.path.dirname(__file__), "golden", "conversion_digests.json")
@@ -65,18 +66,7 @@ def convert(name):
     return D.debug_convert(flat(name), flags=flags, rng_mode=rng)
 
 
-def parse(line):
-    """'name value [value]' ... on either side of ' | ' -> {"static": {name: "value [value]"}, "dynamic": {...}} (values are decimal or hex numbers)"""
-    out = {}
-    for half, part in zip(("static", "dynamic"), line.split(" | ")):
-        fields, key = {}, None
-        for tok in part.split():
-            if re.fullmatch(r"[0-9a-f]+", tok):
-                fields[key] = f"{fields[key]} {tok}".strip()
-            else:
-                key, fields[tok] = tok, ""
-        out[half] = fields
-    return out
+parse = parse_digest  # (tests/gpu_util.py: tests/test_transforms_cpu.py reads the same lines)
 
 
 @functools.lru_cache(maxsize=None)

@@ -18,10 +18,12 @@ def _scene(name):
         return scenes.instanced_crowd(64, 36, nx=2, nz=2, level=2, transform="general")
     if name == "textured_floor":
         return scenes.blob_room(64, 36, level=2, textured_floor=True)
+    if name == "zoo_room":  # a mirrored, a sheared, a non-uniformly scaled and a small instance: the world-space normal behind such transforms
+        return scenes.zoo_room(64, 36)
     return scenes.glass_first()
 
 
-@pytest.mark.parametrize("name", ["cornell", "crowd_general", "textured_floor", "glass_first"])
+@pytest.mark.parametrize("name", ["cornell", "crowd_general", "textured_floor", "glass_first", "zoo_room"])
 def test_guides_match_the_oracle_at_one_sample(gpu, name):
     """Guide VALUES for the rays of sample 0 (ctx.gen_rays) against deposits restated from the oracle's hits: albedo / coverage and
     normal to 1e-5 absolute, distance to 2e-4 relative; at most 1 % of the pixels outside (hit / miss and nearest-triangle ties at

@@ -12,34 +12,8 @@ from ptamd import host as H, layout as L, scenes
 pytestmark = pytest.mark.gpu
 
 
-MODES = ["two_level", "baked", "packet", "two_level_packet", "unbaked", "unbaked_packet", "two_level_parked", "unbaked_parked", "team"]
-
-
-def _flags(gpu, mode):
-    """two_level: instances are entered like the reference does (meshes that are a single leaf are still copied); unbaked: every
-    instance is entered; baked: copied to world space (the default); *packet: pt_intersect runs the packet traversal kernel
-    (one wave walks the tree once for 64 rays) -- on the world-space tree, or entering instances as a wave."""
-    return {"two_level": gpu.FLAG_TWO_LEVEL_ONLY, "baked": 0, "packet": gpu.FLAG_PACKET_INTERSECT,
-            "two_level_packet": gpu.FLAG_TWO_LEVEL_ONLY | gpu.FLAG_PACKET_INTERSECT, "unbaked": gpu.FLAG_NO_BAKED_INSTANCES,
-            "unbaked_packet": gpu.FLAG_NO_BAKED_INSTANCES | gpu.FLAG_PACKET_INTERSECT,
-            # *parked: the general route into an instance for every instance (rounds 2-4); without it (round 5) the per-ray kernels walk instances that are a
-            # translation + uniform scale through entry nodes, the ray taken into the instance's space on the fly
-            "two_level_parked": gpu.FLAG_TWO_LEVEL_ONLY | gpu.FLAG_PARKED_INSTANCES, "unbaked_parked": gpu.FLAG_NO_BAKED_INSTANCES | gpu.FLAG_PARKED_INSTANCES,
-            # team: four lanes per ray on the world-space tree (pt_team.h: the kernel of launches that do not fill the machine)
-            "team": gpu.FLAG_TEAM_INTERSECT}[mode]
-
-
-def _entered(mode):
-    return mode.startswith(("two_level", "unbaked"))
-
-
-def _check_kernel_used(ctx, mode, folded=None, general=None):
-    assert (ctx.stats()["packet_launches"] > 0) == mode.endswith("packet"), "wrong traversal kernel ran"
-    assert (ctx.stats()["team_launches"] > 0) == (mode == "team"), "the team kernel did not run where it should (or ran where it should not)"
-    if folded is not None:  # how many instances of the scene the per-ray kernels walk through entry nodes
-        assert ctx.stats()["folded_instances"] == folded, (ctx.stats()["folded_instances"], folded)
-    if general is not None:  # instances of any transform entered as leaf-kind steps (pt_trace.h, LEVELS 2)
-        assert ctx.stats()["general_route"] == (1 if general else 0), (ctx.stats()["general_route"], general)
+# the nine ways through pt_intersect and what tells which kernel and which instance route ran: gpu_util (tests/test_gpu_transforms.py shares them)
+MODES, _flags, _entered, _check_kernel_used = U.MODES, U.mode_flags, U.entered, U.check_kernel_used
 
 
 @pytest.mark.parametrize("mode", MODES)
@@ -246,12 +220,7 @@ def test_first_pass_of_a_batch_finds_the_hits_of_the_per_ray_kernel(gpu, kind, s
         again = queued.intersect(o, d)  # the hook, rays handed in
         for k in ("t", "u", "v", "prim", "inst"):
             assert np.array_equal(again[k], want[k]), k
-        same = (got["prim"] == want["prim"]) & (got["inst"] == want["inst"])
-        diff = ~same
-        assert diff.mean() < 1e-3, diff.sum()
-        assert np.allclose(got["t"][diff], want["t"][diff], rtol=1e-6)
-        for k in ("t", "u", "v"):
-            assert np.array_equal(got[k][same].view(np.uint32), want[k][same].view(np.uint32)), k
+        U.assert_hits_of_the_per_ray_kernel(got, want)
         assert 0.3 < (got["prim"] >= 0).mean() < 1.0
     assert first.stats()["packet_launches"] == 2 and queued.stats()["packet_launches"] == 0
     assert first.stats()["bundle_launches"] == 2  # (rounds 3-5: a thin lens went through packets of 64)
@@ -279,11 +248,7 @@ def test_first_pass_with_a_ragged_tail_and_a_pixel_list(gpu, spp):
     o2, d2, pixel2, want = queued.primary_pass(3, spp, n)
     assert np.array_equal(pixel, pixel2) and len(np.unique(pixel)) == owned
     assert np.array_equal(o.view(np.uint32), o2.view(np.uint32)) and np.array_equal(d.view(np.uint32), d2.view(np.uint32))
-    same = (got["prim"] == want["prim"]) & (got["inst"] == want["inst"])
-    assert (~same).mean() < 1e-3
-    assert np.allclose(got["t"][~same], want["t"][~same], rtol=1e-6)
-    for k in ("t", "u", "v"):
-        assert np.array_equal(got[k][same].view(np.uint32), want[k][same].view(np.uint32)), k
+    U.assert_hits_of_the_per_ray_kernel(got, want)
     assert first.stats()["bundle_launches"] == 1
     first.close()
     queued.close()

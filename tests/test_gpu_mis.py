@@ -35,13 +35,7 @@ CASES = {
 
 
 def _gates(a, ref, st, cnt, spp, cam, close_frac=0.97, name=""):
-    assert st["rays_generated"] == cnt["raysGenerated"] == W * Hh * spp
-    for k, ck in (("rays_extension", "raysExtension"), ("rays_shadow", "raysShadow"), ("shade_hits", "shadeHits")):
-        assert abs(st[k] - cnt[ck]) <= 1e-3 * cnt[ck] + 2, (k, st[k], cnt[ck])
-    assert abs(a.mean() - ref.mean()) / ref.mean() < 1e-3
-    close = np.isclose(a, ref, rtol=1e-3, atol=1e-3 * ref.max()).all(axis=1)
-    U.fraction_gate(f"{name}: pixels within 1e-3 of the oracle", close, MEASURED, legacy=close_frac)
-    assert U.rmse(U.tonemap(a, spp, cam), U.tonemap(ref, spp, cam)) < 5e-3
+    U.render_gates(a, ref, st, cnt, spp, cam, W * Hh, MEASURED, close_frac=close_frac, name=name)
 
 
 @pytest.mark.parametrize("case", sorted(CASES))
