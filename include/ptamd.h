@@ -348,17 +348,70 @@ void* pt_guides_device_ptr(pt_ctx* ctx, int which); /* 0 albedo_hits, 1 normal_d
 #define PT_DENOISE_DEFAULT_SIGMA_DEPTH 0.05f
 #define PT_DENOISE_DEFAULT_SIGMA_LUM 0.7f
 enum { PT_DENOISE_TONEMAPPED = 0, PT_DENOISE_HDR = 1 };
+/* What the filter starts from.  PT_DENOISE_INPUT_ACCUM: d0 = c / max(a, 1e-3) of the accumulator, as above.  PT_DENOISE_INPUT_TEMPORAL: d0 is the
+ * d.rgb of the newest temporal history (below) instead; the guides and the re-modulating albedo stay the current frame's.  With iterations == 0 the
+ * output is then d max(a, 1e-3), linear or through pt_resolve's tone curve.  PT_ERR_STATE when pt_temporal_frames is 0; any other value of `input`
+ * is PT_ERR_INVALID. */
+enum { PT_DENOISE_INPUT_ACCUM = 0, PT_DENOISE_INPUT_TEMPORAL = 1 };
 typedef struct {
     uint32_t iterations; /* 0..6; 0 = no filtering at all */
     uint32_t output; /* PT_DENOISE_TONEMAPPED (as pt_resolve) | PT_DENOISE_HDR (linear mean radiance) */
     float k_normal, sigma_depth, sigma_lum; /* 0 = the documented default */
-    uint32_t _reserved[3];
+    uint32_t input; /* PT_DENOISE_INPUT_ACCUM (0, the default) | PT_DENOISE_INPUT_TEMPORAL */
+    uint32_t _reserved[2];
 } pt_denoise_params;
 /* host image out (width*height*4 floats); ms_out (optional): device ms of the filter's kernels (hipEvents), the copy to the host not included */
 int pt_denoise(pt_ctx* ctx, const pt_denoise_params* params, float* rgba_out, float* ms_out);
 /* the same, output left in DEVICE memory (width*height float4), asynchronous on the context's stream; NULL: the context-owned image
  * pt_resolve_device_ptr returns (shared with pt_resolve_device) */
 int pt_denoise_device(pt_ctx* ctx, const pt_denoise_params* params, void* device_rgba);
+
+/* SAMPLE BASE.  pt_render traces the sample indices base + pt_samples_per_pixel ..., pt_render_guides base + pt_guide_samples ...: a frame loop
+ * that clears before every frame ("move, pt_clear, pt_render(1)") sets the base to its frame number, so that every frame draws other random
+ * numbers -- without it each frame is sample 0 again, with the same counter-PRNG keys, and a history of such frames averages nothing.  Default 0.
+ * pt_samples_per_pixel, pt_resolve's divisor and pt_clear are unchanged, and pt_clear does not reset the base.  Host side only.  Fixed schedule
+ * with PT_RNG_COUNTER only: PT_ERR_UNSUPPORTED in parity / refill mode. */
+int pt_set_sample_base(pt_ctx* ctx, uint32_t base);
+uint32_t pt_sample_base(const pt_ctx* ctx);
+
+/* TEMPORAL HISTORY: the demodulated colour of earlier frames, reprojected through the first hit into the current camera and blended with the
+ * current frame.  The context owns two history sets (ping-pong), each two width*height float4 images,
+ *   colour_count = (d.rgb, N)      the accumulated demodulated colour and the number of frames it stands for
+ *   normal_depth = (n.xyz, z)      the guides of the frame the set was made from
+ * and the pt_camera the newest set was made under; all allocated at the first temporal call, freed by pt_destroy.  pt_clear does NOT touch the
+ * history (a frame loop clears the accumulator every frame; the history is what survives) and neither does pt_set_camera.
+ *
+ * One pt_temporal_accumulate, per pixel p = (x, y) of the W x H image; current camera E = eyePoint, S = screenPoint, u, v; the history's E', S', u', v':
+ *   current frame   c, a, d = c / max(a, 1e-3), n, z exactly as the FILTER above makes them
+ *   first hit       D = normalize(S + u (x + 1/2) / W + v (y + 1/2) / H - E),   X = E + z D   (through the pixel CENTRE; a sky pixel, z = PT_GUIDE_SKY_DEPTH,
+ *                   reprojects as a far point: no special case.  A thin-lens camera is treated as the pinhole through eyePoint: an APPROXIMATION, exact
+ *                   only in the plane of focus)
+ *   into history    q = X - E',  s0 = S' - E',  det = s0.(u' x v'),  lambda = q.(u' x v') / det,  alpha = s0.(q x v') / det,  beta = s0.(u' x q) / det;
+ *                   lambda <= 0: behind that camera, no history.  fx = W alpha / lambda - 1/2, fy = H beta / lambda - 1/2, clamped to [-2, W + 1],
+ *                   [-2, H + 1];  z' = |q|
+ *   taps            (x0 + i, y0 + j), i, j in {0, 1}, x0 = floor(fx), y0 = floor(fy), bilinear weight b_ij; a tap counts if it lies inside the image and
+ *                   its count N_h > 0:   w = b exp(-(e_n + e_z)),   e_n = k_normal max(0, 1 - n(p).n_h),
+ *                   e_z = |z' - z_h| / (sigma_depth (min(z', z_h) + 1e-6))   -- the filter's own two guide terms
+ *   blend           Wsum = sum w.  Wsum < 1e-12, or no history at all (first call, after pt_temporal_reset):  d_out = d, N_out = 1.  Otherwise
+ *                   h = sum w d_h / Wsum,   N_out = min(sum w N_h + 1, max_history),   d_out = h + (d - h) / N_out.
+ *                   The count is scaled by the confidence Wsum <= 1: a pixel that barely sees its history barely uses it, and every quantity is a
+ *                   continuous function of the inputs -- there is no accept / reject threshold that round-off could flip.
+ * (d_out, N_out) and the current (n, z) go into the other set, the current camera is remembered, the sets flip.  Bit-reproducible run to run.
+ * Moving instances have no motion vectors: a pixel of a dynamic scene whose surface moved keeps or loses its history by the depth and normal terms alone.
+ * Refusals: PT_ERR_STATE before a camera is set and when pt_samples_per_pixel or pt_guide_samples is 0; PT_ERR_UNSUPPORTED while tiles are set (as
+ * pt_denoise); PT_ERR_INVALID for max_history > 4096 or a negative k_normal / sigma_depth. */
+typedef struct {
+    uint32_t max_history; /* 0 = 32 */
+    float k_normal, sigma_depth; /* 0 = PT_DENOISE_DEFAULT_K_NORMAL / PT_DENOISE_DEFAULT_SIGMA_DEPTH */
+    uint32_t _reserved[5];
+} pt_temporal_params;
+int pt_temporal_accumulate(pt_ctx* ctx, const pt_temporal_params* params); /* asynchronous on the context's stream */
+int pt_temporal_reset(pt_ctx* ctx); /* forget the history */
+uint32_t pt_temporal_frames(const pt_ctx* ctx); /* pt_temporal_accumulate calls (or 1 after pt_write_temporal) since the last reset */
+int pt_read_temporal(pt_ctx* ctx, float* colour_count, float* normal_depth); /* host, width*height*4 floats each, of the newest set; either may be NULL */
+/* checkpoint restore, mirrors pt_write_guides: the newest set and the camera it was made under (eyePoint, screenPoint, u, v are used) */
+int pt_write_temporal(pt_ctx* ctx, const float* colour_count, const float* normal_depth, const pt_camera* made_under);
+void* pt_temporal_device_ptr(pt_ctx* ctx, int which); /* 0 colour_count, 1 normal_depth of the newest set; NULL before the first temporal call */
 
 /* ---- kernel-granular entry points (parity tests and micro-benchmarks) ------------------
  * Host SoA arrays in, host SoA arrays out; the scene must have been uploaded. */

@@ -215,6 +215,14 @@ struct pt_ctx {
     DevBuf<float4> denoiseColour[2], denoiseGuide;
     hipEvent_t evDenoise[2] = { nullptr, nullptr };
 
+    // temporal history (pt_temporal.h): two sets for ping-pong of two width * height float4 images each -- (d.rgb, N) and (n.xyz, z) --, allocated at
+    // the first temporal call; the camera set `temporalNewest` was made under.  pt_clear and pt_set_camera leave all of it alone.
+    DevBuf<float4> temporalColour[2], temporalGuide[2];
+    int temporalNewest = 0;
+    uint32_t temporalFrames = 0; // pt_temporal_accumulate calls (or 1 after pt_write_temporal) since the last reset: 0 = no history
+    CameraDev temporalCamera {};
+    uint32_t sampleBase = 0; // pt_set_sample_base: added to the sample index pt_render and pt_render_guides key the counter PRNG with
+
     double msLastRender = 0, msIntersect = 0, msShade = 0, msShadow = 0, msGen = 0, msPacket = 0;
 };
 

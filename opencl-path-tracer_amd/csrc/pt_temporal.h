@@ -1,0 +1,129 @@
+// Temporal history of the denoiser: the demodulated colour of earlier frames, reprojected into the current camera through the first hit and blended
+// with the current frame -- include/ptamd.h, "temporal history"; DESIGN.md section 9.  Nothing here is on the render path: k_temporal reads the
+// accumulator and the guide sums like k_denoise_prepare does, and the two history sets the context keeps for it.
+#pragma once
+#include "pt_denoise.h"
+
+namespace ptd {
+
+struct TemporalArgs {
+    const float4* accum; // the current frame's three inputs, as k_denoise_prepare reads them
+    const float4* albedoHits;
+    const float4* normalDepth;
+    const float4* histColour; // (d.rgb, N) of the newest set; nullptr: no history (first call, after a reset)
+    const float4* histGuide; // (n.xyz, z) of that set
+    float4* outColour; // the other set
+    float4* outGuide;
+    uint32_t width, height;
+    float spp, gspp;
+    float kNormal, invSigmaDepth, maxHistory;
+    float invW, invH;
+    V3 eye, screen, u, v; // current camera (a thin lens is taken as the pinhole through eyePoint)
+    // the history's camera: its eye, and the three vectors that give lambda, alpha and beta of q = X - E' as plain dot products:
+    //   s0.(q x v') = q.(v' x s0),   s0.(u' x q) = q.(s0 x u'),   each divided by det = s0.(u' x v') on the host
+    V3 histEye, rowLambda, rowAlpha, rowBeta;
+};
+
+constexpr int kTemporalTileW = kAtrousTileW, kTemporalTileH = kAtrousTileH; // the filter's tile: a wave is two rows of 32 pixels
+
+// One thread per pixel.  Three 16-byte reads of the current frame, up to eight gathered 16-byte reads of the history (the four bilinear taps of the
+// reprojected position in both images: a tap outside the image loads nothing, one whose count is zero does not load its guide), two 16-byte writes.
+// The taps of a wave lie in a compact patch of the history, which the vector cache and L2 serve; there is no fixed halo to stage.  No atomics: the
+// output is bit-reproducible.
+__global__ void __launch_bounds__(256) k_temporal(TemporalArgs a)
+{
+    const int x = blockIdx.x * kTemporalTileW + threadIdx.x, y = blockIdx.y * kTemporalTileH + threadIdx.y;
+    const int W = (int)a.width, H = (int)a.height;
+    if (x >= W || y >= H)
+        return;
+    const size_t p = (size_t)y * W + x;
+    const float4 s = a.accum[p], al = a.albedoHits[p], g = a.normalDepth[p];
+    // exactly k_denoise_prepare's quantities
+    const float dr = s.x / a.spp / albedoOf(al.x, a.gspp), dg = s.y / a.spp / albedoOf(al.y, a.gspp), db = s.z / a.spp / albedoOf(al.z, a.gspp);
+    const float len = sqrtf(g.x * g.x + g.y * g.y + g.z * g.z);
+    const float inv = len > 0.0f ? 1.0f / len : 0.0f;
+    const V3 n = mk(g.x * inv, g.y * inv, g.z * inv);
+    const float z = g.w / a.gspp;
+    a.outGuide[p] = make_float4(n.x, n.y, n.z, z);
+
+    float outR = dr, outG = dg, outB = db, outN = 1.0f;
+    if (a.histColour) {
+        // world point of the first hit through the pixel centre, then into the history's camera
+        const float px = ((float)x + 0.5f) * a.invW, py = ((float)y + 0.5f) * a.invH;
+        const V3 D = normalize(a.screen + a.u * px + a.v * py - a.eye);
+        const V3 q = a.eye + D * z - a.histEye;
+        const float lambda = dot(q, a.rowLambda);
+        if (lambda > 0.0f) {
+            const float alpha = dot(q, a.rowAlpha), beta = dot(q, a.rowBeta);
+            const float fx = fminf(fmaxf((float)W * (alpha / lambda) - 0.5f, -2.0f), (float)W + 1.0f);
+            const float fy = fminf(fmaxf((float)H * (beta / lambda) - 0.5f, -2.0f), (float)H + 1.0f);
+            const float zq = sqrtf(dot(q, q));
+            const float flx = floorf(fx), fly = floorf(fy);
+            const int x0 = (int)flx, y0 = (int)fly;
+            const float ax = fx - flx, ay = fy - fly;
+            // the (up to) four colour taps first, as independent loads in flight together; a tap outside the image reads nothing and counts for nothing
+            float4 ch[4];
+#pragma unroll
+            for (int t = 0; t < 4; t++) {
+                const int tx = x0 + (t & 1), ty = y0 + (t >> 1);
+                ch[t] = make_float4(0.f, 0.f, 0.f, 0.f);
+                if (tx >= 0 && tx < W && ty >= 0 && ty < H)
+                    ch[t] = a.histColour[(size_t)ty * W + tx];
+            }
+            // ... then the guides of the taps that count (N_h > 0)
+            float sr = 0.f, sg = 0.f, sb = 0.f, sn = 0.f, sw = 0.f;
+#pragma unroll
+            for (int t = 0; t < 4; t++) {
+                const bool counts = ch[t].w > 0.0f;
+                float w = 0.0f;
+                if (counts) {
+                    const float4 gh = a.histGuide[(size_t)(y0 + (t >> 1)) * W + (x0 + (t & 1))];
+                    const float b = ((t & 1) ? ax : 1.0f - ax) * ((t >> 1) ? ay : 1.0f - ay);
+                    const float en = a.kNormal * fmaxf(0.0f, 1.0f - (n.x * gh.x + n.y * gh.y + n.z * gh.z));
+                    const float ez = fabsf(zq - gh.w) * a.invSigmaDepth / (fminf(zq, gh.w) + 1e-6f);
+                    w = b * __expf(-(en + ez));
+                }
+                sr += w * (counts ? ch[t].x : 0.0f), sg += w * (counts ? ch[t].y : 0.0f), sb += w * (counts ? ch[t].z : 0.0f);
+                sn += w * (counts ? ch[t].w : 0.0f), sw += w;
+            }
+            if (sw >= 1e-12f) {
+                const float hr = sr / sw, hg = sg / sw, hb = sb / sw;
+                outN = fminf(sn + 1.0f, a.maxHistory);
+                outR = hr + (dr - hr) / outN, outG = hg + (dg - hg) / outN, outB = hb + (db - hb) / outN;
+            }
+        }
+    }
+    a.outColour[p] = make_float4(outR, outG, outB, outN);
+}
+
+// pt_denoise with PT_DENOISE_INPUT_TEMPORAL: k_denoise_prepare with d0 taken from the newest history; the guides are the current frame's
+__global__ void __launch_bounds__(256) k_denoise_prepare_temporal(const float4* __restrict__ histColour, const float4* __restrict__ normalDepth,
+    float4* __restrict__ colour, float4* __restrict__ guide, uint32_t n, float gspp)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n)
+        return;
+    const float4 h = histColour[i], g = normalDepth[i];
+    colour[i] = make_float4(h.x, h.y, h.z, luminance709(h.x, h.y, h.z));
+    const float len = sqrtf(g.x * g.x + g.y * g.y + g.z * g.z);
+    const float inv = len > 0.0f ? 1.0f / len : 0.0f;
+    guide[i] = make_float4(g.x * inv, g.y * inv, g.z * inv, g.w / gspp);
+}
+
+// ... and its iterations == 0: the history re-modulated with the current albedo, linear or through pt_resolve's tone curve
+__global__ void __launch_bounds__(256) k_temporal_resolve(const float4* __restrict__ histColour, const float4* __restrict__ albedoHits,
+    float4* __restrict__ out, uint32_t n, float gspp, uint32_t tonemapped, float relativeAperture, float shutterTime, float ISO)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n)
+        return;
+    const float4 h = histColour[i], al = albedoHits[i];
+    float r = h.x * albedoOf(al.x, gspp), g = h.y * albedoOf(al.y, gspp), b = h.z * albedoOf(al.z, gspp);
+    if (tonemapped) {
+        const float exposure = resolveExposure(relativeAperture, shutterTime, ISO);
+        r = resolveChannel(r * exposure), g = resolveChannel(g * exposure), b = resolveChannel(b * exposure);
+    }
+    out[i] = make_float4(r, g, b, 1.0f);
+}
+
+} // namespace ptd

@@ -9,6 +9,7 @@
 #include "pt_bake.h"
 #include "pt_team.h"
 #include "pt_denoise.h"
+#include "pt_temporal.h"
 #ifndef PT_PACK_WIDE
 #define PT_PACK_WIDE 1
 #endif
@@ -488,6 +489,8 @@ void pt_destroy(pt_ctx* c)
     c->pixelList.release(), c->hitInst.release();
     c->guideAlbedoHits.release(), c->guideNormalDepth.release(), c->guideRayO.release(), c->guideRayD.release(), c->guideHit.release(), c->guideHitInst.release();
     c->guideCtl.release(), c->denoiseColour[0].release(), c->denoiseColour[1].release(), c->denoiseGuide.release();
+    for (int k = 0; k < 2; k++)
+        c->temporalColour[k].release(), c->temporalGuide[k].release();
     for (hipEvent_t ev : c->evDenoise)
         if (ev) (void)hipEventDestroy(ev);
     c->accumPlanes.release(), c->pixelOrdinal.release(), c->resolveTmp.release(), c->activeFlag.release(), c->streams.release(), c->control.release(), c->totals.release(), c->spill.release();
@@ -1128,7 +1131,7 @@ int pt_render(pt_ctx* c, uint32_t spp)
                 g >>= 1;
             batch -= batch % g;
         }
-        rc = fixedSchedule ? renderSampleFixed(c, c->spp, batch, prof) : renderSampleRefill(c, c->spp);
+        rc = fixedSchedule ? renderSampleFixed(c, c->sampleBase + c->spp, batch, prof) : renderSampleRefill(c, c->spp);
         if (rc) {
             foldPlanesNow(c); // what the earlier batches of this call deposited belongs to the samples already counted
             return rc;
@@ -1290,7 +1293,7 @@ int pt_render_guides(pt_ctx* c, uint32_t spp)
     const uint64_t teamLaunches = c->teamLaunches;
     c->batchEntries = 0;
     for (uint32_t s = 0; s < spp; s++) {
-        const FrameParams fp = frameParams(c, c->guideSpp + s);
+        const FrameParams fp = frameParams(c, c->sampleBase + c->guideSpp + s);
         hipLaunchKernelGGL(k_guide_gen, dim3((n + 255u) / 256u), dim3(256), 0, c->stream, fp, c->guideRayO.p, c->guideRayD.p,
             c->identityPixels ? nullptr : c->pixelList.p, n, c->guideCtl.p);
         TraceArgs a = traceArgsBase(c);
@@ -1369,6 +1372,11 @@ int pt_denoise_device(pt_ctx* c, const pt_denoise_params* prm, void* device_rgba
         return fail(c, PT_ERR_STATE, "pt_denoise: no colour samples yet (pt_render)");
     if (c->guideSpp == 0)
         return fail(c, PT_ERR_STATE, "pt_denoise: no guide samples yet (pt_render_guides)");
+    if (prm->input != PT_DENOISE_INPUT_ACCUM && prm->input != PT_DENOISE_INPUT_TEMPORAL)
+        return fail(c, PT_ERR_INVALID, "pt_denoise: input = %u (PT_DENOISE_INPUT_ACCUM or PT_DENOISE_INPUT_TEMPORAL)", prm->input);
+    const bool temporal = prm->input == PT_DENOISE_INPUT_TEMPORAL;
+    if (temporal && c->temporalFrames == 0)
+        return fail(c, PT_ERR_STATE, "pt_denoise: PT_DENOISE_INPUT_TEMPORAL without a history (pt_temporal_accumulate)");
     const bool tonemapped = prm->output == PT_DENOISE_TONEMAPPED;
     if (tonemapped && !c->haveCamera)
         return fail(c, PT_ERR_STATE, "pt_denoise: the tone-mapped output needs the camera's exposure (pt_set_camera)");
@@ -1381,7 +1389,10 @@ int pt_denoise_device(pt_ctx* c, const pt_denoise_params* prm, void* device_rgba
     }
     const dim3 lin((n + 255u) / 256u);
     if (prm->iterations == 0u) { // no filtering, no demodulation: pt_resolve's image, or the mean
-        if (tonemapped)
+        if (temporal) // ... over the history: d times the current albedo
+            hipLaunchKernelGGL(k_temporal_resolve, lin, dim3(256), 0, c->stream, c->temporalColour[c->temporalNewest].p, c->guideAlbedoHits.p,
+                (float4*)device_rgba, n, (float)c->guideSpp, tonemapped ? 1u : 0u, c->camera.relativeAperture, c->camera.shutterTime, c->camera.ISO);
+        else if (tonemapped)
             hipLaunchKernelGGL(k_resolve, lin, dim3(256), 0, c->stream, c->accum, (float4*)device_rgba, n, (float)c->spp, c->camera.relativeAperture,
                 c->camera.shutterTime, c->camera.ISO);
         else
@@ -1394,8 +1405,12 @@ int pt_denoise_device(pt_ctx* c, const pt_denoise_params* prm, void* device_rgba
         HIPCHK(c, c->denoiseColour[1].alloc(n));
         HIPCHK(c, c->denoiseGuide.alloc(n));
     }
-    hipLaunchKernelGGL(k_denoise_prepare, lin, dim3(256), 0, c->stream, c->accum, c->guideAlbedoHits.p, c->guideNormalDepth.p, c->denoiseColour[0].p,
-        c->denoiseGuide.p, n, (float)c->spp, (float)c->guideSpp);
+    if (temporal)
+        hipLaunchKernelGGL(k_denoise_prepare_temporal, lin, dim3(256), 0, c->stream, c->temporalColour[c->temporalNewest].p, c->guideNormalDepth.p,
+            c->denoiseColour[0].p, c->denoiseGuide.p, n, (float)c->guideSpp);
+    else
+        hipLaunchKernelGGL(k_denoise_prepare, lin, dim3(256), 0, c->stream, c->accum, c->guideAlbedoHits.p, c->guideNormalDepth.p, c->denoiseColour[0].p,
+            c->denoiseGuide.p, n, (float)c->spp, (float)c->guideSpp);
     AtrousArgs a {};
     a.guide = c->denoiseGuide.p;
     a.albedoHits = c->guideAlbedoHits.p;
@@ -1441,6 +1456,154 @@ int pt_denoise(pt_ctx* c, const pt_denoise_params* prm, float* rgba_out, float* 
     if (ms_out)
         HIPCHK(c, hipEventElapsedTime(ms_out, c->evDenoise[0], c->evDenoise[1]));
     return checkOverflow(c);
+}
+
+// ---- sample base and temporal history (pt_temporal.h) -------------------------------------------
+
+int pt_set_sample_base(pt_ctx* c, uint32_t base)
+{
+    if (!c)
+        return PT_ERR_INVALID;
+    if (parityMode(c) || c->cfg.max_active_rays != 0)
+        return fail(c, PT_ERR_UNSUPPORTED, "pt_set_sample_base: the fixed schedule with PT_RNG_COUNTER only (not in parity / refill mode)");
+    c->sampleBase = base;
+    return PT_OK;
+}
+
+uint32_t pt_sample_base(const pt_ctx* c) { return c ? c->sampleBase : 0; }
+
+namespace {
+
+// the two history sets: allocated (zeroed) at the first temporal call
+int ensureTemporal(pt_ctx* c)
+{
+    const size_t n = (size_t)c->cfg.width * c->cfg.height;
+    if (c->temporalColour[0].p)
+        return PT_OK;
+    for (int k = 0; k < 2; k++) {
+        HIPCHK(c, c->temporalColour[k].alloc(n));
+        HIPCHK(c, c->temporalGuide[k].alloc(n));
+        HIPCHK(c, hipMemsetAsync(c->temporalColour[k].p, 0, n * sizeof(float4), c->stream));
+        HIPCHK(c, hipMemsetAsync(c->temporalGuide[k].p, 0, n * sizeof(float4), c->stream));
+    }
+    return PT_OK;
+}
+
+struct D3 {
+    double x, y, z;
+};
+D3 d3(float4 f) { return { f.x, f.y, f.z }; }
+D3 crossD(D3 a, D3 b) { return { a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x }; }
+V3 scaledToV3(D3 a, double s) { return mk((float)(a.x * s), (float)(a.y * s), (float)(a.z * s)); }
+
+} // namespace
+
+int pt_temporal_accumulate(pt_ctx* c, const pt_temporal_params* prm)
+{
+    return guarded(c, "pt_temporal_accumulate", [&]() -> int {
+    if (!c || !prm)
+        return PT_ERR_INVALID;
+    if (prm->max_history > 4096u)
+        return fail(c, PT_ERR_INVALID, "pt_temporal_accumulate: max_history = %u (1..4096; 0 = 32)", prm->max_history);
+    if (!(prm->k_normal >= 0.f) || !(prm->sigma_depth >= 0.f))
+        return fail(c, PT_ERR_INVALID, "pt_temporal_accumulate: negative or NaN k_normal / sigma_depth");
+    if (tilesSet(c))
+        return fail(c, PT_ERR_UNSUPPORTED, "pt_temporal_accumulate: tiles are set -- the history is reprojected across the whole frame; accumulate after the reduce, on a context that owns the frame");
+    if (!c->haveCamera)
+        return fail(c, PT_ERR_STATE, "pt_temporal_accumulate: no camera yet (pt_set_camera)");
+    if (c->spp == 0)
+        return fail(c, PT_ERR_STATE, "pt_temporal_accumulate: no colour samples yet (pt_render)");
+    if (c->guideSpp == 0)
+        return fail(c, PT_ERR_STATE, "pt_temporal_accumulate: no guide samples yet (pt_render_guides)");
+    HIPCHK(c, hipSetDevice(c->device));
+    int rc = ensureTemporal(c);
+    if (rc)
+        return rc;
+    const int from = c->temporalNewest, to = from ^ 1;
+    TemporalArgs a {};
+    a.accum = c->accum, a.albedoHits = c->guideAlbedoHits.p, a.normalDepth = c->guideNormalDepth.p;
+    a.outColour = c->temporalColour[to].p, a.outGuide = c->temporalGuide[to].p;
+    a.width = c->cfg.width, a.height = c->cfg.height;
+    a.spp = (float)c->spp, a.gspp = (float)c->guideSpp;
+    a.kNormal = prm->k_normal > 0.f ? prm->k_normal : PT_DENOISE_DEFAULT_K_NORMAL;
+    a.invSigmaDepth = 1.0f / (prm->sigma_depth > 0.f ? prm->sigma_depth : PT_DENOISE_DEFAULT_SIGMA_DEPTH);
+    a.maxHistory = (float)(prm->max_history ? prm->max_history : 32u);
+    a.invW = 1.0f / (float)a.width, a.invH = 1.0f / (float)a.height;
+    a.eye = xyz(c->camera.eye), a.screen = xyz(c->camera.screen), a.u = xyz(c->camera.u), a.v = xyz(c->camera.v);
+    if (c->temporalFrames != 0) {
+        const CameraDev& h = c->temporalCamera;
+        const D3 e = d3(h.eye), sp = d3(h.screen), u = d3(h.u), v = d3(h.v);
+        const D3 s0 { sp.x - e.x, sp.y - e.y, sp.z - e.z };
+        const D3 uv = crossD(u, v), vs = crossD(v, s0), su = crossD(s0, u);
+        const double det = s0.x * uv.x + s0.y * uv.y + s0.z * uv.z;
+        if (det != 0.0 && std::isfinite(det)) { // (a degenerate camera has nothing to reproject into: the frame starts a history)
+            a.histColour = c->temporalColour[from].p, a.histGuide = c->temporalGuide[from].p;
+            a.histEye = xyz(h.eye);
+            a.rowLambda = scaledToV3(uv, 1.0 / det), a.rowAlpha = scaledToV3(vs, 1.0 / det), a.rowBeta = scaledToV3(su, 1.0 / det);
+        }
+    }
+    const dim3 grid((a.width + kTemporalTileW - 1) / kTemporalTileW, (a.height + kTemporalTileH - 1) / kTemporalTileH), block(kTemporalTileW, kTemporalTileH);
+    hipLaunchKernelGGL(k_temporal, grid, block, 0, c->stream, a);
+    HIPCHK(c, hipGetLastError());
+    c->temporalCamera = c->camera;
+    c->temporalNewest = to;
+    c->temporalFrames++;
+    return PT_OK;
+    });
+}
+
+int pt_temporal_reset(pt_ctx* c)
+{
+    if (!c)
+        return PT_ERR_INVALID;
+    c->temporalFrames = 0;
+    return PT_OK;
+}
+
+uint32_t pt_temporal_frames(const pt_ctx* c) { return c ? c->temporalFrames : 0; }
+
+int pt_read_temporal(pt_ctx* c, float* colour_count, float* normal_depth)
+{
+    if (!c)
+        return PT_ERR_INVALID;
+    HIPCHK(c, hipSetDevice(c->device));
+    int rc = ensureTemporal(c);
+    if (rc)
+        return rc;
+    const size_t bytes = (size_t)c->cfg.width * c->cfg.height * sizeof(float4);
+    if (colour_count)
+        HIPCHK(c, hipMemcpyAsync(colour_count, c->temporalColour[c->temporalNewest].p, bytes, hipMemcpyDeviceToHost, c->stream));
+    if (normal_depth)
+        HIPCHK(c, hipMemcpyAsync(normal_depth, c->temporalGuide[c->temporalNewest].p, bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return PT_OK;
+}
+
+int pt_write_temporal(pt_ctx* c, const float* colour_count, const float* normal_depth, const pt_camera* made_under)
+{
+    if (!c || !colour_count || !normal_depth || !made_under)
+        return PT_ERR_INVALID;
+    HIPCHK(c, hipSetDevice(c->device));
+    int rc = ensureTemporal(c);
+    if (rc)
+        return rc;
+    const size_t bytes = (size_t)c->cfg.width * c->cfg.height * sizeof(float4);
+    HIPCHK(c, hipMemcpyAsync(c->temporalColour[c->temporalNewest].p, colour_count, bytes, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->temporalGuide[c->temporalNewest].p, normal_depth, bytes, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    auto f4 = [](const float* p) { return make_float4(p[0], p[1], p[2], 0.f); };
+    c->temporalCamera = CameraDev {};
+    c->temporalCamera.eye = f4(made_under->eyePoint), c->temporalCamera.screen = f4(made_under->screenPoint);
+    c->temporalCamera.u = f4(made_under->u), c->temporalCamera.v = f4(made_under->v);
+    c->temporalFrames = 1;
+    return PT_OK;
+}
+
+void* pt_temporal_device_ptr(pt_ctx* c, int which)
+{
+    if (!c || which < 0 || which > 1)
+        return nullptr;
+    return which == 0 ? (void*)c->temporalColour[c->temporalNewest].p : (void*)c->temporalGuide[c->temporalNewest].p;
 }
 
 int pt_stats_get(pt_ctx* c, pt_stats* out)

@@ -126,6 +126,7 @@ void RayTracer::rayTrace(const Camera& camera)
     if (getSamplesPerPixel() >= getMaxSamplesPerPixel())
         return;
     check(pt_render(m_ctx, 1), "pt_render");
+    m_temporalDirty = true;
     check(pt_synchronize(m_ctx), "pt_synchronize"); // queue.finish(), src/raytracer.cpp:117-118
 }
 
@@ -162,6 +163,27 @@ std::vector<float> RayTracer::getDenoisedOutput(int iterations)
     check(pt_denoise(m_ctx, &prm, out.data(), nullptr), "pt_denoise");
     return out;
 }
+
+std::vector<float> RayTracer::getTemporalOutput(int iterations)
+{
+    renderMissingGuides();
+    if (m_temporalDirty || pt_temporal_frames(m_ctx) == 0) {
+        pt_temporal_params tp {};
+        check(pt_temporal_accumulate(m_ctx, &tp), "pt_temporal_accumulate");
+        m_temporalDirty = false;
+    }
+    pt_denoise_params prm {};
+    prm.iterations = (uint32_t)iterations;
+    prm.output = PT_DENOISE_TONEMAPPED;
+    prm.input = PT_DENOISE_INPUT_TEMPORAL;
+    std::vector<float> out((size_t)m_width * m_height * 4);
+    check(pt_denoise(m_ctx, &prm, out.data(), nullptr), "pt_denoise");
+    return out;
+}
+
+void RayTracer::resetTemporalHistory() { check(pt_temporal_reset(m_ctx), "pt_temporal_reset"); }
+
+void RayTracer::setSampleBase(uint32_t base) { check(pt_set_sample_base(m_ctx, base), "pt_set_sample_base"); }
 
 RayTracer::Guides RayTracer::getGuides()
 {

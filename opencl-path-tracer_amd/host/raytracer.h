@@ -89,6 +89,12 @@ public:
     // the image of getOutput() through the edge-avoiding a-trous filter (include/ptamd.h, "guides and denoiser"): renders as many guide samples as are
     // missing to match getSamplesPerPixel(), then filters `iterations` times (0..6; 0: getOutput())
     std::vector<float> getDenoisedOutput(int iterations = 5);
+    // the same over the temporal history (include/ptamd.h, "temporal history"): blends the frame just traced into the history reprojected into its
+    // camera (once per frame: a second call for the same frame filters the same history again), then filters the history `iterations` times.  For a
+    // frame loop that moves the camera every frame: setSampleBase(frame); rayTrace(camera); getTemporalOutput().
+    std::vector<float> getTemporalOutput(int iterations = 5);
+    void resetTemporalHistory(); // forget the history: after a cut, or when the scene changed beyond what depth and normal can tell
+    void setSampleBase(uint32_t base); // pt_set_sample_base: frames that restart at sample 0 draw other random numbers each
     struct Guides {
         std::vector<float> albedoHits, normalDepth; // width*height float4 sums over `samples` guide samples
         int samples = 0;
@@ -106,6 +112,7 @@ private:
     FlattenedScene m_flat;
     CameraData m_prevCamera;
     bool m_haveCamera = false;
+    bool m_temporalDirty = false; // samples were traced since the last getTemporalOutput
     int m_width, m_height;
 };
 

@@ -69,7 +69,15 @@ GUIDE_SKY_DEPTH = 1e6
 class DenoiseParams(C.Structure):
     """pt_denoise_params (32 bytes); a filter parameter of 0 selects the default documented in include/ptamd.h"""
     _fields_ = [("iterations", C.c_uint32), ("output", C.c_uint32), ("k_normal", C.c_float), ("sigma_depth", C.c_float),
-                ("sigma_lum", C.c_float), ("_reserved", C.c_uint32 * 3)]
+                ("sigma_lum", C.c_float), ("input", C.c_uint32), ("_reserved", C.c_uint32 * 2)]
+
+
+DENOISE_INPUT_ACCUM, DENOISE_INPUT_TEMPORAL = 0, 1
+
+
+class TemporalParams(C.Structure):
+    """pt_temporal_params (32 bytes); a parameter of 0 selects the default documented in include/ptamd.h"""
+    _fields_ = [("max_history", C.c_uint32), ("k_normal", C.c_float), ("sigma_depth", C.c_float), ("_reserved", C.c_uint32 * 5)]
 
 
 EXPORTS = ["pt_create", "pt_destroy", "pt_last_error", "pt_set_stream", "pt_upload_static", "pt_upload_static_async", "pt_upload_dynamic",
@@ -77,7 +85,8 @@ EXPORTS = ["pt_create", "pt_destroy", "pt_last_error", "pt_set_stream", "pt_uplo
            "pt_upload_texture_array", "pt_set_camera", "pt_set_tiles", "pt_set_accum_buffer", "pt_clear", "pt_render",
            "pt_synchronize", "pt_resolve", "pt_resolve_device", "pt_resolve_device_ptr", "pt_read_accum", "pt_write_accum", "pt_accum_device_ptr",
            "pt_samples_per_pixel", "pt_render_guides", "pt_guide_samples", "pt_read_guides", "pt_write_guides", "pt_guides_device_ptr",
-           "pt_denoise", "pt_denoise_device", "pt_stats_get", "pt_stats_reset", "pt_profile_kernels", "pt_reduce_accum",
+           "pt_denoise", "pt_denoise_device", "pt_set_sample_base", "pt_sample_base", "pt_temporal_accumulate", "pt_temporal_reset",
+           "pt_temporal_frames", "pt_read_temporal", "pt_write_temporal", "pt_temporal_device_ptr", "pt_stats_get", "pt_stats_reset", "pt_profile_kernels", "pt_reduce_accum",
            "pt_intersect", "pt_gen_rays", "pt_primary_pass", "pt_shade_batch", "pt_debug_quantise_node", "pt_debug_convert", "pt_debug_copy_bandwidth", "pt_debug_math_probe", "pt_version"]
 
 _lib = None
@@ -136,6 +145,17 @@ def lib():
         l.pt_guides_device_ptr.argtypes = [C.c_void_p, C.c_int]
         l.pt_denoise.argtypes = [C.c_void_p, C.POINTER(DenoiseParams), C.c_void_p, C.POINTER(C.c_float)]
         l.pt_denoise_device.argtypes = [C.c_void_p, C.POINTER(DenoiseParams), C.c_void_p]
+        l.pt_set_sample_base.argtypes = [C.c_void_p, C.c_uint32]
+        l.pt_sample_base.restype = C.c_uint32
+        l.pt_sample_base.argtypes = [C.c_void_p]
+        l.pt_temporal_accumulate.argtypes = [C.c_void_p, C.POINTER(TemporalParams)]
+        l.pt_temporal_reset.argtypes = [C.c_void_p]
+        l.pt_temporal_frames.restype = C.c_uint32
+        l.pt_temporal_frames.argtypes = [C.c_void_p]
+        l.pt_read_temporal.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        l.pt_write_temporal.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        l.pt_temporal_device_ptr.restype = C.c_void_p
+        l.pt_temporal_device_ptr.argtypes = [C.c_void_p, C.c_int]
         l.pt_stats_get.argtypes = [C.c_void_p, C.POINTER(Stats)]
         l.pt_stats_reset.argtypes = [C.c_void_p]
         l.pt_profile_kernels.argtypes = [C.c_void_p, C.c_int]
@@ -342,19 +362,64 @@ class Context:
         """Device address of the albedo_hits (0) / normal_depth (1) image (0 before the first guide call)."""
         return lib().pt_guides_device_ptr(self._h, which) or 0
 
-    def denoise(self, iterations=5, hdr=False, k_normal=0.0, sigma_depth=0.0, sigma_lum=0.0, with_ms=False):
+    def denoise(self, iterations=5, hdr=False, k_normal=0.0, sigma_depth=0.0, sigma_lum=0.0, with_ms=False, input_temporal=False):
         """The edge-avoiding a-trous filter over the accumulator under the guides: (height, width, 4) tone-mapped like resolve(), or linear
-        mean radiance (hdr=True); with_ms: also the device ms of the filter's kernels."""
-        prm = DenoiseParams(iterations, DENOISE_HDR if hdr else DENOISE_TONEMAPPED, k_normal, sigma_depth, sigma_lum)
+        mean radiance (hdr=True); with_ms: also the device ms of the filter's kernels; input_temporal: the filter starts from the temporal
+        history (temporal_accumulate) instead of the accumulator."""
+        prm = DenoiseParams(iterations, DENOISE_HDR if hdr else DENOISE_TONEMAPPED, k_normal, sigma_depth, sigma_lum,
+                            DENOISE_INPUT_TEMPORAL if input_temporal else DENOISE_INPUT_ACCUM)
         out = np.zeros((self.height, self.width, 4), np.float32)
         ms = C.c_float(0)
         self._chk(lib().pt_denoise(self._h, C.byref(prm), _p(out), C.byref(ms)), "pt_denoise")
         return (out, float(ms.value)) if with_ms else out
 
-    def denoise_device(self, iterations=5, hdr=False, k_normal=0.0, sigma_depth=0.0, sigma_lum=0.0, device_ptr=None):
+    def denoise_device(self, iterations=5, hdr=False, k_normal=0.0, sigma_depth=0.0, sigma_lum=0.0, device_ptr=None, input_temporal=False):
         """The same into device memory (None: the context-owned image, resolve_device_ptr); asynchronous."""
-        prm = DenoiseParams(iterations, DENOISE_HDR if hdr else DENOISE_TONEMAPPED, k_normal, sigma_depth, sigma_lum)
+        prm = DenoiseParams(iterations, DENOISE_HDR if hdr else DENOISE_TONEMAPPED, k_normal, sigma_depth, sigma_lum,
+                            DENOISE_INPUT_TEMPORAL if input_temporal else DENOISE_INPUT_ACCUM)
         self._chk(lib().pt_denoise_device(self._h, C.byref(prm), C.c_void_p(device_ptr) if device_ptr else None), "pt_denoise_device")
+
+    # ---- sample base and temporal history
+    def set_sample_base(self, base):
+        """render / render_guides trace the sample indices base + samples_per_pixel ... (a frame loop that clears every frame sets its frame number)."""
+        self._chk(lib().pt_set_sample_base(self._h, base), "pt_set_sample_base")
+
+    @property
+    def sample_base(self):
+        return int(lib().pt_sample_base(self._h))
+
+    def temporal_accumulate(self, max_history=0, k_normal=0.0, sigma_depth=0.0, sync=True):
+        """Reproject the history into the current camera and blend the current frame (accumulator + guides) into it."""
+        prm = TemporalParams(max_history, k_normal, sigma_depth)
+        self._chk(lib().pt_temporal_accumulate(self._h, C.byref(prm)), "pt_temporal_accumulate")
+        if sync:
+            self.synchronize()
+
+    def temporal_reset(self):
+        self._chk(lib().pt_temporal_reset(self._h), "pt_temporal_reset")
+
+    @property
+    def temporal_frames(self):
+        return int(lib().pt_temporal_frames(self._h))
+
+    def read_temporal(self):
+        """(colour_count, normal_depth) of the newest history set: two (width*height, 4) arrays, (d.rgb, N) and (n.xyz, z)"""
+        cn = np.zeros((self.height * self.width, 4), np.float32)
+        nd = np.zeros((self.height * self.width, 4), np.float32)
+        self._chk(lib().pt_read_temporal(self._h, _p(cn), _p(nd)), "pt_read_temporal")
+        return cn, nd
+
+    def write_temporal(self, colour_count, normal_depth, camera):
+        """Install a history (a checkpoint, a test input) and the camera it was made under."""
+        cn = np.ascontiguousarray(colour_count, np.float32)
+        nd = np.ascontiguousarray(normal_depth, np.float32)
+        assert cn.size == nd.size == self.width * self.height * 4
+        cam = np.ascontiguousarray(np.asarray(camera, L.CAMERA).reshape(1))
+        self._chk(lib().pt_write_temporal(self._h, _p(cn), _p(nd), _p(cam)), "pt_write_temporal")
+
+    def temporal_device_ptr(self, which):
+        """Device address of the colour_count (0) / normal_depth (1) image of the newest set (0 before the first temporal call)."""
+        return lib().pt_temporal_device_ptr(self._h, which) or 0
 
     def stats(self):
         s = Stats()

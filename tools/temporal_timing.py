@@ -1,0 +1,83 @@
+#!/usr/bin/env python3
+"""Device time of pt_temporal_accumulate at 1280 x 720 and 1920 x 1080, one JSON line (EXPERIMENTS.md).
+Not part of bench.py.     usage: python tools/temporal_timing.py [--calls 25] [--batch 20] [--scene cornell|blob]
+
+temporal_ms.static / .panned: median device ms of ONE pt_temporal_accumulate, measured between two events on the stream the context renders on
+around `batch` calls in a row (one call is tens of microseconds: a pair of events around a single launch would time the events).  static: the camera
+of the history is the current one (every pixel finds its four taps around its own position); panned: the camera alternates between two poses 1.5
+degrees apart about the room's centre, so every call reprojects.  frame_ms: the same measurement of pt_render(1), the 1-spp frame the history serves.
+floor_bytes: what a call must move -- three 16-byte reads of the current frame, two 16-byte writes and the history's two images read once (neighbours
+share their taps): 7 x 16 = 112 bytes per pixel; fraction_of_copy: that traffic per second against pt_debug_copy_bandwidth."""
+import argparse
+import json
+import math
+import os
+import statistics
+import sys
+
+ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
+sys.path[:0] = [os.path.join(ROOT, "opencl-path-tracer_amd"), ROOT]
+
+FLOOR_BYTES_PER_PIXEL = 7 * 16
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--calls", type=int, default=25)
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--batch", type=int, default=20)
+    ap.add_argument("--scene", default="cornell")
+    args = ap.parse_args()
+    import torch
+    from ptamd import device as D, scenes
+
+    out = {"calls": args.calls, "batch": args.batch, "scene": args.scene, "floor_bytes_per_pixel": FLOOR_BYTES_PER_PIXEL, "sizes": {}}
+    stream = torch.cuda.Stream()
+    for width, height in ((1280, 720), (1920, 1080)):
+        b = scenes.cornell_box(width, height) if args.scene == "cornell" else scenes.blob_room(width, height, level=5)
+        ctx = D.Context(width, height, samples_in_flight=1)
+        ctx.upload_scene(b.flat, sky=b.sky, material_textures=b.material_textures)
+        ctx.set_camera(b.camera)
+        ctx.set_stream(stream.cuda_stream)
+        t = math.radians(1.5)
+        turned = scenes._camera(width, height, (-3.9 * math.sin(t), 1.0, -3.9 * math.cos(t)), (0.0, 1.0, 0.0), 40.0)
+
+        def timed(fn, per=1):
+            ms = []
+            for k in range(args.warmup + args.calls):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record(stream)
+                for i in range(per):
+                    fn(i)
+                e1.record(stream)
+                ctx.synchronize()
+                if k >= args.warmup:
+                    ms.append(e0.elapsed_time(e1) / per)
+            return statistics.median(ms)
+
+        frame = timed(lambda i: ctx.render(1, sync=False))
+        ctx.clear()
+        ctx.render(1)
+        ctx.render_guides(1)
+        ctx.temporal_reset()
+        ctx.temporal_accumulate()
+        static = timed(lambda i: ctx.temporal_accumulate(sync=False), args.batch)
+
+        def panned_call(i):
+            ctx.set_camera(turned if i % 2 else b.camera)  # (host side only: the accumulator and the guides stay what they are)
+            ctx.temporal_accumulate(sync=False)
+        panned = timed(panned_call, args.batch)
+        cn, _ = ctx.read_temporal()
+        floor = FLOOR_BYTES_PER_PIXEL * width * height
+        copy = ctx.copy_bandwidth(1 << 28, 5)
+        out["sizes"][f"{width}x{height}"] = {
+            "frame_ms": round(frame, 4), "temporal_ms": {"static": round(static, 5), "panned": round(panned, 5)}, "floor_bytes": floor,
+            "gbps": {"static": round(floor / static / 1e6, 1), "panned": round(floor / panned / 1e6, 1)}, "copy_gbps": round(copy, 1),
+            "fraction_of_copy": {"static": round(floor / static / 1e6 / copy, 3), "panned": round(floor / panned / 1e6 / copy, 3)},
+            "mean_history_count_panned": round(float(cn[:, 3].mean()), 2)}
+        ctx.close()
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
