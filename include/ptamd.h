@@ -177,6 +177,16 @@ typedef struct {
  * shading point (weightedRandomPointOnLight, shading_helper.cl:216-259) instead of uniformly (randomPointOnLight, :261-278) */
 #define PT_FLAG_SOLID_ANGLE_LIGHTS 128u
 
+/* Shading, where it deliberately departs from the reference's kernels (every other quirk of shade is reproduced):
+ *   - tangent frames.  The reference builds the frame of its GGX (PBR), Beckmann (rough glass) and cosine (diffuse) samplers on
+ *     normalize(cross(normal, seed)), seed = (1,0,0) for the first two (shading_helper.cl:62-160): an OBJECT-space shading normal of exactly
+ *     +-x -- an axis-aligned box under any instance transform -- gives NaN, and the path goes on with a NaN direction and throughput.  Here,
+ *     where the squared length of that cross product is zero, denormal or NaN, the frame is built on (0,1,0); everywhere else the result is
+ *     the reference's bit for bit.  Zero-length vertex normals remain garbage input.
+ *   - rough glass at exactly normal incidence on a face whose normal is not an axis may end the path (tan(acos(x)) of an x that rounded
+ *     above 1 is NaN, the weight 0): reproduced as the reference has it (pinned by
+ *     tests/test_shade_grid_cpu.py::test_rough_glass_at_exactly_normal_incidence_ends_paths_as_the_reference_does). */
+
 typedef struct { uint32_t x0, y0, x1, y1; } pt_rect; /* [x0,x1) x [y0,y1) */
 
 typedef struct {

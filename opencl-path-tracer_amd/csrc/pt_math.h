@@ -33,6 +33,7 @@ __device__ inline float fastDiv(float a, float b) { return a / b; }
 __device__ inline float fastSqrt(float x) { return sqrtf(x); }
 __device__ inline V3 fastDiv(V3 a, float s) { return a / s; }
 __device__ inline V3 fastNormalize(V3 a) { return normalize(a); }
+__device__ inline V3 fastNormalize(V3 a, float) { return normalize(a); }
 #else
 __device__ inline float fastDiv(float a, float b)
 {
@@ -51,15 +52,15 @@ __device__ inline V3 fastDiv(V3 a, float s) // one reciprocal, three products
     const float r = fastRcp(s);
     return { a.x * r, a.y * r, a.z * r };
 }
-__device__ inline V3 fastNormalize(V3 a) // one root, one reciprocal, three products
+__device__ inline V3 fastNormalize(V3 a, float len2) // len2 = dot(a, a), which the caller already has: one root, one reciprocal, three products
 {
-    const float len2 = dot(a, a); // (contracted as normalize's is: pt_hostdev.h)
     const float r = fastRcp(fastSqrt(len2));
     {
 #pragma clang fp contract(off)
         return { a.x * r, a.y * r, a.z * r };
     }
 }
+__device__ inline V3 fastNormalize(V3 a) { return fastNormalize(a, dot(a, a)); } // (the dot contracted as normalize's is: pt_hostdev.h)
 #endif
 
 // ---- production PRNG: counter-based, stateless (replaces clRNG; DESIGN.md "PRNG") ------------

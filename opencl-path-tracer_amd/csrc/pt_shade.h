@@ -240,9 +240,23 @@ __device__ inline V3 normalTransform(const Instance& in, V3 v)
     const V3 c3 = v.z * mk(in.r2.x, in.r2.y, in.r2.z);
     return c1 + c2 + c3;
 }
+// Tangent frame of the three samplers (shading_helper.cl:62-160).  DEVIATION from the reference (include/ptamd.h): the GGX and
+// Beckmann samplers seed with the constant (1,0,0), so for every object-space shading normal that is exactly +-x cross(normal, tangentSeed) is zero; the
+// reference normalizes it all the same, and the path goes on with a NaN direction and a NaN throughput that no later comparison ends.  Here, where the
+// squared length of the cross product is zero, denormal or NaN, the frame is built on (0,1,0) instead.  Wherever it is a normal float the result is
+// the reference's, bit for bit.
 __device__ inline V3 orient(V3 sample, V3 normal, V3 tangentSeed, const Instance& in)
 {
-    const V3 tangent = fastNormalize(cross(normal, tangentSeed));
+    V3 tc = cross(normal, tangentSeed);
+    float len2 = dot(tc, tc);
+    if (__builtin_expect(!(len2 >= FLT_MIN), 0)) { // a branch the wave skips, not a select: the squared length of the common case is then computed once
+        asm volatile(""); // (keeps the compiler from turning the branch into selects: ten vector instructions per call site, four call sites, 0.22 % of
+                          // the benchmark -- profiles/round6/r6i_ab_bench_select_*.  Nothing but this compiler's habits makes an empty asm do that: after a
+                          // ROCm upgrade look for `s_cbranch_execnz` behind the compare with 0x800000 in k_shade's assembly, tools/asm_diff.py)
+        tc = cross(normal, mk(0.0f, 1.0f, 0.0f));
+        len2 = dot(tc, tc);
+    }
+    const V3 tangent = fastNormalize(tc, len2);
     const V3 bitangent = cross(normal, tangent);
     const V3 os = sample.x * tangent + sample.y * bitangent + sample.z * normal;
     return fastNormalize(normalTransform(in, os));
@@ -456,7 +470,11 @@ __device__ inline void shadeHit(const SceneDev& sc, V3 X, V3 D, float t, float u
         const float phi = 2.0f * kPI * r0;
         const float r1 = rng.u01();
         // theta = acos(c); the reference then takes cos(pi/2 - theta) = sin(theta) and sin(pi/2 - theta) = cos(theta) = c
-        const float cosTheta = fastSqrt(fastDiv(1.0f - r1, (alpha * alpha - 1.0f) * r1 + 1.0f));
+        // x / x is 1: v_rcp_f32 is good to 1 ulp, (1 - r1) * rcp(1 - r1) came out as 1 - 2^-24 for about a tenth of the draws of a perfect mirror
+        // (alpha = 0, or alpha^2 * r1 below an ulp of 1), and the root below turns that ulp into sin(theta) = 3.4e-4: the mirror direction of smoothness 1
+        // was off by up to 7e-4 where the reference's is exact (tests/test_gpu_shade_grid.py, pbr metal s=1).  Other operands: fastDiv as before.
+        const float num = 1.0f - r1, den = (alpha * alpha - 1.0f) * r1 + 1.0f;
+        const float cosTheta = fastSqrt(num == den ? 1.0f : fastDiv(num, den));
         const float sinTheta = fastSqrt(fmaxf(0.0f, 1.0f - cosTheta * cosTheta));
         const V3 halfway = orient(mk(cosf(phi) * sinTheta, sinf(phi) * sinTheta, cosTheta), shadingNormal, mk(1.0f, 0.0f, 0.0f), in);
         reflection = fastNormalize(2 * dot(halfway, V) * halfway - V);

@@ -593,9 +593,19 @@ inline float evaluateRefract(V3 I, V3 N, V3 M, float n1n2, float IdotM, float K,
 }
 
 // tangent frame + instance normal transform shared by the three half-vector / hemisphere samplers
+//   FIXED  -- the reference builds the tangent as normalize(cross(normal, tangentSeed)) (shading_helper.cl:62-160) and seeds the GGX and the
+//             Beckmann half-vector with the constant (1,0,0): an object-space shading normal that is exactly +-x (any axis-aligned box, whatever
+//             its instance's rotation) gives a zero cross product, normalize gives NaN, every comparison that could end the path is false on
+//             NaN, and the path goes on with a NaN direction and a NaN throughput (oracle/_ref does exactly that:
+//             tests/test_shade_grid_cpu.py).  A deliberate deviation, like the MIS density below: where the squared length of the cross
+//             product is not a normal float (zero, denormal, NaN) the frame is built on (0,1,0) instead; everywhere else the result is the
+//             reference's, bit for bit.  One rule for every caller, the diffuse sampler's edge1 seed included; csrc/pt_shade.h has the same.
 inline V3 orient(V3 sample, V3 normal, V3 tangentSeed, const float* invT)
 {
-    V3 tangent = normalize(cross(normal, tangentSeed));
+    V3 tc = cross(normal, tangentSeed);
+    if (!(dot(tc, tc) >= FLT_MIN))
+        tc = cross(normal, mk(0.0f, 1.0f, 0.0f));
+    V3 tangent = normalize(tc);
     V3 bitangent = cross(normal, tangent);
     V3 os = sample.x * tangent + sample.y * bitangent + sample.z * normal;
     return normalize(matMulTranspose(invT, os));
