@@ -407,7 +407,13 @@ uint32_t pt_sample_base(const pt_ctx* ctx);
  *                   The count is scaled by the confidence Wsum <= 1: a pixel that barely sees its history barely uses it, and every quantity is a
  *                   continuous function of the inputs -- there is no accept / reject threshold that round-off could flip.
  * (d_out, N_out) and the current (n, z) go into the other set, the current camera is remembered, the sets flip.  Bit-reproducible run to run.
- * Moving instances have no motion vectors: a pixel of a dynamic scene whose surface moved keeps or loses its history by the depth and normal terms alone.
+ * A pixel of a dynamic scene whose surface moved keeps or loses its history by the depth and normal terms alone, unless the motion of its instance was set
+ * (INSTANCE MOTION below), which changes two lines of the above:
+ *   into history    q = (X + m / gspp) - E',  m the pixel's motion sum: the displacement is added to X BEFORE the history's eye is subtracted;  z' = |q| as before
+ *   taps            e_n = k_normal max(0, 1 - n_then(p).n_h),  n_then the pixel's prev_normal sum normalised exactly as n is (zero stays zero)
+ * and nothing else: the set written out still holds the CURRENT (n, z); blend, clamps and the 1e-12 rule are the same.  Zero motion sums and
+ * prev_normal == normal_depth.xyz give the plain output bit for bit.  Still without motion vectors: deforming meshes (pt_refit_vertices, pt_update_geometry,
+ * rebuilt trees) and moving lights.
  * Refusals: PT_ERR_STATE before a camera is set and when pt_samples_per_pixel or pt_guide_samples is 0; PT_ERR_UNSUPPORTED while tiles are set (as
  * pt_denoise); PT_ERR_INVALID for max_history > 4096 or a negative k_normal / sigma_depth. */
 typedef struct {
@@ -422,6 +428,41 @@ int pt_read_temporal(pt_ctx* ctx, float* colour_count, float* normal_depth); /* 
 /* checkpoint restore, mirrors pt_write_guides: the newest set and the camera it was made under (eyePoint, screenPoint, u, v are used) */
 int pt_write_temporal(pt_ctx* ctx, const float* colour_count, const float* normal_depth, const pt_camera* made_under);
 void* pt_temporal_device_ptr(pt_ctx* ctx, int which); /* 0 colour_count, 1 normal_depth of the newest set; NULL before the first temporal call */
+
+/* INSTANCE MOTION: motion vectors for instances that were re-posed between the frame the history was made from and the current one.  Opt-in: with no
+ * motion set, every entry point launches exactly the kernels it launches without this block and returns the same bits.
+ *
+ * The caller hands in, per top-level node of the ACTIVE dynamic state, the invTransform its instance had in the scene state the newest temporal history
+ * was made under.  Per leaf the host forms, in double, P = inverse(prev_inv) * cur_inv (world now -> world then) and keeps a 96-byte record:
+ *   three float4 rows (A | t),  A = P_linear - I,  t = P's translation, each rounded to float once -- storing P - I keeps a static instance's
+ *     displacement exactly 0 and avoids the cancellation of P X - X;
+ *   the three rows of prev_inv (row i = m[i], m[4+i], m[8+i], m[12+i]), which the normal transform takes.
+ * Where prev_inv has cur_inv's bits, A and t are exact zeros (no inverse round trip).  The fourth row of an invTransform is taken as (0, 0, 0, 1), as
+ * the traversal takes it.
+ * With the motion set, pt_render_guides additionally deposits, per guide sample and owned pixel, into two more width*height float4 SUMS:
+ *   motion      += (A X + t, 0)    X = O + t D, the world hit point of that guide ray (its own origin, its un-normalised direction); a miss deposits 0
+ *   prev_normal += (n_then, 0)     the normal deposit's expression on prev_inv's rows, flipped if and only if N was; a miss deposits -D
+ * in sample order like the other two sums (bit-reproducible, tiles add up bit for bit, independent of samples_in_flight); an instance whose previous
+ * transform has the same bits deposits exact zeros and the bits of N.  pt_temporal_accumulate then reprojects through them (TEMPORAL HISTORY above).
+ * A frame loop: tick, pt_clear, pt_set_instance_motion, pt_render, pt_render_guides, pt_temporal_accumulate, pt_denoise.
+ *
+ * pt_set_instance_motion refuses: PT_ERR_UNSUPPORTED in parity / refill mode (as pt_render_guides); PT_ERR_STATE before a dynamic state is active, and
+ * while pt_guide_samples() != 0 -- for setting and for forgetting alike: the motion sums must cover the same samples as the other two guide sums, so the
+ * motion is set right after the frame's pt_clear; PT_ERR_INVALID when n_top is not the active state's node count, or when a leaf's previous matrix is
+ * singular or not finite.  The indices are the active state's: pt_frame_tick (and with it pt_upload_dynamic) forgets the motion.  pt_clear zeroes the two
+ * motion sums with the other guides and keeps the motion set; pt_write_guides leaves the motion sums alone.  The records live in a device buffer of n_top
+ * entries, the two images are allocated at the first pt_set_instance_motion / pt_write_motion_guides; pt_destroy frees all of it. */
+/* prev_inv_transforms: n_top x 16 floats, column-major, indexed like the top_nodes of the ACTIVE dynamic state: entry i is the invTransform
+ * the instance of top-level leaf i had in the scene state the newest temporal history was made under (entries of inner nodes are ignored).
+ * NULL / 0 forgets the motion. */
+int pt_set_instance_motion(pt_ctx* ctx, const float* prev_inv_transforms, uint32_t n_top);
+int pt_instance_motion(const pt_ctx* ctx, uint32_t* moving_out); /* 1 / 0: set or not; moving_out (optional): leaves whose previous transform differs in any bit */
+int pt_read_motion_guides(pt_ctx* ctx, float* motion, float* prev_normal); /* host, width*height*4 floats each; either may be NULL */
+int pt_write_motion_guides(pt_ctx* ctx, const float* motion, const float* prev_normal); /* checkpoint restore / tests; the count is pt_guide_samples */
+void* pt_motion_guides_device_ptr(pt_ctx* ctx, int which); /* 0 motion, 1 prev_normal; NULL before they are allocated */
+/* test hook, no device needed: the records pt_set_instance_motion makes, for n (prev_inv, cur_inv) pairs of 16 floats; out24: n x 24 floats -- the
+ * three (A | t) rows, then the three rows of prev_inv.  Refusals as pt_set_instance_motion's, through pt_last_error(NULL). */
+int pt_debug_motion_records(const float* prev_inv, const float* cur_inv, uint32_t n, float* out24);
 
 /* ---- kernel-granular entry points (parity tests and micro-benchmarks) ------------------
  * Host SoA arrays in, host SoA arrays out; the scene must have been uploaded. */

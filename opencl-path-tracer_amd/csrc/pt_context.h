@@ -119,6 +119,8 @@ struct pt_ctx {
         bool generalRoute = false; // ... and the per-ray kernels enter them as leaf-kind steps (pt_trace.h, LEVELS 2): some transform is not a translation + uniform scale, or there are more than the fold table holds
         uint32_t enteredInstances = 0; // instances that are entered at traversal (not copied to world space)
         std::vector<uint32_t> instanceTopNode; // instance index -> top-level leaf node index
+        std::vector<Instance> hostInstances; // the instance table as uploaded (pt_set_instance_motion reads the current invTransform rows from it)
+        uint32_t numTopNodes = 0; // top-level nodes of this state as the caller counts them
         hipEvent_t uploaded = nullptr; // recorded on the copy stream after the set's last upload
         hipEvent_t lastUse = nullptr; // recorded on the render stream when the set stopped being the active one
         bool used = false;
@@ -222,6 +224,15 @@ struct pt_ctx {
     uint32_t temporalFrames = 0; // pt_temporal_accumulate calls (or 1 after pt_write_temporal) since the last reset: 0 = no history
     CameraDev temporalCamera {};
     uint32_t sampleBase = 0; // pt_set_sample_base: added to the sample index pt_render and pt_render_guides key the counter PRNG with
+
+    // instance motion (include/ptamd.h): one record per instance of the ACTIVE dynamic state (indexed like its instance table, which is how the guide
+    // pass meets a hit), and the two guide sums made from them -- (displacement.xyz, 0) and (normal then.xyz, 0), width * height float4 each, allocated at
+    // the first pt_set_instance_motion / pt_write_motion_guides.  pt_frame_tick forgets the motion; pt_clear zeroes the sums and keeps it.
+    DevBuf<MotionRecord> motionRecords;
+    std::vector<MotionRecord> motionHost;
+    bool motionSet = false;
+    uint32_t motionMoving = 0;
+    DevBuf<float4> guideMotion, guidePrevNormal;
 
     double msLastRender = 0, msIntersect = 0, msShade = 0, msShadow = 0, msGen = 0, msPacket = 0;
 };

@@ -13,7 +13,7 @@
 namespace ptconv {
 
 // the records travel between this unit and the kernels' one, which another compiler driver builds: their layouts must agree
-static_assert(sizeof(float4) == 16 && alignof(float4) == 16 && sizeof(PairNode) == 64 && sizeof(WideNode) == 64 && sizeof(TriFat) == 128 && sizeof(BakeJob) == 128,
+static_assert(sizeof(float4) == 16 && alignof(float4) == 16 && sizeof(PairNode) == 64 && sizeof(WideNode) == 64 && sizeof(TriFat) == 128 && sizeof(BakeJob) == 128 && sizeof(MotionRecord) == 96,
     "record layouts of pt_device.h");
 
 // a refusal: its PT_* code, and the message formatted as the entry points' fail() formats it
@@ -1258,6 +1258,47 @@ int convertDynamic(StaticHost& s, const ConvertOptions& o, uint64_t& versions, L
     }
     out.numLights = nL;
     out.rootRef = rootRef;
+    return PT_OK;
+}
+
+// ---- instance motion ------------------------------------------------------------------------------------------------------------------
+int motionRecords(const float* prevInv, const float* curInv, uint32_t n, const uint8_t* use, MotionRecord* out, uint32_t* moving, std::string& why)
+{
+    uint32_t moved = 0;
+    for (uint32_t i = 0; i < n; i++) {
+        MotionRecord r {};
+        if (use && !use[i]) {
+            out[i] = r;
+            continue;
+        }
+        const float *p = prevInv + (size_t)i * 16, *c = curInv + (size_t)i * 16;
+        for (int k = 0; k < 16; k++)
+            if (!std::isfinite(p[k]))
+                return refuse(why, PT_ERR_INVALID, "instance motion: the previous invTransform of entry %u is not finite", i);
+        r.p0 = make_float4(p[0], p[4], p[8], p[12]);
+        r.p1 = make_float4(p[1], p[5], p[9], p[13]);
+        r.p2 = make_float4(p[2], p[6], p[10], p[14]);
+        double w[4][8];
+        if (!invertTransform(p, w)) // (also where the bits are the current ones: a state that cannot be inverted has no "then" to go to)
+            return refuse(why, PT_ERR_INVALID, "instance motion: the previous invTransform of entry %u is singular", i);
+        if (std::memcmp(p, c, 16 * sizeof(float)) != 0) {
+            moved++;
+            float4* rows[3] = { &r.a0, &r.a1, &r.a2 };
+            for (int row = 0; row < 3; row++) {
+                double e[4];
+                for (int col = 0; col < 4; col++) {
+                    double s = 0.0;
+                    for (int k = 0; k < 4; k++)
+                        s += w[row][4 + k] * (double)c[col * 4 + k]; // element (row, k) of inverse(prev) times element (k, col) of cur
+                    e[col] = s - (row == col ? 1.0 : 0.0);
+                }
+                *rows[row] = make_float4((float)e[0], (float)e[1], (float)e[2], (float)e[3]);
+            }
+        }
+        out[i] = r;
+    }
+    if (moving)
+        *moving = moved;
     return PT_OK;
 }
 

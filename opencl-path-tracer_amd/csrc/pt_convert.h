@@ -168,6 +168,13 @@ int convertStatic(StaticHost& s, const ConvertOptions& o, uint64_t& versions, co
 int convertDynamic(StaticHost& s, const ConvertOptions& o, uint64_t& versions, Latest latest, const pt_emissive_triangle* lights, uint32_t nL,
     const pt_top_bvh_node* topNodes, uint32_t nTop, uint32_t topRoot, DynamicHost& out, std::string& why);
 
+// Instance motion (pt_set_instance_motion, pt_debug_motion_records): entry i of `out` from the previous and the current invTransform of entry i, 16 floats
+// each, column-major.  In double, P = inverse(prev) * cur (world now -> world then); the record holds P - I and the translation, rounded to float once, and
+// prev's rows 0..2.  Where prev has cur's bits the displacement is written as exact zeros (no inverse involved).  `use` (optional): entries whose byte is 0
+// are skipped (their record is all zero).  `moving` (optional): entries whose matrices differ in any bit.  A previous matrix that is singular or not finite
+// is refused (PT_ERR_INVALID, `why`).
+int motionRecords(const float* prevInv, const float* curInv, uint32_t n, const uint8_t* use, MotionRecord* out, uint32_t* moving, std::string& why);
+
 // refits on the host (pt_update_geometry before the master copy reached the device, or a conversion after a refit on the device)
 void refitPairBoxes(StaticHost& s, const pt_vertex* verts, const pt_sub_bvh_node* nodes, bool onlyExtra);
 void refitWideOnHost(StaticHost& s);

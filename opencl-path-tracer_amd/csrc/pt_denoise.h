@@ -37,13 +37,26 @@ __global__ void __launch_bounds__(256) k_guide_gen(FrameParams fp, float4* __res
 //                                    the ray.  A miss: (-D, PT_GUIDE_SKY_DEPTH).
 // A thin lens traces un-normalised directions (camera.cl:71-75): its deposits use D / |D| and t * |D|, so that normal and distance mean the same
 // for both cameras.
+// MOTION (pt_set_instance_motion; include/ptamd.h, "instance motion"): two more sums, from the MotionRecord of the hit instance --
+//   motion     += (A X + t, 0)       X = O + t D, the world hit point with the queue's own origin and un-normalised direction: where that point was in the
+//                                    scene state the history was made under, minus where it is.  A miss: 0.
+//   prevNormal += (n_then, 0)        N's expression on the previous invTransform's rows, flipped iff N was.  A miss: -D.
+// An instance whose previous transform has the current one's bits deposits exact zeros and the bits of N.  k_guides<false> is the kernel of before.
+struct GuideMotionArgs {
+    const MotionRecord* records; // indexed like sc.instances
+    float4* motion;
+    float4* prevNormal;
+};
+
+template <bool MOTION>
 __global__ void __launch_bounds__(256) k_guides(SceneDev sc, const float4* __restrict__ qO, const float4* __restrict__ qD, const float4* __restrict__ hit,
-    const int32_t* __restrict__ hitInst, uint32_t n, uint32_t thinLens, float4* __restrict__ albedoHits, float4* __restrict__ normalDepth)
+    const int32_t* __restrict__ hitInst, uint32_t n, uint32_t thinLens, float4* __restrict__ albedoHits, float4* __restrict__ normalDepth, GuideMotionArgs mo)
 {
     const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= n)
         return;
-    const uint32_t pixel = asU(qO[k].w);
+    const float4 ro = qO[k];
+    const uint32_t pixel = asU(ro.w);
     const float4 rd = qD[k], h = hit[k];
     V3 D = xyz(rd);
     float scale = 1.0f;
@@ -53,17 +66,31 @@ __global__ void __launch_bounds__(256) k_guides(SceneDev sc, const float4* __res
     }
     const int32_t prim = (int32_t)asU(h.w);
     V3 albedo = mk(1.0f), N = D * -1.0f;
+    V3 moved = mk(0.0f), nThen = N;
     float t = kGuideSkyDepth, hits = 0.0f;
     if (prim >= 0) {
         const TriFat* fp = &sc.triFat[prim];
         const float4 f0 = fp->n0u, f1 = fp->n1u, f2 = fp->n2u, f3 = fp->vvvm, f6 = fp->v0c, f7 = fp->mat;
         const float u = h.y, v = h.z;
         const Instance in = sc.instances[hitInst[k]];
+        MotionRecord rec;
+        if constexpr (MOTION) // six more 16-byte loads, in flight with the triangle's and the instance's
+            rec = mo.records[hitInst[k]];
         const V3 n0 = xyz(f0), n1 = xyz(f1), n2 = xyz(f2);
         const V3 shadingNormal = normalize(n0 + (n1 - n0) * u + (n2 - n0) * v); // object space (shadeHit)
         N = normalize(normalTransform(in, shadingNormal));
-        if (dot(N, D) > 0.0f)
+        const bool flip = dot(N, D) > 0.0f;
+        if (flip)
             N = N * -1.0f;
+        if constexpr (MOTION) {
+            Instance then = in;
+            then.r0 = rec.p0, then.r1 = rec.p1, then.r2 = rec.p2;
+            nThen = normalize(normalTransform(then, shadingNormal));
+            if (flip)
+                nThen = nThen * -1.0f;
+            const V3 X = xyz(ro) + xyz(rd) * h.x;
+            moved = mk(dot(xyz(rec.a0), X) + rec.a0.w, dot(xyz(rec.a1), X) + rec.a1.w, dot(xyz(rec.a2), X) + rec.a2.w);
+        }
         const MatView mat = loadMaterial(f6, f7);
         if (mat.type == MAT_PBR) {
             albedo = mat.colour;
@@ -78,11 +105,19 @@ __global__ void __launch_bounds__(256) k_guides(SceneDev sc, const float4* __res
         t = h.x * scale;
         hits = 1.0f;
     }
-    float4 a = albedoHits[pixel], g = normalDepth[pixel];
+    float4 a = albedoHits[pixel], g = normalDepth[pixel], m, pn;
+    if constexpr (MOTION)
+        m = mo.motion[pixel], pn = mo.prevNormal[pixel];
     a.x += albedo.x, a.y += albedo.y, a.z += albedo.z, a.w += hits;
     g.x += N.x, g.y += N.y, g.z += N.z, g.w += t;
     albedoHits[pixel] = a;
     normalDepth[pixel] = g;
+    if constexpr (MOTION) {
+        m.x += moved.x, m.y += moved.y, m.z += moved.z;
+        pn.x += nThen.x, pn.y += nThen.y, pn.z += nThen.z;
+        mo.motion[pixel] = m;
+        mo.prevNormal[pixel] = pn;
+    }
 }
 
 // ---- filter -------------------------------------------------------------------------------------

@@ -95,6 +95,12 @@ struct Instance {
     uint32_t simple; // the transform is a translation + uniform scale: a bundle of camera rays enters by scaling its beam (pt_packet_multi.h)
 };
 
+// instance motion (96 B; include/ptamd.h, "instance motion"): where the points of an instance were in the scene state the temporal history was made under
+struct MotionRecord {
+    float4 a0, a1, a2; // rows (A | t) of P - I, P = inverse(previous invTransform) * invTransform: world now -> world then; a point X moved by A X + t
+    float4 p0, p1, p2; // the previous invTransform's rows, laid out like Instance::r0..r2 (normalTransform takes them)
+};
+
 struct Material { // the reference's 48-byte record, read as 3 x float4
     float4 colour; // diffuse / base|reflectance / absorption / emissive
     float4 params; // bits: x = textureId | smoothness | iorBasic ; y = f0NonMetal | iorRough ; z = metallic byte

@@ -22,6 +22,9 @@ struct TemporalArgs {
     // the history's camera: its eye, and the three vectors that give lambda, alpha and beta of q = X - E' as plain dot products:
     //   s0.(q x v') = q.(v' x s0),   s0.(u' x q) = q.(s0 x u'),   each divided by det = s0.(u' x v') on the host
     V3 histEye, rowLambda, rowAlpha, rowBeta;
+    // k_temporal<true> (instance motion): the two motion sums of the guide pass -- (sum of displacements.xyz, 0) and (sum of the normals then.xyz, 0)
+    const float4* motion;
+    const float4* prevNormal;
 };
 
 constexpr int kTemporalTileW = kAtrousTileW, kTemporalTileH = kAtrousTileH; // the filter's tile: a wave is two rows of 32 pixels
@@ -30,6 +33,11 @@ constexpr int kTemporalTileW = kAtrousTileW, kTemporalTileH = kAtrousTileH; // t
 // reprojected position in both images: a tap outside the image loads nothing, one whose count is zero does not load its guide), two 16-byte writes.
 // The taps of a wave lie in a compact patch of the history, which the vector cache and L2 serve; there is no fixed halo to stage.  No atomics: the
 // output is bit-reproducible.
+// MOTION (pt_set_instance_motion): two more 16-byte reads, issued with the first three -- 144 bytes per pixel instead of 112.  The first hit is taken to where
+// it WAS before it goes into the history's camera, q = (E + z D + m / gspp) - E', and the taps' normal term compares the history's normal with the
+// surface's normal THEN (the sum normalised as n is).  The set written out holds the current (n, z) all the same.  Zero motion sums and prevNormal ==
+// normalDepth.xyz give the plain kernel's bits.
+template <bool MOTION>
 __global__ void __launch_bounds__(256) k_temporal(TemporalArgs a)
 {
     const int x = blockIdx.x * kTemporalTileW + threadIdx.x, y = blockIdx.y * kTemporalTileH + threadIdx.y;
@@ -38,6 +46,9 @@ __global__ void __launch_bounds__(256) k_temporal(TemporalArgs a)
         return;
     const size_t p = (size_t)y * W + x;
     const float4 s = a.accum[p], al = a.albedoHits[p], g = a.normalDepth[p];
+    float4 mv, pn;
+    if constexpr (MOTION)
+        mv = a.motion[p], pn = a.prevNormal[p];
     // exactly k_denoise_prepare's quantities
     const float dr = s.x / a.spp / albedoOf(al.x, a.gspp), dg = s.y / a.spp / albedoOf(al.y, a.gspp), db = s.z / a.spp / albedoOf(al.z, a.gspp);
     const float len = sqrtf(g.x * g.x + g.y * g.y + g.z * g.z);
@@ -45,13 +56,22 @@ __global__ void __launch_bounds__(256) k_temporal(TemporalArgs a)
     const V3 n = mk(g.x * inv, g.y * inv, g.z * inv);
     const float z = g.w / a.gspp;
     a.outGuide[p] = make_float4(n.x, n.y, n.z, z);
+    V3 nThen = n; // what the history's normals are compared with
+    if constexpr (MOTION) {
+        const float lenT = sqrtf(pn.x * pn.x + pn.y * pn.y + pn.z * pn.z);
+        const float invT = lenT > 0.0f ? 1.0f / lenT : 0.0f;
+        nThen = mk(pn.x * invT, pn.y * invT, pn.z * invT);
+    }
 
     float outR = dr, outG = dg, outB = db, outN = 1.0f;
     if (a.histColour) {
         // world point of the first hit through the pixel centre, then into the history's camera
         const float px = ((float)x + 0.5f) * a.invW, py = ((float)y + 0.5f) * a.invH;
         const V3 D = normalize(a.screen + a.u * px + a.v * py - a.eye);
-        const V3 q = a.eye + D * z - a.histEye;
+        V3 X = a.eye + D * z;
+        if constexpr (MOTION)
+            X = X + mk(mv.x / a.gspp, mv.y / a.gspp, mv.z / a.gspp); // where the surface was: added before the history's eye is subtracted
+        const V3 q = X - a.histEye;
         const float lambda = dot(q, a.rowLambda);
         if (lambda > 0.0f) {
             const float alpha = dot(q, a.rowAlpha), beta = dot(q, a.rowBeta);
@@ -79,7 +99,7 @@ __global__ void __launch_bounds__(256) k_temporal(TemporalArgs a)
                 if (counts) {
                     const float4 gh = a.histGuide[(size_t)(y0 + (t >> 1)) * W + (x0 + (t & 1))];
                     const float b = ((t & 1) ? ax : 1.0f - ax) * ((t >> 1) ? ay : 1.0f - ay);
-                    const float en = a.kNormal * fmaxf(0.0f, 1.0f - (n.x * gh.x + n.y * gh.y + n.z * gh.z));
+                    const float en = a.kNormal * fmaxf(0.0f, 1.0f - (nThen.x * gh.x + nThen.y * gh.y + nThen.z * gh.z));
                     const float ez = fabsf(zq - gh.w) * a.invSigmaDepth / (fminf(zq, gh.w) + 1e-6f);
                     w = b * __expf(-(en + ez));
                 }

@@ -491,6 +491,7 @@ void pt_destroy(pt_ctx* c)
     c->guideCtl.release(), c->denoiseColour[0].release(), c->denoiseColour[1].release(), c->denoiseGuide.release();
     for (int k = 0; k < 2; k++)
         c->temporalColour[k].release(), c->temporalGuide[k].release();
+    c->motionRecords.release(), c->guideMotion.release(), c->guidePrevNormal.release();
     for (hipEvent_t ev : c->evDenoise)
         if (ev) (void)hipEventDestroy(ev);
     c->accumPlanes.release(), c->pixelOrdinal.release(), c->resolveTmp.release(), c->activeFlag.release(), c->streams.release(), c->control.release(), c->totals.release(), c->spill.release();
@@ -885,6 +886,8 @@ int pt_upload_dynamic_async(pt_ctx* c, const pt_emissive_triangle* lights, uint3
     d.hasInstances = h.hasInstances;
     d.generalRoute = h.generalRoute && h.hasInstances, d.enteredInstances = h.enteredInstances;
     d.instanceTopNode = std::move(h.instanceTopNode);
+    d.hostInstances = std::move(h.instances); // (copied into the staging memory above)
+    d.numTopNodes = nTop;
     c->pending = target;
     return PT_OK;
     });
@@ -912,6 +915,8 @@ int pt_frame_tick(pt_ctx* c)
     newEpoch(c); // (what a batch's first pass emits belongs to the scene state it was measured on)
     c->pending = -1;
     c->haveDynamic = true;
+    c->motionSet = false; // (its records are indexed by the state that was just replaced)
+    c->motionMoving = 0;
     if (next.staticIndex != c->statCur) { // the state was built on a rebuilt scene (pt_upload_static_async): that scene is the current one from here on
         c->statCur = next.staticIndex;
         c->st = &c->stat[c->statCur];
@@ -1061,6 +1066,10 @@ int pt_clear(pt_ctx* c)
     if (c->guideAlbedoHits.p) { // the guide sums belong to the image they describe
         HIPCHK(c, hipMemsetAsync(c->guideAlbedoHits.p, 0, c->guideAlbedoHits.n * sizeof(float4), c->stream));
         HIPCHK(c, hipMemsetAsync(c->guideNormalDepth.p, 0, c->guideNormalDepth.n * sizeof(float4), c->stream));
+    }
+    if (c->guideMotion.p) { // ... and so do the two motion sums (the motion itself stays set)
+        HIPCHK(c, hipMemsetAsync(c->guideMotion.p, 0, c->guideMotion.n * sizeof(float4), c->stream));
+        HIPCHK(c, hipMemsetAsync(c->guidePrevNormal.p, 0, c->guidePrevNormal.n * sizeof(float4), c->stream));
     }
     c->guideSpp = 0;
     if (c->overflowPinned && *c->overflowPinned) { // a reported overflow is cleared with the image it spoiled (whatever set it has run: the word is only read after a synchronisation)
@@ -1302,8 +1311,13 @@ int pt_render_guides(pt_ctx* c, uint32_t spp)
         a.hit = c->guideHit.p, a.inst = c->guideHitInst.p, a.accum = AccumView { nullptr, nullptr, nullptr, 0u }, a.occluded = nullptr;
         a.ctl = c->guideCtl.p, a.pass = 0;
         launchTrace(c, false, a);
-        hipLaunchKernelGGL(k_guides, dim3((n + 255u) / 256u), dim3(256), 0, c->stream, c->scene, c->guideRayO.p, c->guideRayD.p, c->guideHit.p,
-            c->guideHitInst.p, n, c->camera.thinLens, c->guideAlbedoHits.p, c->guideNormalDepth.p);
+        if (c->motionSet)
+            hipLaunchKernelGGL(k_guides<true>, dim3((n + 255u) / 256u), dim3(256), 0, c->stream, c->scene, c->guideRayO.p, c->guideRayD.p, c->guideHit.p,
+                c->guideHitInst.p, n, c->camera.thinLens, c->guideAlbedoHits.p, c->guideNormalDepth.p,
+                GuideMotionArgs { c->motionRecords.p, c->guideMotion.p, c->guidePrevNormal.p });
+        else
+            hipLaunchKernelGGL(k_guides<false>, dim3((n + 255u) / 256u), dim3(256), 0, c->stream, c->scene, c->guideRayO.p, c->guideRayD.p, c->guideHit.p,
+                c->guideHitInst.p, n, c->camera.thinLens, c->guideAlbedoHits.p, c->guideNormalDepth.p, GuideMotionArgs { nullptr, nullptr, nullptr });
     }
     c->batchEntries = batchEntries;
     c->teamLaunches = teamLaunches;
@@ -1543,7 +1557,11 @@ int pt_temporal_accumulate(pt_ctx* c, const pt_temporal_params* prm)
         }
     }
     const dim3 grid((a.width + kTemporalTileW - 1) / kTemporalTileW, (a.height + kTemporalTileH - 1) / kTemporalTileH), block(kTemporalTileW, kTemporalTileH);
-    hipLaunchKernelGGL(k_temporal, grid, block, 0, c->stream, a);
+    if (c->motionSet) { // the history is met where the surfaces were (the two sums are there: pt_set_instance_motion made them)
+        a.motion = c->guideMotion.p, a.prevNormal = c->guidePrevNormal.p;
+        hipLaunchKernelGGL(k_temporal<true>, grid, block, 0, c->stream, a);
+    } else
+        hipLaunchKernelGGL(k_temporal<false>, grid, block, 0, c->stream, a);
     HIPCHK(c, hipGetLastError());
     c->temporalCamera = c->camera;
     c->temporalNewest = to;
@@ -1604,6 +1622,142 @@ void* pt_temporal_device_ptr(pt_ctx* c, int which)
     if (!c || which < 0 || which > 1)
         return nullptr;
     return which == 0 ? (void*)c->temporalColour[c->temporalNewest].p : (void*)c->temporalGuide[c->temporalNewest].p;
+}
+
+// ---- instance motion (k_guides<true>, k_temporal<true>) -----------------------------------------
+
+namespace {
+
+// the two motion sums: allocated (zeroed) at the first pt_set_instance_motion / pt_write_motion_guides
+int ensureMotionGuides(pt_ctx* c)
+{
+    const size_t n = (size_t)c->cfg.width * c->cfg.height;
+    if (c->guideMotion.p)
+        return PT_OK;
+    HIPCHK(c, c->guideMotion.alloc(n));
+    HIPCHK(c, c->guidePrevNormal.alloc(n));
+    HIPCHK(c, hipMemsetAsync(c->guideMotion.p, 0, n * sizeof(float4), c->stream));
+    HIPCHK(c, hipMemsetAsync(c->guidePrevNormal.p, 0, n * sizeof(float4), c->stream));
+    return PT_OK;
+}
+
+} // namespace
+
+int pt_set_instance_motion(pt_ctx* c, const float* prevInv, uint32_t nTop)
+{
+    return guarded(c, "pt_set_instance_motion", [&]() -> int {
+    if (!c)
+        return PT_ERR_INVALID;
+    if (parityMode(c) || c->cfg.max_active_rays != 0)
+        return fail(c, PT_ERR_UNSUPPORTED, "pt_set_instance_motion: the fixed schedule with PT_RNG_COUNTER only (not in parity / refill mode)");
+    if (!c->haveDynamic)
+        return fail(c, PT_ERR_STATE, "pt_set_instance_motion: no dynamic state is active yet (pt_upload_dynamic)");
+    if (c->guideSpp != 0)
+        return fail(c, PT_ERR_STATE, "pt_set_instance_motion: %u guide samples are in the sums already -- set or forget the motion right after pt_clear", c->guideSpp);
+    if (!prevInv || nTop == 0) {
+        c->motionSet = false;
+        c->motionMoving = 0;
+        return PT_OK;
+    }
+    const pt_ctx::DynamicSet& d = c->dyn[c->active];
+    if (nTop != d.numTopNodes)
+        return fail(c, PT_ERR_INVALID, "pt_set_instance_motion: %u previous transforms for an active state of %u top-level nodes", nTop, d.numTopNodes);
+    HIPCHK(c, hipSetDevice(c->device));
+    // one record per INSTANCE (the index the guide pass meets a hit with); the fourth row of an invTransform is (0, 0, 0, 1) to the traversal, and here
+    const size_t nInst = d.hostInstances.size();
+    std::vector<float> prev(nInst * 16), cur(nInst * 16);
+    for (size_t j = 0; j < nInst; j++) {
+        const Instance& in = d.hostInstances[j];
+        const float* p = prevInv + (size_t)in.topNode * 16;
+        const float rows[3][4] = { { in.r0.x, in.r0.y, in.r0.z, in.r0.w }, { in.r1.x, in.r1.y, in.r1.z, in.r1.w }, { in.r2.x, in.r2.y, in.r2.z, in.r2.w } };
+        float *pm = &prev[j * 16], *cm = &cur[j * 16];
+        for (int col = 0; col < 4; col++) {
+            for (int row = 0; row < 3; row++)
+                pm[col * 4 + row] = p[col * 4 + row], cm[col * 4 + row] = rows[row][col];
+            pm[col * 4 + 3] = cm[col * 4 + 3] = col == 3 ? 1.0f : 0.0f;
+        }
+    }
+    std::vector<MotionRecord> records(std::max<size_t>(nInst, 1));
+    uint32_t moving = 0;
+    std::string why;
+    int rc = ptconv::motionRecords(prev.data(), cur.data(), (uint32_t)nInst, nullptr, records.data(), &moving, why);
+    if (rc)
+        return fail(c, rc, "pt_set_instance_motion: %s (entries count the state's instances, in the order of its top-level leaves)", why.c_str());
+    if ((rc = ensureMotionGuides(c)))
+        return rc;
+    if (c->motionRecords.n < std::max<size_t>(nTop, 1)) { // n_top entries: never fewer than the state has instances
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        HIPCHK(c, c->motionRecords.alloc(std::max<size_t>(nTop, 1)));
+    }
+    c->motionHost = std::move(records);
+    if (nInst)
+        HIPCHK(c, hipMemcpyAsync(c->motionRecords.p, c->motionHost.data(), nInst * sizeof(MotionRecord), hipMemcpyHostToDevice, c->stream));
+    c->motionSet = true;
+    c->motionMoving = moving;
+    return PT_OK;
+    });
+}
+
+int pt_instance_motion(const pt_ctx* c, uint32_t* movingOut)
+{
+    if (movingOut)
+        *movingOut = c && c->motionSet ? c->motionMoving : 0u;
+    return c && c->motionSet ? 1 : 0;
+}
+
+int pt_read_motion_guides(pt_ctx* c, float* motion, float* prevNormal)
+{
+    if (!c)
+        return PT_ERR_INVALID;
+    HIPCHK(c, hipSetDevice(c->device));
+    int rc = ensureMotionGuides(c);
+    if (rc)
+        return rc;
+    const size_t bytes = (size_t)c->cfg.width * c->cfg.height * sizeof(float4);
+    if (motion)
+        HIPCHK(c, hipMemcpyAsync(motion, c->guideMotion.p, bytes, hipMemcpyDeviceToHost, c->stream));
+    if (prevNormal)
+        HIPCHK(c, hipMemcpyAsync(prevNormal, c->guidePrevNormal.p, bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return PT_OK;
+}
+
+int pt_write_motion_guides(pt_ctx* c, const float* motion, const float* prevNormal)
+{
+    if (!c || !motion || !prevNormal)
+        return PT_ERR_INVALID;
+    HIPCHK(c, hipSetDevice(c->device));
+    int rc = ensureMotionGuides(c);
+    if (rc)
+        return rc;
+    const size_t bytes = (size_t)c->cfg.width * c->cfg.height * sizeof(float4);
+    HIPCHK(c, hipMemcpyAsync(c->guideMotion.p, motion, bytes, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->guidePrevNormal.p, prevNormal, bytes, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return PT_OK;
+}
+
+void* pt_motion_guides_device_ptr(pt_ctx* c, int which)
+{
+    if (!c || which < 0 || which > 1)
+        return nullptr;
+    return which == 0 ? (void*)c->guideMotion.p : (void*)c->guidePrevNormal.p;
+}
+
+// test hook, no device needed: the host conversion behind pt_set_instance_motion, entry by entry (24 floats each)
+int pt_debug_motion_records(const float* prevInv, const float* curInv, uint32_t n, float* out24)
+{
+    return guarded(nullptr, "pt_debug_motion_records", [&]() -> int {
+    if (!prevInv || !curInv || !out24)
+        return fail(nullptr, PT_ERR_INVALID, "pt_debug_motion_records: null argument");
+    std::vector<MotionRecord> records(std::max<uint32_t>(n, 1u));
+    std::string why;
+    const int rc = ptconv::motionRecords(prevInv, curInv, n, nullptr, records.data(), nullptr, why);
+    if (rc)
+        return fail(nullptr, rc, "pt_debug_motion_records: %s", why.c_str());
+    std::memcpy(out24, records.data(), (size_t)n * sizeof(MotionRecord));
+    return PT_OK;
+    });
 }
 
 int pt_stats_get(pt_ctx* c, pt_stats* out)

@@ -58,6 +58,23 @@ RayTracer::~RayTracer() { pt_destroy(m_ctx); }
 // rendering, then adopted by everything enqueued from here on.  No wait on the host.
 void RayTracer::frameTick()
 {
+    // instance motion: the state about to be replaced is the one the newest history was made under if getTemporalOutput blended a frame of it; if not
+    // (several ticks without a blend) the transforms kept before stay: the oldest.  The leaves of the top level are nodes [0, instances) in scene-graph
+    // order (buildTopBVHOver), so index i names the same instance across ticks while the graph's structure is unchanged.
+    if (m_rebuilt) {
+        m_prevLeafValid = false; // other meshes: nothing to follow
+    } else if (m_blendedThisState) {
+        size_t leaves = 0;
+        while (leaves < m_flat.topBvhNodes.size() && m_flat.topBvhNodes[leaves].isLeaf)
+            leaves++;
+        m_prevLeafInv.resize(leaves * 16);
+        for (size_t i = 0; i < leaves; i++)
+            std::memcpy(&m_prevLeafInv[i * 16], m_flat.topBvhNodes[i].invTransform, 16 * sizeof(float));
+        m_prevLeafValid = true;
+    }
+    m_blendedThisState = false;
+    m_rebuilt = false;
+    m_motionDue = true;
     flattenDynamic(*m_scene, m_flat);
     check(pt_upload_dynamic_async(m_ctx, m_flat.emissiveTriangles.data(), (uint32_t)m_flat.emissiveTriangles.size(), m_flat.topBvhNodes.data(),
               (uint32_t)m_flat.topBvhNodes.size(), m_flat.topBvhRoot),
@@ -112,6 +129,29 @@ void RayTracer::rebuildGeometry()
     check(pt_upload_static_async(m_ctx, m_flat.vertices.data(), (uint32_t)m_flat.vertices.size(), m_flat.triangles.data(), (uint32_t)m_flat.triangles.size(),
               m_flat.materials.data(), (uint32_t)m_flat.materials.size(), m_flat.subBvhNodes.data(), (uint32_t)m_flat.subBvhNodes.size()),
         "pt_upload_static_async");
+    m_rebuilt = true;
+}
+
+// The first rayTrace on a cleared accumulator after a tick: hand the device library the transforms the leaves had when the newest history was made
+// (pt_set_instance_motion wants them before the first guide sample).  Nothing is set without a history, with another number of leaves, or when switched off.
+void RayTracer::setMotionAfterTick()
+{
+    m_motionDue = false;
+    const std::vector<TopBVHNode>& top = m_flat.topBvhNodes;
+    size_t leaves = 0;
+    while (leaves < top.size() && top[leaves].isLeaf)
+        leaves++;
+    bool follow = m_instanceMotion && m_prevLeafValid && pt_temporal_frames(m_ctx) != 0 && leaves * 16 == m_prevLeafInv.size();
+    for (size_t i = leaves; i < top.size(); i++)
+        follow = follow && !top[i].isLeaf; // (leaves behind an inner node: not the host library's top level, the indices mean something else)
+    if (!follow) {
+        if (pt_instance_motion(m_ctx, nullptr)) // a motion set for an earlier frame of this state: the history has caught up since
+            check(pt_set_instance_motion(m_ctx, nullptr, 0), "pt_set_instance_motion");
+        return;
+    }
+    std::vector<float> prev(top.size() * 16, 0.0f); // (entries of inner nodes are ignored)
+    std::memcpy(prev.data(), m_prevLeafInv.data(), m_prevLeafInv.size() * sizeof(float));
+    check(pt_set_instance_motion(m_ctx, prev.data(), (uint32_t)top.size()), "pt_set_instance_motion");
 }
 
 void RayTracer::rayTrace(const Camera& camera)
@@ -125,6 +165,8 @@ void RayTracer::rayTrace(const Camera& camera)
     }
     if (getSamplesPerPixel() >= getMaxSamplesPerPixel())
         return;
+    if (m_motionDue && pt_samples_per_pixel(m_ctx) == 0 && pt_guide_samples(m_ctx) == 0)
+        setMotionAfterTick();
     check(pt_render(m_ctx, 1), "pt_render");
     m_temporalDirty = true;
     check(pt_synchronize(m_ctx), "pt_synchronize"); // queue.finish(), src/raytracer.cpp:117-118
@@ -171,6 +213,10 @@ std::vector<float> RayTracer::getTemporalOutput(int iterations)
         pt_temporal_params tp {};
         check(pt_temporal_accumulate(m_ctx, &tp), "pt_temporal_accumulate");
         m_temporalDirty = false;
+        m_blendedThisState = true; // the newest history is of this scene state: the next frameTick keeps its transforms
+        m_prevLeafValid = false;
+        if (pt_instance_motion(m_ctx, nullptr))
+            m_motionDue = true; // ... and a further frame of this state must not be moved again
     }
     pt_denoise_params prm {};
     prm.iterations = (uint32_t)iterations;

@@ -93,6 +93,13 @@ public:
     // camera (once per frame: a second call for the same frame filters the same history again), then filters the history `iterations` times.  For a
     // frame loop that moves the camera every frame: setSampleBase(frame); rayTrace(camera); getTemporalOutput().
     std::vector<float> getTemporalOutput(int iterations = 5);
+    // Motion vectors for instances re-posed by frameTick (include/ptamd.h, "instance motion"): frameTick keeps the leaves' transforms of the state the last
+    // getTemporalOutput blended (the oldest, if several ticks passed since), and the first rayTrace on a cleared accumulator after the tick hands them to
+    // the device library -- so the guide samples getTemporalOutput renders carry the motion, and the history follows the instances.  Only while the scene
+    // graph's structure is unchanged (same number of leaves: index i then names the same instance), never across rebuildGeometry.  On by default; it acts
+    // for getTemporalOutput users alone (without a history nothing is set): getOutput / getDenoisedOutput are what they were.  A frame loop with a static
+    // camera clears by itself (pt_clear(context())) after its frameTick: rayTrace only clears when the camera changed.
+    void setInstanceMotion(bool on) { m_instanceMotion = on; }
     void resetTemporalHistory(); // forget the history: after a cut, or when the scene changed beyond what depth and normal can tell
     void setSampleBase(uint32_t base); // pt_set_sample_base: frames that restart at sample 0 draw other random numbers each
     struct Guides {
@@ -113,6 +120,14 @@ private:
     CameraData m_prevCamera;
     bool m_haveCamera = false;
     bool m_temporalDirty = false; // samples were traced since the last getTemporalOutput
+    // instance motion: the leaves' invTransform (16 floats each, scene-graph order) of the state the newest history was made under
+    bool m_instanceMotion = true;
+    std::vector<float> m_prevLeafInv;
+    bool m_prevLeafValid = false; // m_prevLeafInv is that state's (false: no history yet, or the geometry was rebuilt since)
+    bool m_blendedThisState = false; // getTemporalOutput blended a frame of the current scene state
+    bool m_motionDue = false; // a tick happened: the next rayTrace on a cleared accumulator sets (or leaves unset) the motion
+    bool m_rebuilt = false; // rebuildGeometry since the last frameTick
+    void setMotionAfterTick();
     int m_width, m_height;
 };
 

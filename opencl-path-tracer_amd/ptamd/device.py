@@ -86,7 +86,8 @@ EXPORTS = ["pt_create", "pt_destroy", "pt_last_error", "pt_set_stream", "pt_uplo
            "pt_synchronize", "pt_resolve", "pt_resolve_device", "pt_resolve_device_ptr", "pt_read_accum", "pt_write_accum", "pt_accum_device_ptr",
            "pt_samples_per_pixel", "pt_render_guides", "pt_guide_samples", "pt_read_guides", "pt_write_guides", "pt_guides_device_ptr",
            "pt_denoise", "pt_denoise_device", "pt_set_sample_base", "pt_sample_base", "pt_temporal_accumulate", "pt_temporal_reset",
-           "pt_temporal_frames", "pt_read_temporal", "pt_write_temporal", "pt_temporal_device_ptr", "pt_stats_get", "pt_stats_reset", "pt_profile_kernels", "pt_reduce_accum",
+           "pt_temporal_frames", "pt_read_temporal", "pt_write_temporal", "pt_temporal_device_ptr", "pt_set_instance_motion", "pt_instance_motion",
+           "pt_read_motion_guides", "pt_write_motion_guides", "pt_motion_guides_device_ptr", "pt_debug_motion_records", "pt_stats_get", "pt_stats_reset", "pt_profile_kernels", "pt_reduce_accum",
            "pt_intersect", "pt_gen_rays", "pt_primary_pass", "pt_shade_batch", "pt_debug_quantise_node", "pt_debug_convert", "pt_debug_copy_bandwidth", "pt_debug_math_probe", "pt_version"]
 
 _lib = None
@@ -156,6 +157,13 @@ def lib():
         l.pt_write_temporal.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         l.pt_temporal_device_ptr.restype = C.c_void_p
         l.pt_temporal_device_ptr.argtypes = [C.c_void_p, C.c_int]
+        l.pt_set_instance_motion.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
+        l.pt_instance_motion.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
+        l.pt_read_motion_guides.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        l.pt_write_motion_guides.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        l.pt_motion_guides_device_ptr.restype = C.c_void_p
+        l.pt_motion_guides_device_ptr.argtypes = [C.c_void_p, C.c_int]
+        l.pt_debug_motion_records.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
         l.pt_stats_get.argtypes = [C.c_void_p, C.POINTER(Stats)]
         l.pt_stats_reset.argtypes = [C.c_void_p]
         l.pt_profile_kernels.argtypes = [C.c_void_p, C.c_int]
@@ -188,6 +196,28 @@ def debug_convert(flat, flags=0, rng_mode=RNG_COUNTER):
     if rc != 0:
         raise PtError(f"pt_debug_convert failed ({rc}): {lib().pt_last_error(None).decode()}")
     return line.value.decode()
+
+
+MOTION_RECORD_BYTES = 96  # three float4 rows (A | t) of P - I, then the three rows of the previous invTransform
+
+
+def _inv_transforms(prev):
+    """(n, 16) float32 from an (n, 16) array or a top_nodes record array (its invTransform)"""
+    prev = np.asarray(prev)
+    if prev.dtype.names and "invTransform" in prev.dtype.names:
+        prev = prev["invTransform"]
+    return np.ascontiguousarray(prev, np.float32).reshape(-1, 16)
+
+
+def debug_motion_records(prev_inv, cur_inv):
+    """pt_debug_motion_records: the (n, 6, 4) float32 records pt_set_instance_motion makes of n (previous, current) invTransforms -- no device needed."""
+    p, c = _inv_transforms(prev_inv), _inv_transforms(cur_inv)
+    assert p.shape == c.shape
+    out = np.zeros((len(p), 6, 4), np.float32)
+    rc = lib().pt_debug_motion_records(_p(p), _p(c), len(p), _p(out))
+    if rc != 0:
+        raise PtError(f"pt_debug_motion_records failed ({rc}): {lib().pt_last_error(None).decode()}")
+    return out
 
 
 class Context:
@@ -420,6 +450,39 @@ class Context:
     def temporal_device_ptr(self, which):
         """Device address of the colour_count (0) / normal_depth (1) image of the newest set (0 before the first temporal call)."""
         return lib().pt_temporal_device_ptr(self._h, which) or 0
+
+    # ---- instance motion
+    def set_instance_motion(self, prev):
+        """The invTransform every top-level node of the active state had when the newest history was made: an (n_top, 16) float32 array, a top_nodes
+        record array (its invTransform is taken), or None to forget the motion.  Right after clear(): refused once guide samples are in."""
+        if prev is None:
+            self._chk(lib().pt_set_instance_motion(self._h, None, 0), "pt_set_instance_motion")
+            return
+        m = _inv_transforms(prev)
+        self._chk(lib().pt_set_instance_motion(self._h, _p(m), len(m)), "pt_set_instance_motion")
+
+    @property
+    def instance_motion(self):
+        """(set, moving): whether a motion is set, and how many leaves' previous transform differs from the current one in any bit"""
+        moving = C.c_uint32(0)
+        return bool(lib().pt_instance_motion(self._h, C.byref(moving))), int(moving.value)
+
+    def read_motion_guides(self):
+        """(motion, prev_normal): two (width*height, 4) arrays of sums over the guide samples"""
+        m = np.zeros((self.height * self.width, 4), np.float32)
+        pn = np.zeros((self.height * self.width, 4), np.float32)
+        self._chk(lib().pt_read_motion_guides(self._h, _p(m), _p(pn)), "pt_read_motion_guides")
+        return m, pn
+
+    def write_motion_guides(self, motion, prev_normal):
+        m = np.ascontiguousarray(motion, np.float32)
+        pn = np.ascontiguousarray(prev_normal, np.float32)
+        assert m.size == pn.size == self.width * self.height * 4
+        self._chk(lib().pt_write_motion_guides(self._h, _p(m), _p(pn)), "pt_write_motion_guides")
+
+    def motion_guides_device_ptr(self, which):
+        """Device address of the motion (0) / prev_normal (1) image (0 before they are allocated)."""
+        return lib().pt_motion_guides_device_ptr(self._h, which) or 0
 
     def stats(self):
         s = Stats()

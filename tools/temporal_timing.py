@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Device time of pt_temporal_accumulate at 1280 x 720 and 1920 x 1080, one JSON line (EXPERIMENTS.md).
-Not part of bench.py.     usage: python tools/temporal_timing.py [--calls 25] [--batch 20] [--scene cornell|blob]
+Not part of bench.py.     usage: python tools/temporal_timing.py [--calls 25] [--batch 20] [--scene cornell|blob] [--motion]
 
 temporal_ms.static / .panned: median device ms of ONE pt_temporal_accumulate, measured between two events on the stream the context renders on
 around `batch` calls in a row (one call is tens of microseconds: a pair of events around a single launch would time the events).  static: the camera
@@ -19,6 +19,7 @@ ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 sys.path[:0] = [os.path.join(ROOT, "opencl-path-tracer_amd"), ROOT]
 
 FLOOR_BYTES_PER_PIXEL = 7 * 16
+MOTION_FLOOR_BYTES_PER_PIXEL = 9 * 16  # --motion: the two motion sums are read as well
 
 
 def main():
@@ -27,6 +28,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--batch", type=int, default=20)
     ap.add_argument("--scene", default="cornell")
+    ap.add_argument("--motion", action="store_true", help="also time k_temporal<true> (instance motion set), next to the plain kernel")
     args = ap.parse_args()
     import torch
     from ptamd import device as D, scenes
@@ -75,6 +77,26 @@ def main():
             "gbps": {"static": round(floor / static / 1e6, 1), "panned": round(floor / panned / 1e6, 1)}, "copy_gbps": round(copy, 1),
             "fraction_of_copy": {"static": round(floor / static / 1e6 / copy, 3), "panned": round(floor / panned / 1e6 / copy, 3)},
             "mean_history_count_panned": round(float(cn[:, 3].mean()), 2)}
+        if args.motion:
+            # k_temporal<true> in the same process, against the same copy rate: every instance was a millimetre to the side, so every pixel of it carries
+            # a displacement; two more 16-byte reads per pixel, 9 x 16 = 144 bytes
+            was = b.flat.top_nodes["invTransform"].copy()
+            was[:, 12] += 1e-3
+            ctx.set_camera(b.camera)
+            ctx.clear()
+            ctx.set_instance_motion(was)
+            is_set, moving = ctx.instance_motion
+            assert is_set and moving == int((b.flat.top_nodes["isLeaf"] != 0).sum())
+            ctx.render(1)
+            ctx.render_guides(1)
+            m_static = timed(lambda i: ctx.temporal_accumulate(sync=False), args.batch)
+            m_panned = timed(panned_call, args.batch)
+            m_floor = MOTION_FLOOR_BYTES_PER_PIXEL * width * height
+            out["sizes"][f"{width}x{height}"]["motion"] = {
+                "temporal_ms": {"static": round(m_static, 5), "panned": round(m_panned, 5)}, "floor_bytes": m_floor, "moving_instances": moving,
+                "expected_ms": {"static": round(static * MOTION_FLOOR_BYTES_PER_PIXEL / FLOOR_BYTES_PER_PIXEL, 5),
+                                "panned": round(panned * MOTION_FLOOR_BYTES_PER_PIXEL / FLOOR_BYTES_PER_PIXEL, 5)},
+                "fraction_of_copy": {"static": round(m_floor / m_static / 1e6 / copy, 3), "panned": round(m_floor / m_panned / 1e6 / copy, 3)}}
         ctx.close()
     print(json.dumps(out))
 
