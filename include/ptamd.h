@@ -408,12 +408,12 @@ uint32_t pt_sample_base(const pt_ctx* ctx);
  *                   continuous function of the inputs -- there is no accept / reject threshold that round-off could flip.
  * (d_out, N_out) and the current (n, z) go into the other set, the current camera is remembered, the sets flip.  Bit-reproducible run to run.
  * A pixel of a dynamic scene whose surface moved keeps or loses its history by the depth and normal terms alone, unless the motion of its instance was set
- * (INSTANCE MOTION below), which changes two lines of the above:
+ * (INSTANCE MOTION below) or its mesh's deformation was (VERTEX MOTION below), which changes two lines of the above:
  *   into history    q = (X + m / gspp) - E',  m the pixel's motion sum: the displacement is added to X BEFORE the history's eye is subtracted;  z' = |q| as before
  *   taps            e_n = k_normal max(0, 1 - n_then(p).n_h),  n_then the pixel's prev_normal sum normalised exactly as n is (zero stays zero)
  * and nothing else: the set written out still holds the CURRENT (n, z); blend, clamps and the 1e-12 rule are the same.  Zero motion sums and
- * prev_normal == normal_depth.xyz give the plain output bit for bit.  Still without motion vectors: deforming meshes (pt_refit_vertices, pt_update_geometry,
- * rebuilt trees) and moving lights.
+ * prev_normal == normal_depth.xyz give the plain output bit for bit.  Still without motion vectors: rebuilt trees (pt_upload_static_async) and
+ * moving lights.
  * Refusals: PT_ERR_STATE before a camera is set and when pt_samples_per_pixel or pt_guide_samples is 0; PT_ERR_UNSUPPORTED while tiles are set (as
  * pt_denoise); PT_ERR_INVALID for max_history > 4096 or a negative k_normal / sigma_depth. */
 typedef struct {
@@ -463,6 +463,44 @@ void* pt_motion_guides_device_ptr(pt_ctx* ctx, int which); /* 0 motion, 1 prev_n
 /* test hook, no device needed: the records pt_set_instance_motion makes, for n (prev_inv, cur_inv) pairs of 16 floats; out24: n x 24 floats -- the
  * three (A | t) rows, then the three rows of prev_inv.  Refusals as pt_set_instance_motion's, through pt_last_error(NULL). */
 int pt_debug_motion_records(const float* prev_inv, const float* cur_inv, uint32_t n, float* out24);
+
+/* VERTEX MOTION: motion vectors for meshes that were refitted (pt_refit_vertices, pt_update_geometry) between the previous dynamic state and the active
+ * one.  Opt-in like the block above: with no vertex motion set, every entry point launches exactly the kernels it launches without this block and returns
+ * the same bits.
+ *
+ * "Then" is the geometry of the dynamic state that was active before the last pt_frame_tick: the shading records (v0, the two edges, the three vertex
+ * normals per triangle, caller's numbering, object space) the now-inactive set still holds.  pt_set_vertex_motion(ctx, 1) copies them, device to device on
+ * the render stream, into a buffer of the context's own (numTris records, allocated at the first enabling, grow-only, freed by pt_destroy) -- the guide
+ * pass reads that copy alone, so a pipelined caller may start the next pt_upload_dynamic_async before the frame's pt_render_guides.  Where both sets hold
+ * the same version of the same static arrays (no refit came between) nothing is copied, deformed_out is 0 and the sums are, bit for bit, those without
+ * vertex motion.
+ * With vertex motion set, pt_render_guides deposits into the two sums of INSTANCE MOTION (allocated as there).  (u, v): the hit's barycentrics; v0, e1, e2,
+ * n0, n1, n2: the current record of the hit triangle, primed: the copy's; X = O + t D as above:
+ *   x_now  = v0 + e1 u + e2 v,   x_then = v0' + e1' u + e2' v     (one function, the same operations in the same order)     delta = x_then - x_now
+ *   motion      += ((A X + t) + L delta, 0)
+ *   prev_normal += (n_then, 0),  n_then = normalize(normalTransform(then, normalize(n0' + (n1' - n0') u + (n2' - n0') v))),  flipped iff N was
+ * (A | t) and `then` (the previous invTransform's rows) are the instance-motion record where an instance motion is set; otherwise A = t = 0 and `then`
+ * holds the current rows' bits.  L, three float4 rows (w = 0), is the linear part of the world transform the instance had then: the 3 x 3 of
+ * inverse(prev_inv) where an instance motion is set, else of inverse(cur_inv); formed in double on the host, rounded once, n_inst x 48 bytes on the
+ * device, made again whenever either setter is called (their order does not matter).  The split is exact: W_then x_then - X = (P X - X) + L_then delta.
+ * A triangle whose copy has the current record's bits gives delta == 0 exactly and deposits what the instance motion alone deposits, bit for bit -- exact
+ * zeros and the bits of N where there is none.  A miss deposits 0 and -D.  Sample order, bit-reproducibility, tiles adding up and the independence of
+ * samples_in_flight are those of the other sums; pt_temporal_accumulate takes the motion route when either motion is set.
+ * A frame loop: refit, pt_upload_dynamic_async, pt_frame_tick, pt_clear, pt_set_instance_motion / pt_set_vertex_motion, pt_render, pt_render_guides,
+ * pt_temporal_accumulate, pt_denoise.
+ *
+ * pt_set_vertex_motion refuses: PT_ERR_UNSUPPORTED in parity / refill mode; PT_ERR_STATE before a dynamic state is active and while
+ * pt_guide_samples() != 0 (setting and forgetting alike); enabling: PT_ERR_STATE when there is no previous state (the other set never held an adopted one)
+ * and while an upload is pending (pt_upload_dynamic_async without its pt_frame_tick: it is overwriting the set that held "then"); PT_ERR_UNSUPPORTED when
+ * the previous state was built on the other static scene (a pt_upload_static_async rebuild) or has another triangle count; PT_ERR_INVALID when a
+ * transform L is made from is singular.  A refused call changes nothing.  pt_frame_tick (and with it pt_upload_dynamic) forgets the vertex motion as it
+ * forgets the instance motion; pt_clear zeroes the sums and keeps it set; pt_set_instance_motion(NULL) forgets the instance part alone. */
+int pt_set_vertex_motion(pt_ctx* ctx, int enable);            /* 1: take the previous state's geometry as "then"; 0: forget */
+int pt_vertex_motion(const pt_ctx* ctx, uint32_t* deformed_out); /* 1 / 0: set or not; deformed_out (optional): 1 when the previous state held another
+                                                                    version of the static arrays (a refit came between), else 0 */
+/* test hook, no device needed: the rows L for n invTransforms of 16 floats (column-major); out12: n x 12 floats.  A singular or non-finite matrix is
+ * PT_ERR_INVALID, through pt_last_error(NULL). */
+int pt_debug_vertex_motion_rows(const float* inv_transforms, uint32_t n, float* out12);
 
 /* ---- kernel-granular entry points (parity tests and micro-benchmarks) ------------------
  * Host SoA arrays in, host SoA arrays out; the scene must have been uploaded. */

@@ -234,6 +234,16 @@ struct pt_ctx {
     uint32_t motionMoving = 0;
     DevBuf<float4> guideMotion, guidePrevNormal;
 
+    // vertex motion (include/ptamd.h): a snapshot of the shading records the previous dynamic state held (numTris of them, taken on the render stream by
+    // pt_set_vertex_motion: the guide pass never reads the inactive set, which the next upload may be overwriting), and three float4 rows per instance of
+    // the active state -- the linear part of the world transform the instance had then.  Grow-only; pt_frame_tick forgets the motion.  While it is set
+    // without an instance motion, motionRecords holds identity records (A = t = 0, the current rows).
+    DevBuf<TriFat> fatThen;
+    DevBuf<float4> vertexRows;
+    std::vector<float4> vertexRowsHost;
+    bool vertexMotionSet = false;
+    bool vertexDeformed = false; // the previous state held another version of the static arrays: k_guides<2> runs
+
     double msLastRender = 0, msIntersect = 0, msShade = 0, msShadow = 0, msGen = 0, msPacket = 0;
 };
 

@@ -1302,4 +1302,25 @@ int motionRecords(const float* prevInv, const float* curInv, uint32_t n, const u
     return PT_OK;
 }
 
+// ---- vertex motion --------------------------------------------------------------------------------------------------------------------
+int vertexMotionRows(const float* inv, uint32_t n, float4* out, std::string& why)
+{
+    for (uint32_t i = 0; i < n; i++) {
+        const float* m = inv + (size_t)i * 16;
+        for (int k = 0; k < 16; k++)
+            if (!std::isfinite(m[k]))
+                return refuse(why, PT_ERR_INVALID, "vertex motion: the invTransform of entry %u is not finite", i);
+        double w[4][8];
+        if (!invertTransform(m, w))
+            return refuse(why, PT_ERR_INVALID, "vertex motion: the invTransform of entry %u is singular", i);
+        for (int row = 0; row < 3; row++) {
+            const float4 r = make_float4((float)w[row][4], (float)w[row][5], (float)w[row][6], 0.0f);
+            if (!std::isfinite(r.x) || !std::isfinite(r.y) || !std::isfinite(r.z)) // (a pivot above the threshold by round-off alone)
+                return refuse(why, PT_ERR_INVALID, "vertex motion: the invTransform of entry %u is singular", i);
+            out[(size_t)i * 3 + row] = r;
+        }
+    }
+    return PT_OK;
+}
+
 } // namespace ptconv

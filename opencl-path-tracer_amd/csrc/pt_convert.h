@@ -175,6 +175,11 @@ int convertDynamic(StaticHost& s, const ConvertOptions& o, uint64_t& versions, L
 // is refused (PT_ERR_INVALID, `why`).
 int motionRecords(const float* prevInv, const float* curInv, uint32_t n, const uint8_t* use, MotionRecord* out, uint32_t* moving, std::string& why);
 
+// Vertex motion (pt_set_vertex_motion, pt_debug_vertex_motion_rows): entry i of `out` is three float4 rows (w = 0), the linear part of the WORLD transform
+// whose inverse entry i of `inv` is (16 floats, column-major): the 3 x 3 of inverse(inv) in double, rounded to float once.  It takes an object-space
+// displacement of a deformed mesh to world space.  A matrix that is singular or not finite is refused (PT_ERR_INVALID, `why`).
+int vertexMotionRows(const float* inv, uint32_t n, float4* out, std::string& why);
+
 // refits on the host (pt_update_geometry before the master copy reached the device, or a conversion after a refit on the device)
 void refitPairBoxes(StaticHost& s, const pt_vertex* verts, const pt_sub_bvh_node* nodes, bool onlyExtra);
 void refitWideOnHost(StaticHost& s);

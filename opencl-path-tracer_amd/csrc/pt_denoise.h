@@ -37,18 +37,34 @@ __global__ void __launch_bounds__(256) k_guide_gen(FrameParams fp, float4* __res
 //                                    the ray.  A miss: (-D, PT_GUIDE_SKY_DEPTH).
 // A thin lens traces un-normalised directions (camera.cl:71-75): its deposits use D / |D| and t * |D|, so that normal and distance mean the same
 // for both cameras.
-// MOTION (pt_set_instance_motion; include/ptamd.h, "instance motion"): two more sums, from the MotionRecord of the hit instance --
+// MODE 1 (pt_set_instance_motion; include/ptamd.h, "instance motion"): two more sums, from the MotionRecord of the hit instance --
 //   motion     += (A X + t, 0)       X = O + t D, the world hit point with the queue's own origin and un-normalised direction: where that point was in the
 //                                    scene state the history was made under, minus where it is.  A miss: 0.
 //   prevNormal += (n_then, 0)        N's expression on the previous invTransform's rows, flipped iff N was.  A miss: -D.
-// An instance whose previous transform has the current one's bits deposits exact zeros and the bits of N.  k_guides<false> is the kernel of before.
+// An instance whose previous transform has the current one's bits deposits exact zeros and the bits of N.  k_guides<0> is the kernel of before.
+// MODE 2 (pt_set_vertex_motion; include/ptamd.h, "vertex motion"): the mesh was refitted since the state the history was made under.  `then` holds that
+// state's shading records (a snapshot: never the inactive dynamic set, which the next upload may be overwriting), `rowsThen` three rows per instance --
+// the linear part L of the world transform the instance had then.  With x(record) = v0 + e1 u + e2 v (guidePoint, the same operations for both records),
+//   motion     += (A X + t + L (x(then) - x(now)), 0)        W_then x_then - X = (P X - X) + L_then (x_then - x_now), exactly
+//   prevNormal += (n_then, 0)                                the snapshot's interpolated normal through the previous rows
+// A triangle whose snapshot has the current record's bits has x(then) - x(now) == 0 and deposits what mode 1 deposits, bit for bit.  The current line,
+// the snapshot's six quarters, the instance, the motion record and the three rows are 27 independent 16-byte loads, issued before the first use.
 struct GuideMotionArgs {
     const MotionRecord* records; // indexed like sc.instances
     float4* motion;
     float4* prevNormal;
+    const TriFat* then; // MODE 2: the previous state's shading records, indexed like sc.triFat
+    const float4* rowsThen; // MODE 2: three per instance
 };
 
-template <bool MOTION>
+// the hit point in object space from a shading record's v0 / edge1 / edge2 quarters (TriFat::e1e, e2v, v0c): spelled with fmaf so that the current record
+// and the snapshot go through the same instructions whatever the compiler would have contracted
+__device__ inline V3 guidePoint(const float4 e1e, const float4 e2v, const float4 v0c, float u, float v)
+{
+    return mk(fmaf(e1e.w, v, fmaf(e1e.x, u, e2v.z)), fmaf(e2v.x, v, fmaf(e1e.y, u, e2v.w)), fmaf(e2v.y, v, fmaf(e1e.z, u, v0c.x)));
+}
+
+template <int MODE> // 0: no motion; 1: instance motion; 2: instance and vertex motion
 __global__ void __launch_bounds__(256) k_guides(SceneDev sc, const float4* __restrict__ qO, const float4* __restrict__ qD, const float4* __restrict__ hit,
     const int32_t* __restrict__ hitInst, uint32_t n, uint32_t thinLens, float4* __restrict__ albedoHits, float4* __restrict__ normalDepth, GuideMotionArgs mo)
 {
@@ -74,22 +90,40 @@ __global__ void __launch_bounds__(256) k_guides(SceneDev sc, const float4* __res
         const float u = h.y, v = h.z;
         const Instance in = sc.instances[hitInst[k]];
         MotionRecord rec;
-        if constexpr (MOTION) // six more 16-byte loads, in flight with the triangle's and the instance's
+        if constexpr (MODE >= 1) // six more 16-byte loads, in flight with the triangle's and the instance's
             rec = mo.records[hitInst[k]];
+        float4 f4, f5, t0, t1, t2, t4, t5, t6, l0, l1, l2;
+        if constexpr (MODE == 2) {
+            const TriFat* tp = &mo.then[prim];
+            const float4* lp = &mo.rowsThen[3 * hitInst[k]];
+            f4 = fp->e1e, f5 = fp->e2v;
+            t0 = tp->n0u, t1 = tp->n1u, t2 = tp->n2u, t4 = tp->e1e, t5 = tp->e2v, t6 = tp->v0c;
+            l0 = lp[0], l1 = lp[1], l2 = lp[2];
+        }
         const V3 n0 = xyz(f0), n1 = xyz(f1), n2 = xyz(f2);
         const V3 shadingNormal = normalize(n0 + (n1 - n0) * u + (n2 - n0) * v); // object space (shadeHit)
         N = normalize(normalTransform(in, shadingNormal));
         const bool flip = dot(N, D) > 0.0f;
         if (flip)
             N = N * -1.0f;
-        if constexpr (MOTION) {
+        if constexpr (MODE >= 1) {
             Instance then = in;
             then.r0 = rec.p0, then.r1 = rec.p1, then.r2 = rec.p2;
-            nThen = normalize(normalTransform(then, shadingNormal));
+            V3 shadingNormalThen = shadingNormal;
+            if constexpr (MODE == 2) {
+                const V3 m0 = xyz(t0), m1 = xyz(t1), m2 = xyz(t2);
+                shadingNormalThen = normalize(m0 + (m1 - m0) * u + (m2 - m0) * v);
+            }
+            nThen = normalize(normalTransform(then, shadingNormalThen));
             if (flip)
                 nThen = nThen * -1.0f;
             const V3 X = xyz(ro) + xyz(rd) * h.x;
             moved = mk(dot(xyz(rec.a0), X) + rec.a0.w, dot(xyz(rec.a1), X) + rec.a1.w, dot(xyz(rec.a2), X) + rec.a2.w);
+            if constexpr (MODE == 2) {
+                const V3 delta = guidePoint(t4, t5, t6, u, v) - guidePoint(f4, f5, f6, u, v); // object space; 0 exactly where the bits agree
+                moved = moved + mk(fmaf(l0.z, delta.z, fmaf(l0.y, delta.y, l0.x * delta.x)), fmaf(l1.z, delta.z, fmaf(l1.y, delta.y, l1.x * delta.x)),
+                                    fmaf(l2.z, delta.z, fmaf(l2.y, delta.y, l2.x * delta.x)));
+            }
         }
         const MatView mat = loadMaterial(f6, f7);
         if (mat.type == MAT_PBR) {
@@ -106,13 +140,13 @@ __global__ void __launch_bounds__(256) k_guides(SceneDev sc, const float4* __res
         hits = 1.0f;
     }
     float4 a = albedoHits[pixel], g = normalDepth[pixel], m, pn;
-    if constexpr (MOTION)
+    if constexpr (MODE >= 1)
         m = mo.motion[pixel], pn = mo.prevNormal[pixel];
     a.x += albedo.x, a.y += albedo.y, a.z += albedo.z, a.w += hits;
     g.x += N.x, g.y += N.y, g.z += N.z, g.w += t;
     albedoHits[pixel] = a;
     normalDepth[pixel] = g;
-    if constexpr (MOTION) {
+    if constexpr (MODE >= 1) {
         m.x += moved.x, m.y += moved.y, m.z += moved.z;
         pn.x += nThen.x, pn.y += nThen.y, pn.z += nThen.z;
         mo.motion[pixel] = m;

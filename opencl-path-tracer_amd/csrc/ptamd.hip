@@ -492,6 +492,7 @@ void pt_destroy(pt_ctx* c)
     for (int k = 0; k < 2; k++)
         c->temporalColour[k].release(), c->temporalGuide[k].release();
     c->motionRecords.release(), c->guideMotion.release(), c->guidePrevNormal.release();
+    c->fatThen.release(), c->vertexRows.release();
     for (hipEvent_t ev : c->evDenoise)
         if (ev) (void)hipEventDestroy(ev);
     c->accumPlanes.release(), c->pixelOrdinal.release(), c->resolveTmp.release(), c->activeFlag.release(), c->streams.release(), c->control.release(), c->totals.release(), c->spill.release();
@@ -917,6 +918,7 @@ int pt_frame_tick(pt_ctx* c)
     c->haveDynamic = true;
     c->motionSet = false; // (its records are indexed by the state that was just replaced)
     c->motionMoving = 0;
+    c->vertexMotionSet = c->vertexDeformed = false; // (its "then" is the state before the one that was just replaced)
     if (next.staticIndex != c->statCur) { // the state was built on a rebuilt scene (pt_upload_static_async): that scene is the current one from here on
         c->statCur = next.staticIndex;
         c->st = &c->stat[c->statCur];
@@ -1311,13 +1313,17 @@ int pt_render_guides(pt_ctx* c, uint32_t spp)
         a.hit = c->guideHit.p, a.inst = c->guideHitInst.p, a.accum = AccumView { nullptr, nullptr, nullptr, 0u }, a.occluded = nullptr;
         a.ctl = c->guideCtl.p, a.pass = 0;
         launchTrace(c, false, a);
-        if (c->motionSet)
-            hipLaunchKernelGGL(k_guides<true>, dim3((n + 255u) / 256u), dim3(256), 0, c->stream, c->scene, c->guideRayO.p, c->guideRayD.p, c->guideHit.p,
+        if (c->vertexMotionSet && c->vertexDeformed) // (the snapshot, never the inactive set: the next state may be on its way into that)
+            hipLaunchKernelGGL(k_guides<2>, dim3((n + 255u) / 256u), dim3(256), 0, c->stream, c->scene, c->guideRayO.p, c->guideRayD.p, c->guideHit.p,
                 c->guideHitInst.p, n, c->camera.thinLens, c->guideAlbedoHits.p, c->guideNormalDepth.p,
-                GuideMotionArgs { c->motionRecords.p, c->guideMotion.p, c->guidePrevNormal.p });
+                GuideMotionArgs { c->motionRecords.p, c->guideMotion.p, c->guidePrevNormal.p, c->fatThen.p, c->vertexRows.p });
+        else if (c->motionSet || c->vertexMotionSet) // (vertex motion with nothing deformed: identity records, exact zeros and the bits of N)
+            hipLaunchKernelGGL(k_guides<1>, dim3((n + 255u) / 256u), dim3(256), 0, c->stream, c->scene, c->guideRayO.p, c->guideRayD.p, c->guideHit.p,
+                c->guideHitInst.p, n, c->camera.thinLens, c->guideAlbedoHits.p, c->guideNormalDepth.p,
+                GuideMotionArgs { c->motionRecords.p, c->guideMotion.p, c->guidePrevNormal.p, nullptr, nullptr });
         else
-            hipLaunchKernelGGL(k_guides<false>, dim3((n + 255u) / 256u), dim3(256), 0, c->stream, c->scene, c->guideRayO.p, c->guideRayD.p, c->guideHit.p,
-                c->guideHitInst.p, n, c->camera.thinLens, c->guideAlbedoHits.p, c->guideNormalDepth.p, GuideMotionArgs { nullptr, nullptr, nullptr });
+            hipLaunchKernelGGL(k_guides<0>, dim3((n + 255u) / 256u), dim3(256), 0, c->stream, c->scene, c->guideRayO.p, c->guideRayD.p, c->guideHit.p,
+                c->guideHitInst.p, n, c->camera.thinLens, c->guideAlbedoHits.p, c->guideNormalDepth.p, GuideMotionArgs { nullptr, nullptr, nullptr, nullptr, nullptr });
     }
     c->batchEntries = batchEntries;
     c->teamLaunches = teamLaunches;
@@ -1557,7 +1563,7 @@ int pt_temporal_accumulate(pt_ctx* c, const pt_temporal_params* prm)
         }
     }
     const dim3 grid((a.width + kTemporalTileW - 1) / kTemporalTileW, (a.height + kTemporalTileH - 1) / kTemporalTileH), block(kTemporalTileW, kTemporalTileH);
-    if (c->motionSet) { // the history is met where the surfaces were (the two sums are there: pt_set_instance_motion made them)
+    if (c->motionSet || c->vertexMotionSet) { // the history is met where the surfaces were (the two sums are there: the setters made them)
         a.motion = c->guideMotion.p, a.prevNormal = c->guidePrevNormal.p;
         hipLaunchKernelGGL(k_temporal<true>, grid, block, 0, c->stream, a);
     } else
@@ -1624,7 +1630,7 @@ void* pt_temporal_device_ptr(pt_ctx* c, int which)
     return which == 0 ? (void*)c->temporalColour[c->temporalNewest].p : (void*)c->temporalGuide[c->temporalNewest].p;
 }
 
-// ---- instance motion (k_guides<true>, k_temporal<true>) -----------------------------------------
+// ---- instance motion (k_guides<1>, k_temporal<true>) --------------------------------------------
 
 namespace {
 
@@ -1638,6 +1644,56 @@ int ensureMotionGuides(pt_ctx* c)
     HIPCHK(c, c->guidePrevNormal.alloc(n));
     HIPCHK(c, hipMemsetAsync(c->guideMotion.p, 0, n * sizeof(float4), c->stream));
     HIPCHK(c, hipMemsetAsync(c->guidePrevNormal.p, 0, n * sizeof(float4), c->stream));
+    return PT_OK;
+}
+
+// Vertex motion's per-instance tables for the ACTIVE state, made again whenever either setter is called (so their order does not matter): the rows L of
+// the world transform each instance had THEN -- from `records`' previous rows where an instance motion is set (withMotion), from the current rows
+// otherwise -- and, without an instance motion, identity records (A = t = 0, the current rows).  Host only: nothing of the context changes.
+int makeVertexTables(pt_ctx* c, bool withMotion, std::vector<MotionRecord>& records, std::vector<float4>& rows, const char* who)
+{
+    const pt_ctx::DynamicSet& d = c->dyn[c->active];
+    const size_t nInst = d.hostInstances.size();
+    if (!withMotion) {
+        records.assign(std::max<size_t>(nInst, 1), MotionRecord {});
+        for (size_t j = 0; j < nInst; j++)
+            records[j].p0 = d.hostInstances[j].r0, records[j].p1 = d.hostInstances[j].r1, records[j].p2 = d.hostInstances[j].r2;
+    }
+    std::vector<float> inv(std::max<size_t>(nInst, 1) * 16);
+    for (size_t j = 0; j < nInst; j++) {
+        const float4 r[3] = { records[j].p0, records[j].p1, records[j].p2 };
+        float* m = &inv[j * 16];
+        for (int row = 0; row < 3; row++)
+            m[row] = r[row].x, m[4 + row] = r[row].y, m[8 + row] = r[row].z, m[12 + row] = r[row].w;
+        m[3] = m[7] = m[11] = 0.0f, m[15] = 1.0f;
+    }
+    rows.assign(std::max<size_t>(nInst, 1) * 3, make_float4(0.0f, 0.0f, 0.0f, 0.0f));
+    std::string why;
+    const int rc = ptconv::vertexMotionRows(inv.data(), (uint32_t)nInst, rows.data(), why);
+    if (rc)
+        return fail(c, rc, "%s: %s (entries count the state's instances, in the order of its top-level leaves)", who, why.c_str());
+    return PT_OK;
+}
+
+// ... and their way to the device, on the render stream (the host copies stay with the context)
+int commitVertexTables(pt_ctx* c, bool withMotion, std::vector<MotionRecord>& records, std::vector<float4>& rows)
+{
+    const pt_ctx::DynamicSet& d = c->dyn[c->active];
+    if (!withMotion) {
+        const size_t need = std::max<size_t>(std::max<size_t>(d.numTopNodes, records.size()), 1);
+        if (c->motionRecords.n < need) {
+            HIPCHK(c, hipStreamSynchronize(c->stream));
+            HIPCHK(c, c->motionRecords.alloc(need));
+        }
+        c->motionHost = std::move(records);
+        HIPCHK(c, hipMemcpyAsync(c->motionRecords.p, c->motionHost.data(), c->motionHost.size() * sizeof(MotionRecord), hipMemcpyHostToDevice, c->stream));
+    }
+    if (c->vertexRows.n < rows.size()) {
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        HIPCHK(c, c->vertexRows.alloc(rows.size() + rows.size() / 8));
+    }
+    c->vertexRowsHost = std::move(rows);
+    HIPCHK(c, hipMemcpyAsync(c->vertexRows.p, c->vertexRowsHost.data(), c->vertexRowsHost.size() * sizeof(float4), hipMemcpyHostToDevice, c->stream));
     return PT_OK;
 }
 
@@ -1655,6 +1711,14 @@ int pt_set_instance_motion(pt_ctx* c, const float* prevInv, uint32_t nTop)
     if (c->guideSpp != 0)
         return fail(c, PT_ERR_STATE, "pt_set_instance_motion: %u guide samples are in the sums already -- set or forget the motion right after pt_clear", c->guideSpp);
     if (!prevInv || nTop == 0) {
+        if (c->vertexMotionSet) { // only the instance part goes: the vertex motion goes on from the current transforms
+            HIPCHK(c, hipSetDevice(c->device));
+            std::vector<MotionRecord> ident;
+            std::vector<float4> rows;
+            int rc = makeVertexTables(c, false, ident, rows, "pt_set_instance_motion");
+            if (rc || (rc = commitVertexTables(c, false, ident, rows)))
+                return rc;
+        }
         c->motionSet = false;
         c->motionMoving = 0;
         return PT_OK;
@@ -1683,6 +1747,9 @@ int pt_set_instance_motion(pt_ctx* c, const float* prevInv, uint32_t nTop)
     int rc = ptconv::motionRecords(prev.data(), cur.data(), (uint32_t)nInst, nullptr, records.data(), &moving, why);
     if (rc)
         return fail(c, rc, "pt_set_instance_motion: %s (entries count the state's instances, in the order of its top-level leaves)", why.c_str());
+    std::vector<float4> rows;
+    if (c->vertexMotionSet && (rc = makeVertexTables(c, true, records, rows, "pt_set_instance_motion")))
+        return rc;
     if ((rc = ensureMotionGuides(c)))
         return rc;
     if (c->motionRecords.n < std::max<size_t>(nTop, 1)) { // n_top entries: never fewer than the state has instances
@@ -1694,6 +1761,8 @@ int pt_set_instance_motion(pt_ctx* c, const float* prevInv, uint32_t nTop)
         HIPCHK(c, hipMemcpyAsync(c->motionRecords.p, c->motionHost.data(), nInst * sizeof(MotionRecord), hipMemcpyHostToDevice, c->stream));
     c->motionSet = true;
     c->motionMoving = moving;
+    if (c->vertexMotionSet && (rc = commitVertexTables(c, true, c->motionHost, rows)))
+        return rc;
     return PT_OK;
     });
 }
@@ -1703,6 +1772,83 @@ int pt_instance_motion(const pt_ctx* c, uint32_t* movingOut)
     if (movingOut)
         *movingOut = c && c->motionSet ? c->motionMoving : 0u;
     return c && c->motionSet ? 1 : 0;
+}
+
+// ---- vertex motion (k_guides<2>) ------------------------------------------------------------------
+int pt_set_vertex_motion(pt_ctx* c, int enable)
+{
+    return guarded(c, "pt_set_vertex_motion", [&]() -> int {
+    if (!c)
+        return PT_ERR_INVALID;
+    if (parityMode(c) || c->cfg.max_active_rays != 0)
+        return fail(c, PT_ERR_UNSUPPORTED, "pt_set_vertex_motion: the fixed schedule with PT_RNG_COUNTER only (not in parity / refill mode)");
+    if (!c->haveDynamic)
+        return fail(c, PT_ERR_STATE, "pt_set_vertex_motion: no dynamic state is active yet (pt_upload_dynamic)");
+    if (c->guideSpp != 0)
+        return fail(c, PT_ERR_STATE, "pt_set_vertex_motion: %u guide samples are in the sums already -- set or forget the motion right after pt_clear", c->guideSpp);
+    if (!enable) {
+        c->vertexMotionSet = c->vertexDeformed = false;
+        return PT_OK;
+    }
+    if (c->pending >= 0)
+        return fail(c, PT_ERR_STATE, "pt_set_vertex_motion: an upload is pending (pt_upload_dynamic_async without its pt_frame_tick): it is overwriting the set that held the previous state");
+    pt_ctx::DynamicSet &cur = c->dyn[c->active], &old = c->dyn[1 - c->active];
+    if (!old.used)
+        return fail(c, PT_ERR_STATE, "pt_set_vertex_motion: there is no previous state (one pt_frame_tick adopted the only state so far)");
+    if (old.staticIndex != cur.staticIndex)
+        return fail(c, PT_ERR_UNSUPPORTED, "pt_set_vertex_motion: the previous state was built on another static scene (pt_upload_static_async): rebuilt trees have no vertex motion");
+    if (old.numTris != cur.numTris)
+        return fail(c, PT_ERR_UNSUPPORTED, "pt_set_vertex_motion: the previous state has %u triangles, the active one %u", old.numTris, cur.numTris);
+    HIPCHK(c, hipSetDevice(c->device));
+    const bool deformed = old.staticVersion != cur.staticVersion && cur.numTris != 0;
+    if (deformed && (old.fat.n < cur.numTris || cur.fat.n < cur.numTris))
+        return fail(c, PT_ERR_STATE, "pt_set_vertex_motion: the states hold no shading records for %u triangles", cur.numTris);
+    std::vector<MotionRecord> records;
+    std::vector<float4> rows;
+    if (c->motionSet)
+        records = c->motionHost;
+    int rc = makeVertexTables(c, c->motionSet, records, rows, "pt_set_vertex_motion");
+    if (rc || (rc = ensureMotionGuides(c)))
+        return rc;
+    if (deformed) {
+        if (c->fatThen.n < cur.numTris) {
+            HIPCHK(c, hipStreamSynchronize(c->stream)); // (growing frees what an earlier guide pass may still read)
+            HIPCHK(c, c->fatThen.alloc(cur.numTris));
+        }
+        // "then": the inactive set still holds the previous state's records.  Taken on the render stream, which has waited for that set's upload at its tick;
+        // the next pt_upload_dynamic_async writes the set on the copy stream after the set's lastUse event, which therefore moves behind this copy.
+        HIPCHK(c, hipMemcpyAsync(c->fatThen.p, old.fat.p, (size_t)cur.numTris * sizeof(TriFat), hipMemcpyDeviceToDevice, c->stream));
+        HIPCHK(c, hipEventRecord(old.lastUse, c->stream));
+    }
+    if ((rc = commitVertexTables(c, c->motionSet, records, rows)))
+        return rc;
+    c->vertexMotionSet = true;
+    c->vertexDeformed = deformed;
+    return PT_OK;
+    });
+}
+
+int pt_vertex_motion(const pt_ctx* c, uint32_t* deformedOut)
+{
+    if (deformedOut)
+        *deformedOut = c && c->vertexMotionSet && c->vertexDeformed ? 1u : 0u;
+    return c && c->vertexMotionSet ? 1 : 0;
+}
+
+// test hook, no device needed: the rows pt_set_vertex_motion makes of n invTransforms (12 floats each)
+int pt_debug_vertex_motion_rows(const float* invTransforms, uint32_t n, float* out12)
+{
+    return guarded(nullptr, "pt_debug_vertex_motion_rows", [&]() -> int {
+    if (!invTransforms || !out12)
+        return fail(nullptr, PT_ERR_INVALID, "pt_debug_vertex_motion_rows: null argument");
+    std::vector<float4> rows(std::max<size_t>((size_t)n * 3, 1));
+    std::string why;
+    const int rc = ptconv::vertexMotionRows(invTransforms, n, rows.data(), why);
+    if (rc)
+        return fail(nullptr, rc, "pt_debug_vertex_motion_rows: %s", why.c_str());
+    std::memcpy(out12, rows.data(), (size_t)n * 3 * sizeof(float4));
+    return PT_OK;
+    });
 }
 
 int pt_read_motion_guides(pt_ctx* c, float* motion, float* prevNormal)

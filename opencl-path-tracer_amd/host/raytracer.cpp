@@ -72,6 +72,9 @@ void RayTracer::frameTick()
             std::memcpy(&m_prevLeafInv[i * 16], m_flat.topBvhNodes[i].invTransform, 16 * sizeof(float));
         m_prevLeafValid = true;
     }
+    // vertex motion: the device library takes the state about to be replaced as "then", which is the history's only under the same condition
+    m_vertexDue = m_refitted && m_blendedThisState && !m_rebuilt;
+    m_refitted = false;
     m_blendedThisState = false;
     m_rebuilt = false;
     m_motionDue = true;
@@ -108,11 +111,13 @@ void RayTracer::updateGeometry()
         }
         check(rc, "pt_refit_vertices");
         pair.uploadedGeneration = gen;
+        m_refitted = true;
     }
     if (hostRoute) { // the reference's way: boxes refitted on the host, the whole vertex and node arrays handed over
         flattenStatic(*m_scene, m_flat);
         check(pt_update_geometry(m_ctx, m_flat.vertices.data(), (uint32_t)m_flat.vertices.size(), m_flat.subBvhNodes.data(), (uint32_t)m_flat.subBvhNodes.size()),
             "pt_update_geometry");
+        m_refitted = true;
         for (MeshBvhPair& pair : m_scene->getMeshes())
             pair.uploadedGeneration = pair.meshPtr->generation();
     }
@@ -134,9 +139,21 @@ void RayTracer::rebuildGeometry()
 
 // The first rayTrace on a cleared accumulator after a tick: hand the device library the transforms the leaves had when the newest history was made
 // (pt_set_instance_motion wants them before the first guide sample).  Nothing is set without a history, with another number of leaves, or when switched off.
+// Next to it the vertex motion, when a mesh was refitted (updateGeometry) since the previous tick and the history is of the state that tick replaced.
 void RayTracer::setMotionAfterTick()
 {
     m_motionDue = false;
+    setInstanceMotionAfterTick();
+    const bool deformed = m_vertexMotion && m_vertexDue && pt_temporal_frames(m_ctx) != 0;
+    m_vertexDue = false;
+    if (deformed)
+        check(pt_set_vertex_motion(m_ctx, 1), "pt_set_vertex_motion");
+    else if (pt_vertex_motion(m_ctx, nullptr)) // set for an earlier frame of this state: the history has caught up since
+        check(pt_set_vertex_motion(m_ctx, 0), "pt_set_vertex_motion");
+}
+
+void RayTracer::setInstanceMotionAfterTick()
+{
     const std::vector<TopBVHNode>& top = m_flat.topBvhNodes;
     size_t leaves = 0;
     while (leaves < top.size() && top[leaves].isLeaf)
@@ -215,7 +232,7 @@ std::vector<float> RayTracer::getTemporalOutput(int iterations)
         m_temporalDirty = false;
         m_blendedThisState = true; // the newest history is of this scene state: the next frameTick keeps its transforms
         m_prevLeafValid = false;
-        if (pt_instance_motion(m_ctx, nullptr))
+        if (pt_instance_motion(m_ctx, nullptr) || pt_vertex_motion(m_ctx, nullptr))
             m_motionDue = true; // ... and a further frame of this state must not be moved again
     }
     pt_denoise_params prm {};

@@ -100,6 +100,10 @@ public:
     // for getTemporalOutput users alone (without a history nothing is set): getOutput / getDenoisedOutput are what they were.  A frame loop with a static
     // camera clears by itself (pt_clear(context())) after its frameTick: rayTrace only clears when the camera changed.
     void setInstanceMotion(bool on) { m_instanceMotion = on; }
+    // Motion vectors for meshes refitted between two ticks (include/ptamd.h, "vertex motion"): when updateGeometry handed a refitted mesh over since the
+    // previous frameTick, and getTemporalOutput blended a frame of the state that tick replaced, the first rayTrace on a cleared accumulator after the tick
+    // sets pt_set_vertex_motion next to the instance motion -- the history follows the deforming surface.  Never across rebuildGeometry.  On by default.
+    void setVertexMotion(bool on) { m_vertexMotion = on; }
     void resetTemporalHistory(); // forget the history: after a cut, or when the scene changed beyond what depth and normal can tell
     void setSampleBase(uint32_t base); // pt_set_sample_base: frames that restart at sample 0 draw other random numbers each
     struct Guides {
@@ -127,7 +131,11 @@ private:
     bool m_blendedThisState = false; // getTemporalOutput blended a frame of the current scene state
     bool m_motionDue = false; // a tick happened: the next rayTrace on a cleared accumulator sets (or leaves unset) the motion
     bool m_rebuilt = false; // rebuildGeometry since the last frameTick
+    bool m_vertexMotion = true;
+    bool m_refitted = false; // updateGeometry handed a refitted mesh to the device library since the last frameTick
+    bool m_vertexDue = false; // ... and that tick replaced the state the newest history was made under: the device library's "then" is the history's
     void setMotionAfterTick();
+    void setInstanceMotionAfterTick();
     int m_width, m_height;
 };
 

@@ -136,6 +136,10 @@ def build_raytracer(force=False):
     if force or _newer(exe7, [os.path.join(ex_dir, "moving_cornell.cpp"), out]):
         subprocess.run(["g++", "-std=c++17", "-O2", "-Wall", "moving_cornell.cpp", "-o", "moving_cornell", "-L" + HOST_DIR, "-lptamd_raytracer",
                         "-lptamd_host", "-L" + CSRC_DIR, "-lptamd", "-Wl,-rpath," + HOST_DIR, "-Wl,-rpath," + CSRC_DIR], cwd=ex_dir, check=True)
+    exe8 = os.path.join(ex_dir, "deforming_cornell")
+    if force or _newer(exe8, [os.path.join(ex_dir, "deforming_cornell.cpp"), out]):
+        subprocess.run(["g++", "-std=c++17", "-O2", "-Wall", "deforming_cornell.cpp", "-o", "deforming_cornell", "-L" + HOST_DIR, "-lptamd_raytracer",
+                        "-lptamd_host", "-L" + CSRC_DIR, "-lptamd", "-Wl,-rpath," + HOST_DIR, "-Wl,-rpath," + CSRC_DIR], cwd=ex_dir, check=True)
     return out, exe
 
 

@@ -87,7 +87,8 @@ EXPORTS = ["pt_create", "pt_destroy", "pt_last_error", "pt_set_stream", "pt_uplo
            "pt_samples_per_pixel", "pt_render_guides", "pt_guide_samples", "pt_read_guides", "pt_write_guides", "pt_guides_device_ptr",
            "pt_denoise", "pt_denoise_device", "pt_set_sample_base", "pt_sample_base", "pt_temporal_accumulate", "pt_temporal_reset",
            "pt_temporal_frames", "pt_read_temporal", "pt_write_temporal", "pt_temporal_device_ptr", "pt_set_instance_motion", "pt_instance_motion",
-           "pt_read_motion_guides", "pt_write_motion_guides", "pt_motion_guides_device_ptr", "pt_debug_motion_records", "pt_stats_get", "pt_stats_reset", "pt_profile_kernels", "pt_reduce_accum",
+           "pt_read_motion_guides", "pt_write_motion_guides", "pt_motion_guides_device_ptr", "pt_debug_motion_records",
+           "pt_set_vertex_motion", "pt_vertex_motion", "pt_debug_vertex_motion_rows", "pt_stats_get", "pt_stats_reset", "pt_profile_kernels", "pt_reduce_accum",
            "pt_intersect", "pt_gen_rays", "pt_primary_pass", "pt_shade_batch", "pt_debug_quantise_node", "pt_debug_convert", "pt_debug_copy_bandwidth", "pt_debug_math_probe", "pt_version"]
 
 _lib = None
@@ -164,6 +165,9 @@ def lib():
         l.pt_motion_guides_device_ptr.restype = C.c_void_p
         l.pt_motion_guides_device_ptr.argtypes = [C.c_void_p, C.c_int]
         l.pt_debug_motion_records.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
+        l.pt_set_vertex_motion.argtypes = [C.c_void_p, C.c_int]
+        l.pt_vertex_motion.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
+        l.pt_debug_vertex_motion_rows.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
         l.pt_stats_get.argtypes = [C.c_void_p, C.POINTER(Stats)]
         l.pt_stats_reset.argtypes = [C.c_void_p]
         l.pt_profile_kernels.argtypes = [C.c_void_p, C.c_int]
@@ -217,6 +221,17 @@ def debug_motion_records(prev_inv, cur_inv):
     rc = lib().pt_debug_motion_records(_p(p), _p(c), len(p), _p(out))
     if rc != 0:
         raise PtError(f"pt_debug_motion_records failed ({rc}): {lib().pt_last_error(None).decode()}")
+    return out
+
+
+def debug_vertex_motion_rows(inv):
+    """pt_debug_vertex_motion_rows: the (n, 3, 4) float32 rows pt_set_vertex_motion makes of n invTransforms -- the linear part of each one's inverse,
+    w = 0 -- no device needed."""
+    m = _inv_transforms(inv)
+    out = np.zeros((len(m), 3, 4), np.float32)
+    rc = lib().pt_debug_vertex_motion_rows(_p(m), len(m), _p(out))
+    if rc != 0:
+        raise PtError(f"pt_debug_vertex_motion_rows failed ({rc}): {lib().pt_last_error(None).decode()}")
     return out
 
 
@@ -483,6 +498,18 @@ class Context:
     def motion_guides_device_ptr(self, which):
         """Device address of the motion (0) / prev_normal (1) image (0 before they are allocated)."""
         return lib().pt_motion_guides_device_ptr(self._h, which) or 0
+
+    # ---- vertex motion
+    def set_vertex_motion(self, on=True):
+        """Take the geometry of the previous dynamic state (the one before the last frame_tick) as where the refitted meshes were when the newest
+        history was made; False forgets it.  Right after clear(), like set_instance_motion."""
+        self._chk(lib().pt_set_vertex_motion(self._h, 1 if on else 0), "pt_set_vertex_motion")
+
+    @property
+    def vertex_motion(self):
+        """(set, deformed): whether a vertex motion is set, and 1 when a refit came between the previous state and the active one (else 0)"""
+        deformed = C.c_uint32(0)
+        return bool(lib().pt_vertex_motion(self._h, C.byref(deformed))), int(deformed.value)
 
     def stats(self):
         s = Stats()
