@@ -920,7 +920,7 @@ int convertDynamic(StaticHost& s, const ConvertOptions& o, uint64_t& versions, L
                                 && std::isfinite(in.r2.w))
                     ? 1u : 0u;
             }
-            if (hInst.size() >= kSpecialLeaveInstance)
+            if (hInst.size() >= kSpecialIdle) // (the indices from there on are the markers of pt_device.h)
                 return refuse(why, PT_ERR_UNSUPPORTED, "too many instances");
             topRef[i] = makeRef((uint32_t)hInst.size(), kRefSpecial);
             hInst.push_back(in);

@@ -53,6 +53,11 @@ constexpr uint32_t kSpecialLeaveInstance = kRefIndexMask - 1u; // stack sentinel
 constexpr uint32_t kRefFinish = 0xFFFFFFFFu;
 constexpr uint32_t kRefLeaveInstance = (kRefSpecial << kRefIndexBits) | kSpecialLeaveInstance;
 constexpr uint32_t kRefNone = kRefFinish;
+// what a lane of the per-ray kernels that holds NO ray keeps in its current reference (pt_trace.h): "this lane has no ray" is then a property of the value
+// the step votes look at -- every vote is one compare -- and not a second predicate.  Never in a tree or on a stack.
+constexpr uint32_t kSpecialIdle = kRefIndexMask - 2u;
+constexpr uint32_t kRefIdle = (kRefSpecial << kRefIndexBits) | kSpecialIdle;
+constexpr uint32_t kRefFirstSpecial = kRefSpecial << kRefIndexBits; // references from here on are instances, markers or idle; below it nodes and leaves
 __host__ __device__ inline uint32_t makeRef(uint32_t index, uint32_t count) { return (count << kRefIndexBits) | index; }
 __host__ __device__ inline uint32_t refIndex(uint32_t r) { return r & kRefIndexMask; }
 __host__ __device__ inline uint32_t refCount(uint32_t r) { return r >> kRefIndexBits; }

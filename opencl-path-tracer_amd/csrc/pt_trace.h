@@ -14,8 +14,8 @@
 //    atomics/us) and copies the 64 entries it will hand out next into LDS ASYNCHRONOUSLY (two global_load_lds_dwordx4:
 //    no staging registers, the kernel stays at 72 VGPRs): a hand-out -- consecutive entries for consecutive idle lanes
 //    (ballot rank) -- reads LDS instead of stalling on HBM, so it can run as soon as 8 lanes are idle;
-//  * ONE traversal stack in LDS, laid out [entry][lane] (a wave's push/pop touches 64 consecutive dwords:
-//    conflict-free ds_read/ds_write_b32), 12 entries; top level and bottom level share it, separated by a
+//  * ONE traversal stack in LDS, laid out [entry][thread of the block] (a wave's push/pop touches 64 consecutive dwords:
+//    conflict-free ds_read/ds_write_b32; the stack position is kept as the byte offset into it), 12 entries; top level and bottom level share it, separated by a
 //    sentinel entry that restores the world-space ray (re-read from the queue: instances are rarely entered, see
 //    below); deeper entries spill to a lane-interleaved region in global memory;
 //  * 4-wide nodes with 8-bit quantised child boxes (WideNode, 64 B = four 16-byte loads for four children) at
@@ -25,7 +25,7 @@
 //    (distance, reference) pairs go through a 5-comparator network, pushes are branch-free and the stack top is
 //    prefetched before the node fetch;
 //  * each loop iteration executes the step kind most lanes are waiting for (ballot majority vote: inner step or
-//    leaf) instead of serialising both for a fraction of the lanes; the rare kinds -- enter / leave an instance,
+//    leaf; one compare on the lane's current reference per vote -- a lane without a ray holds kRefIdle there) instead of serialising both for a fraction of the lanes; the rare kinds -- enter / leave an instance,
 //    write the result -- park the lane until the hot loop breaks and are served in batches outside it.  (Most
 //    scenes never enter an instance: ptamd.hip copies instances to world space at upload while a byte budget
 //    lasts, which removed two parked steps per instance visit.)  Measured in round 3 and not kept: an any-hit lane on the
@@ -121,7 +121,7 @@ __global__ void __launch_bounds__(kTraceBlock, LEVELS == 2 ? PT_TRACE_MIN_WAVES_
     constexpr bool TWO_LEVEL = LEVELS == 1, GENERAL = LEVELS == 2;
     constexpr bool STAGED = !GENERAL; // the next 64 queue entries of the wave copied into LDS ahead of the hand-out
     constexpr int kLdsStack = GENERAL ? PT_LDS_STACK_GEN : (TWO_LEVEL ? kLdsStackTL : ptd::kLdsStack); // (shadows the namespace constant inside this kernel)
-    __shared__ uint32_t ldsStack[kTraceBlock / 64][kLdsStack][64];
+    __shared__ uint32_t ldsStack[kLdsStack][kTraceBlock]; // [entry][thread]: a lane's entries lie kSpStep bytes apart whichever wave it is in (see spB)
     __shared__ float4 ldsRays[STAGED ? kTraceBlock / 64 : 1][2][STAGED ? 64 : 1]; // the claimed packet: origins, directions (entry e of the packet at [.][e])
     __shared__ float ldsObj[GENERAL ? kTraceBlock / 64 : 1][GENERAL ? kObjPlanes : 1][GENERAL ? 65 : 1]; // [.][plane][lane]; [.][plane][64] = 0: what world-space steps read
     // TWO_LEVEL, round 5: instances whose transform is a translation + uniform scale are traversed WITHOUT parking and without an entry step.
@@ -161,7 +161,7 @@ __global__ void __launch_bounds__(kTraceBlock, LEVELS == 2 ? PT_TRACE_MIN_WAVES_
             a.hit[rayIdx] = make_float4(hprim >= 0 ? tClosest : INFINITY, hu, hv, asF((uint32_t)hprim));             \
             a.inst[rayIdx] = hinst;                                                                                  \
         }                                                                                                            \
-        active = false;                                                                                              \
+        cur = kRefIdle;                                                                                              \
     }
     const uint32_t total = a.totalThreads;
     const uint32_t count = ANY_HIT ? a.ctl->shadowCount[a.pass] : a.ctl->extCount[a.pass];
@@ -184,14 +184,14 @@ __global__ void __launch_bounds__(kTraceBlock, LEVELS == 2 ? PT_TRACE_MIN_WAVES_
 
     auto push = [&](int slot, uint32_t v) {
         if (slot < kLdsStack)
-            ldsStack[wave][slot][lane] = v;
+            ldsStack[slot][threadIdx.x] = v;
         else
             spill[(size_t)(slot - kLdsStack) * total] = v;
     };
     // always a plain ds_read_b32; the (rare) spilled entry overrides it.  Selecting between the two
     // addresses instead makes hipcc emit ONE flat_load on the critical pop -> node-fetch path.
     auto pop = [&](int slot) -> uint32_t {
-        uint32_t v = ldsStack[wave][min(slot, kLdsStack - 1)][lane];
+        uint32_t v = ldsStack[min(slot, kLdsStack - 1)][threadIdx.x];
         if (slot >= kLdsStack)
             v = ((const volatile uint32_t*)spill)[(size_t)(slot - kLdsStack) * total]; // volatile: keeps the two loads apart
         return v;
@@ -199,20 +199,36 @@ __global__ void __launch_bounds__(kTraceBlock, LEVELS == 2 ? PT_TRACE_MIN_WAVES_
 
     PT_STAT_BEGIN;
     PT_TIC(tKernel);
-    bool active = false;
+    // A lane without a ray holds kRefIdle in `cur`: there is no separate "active" flag.  Every vote below is a ballot of ONE compare on `cur` (the
+    // compiler turns that into the compare alone; a ballot of `flag && compare` it lowers as the and, a select to 0 / 1 and a compare with 0 -- two
+    // more vector instructions per vote of a vector-issue-bound loop), and the counts that have no compare of their own are differences of the ones that have.
+    static_assert(kTraceBlock % 64 == 0, "the votes count 64 lanes per wave");
+    auto lanesOf = [](unsigned long long mask) -> int { // lanes in a ballot's mask: a 32-bit scalar
+        int n = __popcll(mask);
+        asm("" : "+s"(n)); // (comparing the 64-bit population count with a constant otherwise goes to the VECTOR unit as a 64-bit compare)
+        return n;
+    };
+    auto votes = [&](bool p) -> int { return lanesOf(__ballot(p)); };
     bool exhausted = false; // wave-uniform: queue has no more rays
     uint32_t rayIdx = 0;
     // ray of the space being traversed (world or instance): origin, direction, 1/direction, -origin/direction
     V3 co = mk(0.f), cd = mk(0.f), cid = mk(0.f);
     float tClosest = 0.f, hu = 0.f, hv = 0.f;
     int hprim = -1, hinst = -1, curInst = -1;
-    uint32_t cur = kRefFinish;
-    int sp = 0;
-    // value of pop() given the prefetched LDS entry `top` (does not move sp)
+    uint32_t cur = kRefIdle;
+    // The stack position, in the form the LDS address needs: the byte offset of the lane's next free entry in ldsStack, entries * kSpStep + thread * 4.
+    // A push stores at spB and adds kSpStep, the prefetch of the top reads at spB - kSpStep, and "empty" / "three more fit" / "spilled" are compares
+    // of spB with constants: no `entry << 8 | lane` rebuilt per access, no register for the lane's base.  The cold paths (spill, the parked steps)
+    // take the entry count out of it.
+    constexpr uint32_t kSpStep = kTraceBlock * 4u;
+    uint32_t spB = threadIdx.x * 4u;
+    auto spEntries = [&]() -> int { return (int)(spB / kSpStep); };
+    auto ldsAt = [&](uint32_t ofs) -> uint32_t& { return *(uint32_t*)((char*)&ldsStack[0][0] + ofs); };
+    // value of pop() given the prefetched LDS entry `top` (does not move the stack position)
     auto popTop = [&](uint32_t top) -> uint32_t {
-        uint32_t v = sp > 0 ? top : kRefFinish;
-        if (sp > kLdsStack)
-            v = ((const volatile uint32_t*)spill)[(size_t)(sp - 1 - kLdsStack) * total];
+        uint32_t v = spB >= kSpStep ? top : kRefFinish;
+        if (spB >= (uint32_t)(kLdsStack + 1) * kSpStep)
+            v = ((const volatile uint32_t*)spill)[(size_t)(spEntries() - 1 - kLdsStack) * total];
         return v;
     };
     auto setRay = [&](V3 o, V3 d) {
@@ -245,7 +261,7 @@ __global__ void __launch_bounds__(kTraceBlock, LEVELS == 2 ? PT_TRACE_MIN_WAVES_
             if (gwave * 64u < count && (count + 63u) / 64u > totalWaves) {
                 if (lane == 0)
                     base = atomicAdd(ANY_HIT ? &a.ctl->shadowCursor[a.pass] : &a.ctl->extCursor[a.pass], claim);
-                base = totalWaves * 64u + __shfl(base, 0);
+                base = totalWaves * 64u + (uint32_t)__builtin_amdgcn_readfirstlane((int)base); // (lane 0's: every lane of the wave is here)
             }
             spanNext = base;
             spanEnd = base + claim;
@@ -268,8 +284,8 @@ __global__ void __launch_bounds__(kTraceBlock, LEVELS == 2 ? PT_TRACE_MIN_WAVES_
         // ---- hand rays to idle lanes ----------------------------------------------------------
         PT_TIC(tHand);
         if (!exhausted) {
-            const unsigned long long idle = __ballot(!active);
-            const int nIdle = __popcll(idle);
+            const unsigned long long idle = __ballot(cur == kRefIdle);
+            const int nIdle = lanesOf(idle);
             if (nIdle >= (TWO_LEVEL ? PT_REFILL_IDLE_TL : kRefillIdleLanes)) {
                 const uint32_t avail = poolEnd - poolNext;
                 if (avail == 0u) {
@@ -284,17 +300,17 @@ __global__ void __launch_bounds__(kTraceBlock, LEVELS == 2 ? PT_TRACE_MIN_WAVES_
                     ro = rd = make_float4(0, 0, 0, 0);
                     if constexpr (STAGED) {
                         asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // the packet's copy into LDS has landed
-                        if (!active && rank < avail) {
+                        if (cur == kRefIdle && rank < avail) {
                             ro = ldsRays[wave][0][e];
                             rd = ldsRays[wave][1][e];
                         }
-                    } else if (!active && rank < avail) {
+                    } else if (cur == kRefIdle && rank < avail) {
                         ro = a.rayO[poolBase + (uint32_t)e];
                         rd = a.rayD[poolBase + (uint32_t)e];
                     }
                     PT_TOC(16, tShfl);
                     PT_TIC(tAssign);
-                    if (!active && rank < avail) {
+                    if (cur == kRefIdle && rank < avail) {
                         const uint32_t idx = poolBase + (uint32_t)e;
                         float tMax = ANY_HIT ? ro.w : INFINITY;
                         asm volatile("" : "+v"(tMax)); // own register: hipcc 7.2 otherwise lets the flag load below alias ro.w and drops the tClosest assignment
@@ -315,9 +331,8 @@ __global__ void __launch_bounds__(kTraceBlock, LEVELS == 2 ? PT_TRACE_MIN_WAVES_
                             hinst = -1;
                             curInst = -1;
                             hu = hv = 0.f;
-                            cur = sc.rootRef;
-                            sp = 0;
-                            active = true;
+                            cur = sc.rootRef; // (the lane has a ray from here on)
+                            spB = threadIdx.x * 4u;
                         }
                     }
                     PT_TOC(17, tAssign);
@@ -340,17 +355,22 @@ __global__ void __launch_bounds__(kTraceBlock, LEVELS == 2 ? PT_TRACE_MIN_WAVES_
             // what comes NEXT: after the sentinel the next stack entry -- an instance (world-space ray from the queue, then the
             // transform: exit and entry in one step), a top-level node or leaf (the world-space ray), nothing (the result).  Round 2
             // looped here, one kind of step per round: an exit followed by an entry was two rounds.
-            const bool wantSpecial = active && refCount(cur) == kRefSpecial;
-            const unsigned long long m = __ballot(wantSpecial);
+            const bool wantSpecial = cur >= kRefFirstSpecial && cur != kRefIdle;
+            const unsigned long long m = __ballot(cur >= kRefFirstSpecial) & ~__ballot(cur == kRefIdle); // (one compare per ballot, see `votes`)
             if (m != 0ull) {
                 PT_STAT(4, 1);
                 PT_STAT(7, __popcll(m));
                 const bool leaving = wantSpecial && cur == kRefLeaveInstance;
                 if (leaving) {
                     curInst = -1;
-                    cur = sp > 0 ? pop(--sp) : kRefFinish;
+                    if (spB >= kSpStep) {
+                        spB -= kSpStep;
+                        cur = pop(spEntries());
+                    } else {
+                        cur = kRefFinish;
+                    }
                 }
-                const bool finishing = wantSpecial && cur == kRefFinish;
+                const bool finishing = cur == kRefFinish; // (such a lane was parked: it stood on this reference or has just popped its way to it)
                 if (ANY_HIT) { // a shadow ray only gets here unoccluded (an occluded one retires in its leaf step)
                     const uint32_t nFin = (uint32_t)__popcll(__ballot(finishing));
                     if (lane == 0)
@@ -378,8 +398,8 @@ __global__ void __launch_bounds__(kTraceBlock, LEVELS == 2 ? PT_TRACE_MIN_WAVES_
                             V3 to, td;
                             rayIntoInstance(in.r0, in.r1, in.r2, wo, wd, &to, &td);
                             setRay(to, td);
-                            push(sp, kRefLeaveInstance);
-                            sp++;
+                            push(spEntries(), kRefLeaveInstance);
+                            spB += kSpStep;
                         }
                         cur = in.rootRef;
                     } else {
@@ -391,26 +411,26 @@ __global__ void __launch_bounds__(kTraceBlock, LEVELS == 2 ? PT_TRACE_MIN_WAVES_
             // ---- resolve special references: in these instantiations the end of a traversal alone (one world-space tree has no instance
             // references, GENERAL enters them in its leaf steps) -------------------
             // They are kept OUT of the hot loop below: lanes that reach one park until the loop breaks, then all
-            // of them are served here at once.  The hot loop thus only ever changes (cur, sp, closest hit) and
+            // of them are served here at once.  The hot loop thus only ever changes (cur, spB, closest hit) and
             // the ray-space registers stay loop-invariant in it.
-            while (true) {
-                const bool wantSpecial = active && (GENERAL ? cur == kRefFinish : refCount(cur) == kRefSpecial); // (GENERAL: an instance reference is a leaf-kind step of the hot loop)
-                const unsigned long long m = __ballot(wantSpecial);
-                if (m == 0ull)
-                    break;
+            // The one special reference a lane of these instantiations can stand on is kRefFinish (the tree holds no other; kRefIdle is no ray), and
+            // finishing leaves the lane idle: one vote, one pass.
+            const bool finishing = cur == kRefFinish; // (GENERAL: an instance reference is a leaf-kind step of the hot loop)
+            const unsigned long long m = __ballot(finishing);
+            if (m != 0ull) {
                 PT_STAT(4, 1);
                 PT_STAT(7, __popcll(m));
                 if (ANY_HIT) { // a shadow ray only gets here unoccluded (an occluded one retires in its leaf step)
-                    const uint32_t nFin = (uint32_t)__popcll(__ballot(wantSpecial && refIndex(cur) == kSpecialFinish));
+                    const uint32_t nFin = (uint32_t)__popcll(m);
                     if (lane == 0)
                         ldsDeposits[wave] += nFin;
                 }
-                if (wantSpecial && refIndex(cur) == kSpecialFinish)
+                if (finishing)
                     finishRay()
             }
         }
         PT_TOC(13, tSpec);
-        if (__ballot(active) == 0ull) {
+        if (__ballot(cur != kRefIdle) == 0ull) {
             if (exhausted)
                 break;
             continue;
@@ -421,16 +441,22 @@ __global__ void __launch_bounds__(kTraceBlock, LEVELS == 2 ? PT_TRACE_MIN_WAVES_
             // the entry a pop would return, fetched before the node / triangle loads so that its LDS latency
             // hides under theirs (whichever step runs this iteration pops at most once, and only when it has
             // pushed nothing)
-            const uint32_t stackTop = ldsStack[wave][min(max(sp - 1, 0), kLdsStack - 1)][lane];
-            const uint32_t kindBits = refCount(cur);
-            const bool wantInner = active && kindBits == 0u;
-            const bool wantLeaf = active && kindBits != 0u && (GENERAL ? cur != kRefFinish : kindBits != kRefSpecial);
-            const int nInner = __popcll(__ballot(wantInner)), nLeaf = __popcll(__ballot(wantLeaf));
+            // (two instructions: a minimum and a saturating subtraction.  An empty stack reads the block's first dword, a spilled one entry
+            // kLdsStack - 1 of the block's last thread: inside the array, and popTop does not use the value in either case.)
+            const uint32_t topOf = min(spB, (uint32_t)kLdsStack * kSpStep + (kSpStep - 4u));
+            const uint32_t stackTop = ldsAt(topOf >= kSpStep ? topOf - kSpStep : 0u);
+            // Three votes, one compare each: inner nodes lie below the leaves, the parked kinds and kRefIdle above them.  (GENERAL: an instance reference
+            // is a leaf-kind step; what parks is kRefFinish alone, which with kRefIdle tops the range -- instance indices end below kSpecialIdle.)
+            const bool wantInner = cur < (1u << kRefIndexBits);
+            const bool parkedOrIdle = cur >= (GENERAL ? kRefIdle : kRefFirstSpecial);
+            const bool wantLeaf = !wantInner && !parkedOrIdle;
+            const int nInner = votes(wantInner), nParkedOrIdle = votes(parkedOrIdle), nIdle = votes(cur == kRefIdle);
+            const int nLeaf = 64 - nInner - nParkedOrIdle;
             PT_STAT(0, 1);
             PT_STAT(1, nInner + nLeaf);
             // leave when nothing is left to do here, when enough lanes are parked on a special step, or when
             // enough lanes are idle for a hand-out (and the queue still has rays)
-            const int nSpecial = __popcll(__ballot(active && (GENERAL ? cur == kRefFinish : kindBits == kRefSpecial)));
+            const int nSpecial = nParkedOrIdle - nIdle;
             const int nWork = nInner + nLeaf;
             constexpr int parkedBreak = TWO_LEVEL ? (ANY_HIT ? PT_PARKED_BREAK_ANY_TL : PT_PARKED_BREAK_TL) : (ANY_HIT ? kParkedBreakAny : kParkedBreak);
             if (nWork == 0 || nSpecial >= parkedBreak || (!exhausted && 64 - nWork - nSpecial >= (TWO_LEVEL ? PT_REFILL_IDLE_TL : kRefillIdleLanes)))
@@ -494,27 +520,27 @@ __global__ void __launch_bounds__(kTraceBlock, LEVELS == 2 ? PT_TRACE_MIN_WAVES_
                     else
                         sort4Nearest(key, ref);
                     // farthest first onto the stack, continue with the nearest
-                    if (sp + 3 <= kLdsStack) {
-                        // common case, branch-free: every candidate is stored, the stack pointer only moves past the
+                    if (spB < (uint32_t)(kLdsStack - 2) * kSpStep) { // three more entries fit the LDS part
+                        // common case, branch-free: every candidate is stored, the stack position only moves past the
                         // ones that are kept (a rejected one is overwritten by the next store)
-                        ldsStack[wave][sp][lane] = ref[3];
-                        sp += visible(3);
-                        ldsStack[wave][sp][lane] = ref[2];
-                        sp += visible(2);
-                        ldsStack[wave][sp][lane] = ref[1];
-                        sp += visible(1);
+                        ldsAt(spB) = ref[3];
+                        spB += visible(3) ? kSpStep : 0u;
+                        ldsAt(spB) = ref[2];
+                        spB += visible(2) ? kSpStep : 0u;
+                        ldsAt(spB) = ref[1];
+                        spB += visible(1) ? kSpStep : 0u;
                     } else {
                         if (visible(3)) {
-                            push(sp, ref[3]);
-                            sp++;
+                            push(spEntries(), ref[3]);
+                            spB += kSpStep;
                         }
                         if (visible(2)) {
-                            push(sp, ref[2]);
-                            sp++;
+                            push(spEntries(), ref[2]);
+                            spB += kSpStep;
                         }
                         if (visible(1)) {
-                            push(sp, ref[1]);
-                            sp++;
+                            push(spEntries(), ref[1]);
+                            spB += kSpStep;
                         }
                     }
                     // no visible child => nothing was pushed => the prefetched stack top is still the top
@@ -522,13 +548,14 @@ __global__ void __launch_bounds__(kTraceBlock, LEVELS == 2 ? PT_TRACE_MIN_WAVES_
                     if (visible(0))
                         cur = ref[0];
                     else
-                        cur = next, sp = max(sp - 1, 0);
+                        cur = next, spB = spB >= kSpStep ? spB - kSpStep : spB;
                 }
                 PT_TOC(11, tInner);
             } else {
                 PT_STAT(3, 1);
                 PT_STAT(6, nLeaf);
                 PT_TIC(tLeaf);
+                const uint32_t kindBits = refCount(cur);
                 if (GENERAL && wantLeaf && kindBits == kRefSpecial) {
                     // -------- enter instance refIndex(cur) (scene.cl:116-139): a leaf-kind step.  The lane's registers keep the world-space ray; the
                     // instance-space ray goes into the lane's LDS slot, where the steps on the instance's nodes and triangles read it
@@ -605,11 +632,10 @@ __global__ void __launch_bounds__(kTraceBlock, LEVELS == 2 ? PT_TRACE_MIN_WAVES_
                     if (ANY_HIT && done) { // occluded: nothing to deposit
                         if (a.occluded)
                             a.occluded[rayIdx] = 1u;
-                        active = false;
-                        cur = kRefFinish;
+                        cur = kRefIdle;
                     } else {
                         cur = popTop(stackTop);
-                        sp = max(sp - 1, 0);
+                        spB = spB >= kSpStep ? spB - kSpStep : spB;
                     }
                 }
                 PT_TOC(12, tLeaf);

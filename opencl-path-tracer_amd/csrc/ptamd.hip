@@ -2039,6 +2039,10 @@ int pt_intersect(pt_ctx* c, const pt_rays_soa* rays, uint32_t n, int any_hit, pt
         chk(hipMemcpy(dD.p, hD.data(), n * sizeof(float4), hipMemcpyHostToDevice));
         chk(hipMemcpy(dC.p, hC.data(), n * sizeof(float4), hipMemcpyHostToDevice));
         chk(hipMemsetAsync(dAcc.p, 0, sizeof(float4), c->stream));
+        // sentinels: an entry no lane wrote comes back as t = NaN (closest hit; a miss is +inf) or as verdict -1 (any hit; 0 / 1 otherwise)
+        chk(hipMemsetAsync(dH.p, 0xFF, n * sizeof(float4), c->stream));
+        chk(hipMemsetAsync(dI.p, 0xFF, n * sizeof(int32_t), c->stream));
+        chk(hipMemsetAsync(dOcc.p, 0xFF, n * sizeof(uint32_t), c->stream));
     }
     float msTotal = 0;
     repeat = std::max(repeat, 1u);
