@@ -568,6 +568,10 @@ int pt_debug_copy_bandwidth(pt_ctx* ctx, size_t bytes, uint32_t repeat, float* g
  * receives ten planes of n floats: a / b, fastDiv(a, b), sqrtf(|a|), fastSqrt(|a|), normalize((a, b, a + b)).xyz, fastNormalize((a, b, a + b)).xyz -- the
  * plain forms as the library's build compiles them. */
 int pt_debug_math_probe(pt_ctx* ctx, const float* a, const float* b, uint32_t n, float* out);
+/* Test hook, no device needed: what the library holds alive in this process, all contexts and hooks together -- out[0] device allocations, out[1] pinned
+ * host allocations, out[2] events, out[3] streams it created (a caller's stream, pt_set_stream, is never counted).  After the last pt_destroy every count
+ * is back where it stood before the first pt_create. */
+int pt_debug_live_resources(uint32_t out[4]);
 int pt_debug_quantise_node(const float* lo12, const float* hi12, const uint32_t* refs4, const uint8_t* empty4, uint32_t empty_ref, void* out64);
 /* test hook, no device needed: what pt_upload_static (records made on the host) and -- given a top level (n_top > 0) -- pt_upload_dynamic make of these
  * arrays under cfg's flags and RNG mode, as one line into `line` (line_bytes with its terminating zero): hashes of every array of the static part, then

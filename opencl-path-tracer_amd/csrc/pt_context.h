@@ -7,34 +7,186 @@ namespace {
 
 thread_local std::string g_createError;
 
+// What the runtime allocates is owned by one of the four types below: freed by the destructor, moved but never copied, and counted -- device allocations,
+// pinned allocations, events, owned streams alive in this process (pt_debug_live_resources).  None of them may have static storage duration: nothing is
+// freed after the HIP runtime has shut down.
+std::atomic<uint32_t> g_live[4];
+
 template <typename T>
 struct DevBuf {
     T* p = nullptr;
     size_t n = 0;
+    DevBuf() = default;
+    DevBuf(DevBuf&& o) noexcept : p(std::exchange(o.p, nullptr)), n(std::exchange(o.n, 0)) {} // (no copies: the compiler refuses them from here on)
+    ~DevBuf() { release(); }
     hipError_t alloc(size_t count)
     {
         release();
         n = count;
         if (count == 0)
             return hipSuccess;
-        return hipMalloc((void**)&p, count * sizeof(T));
+        const hipError_t e = hipMalloc((void**)&p, count * sizeof(T));
+        if (e == hipSuccess)
+            g_live[0]++;
+        return e;
     }
     void release()
     {
-        if (p)
+        if (p) {
             (void)hipFree(p);
+            g_live[0]--;
+        }
         p = nullptr;
         n = 0;
     }
 };
 
+// `count` records of pinned host memory
+template <typename T>
+struct Pinned {
+    T* p = nullptr;
+    Pinned() = default;
+    Pinned(Pinned&&) = delete;
+    ~Pinned() { release(); }
+    hipError_t alloc(size_t count)
+    {
+        release();
+        const hipError_t e = hipHostMalloc((void**)&p, count * sizeof(T), hipHostMallocDefault);
+        if (e == hipSuccess)
+            g_live[1]++;
+        else
+            p = nullptr;
+        return e;
+    }
+    void release()
+    {
+        if (p) {
+            (void)hipHostFree(p);
+            g_live[1]--;
+        }
+        p = nullptr;
+    }
+};
+
+struct Event {
+    hipEvent_t e = nullptr;
+    Event() = default;
+    Event(Event&& o) noexcept : e(std::exchange(o.e, nullptr)) {} // (pt_ctx::profEvents grows)
+    ~Event()
+    {
+        if (e) {
+            (void)hipEventDestroy(e);
+            g_live[2]--;
+        }
+    }
+    hipError_t create(bool timing = false) // (if there is none yet)
+    {
+        if (e)
+            return hipSuccess;
+        const hipError_t rc = timing ? hipEventCreate(&e) : hipEventCreateWithFlags(&e, hipEventDisableTiming);
+        if (rc == hipSuccess)
+            g_live[2]++;
+        else
+            e = nullptr;
+        return rc;
+    }
+    operator hipEvent_t() const { return e; }
+};
+
+// a stream the context created (`owned`), or the caller's (pt_set_stream), which is never destroyed
+struct Stream {
+    hipStream_t s = nullptr;
+    bool owned = false;
+    Stream() = default;
+    Stream(Stream&&) = delete;
+    ~Stream() { adopt(nullptr); }
+    hipError_t create()
+    {
+        adopt(nullptr);
+        const hipError_t e = hipStreamCreateWithFlags(&s, hipStreamNonBlocking);
+        if (e == hipSuccess)
+            g_live[3]++, owned = true;
+        else
+            s = nullptr;
+        return e;
+    }
+    void adopt(hipStream_t callers)
+    {
+        if (owned && s) {
+            (void)hipStreamDestroy(s);
+            g_live[3]--;
+        }
+        s = callers;
+        owned = false;
+    }
+    operator hipStream_t() const { return s; }
+};
+
+// Pinned staging memory that asynchronous copies read from (grow-only, like the device buffers), the event recorded behind the copies out of it, and whether
+// such copies may still be in flight.  Each caller states its own capacity when it grows the memory.
+struct Staging {
+    Pinned<unsigned char> mem;
+    size_t bytes = 0;
+    Event read;
+    bool busy = false;
+    hipError_t wait() // until the last copies out of the memory are done (normally long done)
+    {
+        if (busy) {
+            const hipError_t e = hipEventSynchronize(read);
+            if (e != hipSuccess)
+                return e;
+            busy = false;
+        }
+        return hipSuccess;
+    }
+    hipError_t reserve(size_t need, size_t capacity) // (new memory has no copies in flight)
+    {
+        if (bytes >= need)
+            return hipSuccess;
+        bytes = 0;
+        const hipError_t e = mem.alloc(capacity);
+        if (e == hipSuccess)
+            bytes = capacity, busy = false;
+        return e;
+    }
+    hipError_t recordRead(hipStream_t s)
+    {
+        const hipError_t e = hipEventRecord(read, s);
+        if (e == hipSuccess)
+            busy = true;
+        return e;
+    }
+};
+
+// Two width * height float4 planes that are made, cleared, read and written together: allocated (zeroed, on the context's stream) at first use.
+struct PlanePair {
+    DevBuf<float4> plane[2];
+    float4* operator[](int k) const { return plane[k].p; }
+    int ensure(pt_ctx* c);
+    int zero(pt_ctx* c);
+    int read(pt_ctx* c, float* out0, float* out1); // (either may be null)
+    int write(pt_ctx* c, const float* in0, const float* in1);
+};
+
+// a queue's three planes of `count` entries each (stops at the first error)
+inline hipError_t allocPlanes(DevBuf<float4>& a, DevBuf<float4>& b, DevBuf<float4>& c, size_t count)
+{
+    hipError_t e = a.alloc(count);
+    if (e == hipSuccess && (e = b.alloc(count)) == hipSuccess)
+        e = c.alloc(count);
+    return e;
+}
 struct RayQueueBuf {
     DevBuf<float4> o, d, thr;
     RayQueue view() const { return { o.p, d.p, thr.p }; }
+    hipError_t alloc(size_t count) { return allocPlanes(o, d, thr, count); }
+    void release() { o.release(), d.release(), thr.release(); }
 };
 struct ShadowQueueBuf {
     DevBuf<float4> o, d, c;
     ShadowQueue view() const { return { o.p, d.p, c.p }; }
+    hipError_t alloc(size_t count) { return allocPlanes(o, d, c, count); }
+    void release() { o.release(), d.release(), c.release(); }
 };
 
 } // namespace
@@ -62,10 +214,7 @@ struct StaticScene {
     uint64_t refitTablesFor = 0; // topology the tables were made for (0: none)
     bool refitTablesOk = false; // false: a node has two parents (roots that share a subtree): the caller refits on the host (pt_update_geometry)
     bool latestInStage = false; // the caller's latest vertices and nodes live in `stage` (vertices first), not in host.rawVerts / host.hostSubNodes
-    void* stage = nullptr;
-    size_t stageBytes = 0;
-    hipEvent_t stageRead = nullptr;
-    bool stageBusy = false;
+    Staging stage;
     DevBuf<TriShade> triShade;
     DevBuf<Material> materials;
     bool have = false; // holds a converted scene
@@ -76,16 +225,26 @@ struct pt_ctx {
     std::string error;
     int device = 0;
     int numCUs = 0;
-    hipStream_t stream = nullptr;
-    bool ownStream = false;
-    hipEvent_t evStart = nullptr, evStop = nullptr;
-    std::vector<hipEvent_t> profEvents;
+    // The streams come first: members are destroyed in reverse order, so everything below is freed before a stream is destroyed.  ~pt_ctx waits for all four.
+    Stream stream; // renders (the context's own, or the caller's: pt_set_stream)
+    Stream copyStream;
+    // small launches (a 1-spp interactive frame): the shadow rays of bounce b are traced on `sideStream` while the main stream traces
+    // the extension rays of bounce b + 1 (independent: both only need shade b; shade b + 1 waits for both)
+    Stream sideStream;
+    Stream sideStream2; // one sample in flight: the shadow passes of a frame alternate between two side streams (each bounce has its own shadow queue AND
+                        // accumulator plane: nothing orders them but their own shade launch)
+    Event evStart, evStop;
+    std::vector<Event> profEvents;
     bool profile = false;
 
-    // scene (HBM)
-    DevBuf<PairNode> nodes;
-    DevBuf<WideNode> wide;
-    DevBuf<VertexShade> verts;
+    ~pt_ctx()
+    {
+        (void)hipSetDevice(device);
+        for (hipStream_t s : { stream.s, copyStream.s, sideStream.s, sideStream2.s }) // (the copy stream: a never-adopted upload may still be copying into the sets)
+            if (s)
+                (void)hipStreamSynchronize(s);
+    }
+
     // The dynamic part of the scene -- what pt_upload_dynamic(_async) produces: 4-wide nodes of both levels, intersection
     // triangles (object space + world-space copies of instances), instances, lights -- exists TWICE, like the reference's
     // double-buffered cl::Buffers (m_topBvhBuffers[2], m_emissiveTrianglesBuffers[2], ... src/raytracer.h:93-106): renders
@@ -102,11 +261,7 @@ struct pt_ctx {
         uint64_t staticVersion = 0; // version of the static arrays this set holds (0: none)
         int staticIndex = 0; // which of the context's two static scenes this state was built on
         uint32_t numTris = 0, firstWorldNode = 0; // of that scene, as the kernels need them (SceneDev)
-        // pinned staging the asynchronous copies read from (grow-only, like the device buffers)
-        void* stage = nullptr;
-        size_t stageBytes = 0;
-        hipEvent_t stageRead = nullptr; // recorded on the copy stream after the copies out of `stage`
-        bool stageBusy = false;
+        Staging stage; // what the asynchronous copies of an upload read from (its event: recorded on the copy stream)
         uint32_t numLights = 0, rootRef = 0;
         uint32_t foldedInstances = 0, instRootBase = 0, numInstRoots = 0;
         DevBuf<float4> instFold; // the table of folded instance transforms (pt_trace.h)
@@ -121,8 +276,8 @@ struct pt_ctx {
         std::vector<uint32_t> instanceTopNode; // instance index -> top-level leaf node index
         std::vector<Instance> hostInstances; // the instance table as uploaded (pt_set_instance_motion reads the current invTransform rows from it)
         uint32_t numTopNodes = 0; // top-level nodes of this state as the caller counts them
-        hipEvent_t uploaded = nullptr; // recorded on the copy stream after the set's last upload
-        hipEvent_t lastUse = nullptr; // recorded on the render stream when the set stopped being the active one
+        Event uploaded; // recorded on the copy stream after the set's last upload
+        Event lastUse; // recorded on the render stream when the set stopped being the active one
         bool used = false;
     } dyn[2];
     StaticScene stat[2];
@@ -132,14 +287,8 @@ struct pt_ctx {
     uint64_t staticVersions = 0; // versions of the static arrays are drawn from one counter (a dynamic set compares the one it holds with the scene's)
     int active = 0; // set the render kernels read
     int pending = -1; // set with an upload in flight / finished that pt_frame_tick will switch to
-    hipStream_t copyStream = nullptr;
-    // small launches (a 1-spp interactive frame): the shadow rays of bounce b are traced on `sideStream` while the main stream traces
-    // the extension rays of bounce b + 1 (independent: both only need shade b; shade b + 1 waits for both)
-    hipStream_t sideStream = nullptr;
-    hipStream_t sideStream2 = nullptr; // one sample in flight: the shadow passes of a frame alternate between two side streams (each bounce has its own shadow queue AND
-                                       // accumulator plane: nothing orders them but their own shade launch)
-    hipEvent_t evShaded[kMaxPasses] = {}, evShadowed[kMaxPasses] = {};
-    // ... and, with ONE sample in flight, deposit into an accumulator of their own (merged into the accumulator proper at the end of pt_render) from a shadow
+    Event evShaded[kMaxPasses], evShadowed[kMaxPasses]; // (the side streams' shadow passes, at the top of the struct)
+    // With ONE sample in flight the shadow rays deposit into an accumulator of their own (merged into the accumulator proper at the end of pt_render) from a shadow
     // queue per bounce: the shadow passes then depend on nothing but their own shade launch and run back to back on the side stream
     DevBuf<float4> accumShadow;
     ShadowQueueBuf shadowQ[kMaxPasses];
@@ -165,7 +314,7 @@ struct pt_ctx {
     bool ratiosKnown = false;
     double ratioExt = 0, ratioShadow = 0; // (extension rays emitted by pass 0, shadow rays emitted by the pass that emitted most) / (entries of the batch), the largest of this epoch
     double ratioShadowFirst = 0; // (shadow rays emitted by pass 0) / (entries of the batch), the largest of this epoch: pt_stats.first_pass_shadow_ratio
-    uint32_t* overflowPinned = nullptr; // set by k_clamp_counts when a batch emitted more than a queue holds after all: sticky, reported by pt_synchronize and the image reads
+    Pinned<uint32_t> overflowPinned; // one word, set by k_clamp_counts when a batch emitted more than a queue holds after all: sticky, reported by pt_synchronize and the image reads
     uint32_t batchSamples = 0, probeBatches = 0;
     uint32_t epoch = 0, passCountsEpoch = 0; // camera / scene state / tiling the ratios belong to; ... the report in flight was launched in
     bool identityPixels = true;
@@ -174,8 +323,8 @@ struct pt_ctx {
     uint32_t multiBlocks[4] = { 0, 0, 0, 0 }; // persistent grid of k_trace_multi [without | with instance references in the tree], [2], [3]: the same for a thin-lens camera's converging bundles
     // live entries per pass of the most recent batch whose counters have come back (a HINT for the next batch's k_shade launches:
     // copied to pinned memory by the stream at the end of every batch, never waited for)
-    uint32_t* passCountsPinned = nullptr; // kMaxPasses + 1 words
-    hipEvent_t passCountsCopied = nullptr;
+    Pinned<uint32_t> passCountsPinned; // as many words as passCountsHint
+    Event passCountsCopied;
     uint32_t passCountsHint[2 * (kMaxPasses + 1)] = {}; // extension rays per pass, then shadow rays per pass
     uint32_t passCountsEntries = 0; // entries of the batch the hint comes from (0: no hint yet)
     uint32_t passCountsPending = 0; // entries of the batch whose copy is in flight
@@ -209,17 +358,17 @@ struct pt_ctx {
     // first-hit guide buffers and the denoiser (pt_denoise.h): two width * height float4 sums over `guideSpp` guide samples, the scratch queue of the guide
     // pass (one sample of the owned pixels; allocated at first use, whatever the render queues look like), the filter's two ping-pong images and its
     // normalised guide image
-    DevBuf<float4> guideAlbedoHits, guideNormalDepth;
+    PlanePair guides; // [0] (albedo.rgb, hits), [1] (normal.xyz, depth)
     uint32_t guideSpp = 0;
     DevBuf<float4> guideRayO, guideRayD, guideHit;
     DevBuf<int32_t> guideHitInst;
     DevBuf<Control> guideCtl;
     DevBuf<float4> denoiseColour[2], denoiseGuide;
-    hipEvent_t evDenoise[2] = { nullptr, nullptr };
+    Event evDenoise[2];
 
     // temporal history (pt_temporal.h): two sets for ping-pong of two width * height float4 images each -- (d.rgb, N) and (n.xyz, z) --, allocated at
     // the first temporal call; the camera set `temporalNewest` was made under.  pt_clear and pt_set_camera leave all of it alone.
-    DevBuf<float4> temporalColour[2], temporalGuide[2];
+    PlanePair temporal[2]; // of each set: [0] (d.rgb, N), [1] (n.xyz, z)
     int temporalNewest = 0;
     uint32_t temporalFrames = 0; // pt_temporal_accumulate calls (or 1 after pt_write_temporal) since the last reset: 0 = no history
     CameraDev temporalCamera {};
@@ -232,7 +381,7 @@ struct pt_ctx {
     std::vector<MotionRecord> motionHost;
     bool motionSet = false;
     uint32_t motionMoving = 0;
-    DevBuf<float4> guideMotion, guidePrevNormal;
+    PlanePair motionGuides; // [0] (displacement.xyz, 0), [1] (normal then.xyz, 0)
 
     // vertex motion (include/ptamd.h): a snapshot of the shading records the previous dynamic state held (numTris of them, taken on the render stream by
     // pt_set_vertex_motion: the guide pass never reads the inactive set, which the next upload may be overwriting), and three float4 rows per instance of
@@ -295,8 +444,7 @@ inline bool generalShading(const pt_ctx* c) { return (c->cfg.flags & (PT_FLAG_IN
 
 void refreshSceneView(pt_ctx* c)
 {
-    SceneDev& s = c->scene;
-    s.nodes = c->nodes.p;
+    SceneDev& s = c->scene; // (s.nodes stays null: no kernel walks pair nodes)
     const pt_ctx::DynamicSet& d = c->dyn[c->active];
     s.wide = d.wide.p;
     s.tris = d.tris.p;
@@ -323,6 +471,45 @@ int uploadVec(pt_ctx* c, DevBuf<T>& buf, const std::vector<T>& host)
         HIPCHK(c, buf.alloc(std::max<size_t>(host.size() + host.size() / 8, 1)));
     if (!host.empty())
         HIPCHK(c, hipMemcpy(buf.p, host.data(), host.size() * sizeof(T), hipMemcpyHostToDevice));
+    return PT_OK;
+}
+
+int PlanePair::zero(pt_ctx* c)
+{
+    for (DevBuf<float4>& b : plane)
+        HIPCHK(c, hipMemsetAsync(b.p, 0, b.n * sizeof(float4), c->stream));
+    return PT_OK;
+}
+
+int PlanePair::ensure(pt_ctx* c)
+{
+    if (plane[0].p)
+        return PT_OK;
+    for (DevBuf<float4>& b : plane)
+        HIPCHK(c, b.alloc((size_t)c->cfg.width * c->cfg.height));
+    return zero(c);
+}
+
+int PlanePair::read(pt_ctx* c, float* out0, float* out1)
+{
+    if (const int rc = ensure(c))
+        return rc;
+    float* const out[2] = { out0, out1 };
+    for (int k = 0; k < 2; k++)
+        if (out[k])
+            HIPCHK(c, hipMemcpyAsync(out[k], plane[k].p, plane[k].n * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return PT_OK;
+}
+
+int PlanePair::write(pt_ctx* c, const float* in0, const float* in1)
+{
+    if (const int rc = ensure(c))
+        return rc;
+    const float* const in[2] = { in0, in1 };
+    for (int k = 0; k < 2; k++)
+        HIPCHK(c, hipMemcpyAsync(plane[k].p, in[k], plane[k].n * sizeof(float4), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
     return PT_OK;
 }
 

@@ -69,7 +69,7 @@ inline void newEpoch(pt_ctx* c)
 inline bool smallQueues(const pt_ctx* c) { return c->capExt < c->capacity || c->capShadow < c->capacity; }
 inline int checkOverflow(pt_ctx* c)
 {
-    if (c->overflowPinned && *c->overflowPinned)
+    if (c->overflowPinned.p && *c->overflowPinned.p)
         return fail(c, PT_ERR_STATE, "a batch emitted more rays than its queues hold (pt_config.ext_queue_fraction / shadow_queue_fraction; the scene changed under a "
                                     "running batch?): the rays beyond were dropped, the image since the last pt_clear is incomplete -- pt_clear and render again");
     return PT_OK;
@@ -79,7 +79,7 @@ inline int checkOverflow(pt_ctx* c)
 // b >= 1 may emit more of them than pass 0 did (camera rays that hit glass send none, the walls behind it do): sized by pass 0 alone, pass 1 outgrew capShadow
 inline void adoptPassCounts(pt_ctx* c)
 {
-    std::memcpy(c->passCountsHint, c->passCountsPinned, sizeof(c->passCountsHint));
+    std::memcpy(c->passCountsHint, c->passCountsPinned.p, sizeof(c->passCountsHint));
     c->passCountsEntries = c->passCountsPending;
     c->passCountsPending = 0;
     if (c->passCountsEpoch == c->epoch && c->passCountsEntries) {
@@ -142,13 +142,10 @@ int ensureQueues(pt_ctx* c)
         // the buffers of the previous tiling are re-made below anyway: give their memory back first, so that the budget check sees it
         // (a context whose queues use more than half of HBM -- 512 samples in flight at 1080p, two ranks sharing a GPU -- could not be re-tiled)
         HIPCHK(c, hipStreamSynchronize(c->stream));
-        for (int k = 0; k < 2; k++)
-            c->rays[k].o.release(), c->rays[k].d.release(), c->rays[k].thr.release();
-        c->shadow.o.release(), c->shadow.d.release(), c->shadow.c.release(), c->hitH.release(), c->hitInst.release(), c->accumPlanes.release();
+        c->rays[0].release(), c->rays[1].release(), c->shadow.release(), c->hitH.release(), c->hitInst.release(), c->accumPlanes.release();
         for (ShadowQueueBuf& q : c->shadowQ)
-            q.o.release(), q.d.release(), q.c.release();
-        c->stagedRays.o.release(), c->stagedRays.d.release(), c->stagedRays.thr.release();
-        c->stagedShadow.o.release(), c->stagedShadow.d.release(), c->stagedShadow.c.release(), c->activeFlag.release();
+            q.release();
+        c->stagedRays.release(), c->stagedShadow.release(), c->activeFlag.release();
         c->foldPlanes = 0;
         // Memory budget, checked before anything is allocated so that an oversized configuration fails HERE with a
         // message instead of somewhere in a later hipMalloc: per queue entry two extension queues (3 x 16 B each), the
@@ -196,21 +193,13 @@ int ensureQueues(pt_ctx* c)
     HIPCHK(c, c->rays[0].o.alloc(c->q0Small ? c->capExt : cap));
     HIPCHK(c, c->rays[0].d.alloc(cap));
     HIPCHK(c, c->rays[0].thr.alloc(c->q0Small ? c->capExt : cap));
-    HIPCHK(c, c->rays[1].o.alloc(c->capExt));
-    HIPCHK(c, c->rays[1].d.alloc(c->capExt));
-    HIPCHK(c, c->rays[1].thr.alloc(c->capExt));
-    HIPCHK(c, c->shadow.o.alloc(c->capShadow));
-    HIPCHK(c, c->shadow.d.alloc(c->capShadow));
-    HIPCHK(c, c->shadow.c.alloc(c->capShadow));
+    HIPCHK(c, c->rays[1].alloc(c->capExt));
+    HIPCHK(c, c->shadow.alloc(c->capShadow));
     HIPCHK(c, c->hitH.alloc(cap));
     HIPCHK(c, c->hitInst.alloc(cap));
     if (parityMode(c)) {
-        HIPCHK(c, c->stagedRays.o.alloc(cap));
-        HIPCHK(c, c->stagedRays.d.alloc(cap));
-        HIPCHK(c, c->stagedRays.thr.alloc(cap));
-        HIPCHK(c, c->stagedShadow.o.alloc(cap));
-        HIPCHK(c, c->stagedShadow.d.alloc(cap));
-        HIPCHK(c, c->stagedShadow.c.alloc(cap));
+        HIPCHK(c, c->stagedRays.alloc(cap));
+        HIPCHK(c, c->stagedShadow.alloc(cap));
         HIPCHK(c, c->activeFlag.alloc(cap));
         int rc = resetStreams(c);
         if (rc)
@@ -222,11 +211,8 @@ int ensureQueues(pt_ctx* c)
             HIPCHK(c, c->accumShadow.alloc(npx * maxBounces(c)));
             HIPCHK(c, hipMemsetAsync(c->accumShadow.p, 0, npx * maxBounces(c) * sizeof(float4), c->stream));
         }
-        for (uint32_t b = 0; b < maxBounces(c); b++) {
-            HIPCHK(c, c->shadowQ[b].o.alloc(cap));
-            HIPCHK(c, c->shadowQ[b].d.alloc(cap));
-            HIPCHK(c, c->shadowQ[b].c.alloc(cap));
-        }
+        for (uint32_t b = 0; b < maxBounces(c); b++)
+            HIPCHK(c, c->shadowQ[b].alloc(cap));
     }
     HIPCHK(c, c->control.alloc(1));
     HIPCHK(c, hipMemsetAsync(c->control.p, 0, sizeof(Control), c->stream));
@@ -406,10 +392,9 @@ struct Prof {
         if (!c->profile)
             return;
         if (c->profEvents.size() < next + 2) {
-            size_t old = c->profEvents.size();
             c->profEvents.resize(next + 2);
-            for (size_t i = old; i < c->profEvents.size(); i++)
-                (void)hipEventCreate(&c->profEvents[i]);
+            for (Event& e : c->profEvents)
+                (void)e.create(true);
         }
         (void)hipEventRecord(c->profEvents[next], c->stream);
         marks.push_back({ family, next });
@@ -720,7 +705,7 @@ int renderSampleFixed(pt_ctx* c, uint32_t sample, uint32_t batch, Prof& prof)
         // outgrow that too (the batch was sized by the counts of earlier batches: a guess).  k_trace<true> reads as many shadow entries as the count says -- cut it.
         if (b == 0 ? smallQueues(c) : c->capShadow < c->capExt) {
             const uint32_t outCap = out == 1 ? c->capExt : (c->q0Small ? c->capExt : c->capacity); // (the queue pass b writes: launchShade's a.outCap)
-            hipLaunchKernelGGL(k_clamp_counts, dim3(1), dim3(64), 0, c->stream, c->control.p, b, outCap, c->capShadow, c->overflowPinned);
+            hipLaunchKernelGGL(k_clamp_counts, dim3(1), dim3(64), 0, c->stream, c->control.p, b, outCap, c->capShadow, c->overflowPinned.p);
         }
         prof.end();
         prof.begin(3);
@@ -754,8 +739,8 @@ int renderSampleFixed(pt_ctx* c, uint32_t sample, uint32_t batch, Prof& prof)
             HIPCHK(c, hipStreamWaitEvent(c->stream, c->evShadowed[bounces - 2], 0)); // the other side stream's last pass
     }
     // the pass counters go to pinned memory from inside k_end_sample (a report still unread keeps its slot: the host reads it only once its event has fired)
-    const bool report = c->passCountsPinned && !c->passCountsPending;
-    hipLaunchKernelGGL(k_end_sample, dim3(1), dim3(64), 0, c->stream, c->control.p, c->totals.p, bounces, report ? c->passCountsPinned : nullptr);
+    const bool report = c->passCountsPinned.p && !c->passCountsPending;
+    hipLaunchKernelGGL(k_end_sample, dim3(1), dim3(64), 0, c->stream, c->control.p, c->totals.p, bounces, report ? c->passCountsPinned.p : nullptr);
     if (report) {
         HIPCHK(c, hipEventRecord(c->passCountsCopied, c->stream));
         c->passCountsPending = entries;

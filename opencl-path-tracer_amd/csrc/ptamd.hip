@@ -14,6 +14,7 @@
 #define PT_PACK_WIDE 1
 #endif
 #include <algorithm>
+#include <atomic>
 #include <dlfcn.h>
 #if __has_include(<rccl/rccl.h>)
 #include <rccl/rccl.h> // only for the two enumerators pt_reduce_accum passes (the library itself is bound at run time, below)
@@ -28,6 +29,7 @@
 #include <new>
 #include <stdexcept>
 #include <string>
+#include <utility>
 #include <vector>
 
 using namespace ptd;
@@ -71,7 +73,7 @@ static ptconv::Latest latestOf(const StaticScene& s)
 {
     if (!s.latestInStage)
         return {};
-    return { (const pt_vertex*)s.stage, (const pt_sub_bvh_node*)((const unsigned char*)s.stage + (size_t)s.host.numVerts * sizeof(pt_vertex)) };
+    return { (const pt_vertex*)s.stage.mem.p, (const pt_sub_bvh_node*)(s.stage.mem.p + (size_t)s.host.numVerts * sizeof(pt_vertex)) };
 }
 
 // the host's mirrors brought up to the caller's latest arrays (the host vectors take them over from the staging memory)
@@ -79,6 +81,23 @@ static void refreshHost(StaticScene& s)
 {
     ptconv::refreshHostGeometry(s.host, latestOf(s));
     s.latestInStage = false;
+}
+
+// What a refit re-makes from the caller's arrays on the device, enqueued on the copy stream: with `nodes`, every packed node re-quantised from the caller's nodes
+// (k_refit_nodes; pt_refit_vertices has k_refit_tree recompute the boxes instead), then the triangles' intersection and shading records (k_refit_tris).
+static void launchRefit(pt_ctx* c, bool nodes)
+{
+    static_assert(sizeof(VertexIn) == sizeof(pt_vertex) && sizeof(SubNodeIn) == sizeof(pt_sub_bvh_node), "the refit kernels read the caller's records as they are");
+    StaticScene& g = *c->st;
+    if (nodes && !g.host.wide.empty()) {
+        RefitNodeArgs rn {};
+        rn.nodes = (const SubNodeIn*)g.dNodes.p, rn.kidBoxNode = g.dKidBoxNode.p, rn.extra = g.dExtra.p, rn.wide = g.dWide.p, rn.boxes = g.dBoxes.p;
+        rn.emptyRef = g.host.emptyRef, rn.n = (uint32_t)g.host.wide.size();
+        hipLaunchKernelGGL(k_refit_nodes, dim3((rn.n + 127u) / 128u), dim3(128), 0, c->copyStream, rn);
+    }
+    RefitArgs ra {};
+    ra.verts = (const VertexIn*)g.dVerts.p, ra.tri = g.triShade.p, ra.mats = g.materials.p, ra.tris = g.dTris.p, ra.fat = g.dFat.p, ra.n = g.host.numTris;
+    hipLaunchKernelGGL(k_refit_tris, dim3((ra.n + 255u) / 256u), dim3(256), 0, c->copyStream, ra);
 }
 
 // the static arrays' master copy in device memory (the two dynamic sets take theirs from it, device to device)
@@ -112,17 +131,8 @@ static int uploadStaticGeom(pt_ctx* c, const ptconv::ConvertOptions& o)
         if (g.dFat.n < std::max<size_t>(nT, 1))
             HIPCHK(c, g.dFat.alloc(nT + nT / 8 + 1));
         tm.lap("uploads");
-        static_assert(sizeof(VertexIn) == sizeof(pt_vertex) && sizeof(SubNodeIn) == sizeof(pt_sub_bvh_node), "the refit kernels read the caller's records as they are");
         HIPCHK(c, hipMemsetAsync(g.dTris.p + nT, 0, sizeof(TriIsect), c->copyStream)); // what an unused child slot refers to
-        if (!g.host.wide.empty()) {
-            RefitNodeArgs rn {};
-            rn.nodes = (const SubNodeIn*)g.dNodes.p, rn.kidBoxNode = g.dKidBoxNode.p, rn.extra = g.dExtra.p, rn.wide = g.dWide.p, rn.boxes = g.dBoxes.p;
-            rn.emptyRef = g.host.emptyRef, rn.n = (uint32_t)g.host.wide.size();
-            hipLaunchKernelGGL(k_refit_nodes, dim3((rn.n + 127u) / 128u), dim3(128), 0, c->copyStream, rn);
-        }
-        RefitArgs ra {};
-        ra.verts = (const VertexIn*)g.dVerts.p, ra.tri = c->st->triShade.p, ra.mats = c->st->materials.p, ra.tris = g.dTris.p, ra.fat = g.dFat.p, ra.n = (uint32_t)nT;
-        hipLaunchKernelGGL(k_refit_tris, dim3(((uint32_t)nT + 255u) / 256u), dim3(256), 0, c->copyStream, ra);
+        launchRefit(c, true);
         HIPCHK(c, hipGetLastError());
         tm.lap("kernels");
         g.onDeviceTopology = g.host.topology;
@@ -219,6 +229,14 @@ int growTo(pt_ctx* c, DevBuf<T>& buf, size_t count)
     return PT_OK;
 }
 
+// pt_render_guides: the n hits of the guide pass's scratch queue into the guide sums; MOTION as k_guides knows it (pt_denoise.h)
+template <int MOTION>
+void launchGuides(pt_ctx* c, uint32_t n, const GuideMotionArgs& motion)
+{
+    hipLaunchKernelGGL(k_guides<MOTION>, dim3((n + 255u) / 256u), dim3(256), 0, c->stream, c->scene, c->guideRayO.p, c->guideRayD.p, c->guideHit.p, c->guideHitInst.p,
+        n, c->camera.thinLens, c->guides[0], c->guides[1], motion);
+}
+
 } // namespace
 
 
@@ -251,9 +269,9 @@ int pt_debug_copy_bandwidth(pt_ctx* c, size_t bytes, uint32_t repeat, float* gbp
     HIPCHK(c, src.alloc(n));
     HIPCHK(c, dst.alloc(n));
     HIPCHK(c, hipMemsetAsync(src.p, 0x3c, n * sizeof(float4), c->stream));
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    HIPCHK(c, hipEventCreate(&e0));
-    HIPCHK(c, hipEventCreate(&e1));
+    Event e0, e1;
+    HIPCHK(c, e0.create(true));
+    HIPCHK(c, e1.create(true));
     const uint32_t blocks = (uint32_t)c->numCUs * 4u; // 1 024 workgroups of 256 on an MI355X (pt_bake.h: the best of the shapes tried)
     float best = 0.f;
     for (uint32_t r = 0; r <= std::max(repeat, 1u); r++) { // (run 0: warm-up)
@@ -266,8 +284,6 @@ int pt_debug_copy_bandwidth(pt_ctx* c, size_t bytes, uint32_t repeat, float* gbp
         if (r > 0 && ms > 0.f)
             best = std::max(best, (float)(2.0 * (double)n * sizeof(float4) / (ms * 1e-3) / 1e9));
     }
-    (void)hipEventDestroy(e0), (void)hipEventDestroy(e1);
-    src.release(), dst.release();
     *gbps_out = best;
     return PT_OK;
     });
@@ -290,9 +306,19 @@ int pt_debug_math_probe(pt_ctx* c, const float* a, const float* b, uint32_t n, f
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipStreamSynchronize(c->stream));
     HIPCHK(c, hipMemcpy(out, dOut.p, (size_t)n * 10 * sizeof(float), hipMemcpyDeviceToHost));
-    dA.release(), dB.release(), dOut.release();
     return PT_OK;
     });
+}
+
+// Test hook, no device needed (tests/test_gpu_lifetime.py): what the owning types of pt_context.h hold alive in this process, all contexts and hooks together --
+// device allocations, pinned allocations, events, streams the library created.
+int pt_debug_live_resources(uint32_t out[4])
+{
+    if (!out)
+        return PT_ERR_INVALID;
+    for (int k = 0; k < 4; k++)
+        out[k] = g_live[k].load();
+    return PT_OK;
 }
 
 const char* pt_last_error(const pt_ctx* ctx) { return ctx ? ctx->error.c_str() : g_createError.c_str(); }
@@ -402,31 +428,30 @@ int pt_create(const pt_config* cfg, pt_ctx** out)
     if ((e = hipGetDeviceProperties(&prop, c->device)) != hipSuccess)
         return bail(e, "hipGetDeviceProperties");
     c->numCUs = prop.multiProcessorCount;
-    if ((e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking)) != hipSuccess)
+    if ((e = c->stream.create()) != hipSuccess)
         return bail(e, "hipStreamCreate");
-    c->ownStream = true;
-    if ((e = hipStreamCreateWithFlags(&c->copyStream, hipStreamNonBlocking)) != hipSuccess)
+    if ((e = c->copyStream.create()) != hipSuccess)
         return bail(e, "hipStreamCreate (copy stream)");
-    if ((e = hipEventCreate(&c->evStart)) != hipSuccess || (e = hipEventCreate(&c->evStop)) != hipSuccess)
+    if ((e = c->evStart.create(true)) != hipSuccess || (e = c->evStop.create(true)) != hipSuccess || (e = c->evDenoise[0].create(true)) != hipSuccess
+        || (e = c->evDenoise[1].create(true)) != hipSuccess) // (the filter's two with the context: a pt_denoise that refuses leaves nothing behind)
         return bail(e, "hipEventCreate");
-    if ((e = hipStreamCreateWithFlags(&c->sideStream, hipStreamNonBlocking)) != hipSuccess || (e = hipStreamCreateWithFlags(&c->sideStream2, hipStreamNonBlocking)) != hipSuccess)
+    if ((e = c->sideStream.create()) != hipSuccess || (e = c->sideStream2.create()) != hipSuccess)
         return bail(e, "hipStreamCreate (side stream)");
     for (int k = 0; k < kMaxPasses; k++)
-        if ((e = hipEventCreateWithFlags(&c->evShaded[k], hipEventDisableTiming)) != hipSuccess
-            || (e = hipEventCreateWithFlags(&c->evShadowed[k], hipEventDisableTiming)) != hipSuccess)
+        if ((e = c->evShaded[k].create()) != hipSuccess || (e = c->evShadowed[k].create()) != hipSuccess)
             return bail(e, "hipEventCreate");
     for (auto& d : c->dyn)
-        if ((e = hipEventCreateWithFlags(&d.uploaded, hipEventDisableTiming)) != hipSuccess
-            || (e = hipEventCreateWithFlags(&d.lastUse, hipEventDisableTiming)) != hipSuccess
-            || (e = hipEventCreateWithFlags(&d.stageRead, hipEventDisableTiming)) != hipSuccess)
+        if ((e = d.uploaded.create()) != hipSuccess || (e = d.lastUse.create()) != hipSuccess || (e = d.stage.read.create()) != hipSuccess)
             return bail(e, "hipEventCreate");
-    if ((e = hipHostMalloc((void**)&c->passCountsPinned, sizeof(c->passCountsHint), hipHostMallocDefault)) != hipSuccess
-        || (e = hipEventCreateWithFlags(&c->passCountsCopied, hipEventDisableTiming)) != hipSuccess)
+    for (StaticScene& s : c->stat)
+        if ((e = s.stage.read.create()) != hipSuccess)
+            return bail(e, "hipEventCreate");
+    if ((e = c->passCountsPinned.alloc(sizeof(c->passCountsHint) / sizeof(uint32_t))) != hipSuccess || (e = c->passCountsCopied.create()) != hipSuccess)
         return bail(e, "pinned counters");
-    std::memset(c->passCountsPinned, 0, sizeof(c->passCountsHint));
-    if ((e = hipHostMalloc((void**)&c->overflowPinned, sizeof(uint32_t), hipHostMallocDefault)) != hipSuccess)
+    std::memset(c->passCountsPinned.p, 0, sizeof(c->passCountsHint));
+    if ((e = c->overflowPinned.alloc(1)) != hipSuccess)
         return bail(e, "pinned overflow word");
-    *c->overflowPinned = 0u;
+    *c->overflowPinned.p = 0u;
     if ((e = c->totals.alloc(1)) != hipSuccess || (e = hipMemsetAsync(c->totals.p, 0, sizeof(Totals), c->stream)) != hipSuccess)
         return bail(e, "alloc totals");
     if ((e = c->accumOwn.alloc((size_t)cfg->width * cfg->height)) != hipSuccess
@@ -447,72 +472,8 @@ int pt_create(const pt_config* cfg, pt_ctx** out)
     });
 }
 
-void pt_destroy(pt_ctx* c)
-{
-    if (!c)
-        return;
-    (void)hipSetDevice(c->device);
-    if (c->stream)
-        (void)hipStreamSynchronize(c->stream);
-    if (c->copyStream) // a never-adopted upload may still be copying into the sets released below
-        (void)hipStreamSynchronize(c->copyStream);
-    if (c->sideStream)
-        (void)hipStreamSynchronize(c->sideStream);
-    if (c->sideStream2)
-        (void)hipStreamSynchronize(c->sideStream2);
-    c->accumShadow.release();
-    for (ShadowQueueBuf& q : c->shadowQ)
-        q.o.release(), q.d.release(), q.c.release();
-    DevBuf<float4>* f4[] = { &c->accumOwn, &c->hitH, &c->rays[0].o, &c->rays[0].d, &c->rays[0].thr, &c->rays[1].o,
-        &c->rays[1].d, &c->rays[1].thr, &c->stagedRays.o, &c->stagedRays.d, &c->stagedRays.thr, &c->shadow.o, &c->shadow.d, &c->shadow.c,
-        &c->stagedShadow.o, &c->stagedShadow.d, &c->stagedShadow.c };
-    for (auto* b : f4)
-        b->release();
-    c->texMaterial.release(), c->texSky.release();
-    c->nodes.release();
-    for (StaticScene& sc : c->stat) {
-        StaticScene& g = sc;
-        sc.materials.release(), sc.triShade.release();
-        g.dWide.release(), g.dBoxes.release(), g.dLeafOfs.release(), g.dRefTri.release(), g.dTris.release(), g.dFat.release();
-        g.dVerts.release(), g.dNodes.release(), g.dKidBoxNode.release(), g.dExtra.release(), g.dParent.release(), g.dNeed.release(), g.dArrived.release();
-        if (g.stage) (void)hipHostFree(g.stage);
-        if (g.stageRead) (void)hipEventDestroy(g.stageRead);
-    }
-    for (auto& d : c->dyn) {
-        d.wide.release(), d.tris.release(), d.fat.release(), d.instances.release(), d.lights.release(), d.jobs.release(), d.instFold.release(), d.instRootSrc.release();
-        if (d.stage) (void)hipHostFree(d.stage);
-        if (d.stageRead) (void)hipEventDestroy(d.stageRead);
-        if (d.uploaded) (void)hipEventDestroy(d.uploaded);
-        if (d.lastUse) (void)hipEventDestroy(d.lastUse);
-    }
-    if (c->copyStream) (void)hipStreamDestroy(c->copyStream);
-    c->pixelList.release(), c->hitInst.release();
-    c->guideAlbedoHits.release(), c->guideNormalDepth.release(), c->guideRayO.release(), c->guideRayD.release(), c->guideHit.release(), c->guideHitInst.release();
-    c->guideCtl.release(), c->denoiseColour[0].release(), c->denoiseColour[1].release(), c->denoiseGuide.release();
-    for (int k = 0; k < 2; k++)
-        c->temporalColour[k].release(), c->temporalGuide[k].release();
-    c->motionRecords.release(), c->guideMotion.release(), c->guidePrevNormal.release();
-    c->fatThen.release(), c->vertexRows.release();
-    for (hipEvent_t ev : c->evDenoise)
-        if (ev) (void)hipEventDestroy(ev);
-    c->accumPlanes.release(), c->pixelOrdinal.release(), c->resolveTmp.release(), c->activeFlag.release(), c->streams.release(), c->control.release(), c->totals.release(), c->spill.release();
-    for (hipEvent_t ev : c->profEvents)
-        (void)hipEventDestroy(ev);
-    if (c->sideStream) (void)hipStreamDestroy(c->sideStream);
-    if (c->sideStream2) (void)hipStreamDestroy(c->sideStream2);
-    for (int k = 0; k < kMaxPasses; k++) {
-        if (c->evShaded[k]) (void)hipEventDestroy(c->evShaded[k]);
-        if (c->evShadowed[k]) (void)hipEventDestroy(c->evShadowed[k]);
-    }
-    if (c->passCountsPinned) (void)hipHostFree(c->passCountsPinned);
-    if (c->overflowPinned) (void)hipHostFree(c->overflowPinned);
-    if (c->passCountsCopied) (void)hipEventDestroy(c->passCountsCopied);
-    if (c->evStart) (void)hipEventDestroy(c->evStart);
-    if (c->evStop) (void)hipEventDestroy(c->evStop);
-    if (c->ownStream && c->stream)
-        (void)hipStreamDestroy(c->stream);
-    delete c;
-}
+// (~pt_ctx, pt_context.h: waits for the context's streams, then every member frees what it owns; null: nothing)
+void pt_destroy(pt_ctx* c) { delete c; }
 
 int pt_set_stream(pt_ctx* c, void* hip_stream)
 {
@@ -520,15 +481,10 @@ int pt_set_stream(pt_ctx* c, void* hip_stream)
         return PT_ERR_INVALID;
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (c->ownStream && c->stream)
-        (void)hipStreamDestroy(c->stream);
-    if (hip_stream) {
-        c->stream = (hipStream_t)hip_stream;
-        c->ownStream = false;
-    } else {
-        HIPCHK(c, hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
-        c->ownStream = true;
-    }
+    if (hip_stream)
+        c->stream.adopt((hipStream_t)hip_stream); // (the caller's: never destroyed here)
+    else
+        HIPCHK(c, c->stream.create());
     return PT_OK;
 }
 
@@ -619,28 +575,15 @@ int pt_update_geometry(pt_ctx* c, const pt_vertex* verts, uint32_t nV, const pt_
         // ---- the device's master copy: the caller's vertices and nodes AS THEY ARE through pinned staging on the copy stream; the packed nodes
         // re-quantised (k_refit_nodes) and the triangle records re-made (k_refit_tris) there.  The staging memory doubles as the host's copy of the
         // caller's latest arrays (refreshHostGeometry reads it if the whole conversion ever runs again).
-        static_assert(sizeof(VertexIn) == sizeof(pt_vertex), "k_refit_tris reads the caller's vertex records as they are");
-        static_assert(sizeof(SubNodeIn) == sizeof(pt_sub_bvh_node), "k_refit_nodes reads the caller's node records as they are");
         ptconv::refitPairBoxes(g.host, verts, nodes, true); // the boxes of the pair nodes that split an oversized leaf (rare): recomputed here
         const std::vector<float> extra = ptconv::extraBoxes(g.host);
         const size_t bytesV = (size_t)nV * sizeof(pt_vertex), bytesN = (size_t)nN * sizeof(pt_sub_bvh_node), bytesE = extra.size() * sizeof(float);
         const size_t total = bytesV + bytesN + bytesE;
-        if (!g.stageRead)
-            HIPCHK(c, hipEventCreateWithFlags(&g.stageRead, hipEventDisableTiming));
-        if (g.stageBusy) { // the previous refit's copies out of the staging memory (normally long done)
-            HIPCHK(c, hipEventSynchronize(g.stageRead));
-            g.stageBusy = false;
-        }
-        if (g.stageBytes < total) {
-            if (g.latestInStage)
-                refreshHost(g); // (the staging memory holds the host's only copy of the latest arrays: take it over before it goes)
-            if (g.stage)
-                (void)hipHostFree(g.stage);
-            g.stage = nullptr;
-            g.stageBytes = total + total / 8;
-            HIPCHK(c, hipHostMalloc(&g.stage, g.stageBytes, hipHostMallocDefault));
-        }
-        unsigned char* st = (unsigned char*)g.stage;
+        HIPCHK(c, g.stage.wait()); // the previous refit's copies out of the staging memory
+        if (g.stage.bytes < total && g.latestInStage)
+            refreshHost(g); // (the staging memory holds the host's only copy of the latest arrays: take it over before it goes)
+        HIPCHK(c, g.stage.reserve(total, total + total / 8));
+        unsigned char* st = g.stage.mem.p;
         std::memcpy(st, verts, bytesV);
         std::memcpy(st + bytesV, nodes, bytesN);
         g.latestInStage = true;
@@ -654,17 +597,8 @@ int pt_update_geometry(pt_ctx* c, const pt_vertex* verts, uint32_t nV, const pt_
                 HIPCHK(c, g.dExtra.alloc(extra.size()));
             HIPCHK(c, hipMemcpyAsync(g.dExtra.p, st + bytesV + bytesN, bytesE, hipMemcpyHostToDevice, c->copyStream));
         }
-        HIPCHK(c, hipEventRecord(g.stageRead, c->copyStream));
-        g.stageBusy = true;
-        if (!g.host.wide.empty()) {
-            RefitNodeArgs rn {};
-            rn.nodes = (const SubNodeIn*)g.dNodes.p, rn.kidBoxNode = g.dKidBoxNode.p, rn.extra = g.dExtra.p, rn.wide = g.dWide.p, rn.boxes = g.dBoxes.p;
-            rn.emptyRef = g.host.emptyRef, rn.n = (uint32_t)g.host.wide.size();
-            hipLaunchKernelGGL(k_refit_nodes, dim3((rn.n + 127u) / 128u), dim3(128), 0, c->copyStream, rn);
-        }
-        RefitArgs ra {};
-        ra.verts = (const VertexIn*)g.dVerts.p, ra.tri = c->st->triShade.p, ra.mats = c->st->materials.p, ra.tris = g.dTris.p, ra.fat = g.dFat.p, ra.n = c->st->host.numTris;
-        hipLaunchKernelGGL(k_refit_tris, dim3((c->st->host.numTris + 255u) / 256u), dim3(256), 0, c->copyStream, ra);
+        HIPCHK(c, g.stage.recordRead(c->copyStream));
+        launchRefit(c, true);
         HIPCHK(c, hipGetLastError());
         return PT_OK;
     });
@@ -696,11 +630,8 @@ int pt_refit_vertices(pt_ctx* c, uint32_t firstVertex, const pt_vertex* verts, u
             return fail(c, PT_ERR_UNSUPPORTED, "pt_refit_vertices: two roots of the sub-BVH array share a subtree: refit on the host and use pt_update_geometry");
         // the host's copy of the caller's arrays: rawVerts takes the new vertices; the node boxes go stale (nobody refits them here) and are
         // recomputed from the vertices only if the whole conversion ever runs again (refreshHostGeometry)
+        HIPCHK(c, g.stage.wait()); // the previous refit's copies out of the staging memory, which is read and then rewritten below
         if (g.latestInStage) { // an earlier pt_update_geometry left the latest arrays in the staging memory: take them over first
-            if (g.stageBusy) {
-                HIPCHK(c, hipEventSynchronize(g.stageRead));
-                g.stageBusy = false;
-            }
             const ptconv::Latest l = latestOf(g);
             g.host.rawVerts.assign(l.verts, l.verts + g.host.numVerts);
             g.host.hostSubNodes.assign(l.nodes, l.nodes + g.host.numRefNodes);
@@ -710,34 +641,18 @@ int pt_refit_vertices(pt_ctx* c, uint32_t firstVertex, const pt_vertex* verts, u
         c->st->host.hostNodeBoxesStale = true;
         c->st->host.hostGeomStale = true;
         const size_t bytesV = (size_t)nV * sizeof(pt_vertex);
-        if (!g.stageRead)
-            HIPCHK(c, hipEventCreateWithFlags(&g.stageRead, hipEventDisableTiming));
-        if (g.stageBusy) { // the previous refit's copy out of the staging memory (normally long done)
-            HIPCHK(c, hipEventSynchronize(g.stageRead));
-            g.stageBusy = false;
-        }
-        if (g.stageBytes < bytesV) {
-            if (g.stage)
-                (void)hipHostFree(g.stage);
-            g.stage = nullptr;
-            g.stageBytes = bytesV + bytesV / 8;
-            HIPCHK(c, hipHostMalloc(&g.stage, g.stageBytes, hipHostMallocDefault));
-        }
-        std::memcpy(g.stage, verts, bytesV);
+        HIPCHK(c, g.stage.reserve(bytesV, bytesV + bytesV / 8));
+        std::memcpy(g.stage.mem.p, verts, bytesV);
         g.host.version = ++c->staticVersions;
-        HIPCHK(c, hipMemcpyAsync(g.dVerts.p + firstVertex, g.stage, bytesV, hipMemcpyHostToDevice, c->copyStream));
-        HIPCHK(c, hipEventRecord(g.stageRead, c->copyStream));
-        g.stageBusy = true;
-        static_assert(sizeof(VertexIn) == sizeof(pt_vertex), "the refit kernels read the caller's vertex records as they are");
+        HIPCHK(c, hipMemcpyAsync(g.dVerts.p + firstVertex, g.stage.mem.p, bytesV, hipMemcpyHostToDevice, c->copyStream));
+        HIPCHK(c, g.stage.recordRead(c->copyStream));
         if (!g.host.wide.empty()) {
             RefitTreeArgs rt {};
             rt.verts = (const VertexIn*)g.dVerts.p, rt.tri = c->st->triShade.p, rt.wide = g.dWide.p, rt.boxes = g.dBoxes.p;
             rt.parent = g.dParent.p, rt.need = g.dNeed.p, rt.arrived = g.dArrived.p, rt.emptyRef = g.host.emptyRef, rt.n = (uint32_t)g.host.wide.size();
             hipLaunchKernelGGL(k_refit_tree, dim3((rt.n + 127u) / 128u), dim3(128), 0, c->copyStream, rt);
         }
-        RefitArgs ra {};
-        ra.verts = (const VertexIn*)g.dVerts.p, ra.tri = c->st->triShade.p, ra.mats = c->st->materials.p, ra.tris = g.dTris.p, ra.fat = g.dFat.p, ra.n = c->st->host.numTris;
-        hipLaunchKernelGGL(k_refit_tris, dim3((c->st->host.numTris + 255u) / 256u), dim3(256), 0, c->copyStream, ra);
+        launchRefit(c, false);
         HIPCHK(c, hipGetLastError());
         return PT_OK;
     });
@@ -803,7 +718,7 @@ int pt_upload_dynamic_async(pt_ctx* c, const pt_emissive_triangle* lights, uint3
     const size_t total = bytes[0] + bytes[1] + bytes[2] + bytes[3] + bytes[4] + bytes[5] + bytes[6];
     if (d.wide.n < needWide || d.tris.n < needTris || d.fat.n < sg.host.fat.size() || d.instances.n < std::max<size_t>(h.instances.size(), 1)
         || d.lights.n < std::max<size_t>(h.lights.size(), 1) || d.jobs.n < std::max<size_t>(h.jobs.size(), 1) || d.instFold.n < std::max<size_t>(h.instFold.size(), 1)
-        || d.instRootSrc.n < std::max<size_t>(h.instRootSrc.size(), 1) || d.stageBytes < std::max<size_t>(total, 1)) {
+        || d.instRootSrc.n < std::max<size_t>(h.instRootSrc.size(), 1) || d.stage.bytes < std::max<size_t>(total, 1)) {
         // growing frees device memory, which the runtime only does once nothing uses it: wait for both streams (rare: the first
         // uploads, or a state with more world-space copies than any before)
         HIPCHK(c, hipStreamSynchronize(c->copyStream));
@@ -816,19 +731,9 @@ int pt_upload_dynamic_async(pt_ctx* c, const pt_emissive_triangle* lights, uint3
             return rc;
         if (regrown)
             d.staticVersion = 0; // fresh buffers: the static arrays have to be put in again
-        if (d.stageBytes < std::max<size_t>(total, 1)) {
-            if (d.stage)
-                (void)hipHostFree(d.stage);
-            d.stage = nullptr;
-            d.stageBytes = total + total / 8 + 4096;
-            HIPCHK(c, hipHostMalloc(&d.stage, d.stageBytes, hipHostMallocDefault));
-            d.stageBusy = false;
-        }
+        HIPCHK(c, d.stage.reserve(std::max<size_t>(total, 1), total + total / 8 + 4096)); // (new staging memory has no copies in flight)
     }
-    if (d.stageBusy) { // the staging memory of this set is about to be rewritten: its last copies (two ticks ago) must have been read
-        HIPCHK(c, hipEventSynchronize(d.stageRead));
-        d.stageBusy = false;
-    }
+    HIPCHK(c, d.stage.wait()); // the staging memory of this set is about to be rewritten: its last copies (two ticks ago) must have been read
     tm.lap("grow");
     if (d.staticVersion != sg.host.version) { // device to device, from the master copy
         if (staticNodes)
@@ -838,7 +743,7 @@ int pt_upload_dynamic_async(pt_ctx* c, const pt_emissive_triangle* lights, uint3
             HIPCHK(c, hipMemcpyAsync(d.fat.p, sg.dFat.p, sg.host.fat.size() * sizeof(TriFat), hipMemcpyDeviceToDevice, c->copyStream));
         d.staticVersion = sg.host.version;
     }
-    unsigned char* st = (unsigned char*)d.stage;
+    unsigned char* st = d.stage.mem.p;
     const void* src[7] = { h.topWide.data(), h.instances.data(), h.lights.data(), h.jobs.data(), h.instRoots.data(), h.instFold.data(), h.instRootSrc.data() };
     void* dst[7] = { d.wide.p + staticNodes, d.instances.p, d.lights.p, d.jobs.p, d.wide.p + h.instRootBase, d.instFold.p, d.instRootSrc.p };
     for (int k = 0; k < 7; k++) {
@@ -848,10 +753,8 @@ int pt_upload_dynamic_async(pt_ctx* c, const pt_emissive_triangle* lights, uint3
         HIPCHK(c, hipMemcpyAsync(dst[k], st, bytes[k], hipMemcpyHostToDevice, c->copyStream));
         st += bytes[k];
     }
-    if (total) {
-        HIPCHK(c, hipEventRecord(d.stageRead, c->copyStream));
-        d.stageBusy = true;
-    }
+    if (total)
+        HIPCHK(c, d.stage.recordRead(c->copyStream));
     if (!h.instRootSrc.empty()) { // the folded instances' copies of their meshes' root nodes, from the set's own (just refreshed) copy of the static nodes
         const uint32_t n = (uint32_t)h.instRootSrc.size();
         hipLaunchKernelGGL(k_inst_roots, dim3((n + 63u) / 64u), dim3(64), 0, c->copyStream, d.wide.p, d.instRootSrc.p, d.wide.p + h.instRootBase, n);
@@ -1065,28 +968,22 @@ int pt_clear(pt_ctx* c)
         HIPCHK(c, hipMemsetAsync(c->accumPlanes.p, 0, c->accumPlanes.n * sizeof(float4), c->stream));
     c->foldPlanes = 0;
     c->spp = 0;
-    if (c->guideAlbedoHits.p) { // the guide sums belong to the image they describe
-        HIPCHK(c, hipMemsetAsync(c->guideAlbedoHits.p, 0, c->guideAlbedoHits.n * sizeof(float4), c->stream));
-        HIPCHK(c, hipMemsetAsync(c->guideNormalDepth.p, 0, c->guideNormalDepth.n * sizeof(float4), c->stream));
-    }
-    if (c->guideMotion.p) { // ... and so do the two motion sums (the motion itself stays set)
-        HIPCHK(c, hipMemsetAsync(c->guideMotion.p, 0, c->guideMotion.n * sizeof(float4), c->stream));
-        HIPCHK(c, hipMemsetAsync(c->guidePrevNormal.p, 0, c->guidePrevNormal.n * sizeof(float4), c->stream));
-    }
+    int rc;
+    if (c->guides[0] && (rc = c->guides.zero(c))) // the guide sums belong to the image they describe
+        return rc;
+    if (c->motionGuides[0] && (rc = c->motionGuides.zero(c))) // ... and so do the two motion sums (the motion itself stays set)
+        return rc;
     c->guideSpp = 0;
-    if (c->overflowPinned && *c->overflowPinned) { // a reported overflow is cleared with the image it spoiled (whatever set it has run: the word is only read after a synchronisation)
+    if (c->overflowPinned.p && *c->overflowPinned.p) { // a reported overflow is cleared with the image it spoiled (whatever set it has run: the word is only read after a synchronisation)
         HIPCHK(c, hipStreamSynchronize(c->stream));
-        *c->overflowPinned = 0u;
+        *c->overflowPinned.p = 0u;
         newEpoch(c); // the ratios learned since were measured on cut counts: the next render probes again
     }
     if (c->accumShadow.p) // (zero between pt_render calls unless one failed half-way)
         HIPCHK(c, hipMemsetAsync(c->accumShadow.p, 0, c->accumShadow.n * sizeof(float4), c->stream));
     c->mergePending = false;
-    if (parityMode(c) && c->queuesReady) {
-        int rc = resetStreams(c);
-        if (rc)
-            return rc;
-    }
+    if (parityMode(c) && c->queuesReady && (rc = resetStreams(c)))
+        return rc;
     return PT_OK;
     });
 }
@@ -1183,6 +1080,28 @@ int pt_synchronize(pt_ctx* c)
     return checkOverflow(c);
 }
 
+namespace {
+
+// where pt_resolve, pt_resolve_device and pt_denoise_device write: the caller's image or, for null, the context's own (pt_resolve_device_ptr), allocated at
+// first use -- once per context: this is the interactive getOutput() path
+int resolveTarget(pt_ctx* c, void* device_rgba, float4** out)
+{
+    const uint32_t n = c->cfg.width * c->cfg.height;
+    if (!device_rgba && c->resolveTmp.n != n)
+        HIPCHK(c, c->resolveTmp.alloc(n));
+    *out = device_rgba ? (float4*)device_rgba : c->resolveTmp.p;
+    return PT_OK;
+}
+
+void launchResolve(pt_ctx* c, float4* out)
+{
+    const uint32_t n = c->cfg.width * c->cfg.height;
+    hipLaunchKernelGGL(k_resolve, dim3((n + 255) / 256), dim3(256), 0, c->stream, c->accum, out, n, (float)c->spp, c->camera.relativeAperture,
+        c->camera.shutterTime, c->camera.ISO);
+}
+
+} // namespace
+
 int pt_resolve(pt_ctx* c, float* rgba_out)
 {
     return guarded(c, "pt_resolve", [&]() -> int {
@@ -1191,12 +1110,11 @@ int pt_resolve(pt_ctx* c, float* rgba_out)
     if (!c->haveCamera || c->spp == 0)
         return fail(c, PT_ERR_STATE, "pt_resolve: nothing rendered yet");
     HIPCHK(c, hipSetDevice(c->device));
-    const uint32_t n = c->cfg.width * c->cfg.height;
-    if (c->resolveTmp.n != n) // once per context: this is the interactive getOutput() path
-        HIPCHK(c, c->resolveTmp.alloc(n));
-    hipLaunchKernelGGL(k_resolve, dim3((n + 255) / 256), dim3(256), 0, c->stream, c->accum, c->resolveTmp.p, n, (float)c->spp,
-        c->camera.relativeAperture, c->camera.shutterTime, c->camera.ISO);
-    HIPCHK(c, hipMemcpyAsync(rgba_out, c->resolveTmp.p, (size_t)n * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
+    float4* image;
+    if (const int rc = resolveTarget(c, nullptr, &image))
+        return rc;
+    launchResolve(c, image);
+    HIPCHK(c, hipMemcpyAsync(rgba_out, image, c->resolveTmp.n * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return checkOverflow(c);
     });
@@ -1210,14 +1128,10 @@ int pt_resolve_device(pt_ctx* c, void* device_rgba)
     if (!c->haveCamera || c->spp == 0)
         return fail(c, PT_ERR_STATE, "pt_resolve_device: nothing rendered yet");
     HIPCHK(c, hipSetDevice(c->device));
-    const uint32_t n = c->cfg.width * c->cfg.height;
-    if (!device_rgba) { // the context's own image (pt_resolve_device_ptr)
-        if (c->resolveTmp.n != n)
-            HIPCHK(c, c->resolveTmp.alloc(n));
-        device_rgba = c->resolveTmp.p;
-    }
-    hipLaunchKernelGGL(k_resolve, dim3((n + 255) / 256), dim3(256), 0, c->stream, c->accum, (float4*)device_rgba, n, (float)c->spp,
-        c->camera.relativeAperture, c->camera.shutterTime, c->camera.ISO);
+    float4* image;
+    if (const int rc = resolveTarget(c, device_rgba, &image))
+        return rc;
+    launchResolve(c, image);
     HIPCHK(c, hipGetLastError());
     return PT_OK;
     });
@@ -1256,16 +1170,11 @@ uint32_t pt_samples_per_pixel(const pt_ctx* c) { return c ? c->spp : 0; }
 
 namespace {
 
-// the two guide sums: allocated (zeroed) at first use
-int ensureGuides(pt_ctx* c)
+// the guide pass, the sample base and the motion setters key the counter PRNG by sample index: the refusal they share (PT_OK where the schedule is the fixed one)
+int fixedScheduleOnly(pt_ctx* c, const char* who)
 {
-    const size_t n = (size_t)c->cfg.width * c->cfg.height;
-    if (c->guideAlbedoHits.p)
-        return PT_OK;
-    HIPCHK(c, c->guideAlbedoHits.alloc(n));
-    HIPCHK(c, c->guideNormalDepth.alloc(n));
-    HIPCHK(c, hipMemsetAsync(c->guideAlbedoHits.p, 0, n * sizeof(float4), c->stream));
-    HIPCHK(c, hipMemsetAsync(c->guideNormalDepth.p, 0, n * sizeof(float4), c->stream));
+    if (parityMode(c) || c->cfg.max_active_rays != 0)
+        return fail(c, PT_ERR_UNSUPPORTED, "%s: the fixed schedule with PT_RNG_COUNTER only (not in parity / refill mode)", who);
     return PT_OK;
 }
 
@@ -1280,11 +1189,11 @@ int pt_render_guides(pt_ctx* c, uint32_t spp)
         return PT_ERR_INVALID;
     if (!c->haveStatic || !c->haveDynamic || !c->haveCamera)
         return fail(c, PT_ERR_STATE, "pt_render_guides: scene (static + dynamic) and camera must be set first");
-    if (parityMode(c) || c->cfg.max_active_rays != 0)
-        return fail(c, PT_ERR_UNSUPPORTED, "pt_render_guides: the fixed schedule with PT_RNG_COUNTER only (not in parity / refill mode)");
-    HIPCHK(c, hipSetDevice(c->device));
     int rc;
-    if ((rc = ensureSpill(c)) || (rc = ensureGuides(c)))
+    if ((rc = fixedScheduleOnly(c, "pt_render_guides")))
+        return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    if ((rc = ensureSpill(c)) || (rc = c->guides.ensure(c)))
         return rc;
     const uint32_t n = c->numOwned;
     if (c->guideRayO.n < n) { // a scratch queue of its own: one sample of the owned pixels (the render queues may be smaller than that, or hold directions only)
@@ -1314,16 +1223,11 @@ int pt_render_guides(pt_ctx* c, uint32_t spp)
         a.ctl = c->guideCtl.p, a.pass = 0;
         launchTrace(c, false, a);
         if (c->vertexMotionSet && c->vertexDeformed) // (the snapshot, never the inactive set: the next state may be on its way into that)
-            hipLaunchKernelGGL(k_guides<2>, dim3((n + 255u) / 256u), dim3(256), 0, c->stream, c->scene, c->guideRayO.p, c->guideRayD.p, c->guideHit.p,
-                c->guideHitInst.p, n, c->camera.thinLens, c->guideAlbedoHits.p, c->guideNormalDepth.p,
-                GuideMotionArgs { c->motionRecords.p, c->guideMotion.p, c->guidePrevNormal.p, c->fatThen.p, c->vertexRows.p });
+            launchGuides<2>(c, n, GuideMotionArgs { c->motionRecords.p, c->motionGuides[0], c->motionGuides[1], c->fatThen.p, c->vertexRows.p });
         else if (c->motionSet || c->vertexMotionSet) // (vertex motion with nothing deformed: identity records, exact zeros and the bits of N)
-            hipLaunchKernelGGL(k_guides<1>, dim3((n + 255u) / 256u), dim3(256), 0, c->stream, c->scene, c->guideRayO.p, c->guideRayD.p, c->guideHit.p,
-                c->guideHitInst.p, n, c->camera.thinLens, c->guideAlbedoHits.p, c->guideNormalDepth.p,
-                GuideMotionArgs { c->motionRecords.p, c->guideMotion.p, c->guidePrevNormal.p, nullptr, nullptr });
+            launchGuides<1>(c, n, GuideMotionArgs { c->motionRecords.p, c->motionGuides[0], c->motionGuides[1], nullptr, nullptr });
         else
-            hipLaunchKernelGGL(k_guides<0>, dim3((n + 255u) / 256u), dim3(256), 0, c->stream, c->scene, c->guideRayO.p, c->guideRayD.p, c->guideHit.p,
-                c->guideHitInst.p, n, c->camera.thinLens, c->guideAlbedoHits.p, c->guideNormalDepth.p, GuideMotionArgs { nullptr, nullptr, nullptr, nullptr, nullptr });
+            launchGuides<0>(c, n, GuideMotionArgs {});
     }
     c->batchEntries = batchEntries;
     c->teamLaunches = teamLaunches;
@@ -1340,16 +1244,7 @@ int pt_read_guides(pt_ctx* c, float* albedo_hits, float* normal_depth)
     if (!c)
         return PT_ERR_INVALID;
     HIPCHK(c, hipSetDevice(c->device));
-    int rc = ensureGuides(c);
-    if (rc)
-        return rc;
-    const size_t bytes = (size_t)c->cfg.width * c->cfg.height * sizeof(float4);
-    if (albedo_hits)
-        HIPCHK(c, hipMemcpyAsync(albedo_hits, c->guideAlbedoHits.p, bytes, hipMemcpyDeviceToHost, c->stream));
-    if (normal_depth)
-        HIPCHK(c, hipMemcpyAsync(normal_depth, c->guideNormalDepth.p, bytes, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return PT_OK;
+    return c->guides.read(c, albedo_hits, normal_depth);
 }
 
 int pt_write_guides(pt_ctx* c, const float* albedo_hits, const float* normal_depth, uint32_t spp)
@@ -1357,23 +1252,13 @@ int pt_write_guides(pt_ctx* c, const float* albedo_hits, const float* normal_dep
     if (!c || !albedo_hits || !normal_depth)
         return PT_ERR_INVALID;
     HIPCHK(c, hipSetDevice(c->device));
-    int rc = ensureGuides(c);
-    if (rc)
+    if (const int rc = c->guides.write(c, albedo_hits, normal_depth))
         return rc;
-    const size_t bytes = (size_t)c->cfg.width * c->cfg.height * sizeof(float4);
-    HIPCHK(c, hipMemcpyAsync(c->guideAlbedoHits.p, albedo_hits, bytes, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->guideNormalDepth.p, normal_depth, bytes, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
     c->guideSpp = spp;
     return PT_OK;
 }
 
-void* pt_guides_device_ptr(pt_ctx* c, int which)
-{
-    if (!c || which < 0 || which > 1)
-        return nullptr;
-    return which == 0 ? (void*)c->guideAlbedoHits.p : (void*)c->guideNormalDepth.p;
-}
+void* pt_guides_device_ptr(pt_ctx* c, int which) { return c && (which == 0 || which == 1) ? (void*)c->guides[which] : nullptr; }
 
 int pt_denoise_device(pt_ctx* c, const pt_denoise_params* prm, void* device_rgba)
 {
@@ -1402,21 +1287,19 @@ int pt_denoise_device(pt_ctx* c, const pt_denoise_params* prm, void* device_rgba
         return fail(c, PT_ERR_STATE, "pt_denoise: the tone-mapped output needs the camera's exposure (pt_set_camera)");
     HIPCHK(c, hipSetDevice(c->device));
     const uint32_t W = c->cfg.width, H = c->cfg.height, n = W * H;
-    if (!device_rgba) { // the context's own image (pt_resolve_device_ptr)
-        if (c->resolveTmp.n != n)
-            HIPCHK(c, c->resolveTmp.alloc(n));
-        device_rgba = c->resolveTmp.p;
-    }
+    float4* image;
+    if (const int rc = resolveTarget(c, device_rgba, &image))
+        return rc;
+    const PlanePair& history = c->temporal[c->temporalNewest];
     const dim3 lin((n + 255u) / 256u);
     if (prm->iterations == 0u) { // no filtering, no demodulation: pt_resolve's image, or the mean
         if (temporal) // ... over the history: d times the current albedo
-            hipLaunchKernelGGL(k_temporal_resolve, lin, dim3(256), 0, c->stream, c->temporalColour[c->temporalNewest].p, c->guideAlbedoHits.p,
-                (float4*)device_rgba, n, (float)c->guideSpp, tonemapped ? 1u : 0u, c->camera.relativeAperture, c->camera.shutterTime, c->camera.ISO);
+            hipLaunchKernelGGL(k_temporal_resolve, lin, dim3(256), 0, c->stream, history[0], c->guides[0], image, n, (float)c->guideSpp, tonemapped ? 1u : 0u,
+                c->camera.relativeAperture, c->camera.shutterTime, c->camera.ISO);
         else if (tonemapped)
-            hipLaunchKernelGGL(k_resolve, lin, dim3(256), 0, c->stream, c->accum, (float4*)device_rgba, n, (float)c->spp, c->camera.relativeAperture,
-                c->camera.shutterTime, c->camera.ISO);
+            launchResolve(c, image);
         else
-            hipLaunchKernelGGL(k_denoise_mean, lin, dim3(256), 0, c->stream, c->accum, (float4*)device_rgba, n, (float)c->spp);
+            hipLaunchKernelGGL(k_denoise_mean, lin, dim3(256), 0, c->stream, c->accum, image, n, (float)c->spp);
         HIPCHK(c, hipGetLastError());
         return PT_OK;
     }
@@ -1426,14 +1309,14 @@ int pt_denoise_device(pt_ctx* c, const pt_denoise_params* prm, void* device_rgba
         HIPCHK(c, c->denoiseGuide.alloc(n));
     }
     if (temporal)
-        hipLaunchKernelGGL(k_denoise_prepare_temporal, lin, dim3(256), 0, c->stream, c->temporalColour[c->temporalNewest].p, c->guideNormalDepth.p,
-            c->denoiseColour[0].p, c->denoiseGuide.p, n, (float)c->guideSpp);
+        hipLaunchKernelGGL(k_denoise_prepare_temporal, lin, dim3(256), 0, c->stream, history[0], c->guides[1], c->denoiseColour[0].p, c->denoiseGuide.p, n,
+            (float)c->guideSpp);
     else
-        hipLaunchKernelGGL(k_denoise_prepare, lin, dim3(256), 0, c->stream, c->accum, c->guideAlbedoHits.p, c->guideNormalDepth.p, c->denoiseColour[0].p,
-            c->denoiseGuide.p, n, (float)c->spp, (float)c->guideSpp);
+        hipLaunchKernelGGL(k_denoise_prepare, lin, dim3(256), 0, c->stream, c->accum, c->guides[0], c->guides[1], c->denoiseColour[0].p, c->denoiseGuide.p, n,
+            (float)c->spp, (float)c->guideSpp);
     AtrousArgs a {};
     a.guide = c->denoiseGuide.p;
-    a.albedoHits = c->guideAlbedoHits.p;
+    a.albedoHits = c->guides[0];
     a.width = W, a.height = H;
     a.kNormal = prm->k_normal > 0.f ? prm->k_normal : PT_DENOISE_DEFAULT_K_NORMAL;
     a.invSigmaDepth = 1.0f / (prm->sigma_depth > 0.f ? prm->sigma_depth : PT_DENOISE_DEFAULT_SIGMA_DEPTH);
@@ -1444,7 +1327,7 @@ int pt_denoise_device(pt_ctx* c, const pt_denoise_params* prm, void* device_rgba
     for (uint32_t i = 0; i < prm->iterations; i++) {
         const bool last = i + 1u == prm->iterations;
         a.colour = c->denoiseColour[i & 1u].p;
-        a.out = last ? (float4*)device_rgba : c->denoiseColour[(i + 1u) & 1u].p;
+        a.out = last ? image : c->denoiseColour[(i + 1u) & 1u].p;
         a.step = 1 << i;
         a.invSigmaLum = 1.0f / (sigmaLum * std::ldexp(1.0f, -(int)i));
         a.mode = !last ? ATROUS_MORE : (tonemapped ? ATROUS_LAST_TONEMAPPED : ATROUS_LAST_HDR);
@@ -1463,9 +1346,6 @@ int pt_denoise(pt_ctx* c, const pt_denoise_params* prm, float* rgba_out, float* 
     if (!c || !prm || !rgba_out)
         return PT_ERR_INVALID;
     HIPCHK(c, hipSetDevice(c->device));
-    for (hipEvent_t& ev : c->evDenoise)
-        if (!ev)
-            HIPCHK(c, hipEventCreate(&ev));
     HIPCHK(c, hipEventRecord(c->evDenoise[0], c->stream));
     int rc = pt_denoise_device(c, prm, nullptr);
     if (rc)
@@ -1484,8 +1364,8 @@ int pt_set_sample_base(pt_ctx* c, uint32_t base)
 {
     if (!c)
         return PT_ERR_INVALID;
-    if (parityMode(c) || c->cfg.max_active_rays != 0)
-        return fail(c, PT_ERR_UNSUPPORTED, "pt_set_sample_base: the fixed schedule with PT_RNG_COUNTER only (not in parity / refill mode)");
+    if (const int rc = fixedScheduleOnly(c, "pt_set_sample_base"))
+        return rc;
     c->sampleBase = base;
     return PT_OK;
 }
@@ -1494,19 +1374,11 @@ uint32_t pt_sample_base(const pt_ctx* c) { return c ? c->sampleBase : 0; }
 
 namespace {
 
-// the two history sets: allocated (zeroed) at the first temporal call
+// the two history sets: allocated (zeroed) at the first temporal call, both
 int ensureTemporal(pt_ctx* c)
 {
-    const size_t n = (size_t)c->cfg.width * c->cfg.height;
-    if (c->temporalColour[0].p)
-        return PT_OK;
-    for (int k = 0; k < 2; k++) {
-        HIPCHK(c, c->temporalColour[k].alloc(n));
-        HIPCHK(c, c->temporalGuide[k].alloc(n));
-        HIPCHK(c, hipMemsetAsync(c->temporalColour[k].p, 0, n * sizeof(float4), c->stream));
-        HIPCHK(c, hipMemsetAsync(c->temporalGuide[k].p, 0, n * sizeof(float4), c->stream));
-    }
-    return PT_OK;
+    int rc;
+    return (rc = c->temporal[0].ensure(c)) ? rc : c->temporal[1].ensure(c);
 }
 
 struct D3 {
@@ -1541,8 +1413,8 @@ int pt_temporal_accumulate(pt_ctx* c, const pt_temporal_params* prm)
         return rc;
     const int from = c->temporalNewest, to = from ^ 1;
     TemporalArgs a {};
-    a.accum = c->accum, a.albedoHits = c->guideAlbedoHits.p, a.normalDepth = c->guideNormalDepth.p;
-    a.outColour = c->temporalColour[to].p, a.outGuide = c->temporalGuide[to].p;
+    a.accum = c->accum, a.albedoHits = c->guides[0], a.normalDepth = c->guides[1];
+    a.outColour = c->temporal[to][0], a.outGuide = c->temporal[to][1];
     a.width = c->cfg.width, a.height = c->cfg.height;
     a.spp = (float)c->spp, a.gspp = (float)c->guideSpp;
     a.kNormal = prm->k_normal > 0.f ? prm->k_normal : PT_DENOISE_DEFAULT_K_NORMAL;
@@ -1557,14 +1429,14 @@ int pt_temporal_accumulate(pt_ctx* c, const pt_temporal_params* prm)
         const D3 uv = crossD(u, v), vs = crossD(v, s0), su = crossD(s0, u);
         const double det = s0.x * uv.x + s0.y * uv.y + s0.z * uv.z;
         if (det != 0.0 && std::isfinite(det)) { // (a degenerate camera has nothing to reproject into: the frame starts a history)
-            a.histColour = c->temporalColour[from].p, a.histGuide = c->temporalGuide[from].p;
+            a.histColour = c->temporal[from][0], a.histGuide = c->temporal[from][1];
             a.histEye = xyz(h.eye);
             a.rowLambda = scaledToV3(uv, 1.0 / det), a.rowAlpha = scaledToV3(vs, 1.0 / det), a.rowBeta = scaledToV3(su, 1.0 / det);
         }
     }
     const dim3 grid((a.width + kTemporalTileW - 1) / kTemporalTileW, (a.height + kTemporalTileH - 1) / kTemporalTileH), block(kTemporalTileW, kTemporalTileH);
     if (c->motionSet || c->vertexMotionSet) { // the history is met where the surfaces were (the two sums are there: the setters made them)
-        a.motion = c->guideMotion.p, a.prevNormal = c->guidePrevNormal.p;
+        a.motion = c->motionGuides[0], a.prevNormal = c->motionGuides[1];
         hipLaunchKernelGGL(k_temporal<true>, grid, block, 0, c->stream, a);
     } else
         hipLaunchKernelGGL(k_temporal<false>, grid, block, 0, c->stream, a);
@@ -1591,16 +1463,9 @@ int pt_read_temporal(pt_ctx* c, float* colour_count, float* normal_depth)
     if (!c)
         return PT_ERR_INVALID;
     HIPCHK(c, hipSetDevice(c->device));
-    int rc = ensureTemporal(c);
-    if (rc)
+    if (const int rc = ensureTemporal(c))
         return rc;
-    const size_t bytes = (size_t)c->cfg.width * c->cfg.height * sizeof(float4);
-    if (colour_count)
-        HIPCHK(c, hipMemcpyAsync(colour_count, c->temporalColour[c->temporalNewest].p, bytes, hipMemcpyDeviceToHost, c->stream));
-    if (normal_depth)
-        HIPCHK(c, hipMemcpyAsync(normal_depth, c->temporalGuide[c->temporalNewest].p, bytes, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return PT_OK;
+    return c->temporal[c->temporalNewest].read(c, colour_count, normal_depth);
 }
 
 int pt_write_temporal(pt_ctx* c, const float* colour_count, const float* normal_depth, const pt_camera* made_under)
@@ -1608,13 +1473,9 @@ int pt_write_temporal(pt_ctx* c, const float* colour_count, const float* normal_
     if (!c || !colour_count || !normal_depth || !made_under)
         return PT_ERR_INVALID;
     HIPCHK(c, hipSetDevice(c->device));
-    int rc = ensureTemporal(c);
-    if (rc)
+    int rc;
+    if ((rc = ensureTemporal(c)) || (rc = c->temporal[c->temporalNewest].write(c, colour_count, normal_depth)))
         return rc;
-    const size_t bytes = (size_t)c->cfg.width * c->cfg.height * sizeof(float4);
-    HIPCHK(c, hipMemcpyAsync(c->temporalColour[c->temporalNewest].p, colour_count, bytes, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->temporalGuide[c->temporalNewest].p, normal_depth, bytes, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
     auto f4 = [](const float* p) { return make_float4(p[0], p[1], p[2], 0.f); };
     c->temporalCamera = CameraDev {};
     c->temporalCamera.eye = f4(made_under->eyePoint), c->temporalCamera.screen = f4(made_under->screenPoint);
@@ -1623,27 +1484,23 @@ int pt_write_temporal(pt_ctx* c, const float* colour_count, const float* normal_
     return PT_OK;
 }
 
-void* pt_temporal_device_ptr(pt_ctx* c, int which)
-{
-    if (!c || which < 0 || which > 1)
-        return nullptr;
-    return which == 0 ? (void*)c->temporalColour[c->temporalNewest].p : (void*)c->temporalGuide[c->temporalNewest].p;
-}
+void* pt_temporal_device_ptr(pt_ctx* c, int which) { return c && (which == 0 || which == 1) ? (void*)c->temporal[c->temporalNewest][which] : nullptr; }
 
 // ---- instance motion (k_guides<1>, k_temporal<true>) --------------------------------------------
 
 namespace {
 
-// the two motion sums: allocated (zeroed) at the first pt_set_instance_motion / pt_write_motion_guides
-int ensureMotionGuides(pt_ctx* c)
+// The motion records' way to the device, on the render stream: the first `count` of them into a table of at least `capacity` entries (grown behind a
+// synchronisation: a guide pass may still read the old one).  The host copy stays with the context.
+int uploadMotionRecords(pt_ctx* c, std::vector<MotionRecord>& records, size_t capacity, size_t count)
 {
-    const size_t n = (size_t)c->cfg.width * c->cfg.height;
-    if (c->guideMotion.p)
-        return PT_OK;
-    HIPCHK(c, c->guideMotion.alloc(n));
-    HIPCHK(c, c->guidePrevNormal.alloc(n));
-    HIPCHK(c, hipMemsetAsync(c->guideMotion.p, 0, n * sizeof(float4), c->stream));
-    HIPCHK(c, hipMemsetAsync(c->guidePrevNormal.p, 0, n * sizeof(float4), c->stream));
+    if (c->motionRecords.n < capacity) {
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        HIPCHK(c, c->motionRecords.alloc(capacity));
+    }
+    c->motionHost = std::move(records);
+    if (count)
+        HIPCHK(c, hipMemcpyAsync(c->motionRecords.p, c->motionHost.data(), count * sizeof(MotionRecord), hipMemcpyHostToDevice, c->stream));
     return PT_OK;
 }
 
@@ -1679,15 +1536,9 @@ int makeVertexTables(pt_ctx* c, bool withMotion, std::vector<MotionRecord>& reco
 int commitVertexTables(pt_ctx* c, bool withMotion, std::vector<MotionRecord>& records, std::vector<float4>& rows)
 {
     const pt_ctx::DynamicSet& d = c->dyn[c->active];
-    if (!withMotion) {
-        const size_t need = std::max<size_t>(std::max<size_t>(d.numTopNodes, records.size()), 1);
-        if (c->motionRecords.n < need) {
-            HIPCHK(c, hipStreamSynchronize(c->stream));
-            HIPCHK(c, c->motionRecords.alloc(need));
-        }
-        c->motionHost = std::move(records);
-        HIPCHK(c, hipMemcpyAsync(c->motionRecords.p, c->motionHost.data(), c->motionHost.size() * sizeof(MotionRecord), hipMemcpyHostToDevice, c->stream));
-    }
+    int rc;
+    if (!withMotion && (rc = uploadMotionRecords(c, records, std::max<size_t>(std::max<size_t>(d.numTopNodes, records.size()), 1), records.size())))
+        return rc;
     if (c->vertexRows.n < rows.size()) {
         HIPCHK(c, hipStreamSynchronize(c->stream));
         HIPCHK(c, c->vertexRows.alloc(rows.size() + rows.size() / 8));
@@ -1704,8 +1555,8 @@ int pt_set_instance_motion(pt_ctx* c, const float* prevInv, uint32_t nTop)
     return guarded(c, "pt_set_instance_motion", [&]() -> int {
     if (!c)
         return PT_ERR_INVALID;
-    if (parityMode(c) || c->cfg.max_active_rays != 0)
-        return fail(c, PT_ERR_UNSUPPORTED, "pt_set_instance_motion: the fixed schedule with PT_RNG_COUNTER only (not in parity / refill mode)");
+    if (const int rc = fixedScheduleOnly(c, "pt_set_instance_motion"))
+        return rc;
     if (!c->haveDynamic)
         return fail(c, PT_ERR_STATE, "pt_set_instance_motion: no dynamic state is active yet (pt_upload_dynamic)");
     if (c->guideSpp != 0)
@@ -1750,15 +1601,8 @@ int pt_set_instance_motion(pt_ctx* c, const float* prevInv, uint32_t nTop)
     std::vector<float4> rows;
     if (c->vertexMotionSet && (rc = makeVertexTables(c, true, records, rows, "pt_set_instance_motion")))
         return rc;
-    if ((rc = ensureMotionGuides(c)))
+    if ((rc = c->motionGuides.ensure(c)) || (rc = uploadMotionRecords(c, records, std::max<size_t>(nTop, 1), nInst))) // n_top entries: never fewer than the state has instances
         return rc;
-    if (c->motionRecords.n < std::max<size_t>(nTop, 1)) { // n_top entries: never fewer than the state has instances
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        HIPCHK(c, c->motionRecords.alloc(std::max<size_t>(nTop, 1)));
-    }
-    c->motionHost = std::move(records);
-    if (nInst)
-        HIPCHK(c, hipMemcpyAsync(c->motionRecords.p, c->motionHost.data(), nInst * sizeof(MotionRecord), hipMemcpyHostToDevice, c->stream));
     c->motionSet = true;
     c->motionMoving = moving;
     if (c->vertexMotionSet && (rc = commitVertexTables(c, true, c->motionHost, rows)))
@@ -1780,8 +1624,8 @@ int pt_set_vertex_motion(pt_ctx* c, int enable)
     return guarded(c, "pt_set_vertex_motion", [&]() -> int {
     if (!c)
         return PT_ERR_INVALID;
-    if (parityMode(c) || c->cfg.max_active_rays != 0)
-        return fail(c, PT_ERR_UNSUPPORTED, "pt_set_vertex_motion: the fixed schedule with PT_RNG_COUNTER only (not in parity / refill mode)");
+    if (const int rc = fixedScheduleOnly(c, "pt_set_vertex_motion"))
+        return rc;
     if (!c->haveDynamic)
         return fail(c, PT_ERR_STATE, "pt_set_vertex_motion: no dynamic state is active yet (pt_upload_dynamic)");
     if (c->guideSpp != 0)
@@ -1808,7 +1652,7 @@ int pt_set_vertex_motion(pt_ctx* c, int enable)
     if (c->motionSet)
         records = c->motionHost;
     int rc = makeVertexTables(c, c->motionSet, records, rows, "pt_set_vertex_motion");
-    if (rc || (rc = ensureMotionGuides(c)))
+    if (rc || (rc = c->motionGuides.ensure(c)))
         return rc;
     if (deformed) {
         if (c->fatThen.n < cur.numTris) {
@@ -1856,16 +1700,7 @@ int pt_read_motion_guides(pt_ctx* c, float* motion, float* prevNormal)
     if (!c)
         return PT_ERR_INVALID;
     HIPCHK(c, hipSetDevice(c->device));
-    int rc = ensureMotionGuides(c);
-    if (rc)
-        return rc;
-    const size_t bytes = (size_t)c->cfg.width * c->cfg.height * sizeof(float4);
-    if (motion)
-        HIPCHK(c, hipMemcpyAsync(motion, c->guideMotion.p, bytes, hipMemcpyDeviceToHost, c->stream));
-    if (prevNormal)
-        HIPCHK(c, hipMemcpyAsync(prevNormal, c->guidePrevNormal.p, bytes, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return PT_OK;
+    return c->motionGuides.read(c, motion, prevNormal);
 }
 
 int pt_write_motion_guides(pt_ctx* c, const float* motion, const float* prevNormal)
@@ -1873,22 +1708,10 @@ int pt_write_motion_guides(pt_ctx* c, const float* motion, const float* prevNorm
     if (!c || !motion || !prevNormal)
         return PT_ERR_INVALID;
     HIPCHK(c, hipSetDevice(c->device));
-    int rc = ensureMotionGuides(c);
-    if (rc)
-        return rc;
-    const size_t bytes = (size_t)c->cfg.width * c->cfg.height * sizeof(float4);
-    HIPCHK(c, hipMemcpyAsync(c->guideMotion.p, motion, bytes, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->guidePrevNormal.p, prevNormal, bytes, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return PT_OK;
+    return c->motionGuides.write(c, motion, prevNormal);
 }
 
-void* pt_motion_guides_device_ptr(pt_ctx* c, int which)
-{
-    if (!c || which < 0 || which > 1)
-        return nullptr;
-    return which == 0 ? (void*)c->guideMotion.p : (void*)c->guidePrevNormal.p;
-}
+void* pt_motion_guides_device_ptr(pt_ctx* c, int which) { return c && (which == 0 || which == 1) ? (void*)c->motionGuides[which] : nullptr; }
 
 // test hook, no device needed: the host conversion behind pt_set_instance_motion, entry by entry (24 floats each)
 int pt_debug_motion_records(const float* prevInv, const float* curInv, uint32_t n, float* out24)
@@ -2007,6 +1830,38 @@ int pt_reduce_accum(pt_ctx* c, void* nccl_comm, int root)
 
 // ---- kernel-granular hooks ---------------------------------------------------------------------
 
+namespace {
+
+// queue entries read back, as the hooks' callers see them: rays (the pixel is the bits of the origin's w; any output may be null) ...
+void unpackRays(const std::vector<float4>& o, const std::vector<float4>& d, float* ox, float* oy, float* oz, float* dx, float* dy, float* dz, uint32_t* pixel)
+{
+    for (size_t i = 0; i < o.size(); i++) {
+        if (ox) ox[i] = o[i].x;
+        if (oy) oy[i] = o[i].y;
+        if (oz) oz[i] = o[i].z;
+        if (dx) dx[i] = d[i].x;
+        if (dy) dy[i] = d[i].y;
+        if (dz) dz[i] = d[i].z;
+        if (pixel)
+            std::memcpy(&pixel[i], &o[i].w, 4);
+    }
+}
+
+// ... and closest-hit records (the primitive is the bits of w; the instance is reported as its top-level leaf)
+void unpackHits(const pt_ctx* c, const std::vector<float4>& h, const std::vector<int32_t>& in, pt_hits_soa* hits)
+{
+    const std::vector<uint32_t>& top = c->dyn[c->active].instanceTopNode;
+    for (size_t i = 0; i < h.size(); i++) {
+        hits->t[i] = h[i].x, hits->u[i] = h[i].y, hits->v[i] = h[i].z;
+        int32_t prim;
+        std::memcpy(&prim, &h[i].w, 4);
+        hits->prim[i] = prim;
+        hits->inst[i] = (in[i] >= 0 && (size_t)in[i] < top.size()) ? (int32_t)top[in[i]] : -1;
+    }
+}
+
+} // namespace
+
 int pt_intersect(pt_ctx* c, const pt_rays_soa* rays, uint32_t n, int any_hit, pt_hits_soa* hits, uint32_t repeat, float* ms_out)
 {
     return guarded(c, "pt_intersect", [&]() -> int {
@@ -2028,75 +1883,61 @@ int pt_intersect(pt_ctx* c, const pt_rays_soa* rays, uint32_t n, int any_hit, pt
     DevBuf<int32_t> dI;
     DevBuf<uint32_t> dOcc;
     DevBuf<Control> dCtl;
-    hipError_t e = hipSuccess;
-    auto chk = [&](hipError_t x) {
-        if (e == hipSuccess)
-            e = x;
-    };
-    chk(dO.alloc(n)), chk(dD.alloc(n)), chk(dC.alloc(n)), chk(dH.alloc(n)), chk(dI.alloc(n)), chk(dOcc.alloc(n)), chk(dAcc.alloc(1)), chk(dCtl.alloc(1));
-    if (e == hipSuccess) {
-        chk(hipMemcpy(dO.p, hO.data(), n * sizeof(float4), hipMemcpyHostToDevice));
-        chk(hipMemcpy(dD.p, hD.data(), n * sizeof(float4), hipMemcpyHostToDevice));
-        chk(hipMemcpy(dC.p, hC.data(), n * sizeof(float4), hipMemcpyHostToDevice));
-        chk(hipMemsetAsync(dAcc.p, 0, sizeof(float4), c->stream));
-        // sentinels: an entry no lane wrote comes back as t = NaN (closest hit; a miss is +inf) or as verdict -1 (any hit; 0 / 1 otherwise)
-        chk(hipMemsetAsync(dH.p, 0xFF, n * sizeof(float4), c->stream));
-        chk(hipMemsetAsync(dI.p, 0xFF, n * sizeof(int32_t), c->stream));
-        chk(hipMemsetAsync(dOcc.p, 0xFF, n * sizeof(uint32_t), c->stream));
-    }
+    HIPCHK(c, allocPlanes(dO, dD, dC, n));
+    HIPCHK(c, dH.alloc(n));
+    HIPCHK(c, dI.alloc(n));
+    HIPCHK(c, dOcc.alloc(n));
+    HIPCHK(c, dAcc.alloc(1));
+    HIPCHK(c, dCtl.alloc(1));
+    HIPCHK(c, hipMemcpy(dO.p, hO.data(), n * sizeof(float4), hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(dD.p, hD.data(), n * sizeof(float4), hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(dC.p, hC.data(), n * sizeof(float4), hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemsetAsync(dAcc.p, 0, sizeof(float4), c->stream));
+    // sentinels: an entry no lane wrote comes back as t = NaN (closest hit; a miss is +inf) or as verdict -1 (any hit; 0 / 1 otherwise)
+    HIPCHK(c, hipMemsetAsync(dH.p, 0xFF, n * sizeof(float4), c->stream));
+    HIPCHK(c, hipMemsetAsync(dI.p, 0xFF, n * sizeof(int32_t), c->stream));
+    HIPCHK(c, hipMemsetAsync(dOcc.p, 0xFF, n * sizeof(uint32_t), c->stream));
     float msTotal = 0;
     repeat = std::max(repeat, 1u);
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    chk(hipEventCreate(&e0));
-    chk(hipEventCreate(&e1));
-    for (uint32_t r = 0; r < repeat && e == hipSuccess; r++) {
+    Event e0, e1;
+    HIPCHK(c, e0.create(true));
+    HIPCHK(c, e1.create(true));
+    for (uint32_t r = 0; r < repeat; r++) {
         Control ctl {}; // a control block of its own: n entries in pass 0's queue, cursors at zero
         ctl.extCount[0] = ctl.shadowCount[0] = n;
-        chk(hipMemcpyAsync(dCtl.p, &ctl, sizeof(ctl), hipMemcpyHostToDevice, c->stream));
-        chk(hipStreamSynchronize(c->stream)); // `ctl` is a stack object
+        HIPCHK(c, hipMemcpyAsync(dCtl.p, &ctl, sizeof(ctl), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream)); // `ctl` is a stack object
         TraceArgs a = traceArgsBase(c);
         a.parityShadow = 0;
         a.rayO = dO.p, a.rayD = dD.p, a.rayC = dC.p;
         a.hit = dH.p, a.inst = dI.p, a.accum = AccumView { dAcc.p, nullptr, nullptr, 0u }, a.occluded = dOcc.p;
         a.ctl = dCtl.p, a.pass = 0;
-        chk(hipEventRecord(e0, c->stream));
+        HIPCHK(c, hipEventRecord(e0, c->stream));
         if (c->dyn[c->active].packetOk && (c->packetUse & 4u))
             launchPacket(c, any_hit != 0, a);
         else
             launchTrace(c, any_hit != 0, a);
-        chk(hipEventRecord(e1, c->stream));
-        chk(hipStreamSynchronize(c->stream));
-        chk(hipGetLastError());
+        HIPCHK(c, hipEventRecord(e1, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        HIPCHK(c, hipGetLastError());
         float ms = 0;
-        chk(hipEventElapsedTime(&ms, e0, e1));
+        HIPCHK(c, hipEventElapsedTime(&ms, e0, e1));
         msTotal += ms;
     }
-    if (e == hipSuccess) {
-        if (any_hit) {
-            std::vector<uint32_t> occ(n);
-            chk(hipMemcpy(occ.data(), dOcc.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
-            for (uint32_t i = 0; i < n; i++)
-                hits->prim[i] = (int32_t)occ[i];
-        } else {
-            std::vector<float4> h(n);
-            std::vector<int32_t> in(n);
-            chk(hipMemcpy(h.data(), dH.p, n * sizeof(float4), hipMemcpyDeviceToHost));
-            chk(hipMemcpy(in.data(), dI.p, n * sizeof(int32_t), hipMemcpyDeviceToHost));
-            for (uint32_t i = 0; i < n; i++) {
-                hits->t[i] = h[i].x, hits->u[i] = h[i].y, hits->v[i] = h[i].z;
-                int32_t prim;
-                std::memcpy(&prim, &h[i].w, 4);
-                hits->prim[i] = prim;
-                hits->inst[i] = (in[i] >= 0 && (size_t)in[i] < c->dyn[c->active].instanceTopNode.size()) ? (int32_t)c->dyn[c->active].instanceTopNode[in[i]] : -1;
-            }
-        }
+    if (any_hit) {
+        std::vector<uint32_t> occ(n);
+        HIPCHK(c, hipMemcpy(occ.data(), dOcc.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        for (uint32_t i = 0; i < n; i++)
+            hits->prim[i] = (int32_t)occ[i];
+    } else {
+        std::vector<float4> h(n);
+        std::vector<int32_t> in(n);
+        HIPCHK(c, hipMemcpy(h.data(), dH.p, n * sizeof(float4), hipMemcpyDeviceToHost));
+        HIPCHK(c, hipMemcpy(in.data(), dI.p, n * sizeof(int32_t), hipMemcpyDeviceToHost));
+        unpackHits(c, h, in, hits);
     }
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-    dO.release(), dD.release(), dC.release(), dH.release(), dI.release(), dOcc.release(), dAcc.release(), dCtl.release();
     if (ms_out)
         *ms_out = msTotal / (float)repeat;
-    HIPCHK(c, e);
     return PT_OK;
     });
 }
@@ -2123,16 +1964,7 @@ int pt_gen_rays(pt_ctx* c, uint32_t sample, uint32_t n, float* ox, float* oy, fl
     HIPCHK(c, hipMemcpyAsync(d.data(), c->rays[0].d.p, n * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemsetAsync(c->control.p, 0, sizeof(Control), c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    for (uint32_t i = 0; i < n; i++) {
-        if (ox) ox[i] = o[i].x;
-        if (oy) oy[i] = o[i].y;
-        if (oz) oz[i] = o[i].z;
-        if (dx) dx[i] = d[i].x;
-        if (dy) dy[i] = d[i].y;
-        if (dz) dz[i] = d[i].z;
-        if (pixel)
-            std::memcpy(&pixel[i], &o[i].w, 4);
-    }
+    unpackRays(o, d, ox, oy, oz, dx, dy, dz, pixel);
     return PT_OK;
     });
 }
@@ -2177,22 +2009,8 @@ int pt_primary_pass(pt_ctx* c, uint32_t sample, uint32_t batch, uint32_t n, floa
     HIPCHK(c, hipMemsetAsync(c->control.p, 0, sizeof(Control), c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     HIPCHK(c, hipGetLastError());
-    const std::vector<uint32_t>& top = c->dyn[c->active].instanceTopNode;
-    for (uint32_t i = 0; i < n; i++) {
-        if (ox) ox[i] = o[i].x;
-        if (oy) oy[i] = o[i].y;
-        if (oz) oz[i] = o[i].z;
-        if (dx) dx[i] = d[i].x;
-        if (dy) dy[i] = d[i].y;
-        if (dz) dz[i] = d[i].z;
-        if (pixel)
-            std::memcpy(&pixel[i], &o[i].w, 4);
-        hits->t[i] = h[i].x, hits->u[i] = h[i].y, hits->v[i] = h[i].z;
-        int32_t prim;
-        std::memcpy(&prim, &h[i].w, 4);
-        hits->prim[i] = prim;
-        hits->inst[i] = (in[i] >= 0 && (size_t)in[i] < top.size()) ? (int32_t)top[in[i]] : -1;
-    }
+    unpackRays(o, d, ox, oy, oz, dx, dy, dz, pixel);
+    unpackHits(c, h, in, hits);
     return PT_OK;
     });
 }
@@ -2232,36 +2050,30 @@ int pt_shade_batch(pt_ctx* c, pt_shade_batch_io* io)
         if (prim >= 0 && (hI[i] < 0 || (uint32_t)prim >= c->st->host.numTris))
             return fail(c, PT_ERR_INVALID, "pt_shade_batch: entry %u has an invalid prim/inst", i);
     }
-    RayQueueBuf in, out, stagedDummy;
+    RayQueueBuf in, out;
     ShadowQueueBuf sh;
     DevBuf<float4> dH, dAcc;
     DevBuf<int32_t> dI;
     DevBuf<uint32_t> dCtl;
-    hipError_t e = hipSuccess;
-    auto chk = [&](hipError_t x) {
-        if (e == hipSuccess)
-            e = x;
-    };
-    chk(in.o.alloc(n)), chk(in.d.alloc(n)), chk(in.thr.alloc(n)), chk(out.o.alloc(n)), chk(out.d.alloc(n)), chk(out.thr.alloc(n));
-    chk(sh.o.alloc(n)), chk(sh.d.alloc(n)), chk(sh.c.alloc(n)), chk(dH.alloc(n)), chk(dI.alloc(n)), chk(dCtl.alloc(5));
-    const size_t npix = (size_t)c->cfg.width * c->cfg.height;
-    chk(dAcc.alloc(npix));
+    HIPCHK(c, in.alloc(n));
+    HIPCHK(c, out.alloc(n));
+    HIPCHK(c, sh.alloc(n));
+    HIPCHK(c, dH.alloc(n));
+    HIPCHK(c, dI.alloc(n));
+    HIPCHK(c, dCtl.alloc(5));
+    HIPCHK(c, dAcc.alloc((size_t)c->cfg.width * c->cfg.height));
     // per-entry outputs are needed, so every entry is shaded as its own 1-entry queue slice
-    (void)stagedDummy;
-    if (e == hipSuccess) {
-        chk(hipMemcpy(in.o.p, hO.data(), n * sizeof(float4), hipMemcpyHostToDevice));
-        chk(hipMemcpy(in.d.p, hD.data(), n * sizeof(float4), hipMemcpyHostToDevice));
-        chk(hipMemcpy(in.thr.p, hT.data(), n * sizeof(float4), hipMemcpyHostToDevice));
-        chk(hipMemcpy(dH.p, hH.data(), n * sizeof(float4), hipMemcpyHostToDevice));
-        chk(hipMemcpy(dI.p, hI.data(), n * sizeof(int32_t), hipMemcpyHostToDevice));
-    }
-    std::vector<float4> acc(npix);
+    HIPCHK(c, hipMemcpy(in.o.p, hO.data(), n * sizeof(float4), hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(in.d.p, hD.data(), n * sizeof(float4), hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(in.thr.p, hT.data(), n * sizeof(float4), hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(dH.p, hH.data(), n * sizeof(float4), hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(dI.p, hI.data(), n * sizeof(int32_t), hipMemcpyHostToDevice));
     FrameParams fp = frameParams(c, io->sample);
-    for (uint32_t i = 0; i < n && e == hipSuccess; i++) {
+    for (uint32_t i = 0; i < n; i++) {
         // pixel-indexed accumulator: clear only the touched pixel
         uint32_t ctl[5] = { 1, 0, 0, 0, 0 }; // inCount, outCount, shadowCount, shadeHits, deposits
-        chk(hipMemcpyAsync(dCtl.p, ctl, sizeof(ctl), hipMemcpyHostToDevice, c->stream));
-        chk(hipMemsetAsync(dAcc.p + io->pixel[i], 0, sizeof(float4), c->stream));
+        HIPCHK(c, hipMemcpyAsync(dCtl.p, ctl, sizeof(ctl), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemsetAsync(dAcc.p + io->pixel[i], 0, sizeof(float4), c->stream));
         ShadeArgs a {};
         a.sc = c->scene;
         a.fp = fp;
@@ -2278,40 +2090,35 @@ int pt_shade_batch(pt_ctx* c, pt_shade_batch_io* io)
             hipLaunchKernelGGL((k_shade<false, false>), dim3(1), dim3(64), 0, c->stream, a);
         uint32_t back[4];
         float4 px;
-        chk(hipMemcpyAsync(back, dCtl.p, sizeof(back), hipMemcpyDeviceToHost, c->stream));
-        chk(hipMemcpyAsync(&px, dAcc.p + io->pixel[i], sizeof(float4), hipMemcpyDeviceToHost, c->stream));
-        chk(hipStreamSynchronize(c->stream));
+        HIPCHK(c, hipMemcpyAsync(back, dCtl.p, sizeof(back), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(&px, dAcc.p + io->pixel[i], sizeof(float4), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
         io->out_alive[i] = back[1];
         io->shadow_alive[i] = back[2];
         io->radiance[3 * i] = px.x, io->radiance[3 * i + 1] = px.y, io->radiance[3 * i + 2] = px.z;
     }
-    if (e == hipSuccess) {
-        std::vector<float4> o(n), d(n), t(n), so(n), sd(n), sc(n);
-        chk(hipMemcpy(o.data(), out.o.p, n * sizeof(float4), hipMemcpyDeviceToHost));
-        chk(hipMemcpy(d.data(), out.d.p, n * sizeof(float4), hipMemcpyDeviceToHost));
-        chk(hipMemcpy(t.data(), out.thr.p, n * sizeof(float4), hipMemcpyDeviceToHost));
-        chk(hipMemcpy(so.data(), sh.o.p, n * sizeof(float4), hipMemcpyDeviceToHost));
-        chk(hipMemcpy(sd.data(), sh.d.p, n * sizeof(float4), hipMemcpyDeviceToHost));
-        chk(hipMemcpy(sc.data(), sh.c.p, n * sizeof(float4), hipMemcpyDeviceToHost));
-        for (uint32_t i = 0; i < n; i++) {
-            if (io->out_alive[i]) {
-                io->nox[i] = o[i].x, io->noy[i] = o[i].y, io->noz[i] = o[i].z;
-                io->ndx[i] = d[i].x, io->ndy[i] = d[i].y, io->ndz[i] = d[i].z;
-                io->nthr_r[i] = t[i].x, io->nthr_g[i] = t[i].y, io->nthr_b[i] = t[i].z;
-                uint32_t fl;
-                std::memcpy(&fl, &d[i].w, 4);
-                io->nflags[i] = fl & 0xFFu;
-            }
-            if (io->shadow_alive[i]) {
-                io->sox[i] = so[i].x, io->soy[i] = so[i].y, io->soz[i] = so[i].z, io->slen[i] = so[i].w;
-                io->sdx[i] = sd[i].x, io->sdy[i] = sd[i].y, io->sdz[i] = sd[i].z;
-                io->sc_r[i] = sc[i].x, io->sc_g[i] = sc[i].y, io->sc_b[i] = sc[i].z;
-            }
+    std::vector<float4> o(n), d(n), t(n), so(n), sd(n), sc(n);
+    HIPCHK(c, hipMemcpy(o.data(), out.o.p, n * sizeof(float4), hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(d.data(), out.d.p, n * sizeof(float4), hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(t.data(), out.thr.p, n * sizeof(float4), hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(so.data(), sh.o.p, n * sizeof(float4), hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(sd.data(), sh.d.p, n * sizeof(float4), hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(sc.data(), sh.c.p, n * sizeof(float4), hipMemcpyDeviceToHost));
+    for (uint32_t i = 0; i < n; i++) {
+        if (io->out_alive[i]) {
+            io->nox[i] = o[i].x, io->noy[i] = o[i].y, io->noz[i] = o[i].z;
+            io->ndx[i] = d[i].x, io->ndy[i] = d[i].y, io->ndz[i] = d[i].z;
+            io->nthr_r[i] = t[i].x, io->nthr_g[i] = t[i].y, io->nthr_b[i] = t[i].z;
+            uint32_t fl;
+            std::memcpy(&fl, &d[i].w, 4);
+            io->nflags[i] = fl & 0xFFu;
+        }
+        if (io->shadow_alive[i]) {
+            io->sox[i] = so[i].x, io->soy[i] = so[i].y, io->soz[i] = so[i].z, io->slen[i] = so[i].w;
+            io->sdx[i] = sd[i].x, io->sdy[i] = sd[i].y, io->sdz[i] = sd[i].z;
+            io->sc_r[i] = sc[i].x, io->sc_g[i] = sc[i].y, io->sc_b[i] = sc[i].z;
         }
     }
-    in.o.release(), in.d.release(), in.thr.release(), out.o.release(), out.d.release(), out.thr.release();
-    sh.o.release(), sh.d.release(), sh.c.release(), dH.release(), dI.release(), dCtl.release(), dAcc.release();
-    HIPCHK(c, e);
     return PT_OK;
     });
 }

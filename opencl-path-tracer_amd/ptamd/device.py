@@ -89,7 +89,8 @@ EXPORTS = ["pt_create", "pt_destroy", "pt_last_error", "pt_set_stream", "pt_uplo
            "pt_temporal_frames", "pt_read_temporal", "pt_write_temporal", "pt_temporal_device_ptr", "pt_set_instance_motion", "pt_instance_motion",
            "pt_read_motion_guides", "pt_write_motion_guides", "pt_motion_guides_device_ptr", "pt_debug_motion_records",
            "pt_set_vertex_motion", "pt_vertex_motion", "pt_debug_vertex_motion_rows", "pt_stats_get", "pt_stats_reset", "pt_profile_kernels", "pt_reduce_accum",
-           "pt_intersect", "pt_gen_rays", "pt_primary_pass", "pt_shade_batch", "pt_debug_quantise_node", "pt_debug_convert", "pt_debug_copy_bandwidth", "pt_debug_math_probe", "pt_version"]
+           "pt_intersect", "pt_gen_rays", "pt_primary_pass", "pt_shade_batch", "pt_debug_quantise_node", "pt_debug_convert", "pt_debug_copy_bandwidth", "pt_debug_math_probe", "pt_debug_live_resources",
+           "pt_version"]
 
 _lib = None
 
@@ -188,6 +189,16 @@ class PtError(RuntimeError):
 
 def _p(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+def live_resources():
+    """pt_debug_live_resources: (device allocations, pinned allocations, events, streams the library created) alive in this process -- no device needed."""
+    out = (C.c_uint32 * 4)()
+    lib().pt_debug_live_resources.argtypes = [C.POINTER(C.c_uint32)]
+    rc = lib().pt_debug_live_resources(out)
+    if rc != 0:
+        raise PtError(f"pt_debug_live_resources failed ({rc})")
+    return tuple(out)
 
 
 def debug_convert(flat, flags=0, rng_mode=RNG_COUNTER):
