@@ -360,14 +360,15 @@ void* pt_guides_device_ptr(pt_ctx* ctx, int which); /* 0 albedo_hits, 1 normal_d
 enum { PT_DENOISE_TONEMAPPED = 0, PT_DENOISE_HDR = 1 };
 /* What the filter starts from.  PT_DENOISE_INPUT_ACCUM: d0 = c / max(a, 1e-3) of the accumulator, as above.  PT_DENOISE_INPUT_TEMPORAL: d0 is the
  * d.rgb of the newest temporal history (below) instead; the guides and the re-modulating albedo stay the current frame's.  With iterations == 0 the
- * output is then d max(a, 1e-3), linear or through pt_resolve's tone curve.  PT_ERR_STATE when pt_temporal_frames is 0; any other value of `input`
+ * output is then d max(a, 1e-3), linear or through pt_resolve's tone curve.  PT_ERR_STATE when pt_temporal_frames is 0.
+ * PT_DENOISE_INPUT_TEMPORAL_VARIANCE: the same history, filtered under its luminance variance (TEMPORAL VARIANCE below).  Any other value of `input`
  * is PT_ERR_INVALID. */
-enum { PT_DENOISE_INPUT_ACCUM = 0, PT_DENOISE_INPUT_TEMPORAL = 1 };
+enum { PT_DENOISE_INPUT_ACCUM = 0, PT_DENOISE_INPUT_TEMPORAL = 1, PT_DENOISE_INPUT_TEMPORAL_VARIANCE = 2 };
 typedef struct {
     uint32_t iterations; /* 0..6; 0 = no filtering at all */
     uint32_t output; /* PT_DENOISE_TONEMAPPED (as pt_resolve) | PT_DENOISE_HDR (linear mean radiance) */
     float k_normal, sigma_depth, sigma_lum; /* 0 = the documented default */
-    uint32_t input; /* PT_DENOISE_INPUT_ACCUM (0, the default) | PT_DENOISE_INPUT_TEMPORAL */
+    uint32_t input; /* PT_DENOISE_INPUT_ACCUM (0, the default) | PT_DENOISE_INPUT_TEMPORAL | PT_DENOISE_INPUT_TEMPORAL_VARIANCE */
     uint32_t _reserved[2];
 } pt_denoise_params;
 /* host image out (width*height*4 floats); ms_out (optional): device ms of the filter's kernels (hipEvents), the copy to the host not included */
@@ -501,6 +502,52 @@ int pt_vertex_motion(const pt_ctx* ctx, uint32_t* deformed_out); /* 1 / 0: set o
 /* test hook, no device needed: the rows L for n invTransforms of 16 floats (column-major); out12: n x 12 floats.  A singular or non-finite matrix is
  * PT_ERR_INVALID, through pt_last_error(NULL). */
 int pt_debug_vertex_motion_rows(const float* inv_transforms, uint32_t n, float* out12);
+
+/* TEMPORAL VARIANCE: how noisy each pixel of the history still is, and a filter that is guided by it (SVGF's second half).  Opt-in: with the mode off,
+ * every entry point launches exactly the kernels it launches without this block and returns the same bits.
+ *
+ * With the mode on each history set holds one more plane, width*height floats: v, the population variance of the luminance samples the pixel's history
+ * stands for.  pt_temporal_accumulate computes colour_count and normal_depth with the arithmetic of TEMPORAL HISTORY (the same bits) and, per pixel,
+ *   l = L(d)                      Rec.709 luminance of the current frame's demodulated colour
+ *   no history, lambda <= 0 or Wsum < 1e-12:   v_out = 0
+ *   otherwise   mu = L(h),   v_h = sum w v_tap / Wsum   (the colour's own taps and weights),   alpha = 1 / N_out,
+ *               v_out = (1 - alpha) (v_h + alpha (l - mu)^2)
+ * -- Welford's update of the population variance, written for a running mean of weight 1 / N.  Every term is non-negative and nothing is subtracted but
+ * l - mu: the form cannot cancel in float32 (it is NOT E[l^2] - E[l]^2), and every quantity is a continuous function of the inputs.  The motion routes
+ * (INSTANCE MOTION, VERTEX MOTION) meet the plane at the taps they meet the colour at.
+ *
+ * pt_denoise / pt_denoise_device with input == PT_DENOISE_INPUT_TEMPORAL_VARIANCE filter the newest history like PT_DENOISE_INPUT_TEMPORAL does, with
+ * the luminance term moved from the relative one to a variance one as the history grows.  N = the history's count, V_0 = v / max(N, 1) (the variance of
+ * the history's MEAN), s(p) = clamp((N(p) - 1) / (full_history - 1), 0, 1); iteration i (FILTER's step, taps, k, e_n and e_z):
+ *   g(p)    = sqrt(sum G V_i(q) / sum G)    over the 3 x 3 neighbours at distance 1 inside the image, whatever the step; G = outer product of (1/4, 1/2, 1/4)
+ *   e_var   = |L_p - L_q| / (sigma_variance g(p) + relative_floor (max(L_p, L_q) + 1e-3)),   L_x = L(d_i(x))
+ *   e_plain = FILTER's e_l (sigma_lum of pt_denoise_params, the 2^-i factor and all)
+ *   e_l     = s(p) e_var + (1 - s(p)) e_plain
+ *   w       = k exp(-(e_n + e_z + e_l)),   d_{i+1}(p) = sum w d_i(q) / sum w,   V_{i+1}(p) = sum w^2 V_i(q) / (sum w)^2
+ * A history of one frame (s = 0) is filtered as PT_DENOISE_INPUT_TEMPORAL filters it; from full_history frames on the variance term acts alone.  The
+ * last iteration re-modulates and tone-maps as FILTER does; iterations == 0 gives PT_DENOISE_INPUT_TEMPORAL's output.  Defaults chosen on the 64 x 64
+ * Cornell box under a static camera, 1 spp per frame, against 256 spp (tests/test_variance_ref.py; the scan is in EXPERIMENTS.md).
+ *
+ * pt_set_temporal_variance refuses: PT_ERR_UNSUPPORTED in parity / refill mode; PT_ERR_INVALID for a negative or non-finite parameter and for a
+ * full_history below 2 (other than 0); PT_ERR_STATE while pt_temporal_frames() != 0, for setting and for forgetting alike -- reset the history first: a
+ * plane of zeros under counts above 1 would switch the filter off.  pt_temporal_reset keeps the mode set; pt_write_temporal zeroes the plane of the set
+ * it writes.  pt_read_temporal_variance / pt_write_temporal_variance: PT_ERR_STATE when the mode is off or there is no history; input ==
+ * PT_DENOISE_INPUT_TEMPORAL_VARIANCE: PT_ERR_STATE when the mode is off or pt_temporal_frames() == 0.  A refused call changes nothing.  The planes are
+ * allocated at the first temporal call with the mode on and freed by pt_destroy. */
+#define PT_VARIANCE_DEFAULT_SIGMA_VARIANCE 2.0f
+#define PT_VARIANCE_DEFAULT_RELATIVE_FLOOR 0.1f
+#define PT_VARIANCE_DEFAULT_FULL_HISTORY 16.0f
+typedef struct {
+    float sigma_variance; /* 0 = 2.0 */
+    float relative_floor; /* 0 = 0.1 */
+    float full_history; /* 0 = 16: the history length from which the variance term alone acts */
+    uint32_t _reserved[5];
+} pt_variance_params;
+int pt_set_temporal_variance(pt_ctx* ctx, const pt_variance_params* params); /* NULL: off */
+int pt_temporal_variance(const pt_ctx* ctx); /* 1 / 0 */
+int pt_read_temporal_variance(pt_ctx* ctx, float* out); /* host, width*height floats, of the newest set */
+int pt_write_temporal_variance(pt_ctx* ctx, const float* in); /* checkpoint restore: after pt_write_temporal, which zeroes the plane */
+void* pt_temporal_variance_device_ptr(pt_ctx* ctx); /* the newest set's plane; NULL while the mode is off and before the first temporal call with it on */
 
 /* ---- kernel-granular entry points (parity tests and micro-benchmarks) ------------------
  * Host SoA arrays in, host SoA arrays out; the scene must have been uploaded. */

@@ -374,6 +374,12 @@ struct pt_ctx {
     CameraDev temporalCamera {};
     uint32_t sampleBase = 0; // pt_set_sample_base: added to the sample index pt_render and pt_render_guides key the counter PRNG with
 
+    // temporal variance (include/ptamd.h): one more plane per history set, width * height floats -- the variance of the luminances the pixel's history
+    // stands for --, allocated (zeroed) at the first temporal call with the mode on.  The mode changes only while there is no history.
+    DevBuf<float> temporalVariance[2];
+    bool varianceSet = false;
+    float sigmaVariance = 0, relativeFloor = 0, fullHistory = 0; // pt_variance_params, defaults resolved
+
     // instance motion (include/ptamd.h): one record per instance of the ACTIVE dynamic state (indexed like its instance table, which is how the guide
     // pass meets a hit), and the two guide sums made from them -- (displacement.xyz, 0) and (normal then.xyz, 0), width * height float4 each, allocated at
     // the first pt_set_instance_motion / pt_write_motion_guides.  pt_frame_tick forgets the motion; pt_clear zeroes the sums and keeps it.

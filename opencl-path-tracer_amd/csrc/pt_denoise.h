@@ -289,4 +289,132 @@ __global__ void __launch_bounds__(256) k_atrous(AtrousArgs a)
     a.out[p] = make_float4(r, g, b, 1.0f);
 }
 
+// ---- variance-guided filter (pt_set_temporal_variance; include/ptamd.h, "temporal variance") ------
+struct AtrousVarArgs {
+    AtrousArgs f; // k_atrous' own; colour and out hold (d_i.rgb, V_i): the variance of d_i's luminance where k_atrous keeps the luminance itself
+    const float4* history; // (d.rgb, N) of the newest history set: s(p) comes from its count
+    float sigmaVariance, relativeFloor;
+    float invFullHistory; // 1 / (full_history - 1)
+};
+
+// One iteration of the filter over the temporal history, on k_atrous' tiles and with its taps, kernel and guide terms.  The luminance term moves from
+// k_atrous' relative one to a variance one as the pixel's history grows, s(p) = clamp((N(p) - 1) / (full_history - 1), 0, 1):
+//   e_l = s e_var + (1 - s) e_plain,   e_var = |L_p - L_q| / (sigma_variance g(p) + relative_floor (max(L_p, L_q) + 1e-3)),   e_plain = k_atrous' e_l
+//   g(p)^2 = the 3 x 3 binomial mean of V_i over the neighbours at distance 1 inside the image, whatever the step
+//   d_{i+1}(p) = sum w d_i(q) / sum w,   V_{i+1}(p) = sum w^2 V_i(q) / (sum w)^2
+// A tap stays two 16-byte loads: the luminance is recomputed per tap (three FMAs), the fourth component carries V.  STEP_IN_LDS: V is staged a second
+// time as a plane of floats, from which the 3 x 3 comes (the halo is at least 2) -- nine ds_read_b32 at [row][x + const], 32 consecutive dwords per lane
+// group and so on 32 different banks; the same reads out of the float4 image would be 16 bytes apart, four lanes to a bank (MI355X_MICROARCH.md, LDS).
+// Steps >= 4: nine adjacent 4-byte global reads beside the 50 16-byte ones.
+template <bool STEP_IN_LDS>
+__global__ void __launch_bounds__(256) k_atrous_var(AtrousVarArgs v)
+{
+    const AtrousArgs& a = v.f;
+    const int tx = threadIdx.x, ty = threadIdx.y;
+    const int x = blockIdx.x * kAtrousTileW + tx, y = blockIdx.y * kAtrousTileH + ty;
+    const int W = (int)a.width, H = (int)a.height;
+    __shared__ float4 ldsC[STEP_IN_LDS ? kAtrousLdsH * kAtrousLdsW : 1];
+    __shared__ float4 ldsG[STEP_IN_LDS ? kAtrousLdsH * kAtrousLdsW : 1];
+    __shared__ float ldsV[STEP_IN_LDS ? kAtrousLdsH * kAtrousLdsW : 1];
+    const int halo = 2 * a.step, pitch = kAtrousTileW + 2 * halo; // (the launch keeps halo <= kAtrousMaxHalo for this variant)
+    if constexpr (STEP_IN_LDS) {
+        const int rows = kAtrousTileH + 2 * halo, x0 = (int)blockIdx.x * kAtrousTileW - halo, y0 = (int)blockIdx.y * kAtrousTileH - halo;
+        for (int e = ty * kAtrousTileW + tx; e < rows * pitch; e += kAtrousTileW * kAtrousTileH) {
+            const int ly = e / pitch, lx = e - ly * pitch;
+            const int gx = x0 + lx, gy = y0 + ly;
+            float4 c = make_float4(0.f, 0.f, 0.f, 0.f), g = c; // outside the image: never read (the loops skip those)
+            if (gx >= 0 && gx < W && gy >= 0 && gy < H) {
+                c = a.colour[(size_t)gy * W + gx];
+                g = a.guide[(size_t)gy * W + gx];
+            }
+            ldsC[e] = c;
+            ldsG[e] = g;
+            ldsV[e] = c.w;
+        }
+        __syncthreads();
+    }
+    if (x >= W || y >= H)
+        return;
+    const size_t p = (size_t)y * W + x;
+    const float count = v.history[p].w;
+    float4 cp, gp;
+    if constexpr (STEP_IN_LDS) {
+        cp = ldsC[(ty + halo) * pitch + tx + halo];
+        gp = ldsG[(ty + halo) * pitch + tx + halo];
+    } else {
+        cp = a.colour[p];
+        gp = a.guide[p];
+    }
+    const float bin[3] = { 0.25f, 0.5f, 0.25f };
+    float nv = 0.f, nk = 0.f;
+#pragma unroll
+    for (int dy = -1; dy <= 1; dy++) {
+        const int qy = y + dy;
+        if (qy < 0 || qy >= H)
+            continue;
+#pragma unroll
+        for (int dx = -1; dx <= 1; dx++) {
+            const int qx = x + dx;
+            if (qx < 0 || qx >= W)
+                continue;
+            float vq;
+            if constexpr (STEP_IN_LDS)
+                vq = ldsV[(ty + halo + dy) * pitch + tx + halo + dx];
+            else
+                vq = a.colour[(size_t)qy * W + qx].w;
+            const float k = bin[dy + 1] * bin[dx + 1];
+            nv += k * vq, nk += k;
+        }
+    }
+    // (the centre counts with 1/4: nk >= 1/4)
+    const float sigmaG = v.sigmaVariance * sqrtf(nv / nk);
+    const float s = fminf(fmaxf((count - 1.0f) * v.invFullHistory, 0.0f), 1.0f);
+    const float lp = luminance709(cp.x, cp.y, cp.z);
+    const float kern[5] = { 1.0f / 16.0f, 1.0f / 4.0f, 3.0f / 8.0f, 1.0f / 4.0f, 1.0f / 16.0f };
+    float sr = 0.f, sg = 0.f, sb = 0.f, sv = 0.f, sw = 0.f;
+#pragma unroll
+    for (int dy = -2; dy <= 2; dy++) {
+        const int qy = y + dy * a.step;
+        if (qy < 0 || qy >= H)
+            continue;
+#pragma unroll
+        for (int dx = -2; dx <= 2; dx++) {
+            const int qx = x + dx * a.step;
+            if (qx < 0 || qx >= W)
+                continue;
+            float4 cq, gq;
+            if constexpr (STEP_IN_LDS) {
+                const int e = (ty + halo + dy * a.step) * pitch + tx + halo + dx * a.step;
+                cq = ldsC[e];
+                gq = ldsG[e];
+            } else {
+                cq = a.colour[(size_t)qy * W + qx];
+                gq = a.guide[(size_t)qy * W + qx];
+            }
+            const float lq = luminance709(cq.x, cq.y, cq.z);
+            const float en = a.kNormal * fmaxf(0.0f, 1.0f - (gp.x * gq.x + gp.y * gq.y + gp.z * gq.z));
+            const float ez = fabsf(gp.w - gq.w) * a.invSigmaDepth / (fminf(gp.w, gq.w) + 1e-6f);
+            const float diff = fabsf(lp - lq), top = fmaxf(lp, lq) + 1e-3f;
+            const float ePlain = diff * a.invSigmaLum / top;
+            const float eVar = diff / (sigmaG + v.relativeFloor * top);
+            const float el = s * eVar + (1.0f - s) * ePlain;
+            const float w = kern[dy + 2] * kern[dx + 2] * __expf(-(en + ez + el));
+            sr += w * cq.x, sg += w * cq.y, sb += w * cq.z, sv += w * w * cq.w, sw += w;
+        }
+    }
+    // (the centre tap has w = k(0): sw >= 9/64)
+    float r = sr / sw, g = sg / sw, b = sb / sw;
+    if (a.mode == ATROUS_MORE) {
+        a.out[p] = make_float4(r, g, b, sv / (sw * sw));
+        return;
+    }
+    const float4 al = a.albedoHits[p];
+    r *= albedoOf(al.x, a.gspp), g *= albedoOf(al.y, a.gspp), b *= albedoOf(al.z, a.gspp);
+    if (a.mode == ATROUS_LAST_TONEMAPPED) {
+        const float exposure = resolveExposure(a.relativeAperture, a.shutterTime, a.ISO);
+        r = resolveChannel(r * exposure), g = resolveChannel(g * exposure), b = resolveChannel(b * exposure);
+    }
+    a.out[p] = make_float4(r, g, b, 1.0f);
+}
+
 } // namespace ptd

@@ -25,6 +25,9 @@ struct TemporalArgs {
     // k_temporal<true> (instance motion): the two motion sums of the guide pass -- (sum of displacements.xyz, 0) and (sum of the normals then.xyz, 0)
     const float4* motion;
     const float4* prevNormal;
+    // k_temporal<., true> (pt_set_temporal_variance): the luminance-variance plane of the newest set (read where histColour is) and of the other set
+    const float* histVariance;
+    float* outVariance;
 };
 
 constexpr int kTemporalTileW = kAtrousTileW, kTemporalTileH = kAtrousTileH; // the filter's tile: a wave is two rows of 32 pixels
@@ -37,7 +40,13 @@ constexpr int kTemporalTileW = kAtrousTileW, kTemporalTileH = kAtrousTileH; // t
 // it WAS before it goes into the history's camera, q = (E + z D + m / gspp) - E', and the taps' normal term compares the history's normal with the
 // surface's normal THEN (the sum normalised as n is).  The set written out holds the current (n, z) all the same.  Zero motion sums and prevNormal ==
 // normalDepth.xyz give the plain kernel's bits.
-template <bool MOTION>
+// VARIANCE (pt_set_temporal_variance): one more plane per set, v = the population variance of the luminances the pixel's history stands for.  Up to four
+// more gathered 4-byte reads, issued with the colour taps (a tap outside the image loads nothing; one that does not count is not used), and one 4-byte
+// write -- 120 bytes per pixel, 152 with MOTION.  Welford's update for a running mean of weight 1 / N:
+//   v_out = (1 - alpha) (v_h + alpha (l - mu)^2),  alpha = 1 / N_out,  l = L(d),  mu = L(h),  v_h = sum w v_tap / Wsum;  0 where the pixel found no history
+// -- sums and products of non-negative terms, nothing subtracted but l - mu.  The colour's arithmetic is untouched: outColour and outGuide have the bits
+// of the VARIANCE-less kernel.
+template <bool MOTION, bool VARIANCE = false>
 __global__ void __launch_bounds__(256) k_temporal(TemporalArgs a)
 {
     const int x = blockIdx.x * kTemporalTileW + threadIdx.x, y = blockIdx.y * kTemporalTileH + threadIdx.y;
@@ -64,6 +73,7 @@ __global__ void __launch_bounds__(256) k_temporal(TemporalArgs a)
     }
 
     float outR = dr, outG = dg, outB = db, outN = 1.0f;
+    float outV = 0.0f;
     if (a.histColour) {
         // world point of the first hit through the pixel centre, then into the history's camera
         const float px = ((float)x + 0.5f) * a.invW, py = ((float)y + 0.5f) * a.invH;
@@ -83,15 +93,22 @@ __global__ void __launch_bounds__(256) k_temporal(TemporalArgs a)
             const float ax = fx - flx, ay = fy - fly;
             // the (up to) four colour taps first, as independent loads in flight together; a tap outside the image reads nothing and counts for nothing
             float4 ch[4];
+            float vh[4];
 #pragma unroll
             for (int t = 0; t < 4; t++) {
                 const int tx = x0 + (t & 1), ty = y0 + (t >> 1);
                 ch[t] = make_float4(0.f, 0.f, 0.f, 0.f);
-                if (tx >= 0 && tx < W && ty >= 0 && ty < H)
+                if constexpr (VARIANCE)
+                    vh[t] = 0.0f;
+                if (tx >= 0 && tx < W && ty >= 0 && ty < H) {
                     ch[t] = a.histColour[(size_t)ty * W + tx];
+                    if constexpr (VARIANCE)
+                        vh[t] = a.histVariance[(size_t)ty * W + tx];
+                }
             }
             // ... then the guides of the taps that count (N_h > 0)
             float sr = 0.f, sg = 0.f, sb = 0.f, sn = 0.f, sw = 0.f;
+            float sv = 0.f;
 #pragma unroll
             for (int t = 0; t < 4; t++) {
                 const bool counts = ch[t].w > 0.0f;
@@ -105,15 +122,23 @@ __global__ void __launch_bounds__(256) k_temporal(TemporalArgs a)
                 }
                 sr += w * (counts ? ch[t].x : 0.0f), sg += w * (counts ? ch[t].y : 0.0f), sb += w * (counts ? ch[t].z : 0.0f);
                 sn += w * (counts ? ch[t].w : 0.0f), sw += w;
+                if constexpr (VARIANCE)
+                    sv += w * (counts ? vh[t] : 0.0f);
             }
             if (sw >= 1e-12f) {
                 const float hr = sr / sw, hg = sg / sw, hb = sb / sw;
                 outN = fminf(sn + 1.0f, a.maxHistory);
                 outR = hr + (dr - hr) / outN, outG = hg + (dg - hg) / outN, outB = hb + (db - hb) / outN;
+                if constexpr (VARIANCE) {
+                    const float alpha = 1.0f / outN, delta = luminance709(dr, dg, db) - luminance709(hr, hg, hb);
+                    outV = (1.0f - alpha) * (sv / sw + alpha * delta * delta);
+                }
             }
         }
     }
     a.outColour[p] = make_float4(outR, outG, outB, outN);
+    if constexpr (VARIANCE)
+        a.outVariance[p] = outV;
 }
 
 // pt_denoise with PT_DENOISE_INPUT_TEMPORAL: k_denoise_prepare with d0 taken from the newest history; the guides are the current frame's
@@ -125,6 +150,22 @@ __global__ void __launch_bounds__(256) k_denoise_prepare_temporal(const float4* 
         return;
     const float4 h = histColour[i], g = normalDepth[i];
     colour[i] = make_float4(h.x, h.y, h.z, luminance709(h.x, h.y, h.z));
+    const float len = sqrtf(g.x * g.x + g.y * g.y + g.z * g.z);
+    const float inv = len > 0.0f ? 1.0f / len : 0.0f;
+    guide[i] = make_float4(g.x * inv, g.y * inv, g.z * inv, g.w / gspp);
+}
+
+// pt_denoise with PT_DENOISE_INPUT_TEMPORAL_VARIANCE: the same with the variance of the history's MEAN, V_0 = v / max(N, 1), where the luminance was
+// (k_atrous_var recomputes that per tap)
+__global__ void __launch_bounds__(256) k_denoise_prepare_variance(const float4* __restrict__ histColour, const float* __restrict__ histVariance,
+    const float4* __restrict__ normalDepth, float4* __restrict__ colour, float4* __restrict__ guide, uint32_t n, float gspp)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n)
+        return;
+    const float4 h = histColour[i], g = normalDepth[i];
+    const float v = histVariance[i];
+    colour[i] = make_float4(h.x, h.y, h.z, v / fmaxf(h.w, 1.0f));
     const float len = sqrtf(g.x * g.x + g.y * g.y + g.z * g.z);
     const float inv = len > 0.0f ? 1.0f / len : 0.0f;
     guide[i] = make_float4(g.x * inv, g.y * inv, g.z * inv, g.w / gspp);

@@ -1277,11 +1277,14 @@ int pt_denoise_device(pt_ctx* c, const pt_denoise_params* prm, void* device_rgba
         return fail(c, PT_ERR_STATE, "pt_denoise: no colour samples yet (pt_render)");
     if (c->guideSpp == 0)
         return fail(c, PT_ERR_STATE, "pt_denoise: no guide samples yet (pt_render_guides)");
-    if (prm->input != PT_DENOISE_INPUT_ACCUM && prm->input != PT_DENOISE_INPUT_TEMPORAL)
-        return fail(c, PT_ERR_INVALID, "pt_denoise: input = %u (PT_DENOISE_INPUT_ACCUM or PT_DENOISE_INPUT_TEMPORAL)", prm->input);
-    const bool temporal = prm->input == PT_DENOISE_INPUT_TEMPORAL;
+    if (prm->input != PT_DENOISE_INPUT_ACCUM && prm->input != PT_DENOISE_INPUT_TEMPORAL && prm->input != PT_DENOISE_INPUT_TEMPORAL_VARIANCE)
+        return fail(c, PT_ERR_INVALID, "pt_denoise: input = %u (PT_DENOISE_INPUT_ACCUM, PT_DENOISE_INPUT_TEMPORAL or PT_DENOISE_INPUT_TEMPORAL_VARIANCE)", prm->input);
+    const bool guided = prm->input == PT_DENOISE_INPUT_TEMPORAL_VARIANCE; // the history, filtered under its variance
+    const bool temporal = prm->input == PT_DENOISE_INPUT_TEMPORAL || guided;
+    if (guided && !c->varianceSet)
+        return fail(c, PT_ERR_STATE, "pt_denoise: PT_DENOISE_INPUT_TEMPORAL_VARIANCE while the temporal variance is off (pt_set_temporal_variance)");
     if (temporal && c->temporalFrames == 0)
-        return fail(c, PT_ERR_STATE, "pt_denoise: PT_DENOISE_INPUT_TEMPORAL without a history (pt_temporal_accumulate)");
+        return fail(c, PT_ERR_STATE, "pt_denoise: PT_DENOISE_INPUT_TEMPORAL%s without a history (pt_temporal_accumulate)", guided ? "_VARIANCE" : "");
     const bool tonemapped = prm->output == PT_DENOISE_TONEMAPPED;
     if (tonemapped && !c->haveCamera)
         return fail(c, PT_ERR_STATE, "pt_denoise: the tone-mapped output needs the camera's exposure (pt_set_camera)");
@@ -1308,7 +1311,10 @@ int pt_denoise_device(pt_ctx* c, const pt_denoise_params* prm, void* device_rgba
         HIPCHK(c, c->denoiseColour[1].alloc(n));
         HIPCHK(c, c->denoiseGuide.alloc(n));
     }
-    if (temporal)
+    if (guided)
+        hipLaunchKernelGGL(k_denoise_prepare_variance, lin, dim3(256), 0, c->stream, history[0], c->temporalVariance[c->temporalNewest].p, c->guides[1],
+            c->denoiseColour[0].p, c->denoiseGuide.p, n, (float)c->guideSpp);
+    else if (temporal)
         hipLaunchKernelGGL(k_denoise_prepare_temporal, lin, dim3(256), 0, c->stream, history[0], c->guides[1], c->denoiseColour[0].p, c->denoiseGuide.p, n,
             (float)c->guideSpp);
     else
@@ -1331,7 +1337,14 @@ int pt_denoise_device(pt_ctx* c, const pt_denoise_params* prm, void* device_rgba
         a.step = 1 << i;
         a.invSigmaLum = 1.0f / (sigmaLum * std::ldexp(1.0f, -(int)i));
         a.mode = !last ? ATROUS_MORE : (tonemapped ? ATROUS_LAST_TONEMAPPED : ATROUS_LAST_HDR);
-        if (2 * a.step <= kAtrousMaxHalo)
+        const bool inLds = 2 * a.step <= kAtrousMaxHalo;
+        if (guided) {
+            const AtrousVarArgs v { a, history[0], c->sigmaVariance, c->relativeFloor, 1.0f / (c->fullHistory - 1.0f) };
+            if (inLds)
+                hipLaunchKernelGGL(k_atrous_var<true>, grid, block, 0, c->stream, v);
+            else
+                hipLaunchKernelGGL(k_atrous_var<false>, grid, block, 0, c->stream, v);
+        } else if (inLds)
             hipLaunchKernelGGL(k_atrous<true>, grid, block, 0, c->stream, a);
         else
             hipLaunchKernelGGL(k_atrous<false>, grid, block, 0, c->stream, a);
@@ -1374,11 +1387,18 @@ uint32_t pt_sample_base(const pt_ctx* c) { return c ? c->sampleBase : 0; }
 
 namespace {
 
-// the two history sets: allocated (zeroed) at the first temporal call, both
+// the two history sets: allocated (zeroed) at the first temporal call, both -- with their variance planes where that mode is on
 int ensureTemporal(pt_ctx* c)
 {
     int rc;
-    return (rc = c->temporal[0].ensure(c)) ? rc : c->temporal[1].ensure(c);
+    if ((rc = c->temporal[0].ensure(c)) || (rc = c->temporal[1].ensure(c)))
+        return rc;
+    if (c->varianceSet && !c->temporalVariance[0].p)
+        for (DevBuf<float>& plane : c->temporalVariance) {
+            HIPCHK(c, plane.alloc((size_t)c->cfg.width * c->cfg.height));
+            HIPCHK(c, hipMemsetAsync(plane.p, 0, plane.n * sizeof(float), c->stream));
+        }
+    return PT_OK;
 }
 
 struct D3 {
@@ -1435,10 +1455,18 @@ int pt_temporal_accumulate(pt_ctx* c, const pt_temporal_params* prm)
         }
     }
     const dim3 grid((a.width + kTemporalTileW - 1) / kTemporalTileW, (a.height + kTemporalTileH - 1) / kTemporalTileH), block(kTemporalTileW, kTemporalTileH);
-    if (c->motionSet || c->vertexMotionSet) { // the history is met where the surfaces were (the two sums are there: the setters made them)
+    const bool moved = c->motionSet || c->vertexMotionSet; // the history is met where the surfaces were (the two sums are there: the setters made them)
+    if (moved)
         a.motion = c->motionGuides[0], a.prevNormal = c->motionGuides[1];
+    if (c->varianceSet) { // the same arithmetic and one more plane
+        a.histVariance = c->temporalVariance[from].p, a.outVariance = c->temporalVariance[to].p;
+        if (moved)
+            hipLaunchKernelGGL((k_temporal<true, true>), grid, block, 0, c->stream, a);
+        else
+            hipLaunchKernelGGL((k_temporal<false, true>), grid, block, 0, c->stream, a);
+    } else if (moved)
         hipLaunchKernelGGL(k_temporal<true>, grid, block, 0, c->stream, a);
-    } else
+    else
         hipLaunchKernelGGL(k_temporal<false>, grid, block, 0, c->stream, a);
     HIPCHK(c, hipGetLastError());
     c->temporalCamera = c->camera;
@@ -1476,6 +1504,10 @@ int pt_write_temporal(pt_ctx* c, const float* colour_count, const float* normal_
     int rc;
     if ((rc = ensureTemporal(c)) || (rc = c->temporal[c->temporalNewest].write(c, colour_count, normal_depth)))
         return rc;
+    if (c->varianceSet) { // nothing is known about these colours' spread: pt_write_temporal_variance restores it
+        DevBuf<float>& plane = c->temporalVariance[c->temporalNewest];
+        HIPCHK(c, hipMemsetAsync(plane.p, 0, plane.n * sizeof(float), c->stream));
+    }
     auto f4 = [](const float* p) { return make_float4(p[0], p[1], p[2], 0.f); };
     c->temporalCamera = CameraDev {};
     c->temporalCamera.eye = f4(made_under->eyePoint), c->temporalCamera.screen = f4(made_under->screenPoint);
@@ -1485,6 +1517,81 @@ int pt_write_temporal(pt_ctx* c, const float* colour_count, const float* normal_
 }
 
 void* pt_temporal_device_ptr(pt_ctx* c, int which) { return c && (which == 0 || which == 1) ? (void*)c->temporal[c->temporalNewest][which] : nullptr; }
+
+// ---- temporal variance (k_temporal<., true>, k_atrous_var) --------------------------------------
+
+int pt_set_temporal_variance(pt_ctx* c, const pt_variance_params* prm)
+{
+    if (!c)
+        return PT_ERR_INVALID;
+    if (const int rc = fixedScheduleOnly(c, "pt_set_temporal_variance"))
+        return rc;
+    if (prm) {
+        const float given[3] = { prm->sigma_variance, prm->relative_floor, prm->full_history };
+        for (const float f : given)
+            if (!(f >= 0.0f) || !std::isfinite(f))
+                return fail(c, PT_ERR_INVALID, "pt_set_temporal_variance: negative or non-finite parameter");
+        if (prm->full_history != 0.0f && prm->full_history < 2.0f)
+            return fail(c, PT_ERR_INVALID, "pt_set_temporal_variance: full_history = %g (at least 2; 0 = %g)", (double)prm->full_history,
+                (double)PT_VARIANCE_DEFAULT_FULL_HISTORY);
+    }
+    if (c->temporalFrames != 0)
+        return fail(c, PT_ERR_STATE, "pt_set_temporal_variance: a history of %u frames exists -- set or forget the mode right after pt_temporal_reset",
+            c->temporalFrames);
+    c->varianceSet = prm != nullptr;
+    if (prm) {
+        c->sigmaVariance = prm->sigma_variance > 0.f ? prm->sigma_variance : PT_VARIANCE_DEFAULT_SIGMA_VARIANCE;
+        c->relativeFloor = prm->relative_floor > 0.f ? prm->relative_floor : PT_VARIANCE_DEFAULT_RELATIVE_FLOOR;
+        c->fullHistory = prm->full_history > 0.f ? prm->full_history : PT_VARIANCE_DEFAULT_FULL_HISTORY;
+    }
+    return PT_OK;
+}
+
+int pt_temporal_variance(const pt_ctx* c) { return c && c->varianceSet ? 1 : 0; }
+
+namespace {
+
+// what reading and writing the plane share: PT_OK with the newest set's plane in place
+int variancePlane(pt_ctx* c, const char* who, DevBuf<float>** plane)
+{
+    if (!c->varianceSet)
+        return fail(c, PT_ERR_STATE, "%s: the temporal variance is off (pt_set_temporal_variance)", who);
+    if (c->temporalFrames == 0)
+        return fail(c, PT_ERR_STATE, "%s: no history (pt_temporal_accumulate, pt_write_temporal)", who);
+    HIPCHK(c, hipSetDevice(c->device));
+    if (const int rc = ensureTemporal(c))
+        return rc;
+    *plane = &c->temporalVariance[c->temporalNewest];
+    return PT_OK;
+}
+
+} // namespace
+
+int pt_read_temporal_variance(pt_ctx* c, float* out)
+{
+    if (!c || !out)
+        return PT_ERR_INVALID;
+    DevBuf<float>* plane;
+    if (const int rc = variancePlane(c, "pt_read_temporal_variance", &plane))
+        return rc;
+    HIPCHK(c, hipMemcpyAsync(out, plane->p, plane->n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return PT_OK;
+}
+
+int pt_write_temporal_variance(pt_ctx* c, const float* in)
+{
+    if (!c || !in)
+        return PT_ERR_INVALID;
+    DevBuf<float>* plane;
+    if (const int rc = variancePlane(c, "pt_write_temporal_variance", &plane))
+        return rc;
+    HIPCHK(c, hipMemcpyAsync(plane->p, in, plane->n * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return PT_OK;
+}
+
+void* pt_temporal_variance_device_ptr(pt_ctx* c) { return c && c->varianceSet ? (void*)c->temporalVariance[c->temporalNewest].p : nullptr; }
 
 // ---- instance motion (k_guides<1>, k_temporal<true>) --------------------------------------------
 

@@ -238,10 +238,18 @@ std::vector<float> RayTracer::getTemporalOutput(int iterations)
     pt_denoise_params prm {};
     prm.iterations = (uint32_t)iterations;
     prm.output = PT_DENOISE_TONEMAPPED;
-    prm.input = PT_DENOISE_INPUT_TEMPORAL;
+    prm.input = m_temporalVariance ? PT_DENOISE_INPUT_TEMPORAL_VARIANCE : PT_DENOISE_INPUT_TEMPORAL;
     std::vector<float> out((size_t)m_width * m_height * 4);
     check(pt_denoise(m_ctx, &prm, out.data(), nullptr), "pt_denoise");
     return out;
+}
+
+void RayTracer::setTemporalVariance(bool on)
+{
+    check(pt_temporal_reset(m_ctx), "pt_temporal_reset");
+    const pt_variance_params defaults {};
+    check(pt_set_temporal_variance(m_ctx, on ? &defaults : nullptr), "pt_set_temporal_variance");
+    m_temporalVariance = on;
 }
 
 void RayTracer::resetTemporalHistory() { check(pt_temporal_reset(m_ctx), "pt_temporal_reset"); }

@@ -104,6 +104,10 @@ public:
     // previous frameTick, and getTemporalOutput blended a frame of the state that tick replaced, the first rayTrace on a cleared accumulator after the tick
     // sets pt_set_vertex_motion next to the instance motion -- the history follows the deforming surface.  Never across rebuildGeometry.  On by default.
     void setVertexMotion(bool on) { m_vertexMotion = on; }
+    // The luminance variance of every pixel's history beside it, and the filter guided by it (include/ptamd.h, "temporal variance"): resets the history
+    // (the mode changes only while there is none); from then on getTemporalOutput filters with PT_DENOISE_INPUT_TEMPORAL_VARIANCE -- a static camera's
+    // image keeps converging where the fixed-strength filter stops at its own blur.  Off by default.
+    void setTemporalVariance(bool on);
     void resetTemporalHistory(); // forget the history: after a cut, or when the scene changed beyond what depth and normal can tell
     void setSampleBase(uint32_t base); // pt_set_sample_base: frames that restart at sample 0 draw other random numbers each
     struct Guides {
@@ -124,6 +128,7 @@ private:
     CameraData m_prevCamera;
     bool m_haveCamera = false;
     bool m_temporalDirty = false; // samples were traced since the last getTemporalOutput
+    bool m_temporalVariance = false; // setTemporalVariance: getTemporalOutput's filter reads the variance plane
     // instance motion: the leaves' invTransform (16 floats each, scene-graph order) of the state the newest history was made under
     bool m_instanceMotion = true;
     std::vector<float> m_prevLeafInv;

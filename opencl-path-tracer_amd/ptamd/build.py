@@ -140,6 +140,10 @@ def build_raytracer(force=False):
     if force or _newer(exe8, [os.path.join(ex_dir, "deforming_cornell.cpp"), out]):
         subprocess.run(["g++", "-std=c++17", "-O2", "-Wall", "deforming_cornell.cpp", "-o", "deforming_cornell", "-L" + HOST_DIR, "-lptamd_raytracer",
                         "-lptamd_host", "-L" + CSRC_DIR, "-lptamd", "-Wl,-rpath," + HOST_DIR, "-Wl,-rpath," + CSRC_DIR], cwd=ex_dir, check=True)
+    exe9 = os.path.join(ex_dir, "converge_cornell")
+    if force or _newer(exe9, [os.path.join(ex_dir, "converge_cornell.cpp"), out]):
+        subprocess.run(["g++", "-std=c++17", "-O2", "-Wall", "converge_cornell.cpp", "-o", "converge_cornell", "-L" + HOST_DIR, "-lptamd_raytracer",
+                        "-lptamd_host", "-L" + CSRC_DIR, "-lptamd", "-Wl,-rpath," + HOST_DIR, "-Wl,-rpath," + CSRC_DIR], cwd=ex_dir, check=True)
     return out, exe
 
 

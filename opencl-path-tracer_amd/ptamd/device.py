@@ -80,6 +80,14 @@ class TemporalParams(C.Structure):
     _fields_ = [("max_history", C.c_uint32), ("k_normal", C.c_float), ("sigma_depth", C.c_float), ("_reserved", C.c_uint32 * 5)]
 
 
+DENOISE_INPUT_TEMPORAL_VARIANCE = 2
+
+
+class VarianceParams(C.Structure):
+    """pt_variance_params (32 bytes); a parameter of 0 selects the default documented in include/ptamd.h"""
+    _fields_ = [("sigma_variance", C.c_float), ("relative_floor", C.c_float), ("full_history", C.c_float), ("_reserved", C.c_uint32 * 5)]
+
+
 EXPORTS = ["pt_create", "pt_destroy", "pt_last_error", "pt_set_stream", "pt_upload_static", "pt_upload_static_async", "pt_upload_dynamic",
            "pt_upload_dynamic_async", "pt_frame_tick", "pt_update_geometry", "pt_refit_vertices",
            "pt_upload_texture_array", "pt_set_camera", "pt_set_tiles", "pt_set_accum_buffer", "pt_clear", "pt_render",
@@ -88,7 +96,8 @@ EXPORTS = ["pt_create", "pt_destroy", "pt_last_error", "pt_set_stream", "pt_uplo
            "pt_denoise", "pt_denoise_device", "pt_set_sample_base", "pt_sample_base", "pt_temporal_accumulate", "pt_temporal_reset",
            "pt_temporal_frames", "pt_read_temporal", "pt_write_temporal", "pt_temporal_device_ptr", "pt_set_instance_motion", "pt_instance_motion",
            "pt_read_motion_guides", "pt_write_motion_guides", "pt_motion_guides_device_ptr", "pt_debug_motion_records",
-           "pt_set_vertex_motion", "pt_vertex_motion", "pt_debug_vertex_motion_rows", "pt_stats_get", "pt_stats_reset", "pt_profile_kernels", "pt_reduce_accum",
+           "pt_set_vertex_motion", "pt_vertex_motion", "pt_debug_vertex_motion_rows", "pt_set_temporal_variance", "pt_temporal_variance",
+           "pt_read_temporal_variance", "pt_write_temporal_variance", "pt_temporal_variance_device_ptr", "pt_stats_get", "pt_stats_reset", "pt_profile_kernels", "pt_reduce_accum",
            "pt_intersect", "pt_gen_rays", "pt_primary_pass", "pt_shade_batch", "pt_debug_quantise_node", "pt_debug_convert", "pt_debug_copy_bandwidth", "pt_debug_math_probe", "pt_debug_live_resources",
            "pt_version"]
 
@@ -169,6 +178,12 @@ def lib():
         l.pt_set_vertex_motion.argtypes = [C.c_void_p, C.c_int]
         l.pt_vertex_motion.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
         l.pt_debug_vertex_motion_rows.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
+        l.pt_set_temporal_variance.argtypes = [C.c_void_p, C.POINTER(VarianceParams)]
+        l.pt_temporal_variance.argtypes = [C.c_void_p]
+        l.pt_read_temporal_variance.argtypes = [C.c_void_p, C.c_void_p]
+        l.pt_write_temporal_variance.argtypes = [C.c_void_p, C.c_void_p]
+        l.pt_temporal_variance_device_ptr.restype = C.c_void_p
+        l.pt_temporal_variance_device_ptr.argtypes = [C.c_void_p]
         l.pt_stats_get.argtypes = [C.c_void_p, C.POINTER(Stats)]
         l.pt_stats_reset.argtypes = [C.c_void_p]
         l.pt_profile_kernels.argtypes = [C.c_void_p, C.c_int]
@@ -244,6 +259,12 @@ def debug_vertex_motion_rows(inv):
     if rc != 0:
         raise PtError(f"pt_debug_vertex_motion_rows failed ({rc}): {lib().pt_last_error(None).decode()}")
     return out
+
+
+def _denoise_input(input_temporal, input):
+    if input is not None:
+        return int(input)
+    return DENOISE_INPUT_TEMPORAL if input_temporal else DENOISE_INPUT_ACCUM
 
 
 class Context:
@@ -418,21 +439,22 @@ class Context:
         """Device address of the albedo_hits (0) / normal_depth (1) image (0 before the first guide call)."""
         return lib().pt_guides_device_ptr(self._h, which) or 0
 
-    def denoise(self, iterations=5, hdr=False, k_normal=0.0, sigma_depth=0.0, sigma_lum=0.0, with_ms=False, input_temporal=False):
+    def denoise(self, iterations=5, hdr=False, k_normal=0.0, sigma_depth=0.0, sigma_lum=0.0, with_ms=False, input_temporal=False, input=None):
         """The edge-avoiding a-trous filter over the accumulator under the guides: (height, width, 4) tone-mapped like resolve(), or linear
         mean radiance (hdr=True); with_ms: also the device ms of the filter's kernels; input_temporal: the filter starts from the temporal
-        history (temporal_accumulate) instead of the accumulator."""
+        history (temporal_accumulate) instead of the accumulator; input: one of DENOISE_INPUT_* (DENOISE_INPUT_TEMPORAL_VARIANCE: the history
+        under its luminance variance, set_temporal_variance), which overrides input_temporal."""
         prm = DenoiseParams(iterations, DENOISE_HDR if hdr else DENOISE_TONEMAPPED, k_normal, sigma_depth, sigma_lum,
-                            DENOISE_INPUT_TEMPORAL if input_temporal else DENOISE_INPUT_ACCUM)
+                            _denoise_input(input_temporal, input))
         out = np.zeros((self.height, self.width, 4), np.float32)
         ms = C.c_float(0)
         self._chk(lib().pt_denoise(self._h, C.byref(prm), _p(out), C.byref(ms)), "pt_denoise")
         return (out, float(ms.value)) if with_ms else out
 
-    def denoise_device(self, iterations=5, hdr=False, k_normal=0.0, sigma_depth=0.0, sigma_lum=0.0, device_ptr=None, input_temporal=False):
+    def denoise_device(self, iterations=5, hdr=False, k_normal=0.0, sigma_depth=0.0, sigma_lum=0.0, device_ptr=None, input_temporal=False, input=None):
         """The same into device memory (None: the context-owned image, resolve_device_ptr); asynchronous."""
         prm = DenoiseParams(iterations, DENOISE_HDR if hdr else DENOISE_TONEMAPPED, k_normal, sigma_depth, sigma_lum,
-                            DENOISE_INPUT_TEMPORAL if input_temporal else DENOISE_INPUT_ACCUM)
+                            _denoise_input(input_temporal, input))
         self._chk(lib().pt_denoise_device(self._h, C.byref(prm), C.c_void_p(device_ptr) if device_ptr else None), "pt_denoise_device")
 
     # ---- sample base and temporal history
@@ -476,6 +498,34 @@ class Context:
     def temporal_device_ptr(self, which):
         """Device address of the colour_count (0) / normal_depth (1) image of the newest set (0 before the first temporal call)."""
         return lib().pt_temporal_device_ptr(self._h, which) or 0
+
+    # ---- temporal variance
+    def set_temporal_variance(self, on=True, sigma_variance=0.0, relative_floor=0.0, full_history=0.0):
+        """Keep the luminance variance of every pixel's history beside it (temporal_accumulate) for denoise(input=DENOISE_INPUT_TEMPORAL_VARIANCE);
+        False forgets it.  Only while there is no history: right after temporal_reset()."""
+        prm = VarianceParams(sigma_variance, relative_floor, full_history)
+        self._chk(lib().pt_set_temporal_variance(self._h, C.byref(prm) if on else None), "pt_set_temporal_variance")
+
+    @property
+    def temporal_variance(self):
+        return bool(lib().pt_temporal_variance(self._h))
+
+    def read_temporal_variance(self):
+        """the variance plane of the newest history set: (width*height,) float32"""
+        out = np.zeros(self.height * self.width, np.float32)
+        self._chk(lib().pt_read_temporal_variance(self._h, _p(out)), "pt_read_temporal_variance")
+        return out
+
+    def write_temporal_variance(self, variance):
+        """Install the variance plane of the newest set (after write_temporal, which zeroes it)."""
+        v = np.ascontiguousarray(variance, np.float32)
+        assert v.size == self.width * self.height
+        self._chk(lib().pt_write_temporal_variance(self._h, _p(v)), "pt_write_temporal_variance")
+
+    @property
+    def temporal_variance_device_ptr(self):
+        """Device address of the newest set's variance plane (0 while the mode is off or nothing is allocated yet)."""
+        return lib().pt_temporal_variance_device_ptr(self._h) or 0
 
     # ---- instance motion
     def set_instance_motion(self, prev):

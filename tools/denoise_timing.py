@@ -1,11 +1,13 @@
 #!/usr/bin/env python3
 """Device time of the guide pass and of the a-trous denoiser at 1280 x 720 and 1920 x 1080, one JSON line (EXPERIMENTS.md).
-Not part of bench.py.     usage: python tools/denoise_timing.py [--calls 25] [--scene cornell|blob]
+Not part of bench.py.     usage: python tools/denoise_timing.py [--calls 25] [--scene cornell|blob] [--variance]
 
 denoise_ms[N]: median `ms_out` of pt_denoise with N iterations (hipEvents around the filter's kernels); their differences say what each
 iteration costs.  guides_ms: median device ms of pt_render_guides(1), between two events on the stream the context renders on.  frame_ms: the
 same for pt_render(1), the frame the two serve.  bytes: what the filter must move (prepare: 3 reads + 2 writes, every iteration 2 reads + 1
-write of a float4 image); fraction_of_copy: that traffic per second against pt_debug_copy_bandwidth."""
+write of a float4 image); fraction_of_copy: that traffic per second against pt_debug_copy_bandwidth.
+--variance: the same six medians for PT_DENOISE_INPUT_TEMPORAL (k_atrous over the history) and PT_DENOISE_INPUT_TEMPORAL_VARIANCE (k_atrous_var) in the
+same process, and per iteration -- the difference of two consecutive medians -- the ratio of the second to the first."""
 import argparse
 import json
 import os
@@ -21,6 +23,7 @@ def main():
     ap.add_argument("--calls", type=int, default=25)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--scene", default="cornell")
+    ap.add_argument("--variance", action="store_true", help="also time the variance-guided filter against the plain one over the same history")
     args = ap.parse_args()
     import torch
     from ptamd import device as D, scenes
@@ -59,6 +62,25 @@ def main():
             "frame_ms": round(frame, 4), "guides_ms": round(guides, 4), "denoise_ms": {str(k): round(v, 4) for k, v in den.items()},
             "bytes_5_iterations": moved, "gbps_5_iterations": round(moved / den[5] / 1e6, 1), "copy_gbps": round(copy, 1),
             "fraction_of_copy": round(moved / den[5] / 1e6 / copy, 3)}
+        if args.variance:
+            ctx.clear()
+            ctx.render(1)
+            ctx.render_guides(1)
+            ctx.temporal_reset()
+            ctx.set_temporal_variance()
+            for f in range(4):  # a history with counts and a variance plane that are not trivial
+                ctx.temporal_accumulate()
+            per = {}
+            for name, which in (("plain", D.DENOISE_INPUT_TEMPORAL), ("guided", D.DENOISE_INPUT_TEMPORAL_VARIANCE)):
+                per[name] = {}
+                for n in range(1, 7):
+                    ms = [ctx.denoise(n, with_ms=True, input=which)[1] for _ in range(args.warmup + args.calls)][args.warmup:]
+                    per[name][n] = statistics.median(ms)
+            step = {name: {1: per[name][1]} | {n: per[name][n] - per[name][n - 1] for n in range(2, 7)} for name in per}  # (1: prepare included)
+            out["sizes"][f"{width}x{height}"]["variance"] = {
+                "denoise_ms": {name: {str(k): round(v, 4) for k, v in per[name].items()} for name in per},
+                "iteration_ms": {name: {str(2 ** (k - 1)): round(v, 4) for k, v in step[name].items()} for name in per},
+                "ratio_by_step": {str(2 ** (k - 1)): round(step["guided"][k] / step["plain"][k], 3) for k in range(1, 7)}}
         ctx.close()
     print(json.dumps(out))
 

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Device time of pt_temporal_accumulate at 1280 x 720 and 1920 x 1080, one JSON line (EXPERIMENTS.md).
-Not part of bench.py.     usage: python tools/temporal_timing.py [--calls 25] [--batch 20] [--scene cornell|blob] [--motion]
+Not part of bench.py.     usage: python tools/temporal_timing.py [--calls 25] [--batch 20] [--scene cornell|blob] [--motion] [--variance]
 
 temporal_ms.static / .panned: median device ms of ONE pt_temporal_accumulate, measured between two events on the stream the context renders on
 around `batch` calls in a row (one call is tens of microseconds: a pair of events around a single launch would time the events).  static: the camera
@@ -20,6 +20,7 @@ sys.path[:0] = [os.path.join(ROOT, "opencl-path-tracer_amd"), ROOT]
 
 FLOOR_BYTES_PER_PIXEL = 7 * 16
 MOTION_FLOOR_BYTES_PER_PIXEL = 9 * 16  # --motion: the two motion sums are read as well
+VARIANCE_EXTRA_BYTES_PER_PIXEL = 8  # --variance: the history's variance plane read once, the new one written (4 bytes each): 120 and 152
 
 
 def main():
@@ -29,6 +30,7 @@ def main():
     ap.add_argument("--batch", type=int, default=20)
     ap.add_argument("--scene", default="cornell")
     ap.add_argument("--motion", action="store_true", help="also time k_temporal<true> (instance motion set), next to the plain kernel")
+    ap.add_argument("--variance", action="store_true", help="also time k_temporal<., true> (pt_set_temporal_variance), next to the plain kernel")
     args = ap.parse_args()
     import torch
     from ptamd import device as D, scenes
@@ -77,6 +79,22 @@ def main():
             "gbps": {"static": round(floor / static / 1e6, 1), "panned": round(floor / panned / 1e6, 1)}, "copy_gbps": round(copy, 1),
             "fraction_of_copy": {"static": round(floor / static / 1e6 / copy, 3), "panned": round(floor / panned / 1e6 / copy, 3)},
             "mean_history_count_panned": round(float(cn[:, 3].mean()), 2)}
+        if args.variance:
+            # k_temporal<false, true> in the same process, against the same copy rate and the plain kernel above: one more 4-byte plane read and written
+            ctx.set_camera(b.camera)
+            ctx.temporal_reset()
+            ctx.set_temporal_variance()
+            ctx.temporal_accumulate()
+            v_static = timed(lambda i: ctx.temporal_accumulate(sync=False), args.batch)
+            v_panned = timed(panned_call, args.batch)
+            v_floor = (FLOOR_BYTES_PER_PIXEL + VARIANCE_EXTRA_BYTES_PER_PIXEL) * width * height
+            out["sizes"][f"{width}x{height}"]["variance"] = {
+                "temporal_ms": {"static": round(v_static, 5), "panned": round(v_panned, 5)}, "floor_bytes": v_floor,
+                "ratio_to_plain": {"static": round(v_static / static, 3), "panned": round(v_panned / panned, 3)},
+                "fraction_of_copy": {"static": round(v_floor / v_static / 1e6 / copy, 3), "panned": round(v_floor / v_panned / 1e6 / copy, 3)}}
+            ctx.temporal_reset()
+            ctx.set_temporal_variance(False)
+            ctx.temporal_accumulate()
         if args.motion:
             # k_temporal<true> in the same process, against the same copy rate: every instance was a millimetre to the side, so every pixel of it carries
             # a displacement; two more 16-byte reads per pixel, 9 x 16 = 144 bytes
