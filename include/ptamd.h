@@ -615,6 +615,11 @@ int pt_debug_copy_bandwidth(pt_ctx* ctx, size_t bytes, uint32_t repeat, float* g
  * receives ten planes of n floats: a / b, fastDiv(a, b), sqrtf(|a|), fastSqrt(|a|), normalize((a, b, a + b)).xyz, fastNormalize((a, b, a + b)).xyz -- the
  * plain forms as the library's build compiles them. */
 int pt_debug_math_probe(pt_ctx* ctx, const float* a, const float* b, uint32_t n, float* out);
+/* Test hook: the production (counter) PRNG of csrc/pt_math.h, evaluated on the device for n entries of eight words in[8 * i ..]; `out` receives twenty words
+ * per entry.  in[0] == 0, keyed: (pixel, sample, seed, depth) = in[1..4], out[k] = the float bits of the k-th of 20 successive draws of that stage's generator
+ * (draws 16..19 are the next depth's first four).  in[0] == 1, raw: the generator's state (weyl, gamma, k1) = in[1..3] and an integer range (i, j) = in[4..5];
+ * out[0] = the float bits of its next draw, out[1] = the integer in [i, j] the same draw selects, out[2] = the float bits of the draw after that, the rest 0. */
+int pt_debug_rng_probe(pt_ctx* ctx, const uint32_t* in, uint32_t n, uint32_t* out);
 /* Test hook, no device needed: what the library holds alive in this process, all contexts and hooks together -- out[0] device allocations, out[1] pinned
  * host allocations, out[2] events, out[3] streams it created (a caller's stream, pt_set_stream, is never counted).  After the last pt_destroy every count
  * is back where it stood before the first pt_create. */

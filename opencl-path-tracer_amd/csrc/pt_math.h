@@ -71,6 +71,8 @@ __device__ inline V3 fastNormalize(V3 a) { return fastNormalize(a, dot(a, a)); }
 // dim = index of the draw inside that stage, draw order of SURVEY Appendix C):
 //   x = k0 + gamma * ctr;  x ^= x >> 16;  x *= 0x21f0aaad;  x ^= k1;  x ^= x >> 15;  x *= 0x735a2d97;  x ^= x >> 15
 //   u = (x >> 8) * 2^-24 in [0,1)      ('lowbias32' finaliser with the second key word injected between its rounds).
+// A stage owns the 16 slots dim = 0..15; a 17th draw would be the next depth's first.  tests/test_prng_cpu.py holds that budget (the most draws any stage
+// makes, over every integrator, light choice and camera, counted by the oracle) and tests/test_gpu_prng.py states the overlap as a fact.
 // Zero bytes of state traffic; independent of queue slot, compaction order and GPU count.
 __host__ __device__ inline uint32_t mix32(uint32_t x)
 {

@@ -1164,6 +1164,36 @@ __global__ void __launch_bounds__(256) k_math_probe(const float* __restrict__ a,
     out[7 * s + i] = nf.x, out[8 * s + i] = nf.y, out[9 * s + i] = nf.z;
 }
 
+// Test hook (pt_debug_rng_probe): the production PRNG of pt_math.h as this unit compiles it.  Entry i reads eight words in[8 * i ..] and writes twenty words
+// out[20 * i ..]:
+//   in[0] == 0, keyed: (pixel, sample, seed, depth) = in[1..4]; out[k] = the bits of the k-th of 20 successive u01() of rngCounter(pixel, sample, seed, depth)
+//   in[0] == 1, raw:   (weyl, gamma, k1) = in[1..3], (i, j) = in[4..5] as int; out[0] = the bits of u01() of that state, out[1] = randomInteger(i, j) of the
+//                      same state (it consumes the same draw), out[2] = the bits of the u01() that follows randomInteger; out[3..19] = 0
+__global__ void __launch_bounds__(256) k_rng_probe(const uint32_t* __restrict__ in, uint32_t n, uint32_t* __restrict__ out)
+{
+    const uint32_t e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= n)
+        return;
+    const uint32_t* q = in + (size_t)e * 8u;
+    uint32_t* o = out + (size_t)e * 20u;
+    if (q[0] == 0u) {
+        Rng r = rngCounter(q[1], q[2], q[3], q[4]);
+        for (int k = 0; k < 20; k++)
+            o[k] = __float_as_uint(r.u01());
+        return;
+    }
+    Rng r;
+    r.g0 = r.g1 = r.g2 = r.g3 = 0;
+    r.weyl = q[1], r.gamma = q[2], r.k1 = q[3];
+    r.lfsr = false;
+    Rng r2 = r;
+    o[0] = __float_as_uint(r.u01());
+    o[1] = (uint32_t)r2.randomInteger((int)q[4], (int)q[5]);
+    o[2] = __float_as_uint(r2.u01());
+    for (int k = 3; k < 20; k++)
+        o[k] = 0u;
+}
+
 // end-of-sample bookkeeping: fold the per-pass counters into 64-bit totals and zero the control
 // block for the next sample (replaces updateKernelData, kernel.cl:303-317, and the per-pass
 // blocking KernelData read-back of raytracer.cpp:381-389).

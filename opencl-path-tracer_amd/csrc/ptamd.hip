@@ -310,6 +310,25 @@ int pt_debug_math_probe(pt_ctx* c, const float* a, const float* b, uint32_t n, f
     });
 }
 
+// Test hook (tests/test_gpu_prng.py): k_rng_probe over n entries of eight words; `out` receives twenty words per entry (pt_shade.h).
+int pt_debug_rng_probe(pt_ctx* c, const uint32_t* in, uint32_t n, uint32_t* out)
+{
+    return guarded(c, "pt_debug_rng_probe", [&]() -> int {
+    if (!c || !in || !out || n == 0 || n > (1u << 24))
+        return PT_ERR_INVALID;
+    HIPCHK(c, hipSetDevice(c->device));
+    DevBuf<uint32_t> dIn, dOut;
+    HIPCHK(c, dIn.alloc((size_t)n * 8));
+    HIPCHK(c, dOut.alloc((size_t)n * 20));
+    HIPCHK(c, hipMemcpy(dIn.p, in, (size_t)n * 8 * sizeof(uint32_t), hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_rng_probe, dim3((n + 255u) / 256u), dim3(256), 0, c->stream, dIn.p, n, dOut.p);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpy(out, dOut.p, (size_t)n * 20 * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return PT_OK;
+    });
+}
+
 // Test hook, no device needed (tests/test_gpu_lifetime.py): what the owning types of pt_context.h hold alive in this process, all contexts and hooks together --
 // device allocations, pinned allocations, events, streams the library created.
 int pt_debug_live_resources(uint32_t out[4])

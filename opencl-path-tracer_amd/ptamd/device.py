@@ -98,7 +98,7 @@ EXPORTS = ["pt_create", "pt_destroy", "pt_last_error", "pt_set_stream", "pt_uplo
            "pt_read_motion_guides", "pt_write_motion_guides", "pt_motion_guides_device_ptr", "pt_debug_motion_records",
            "pt_set_vertex_motion", "pt_vertex_motion", "pt_debug_vertex_motion_rows", "pt_set_temporal_variance", "pt_temporal_variance",
            "pt_read_temporal_variance", "pt_write_temporal_variance", "pt_temporal_variance_device_ptr", "pt_stats_get", "pt_stats_reset", "pt_profile_kernels", "pt_reduce_accum",
-           "pt_intersect", "pt_gen_rays", "pt_primary_pass", "pt_shade_batch", "pt_debug_quantise_node", "pt_debug_convert", "pt_debug_copy_bandwidth", "pt_debug_math_probe", "pt_debug_live_resources",
+           "pt_intersect", "pt_gen_rays", "pt_primary_pass", "pt_shade_batch", "pt_debug_quantise_node", "pt_debug_convert", "pt_debug_copy_bandwidth", "pt_debug_math_probe", "pt_debug_rng_probe", "pt_debug_live_resources",
            "pt_version"]
 
 _lib = None
@@ -596,6 +596,18 @@ class Context:
         self._chk(lib().pt_debug_math_probe(self._h, _p(a), _p(b), len(a), _p(out)), "pt_debug_math_probe")
         return {"div": out[0], "fast_div": out[1], "sqrt": out[2], "fast_sqrt": out[3],
                 "normalize": np.ascontiguousarray(out[4:7].T), "fast_normalize": np.ascontiguousarray(out[7:10].T)}
+
+    def debug_rng_probe(self, entries):
+        """The production PRNG (csrc/pt_math.h) on the device (pt_debug_rng_probe).  entries: (n, 8) uint32 -- [0, pixel, sample, seed, depth, ...] for 20
+        successive draws of that stage's generator, [1, weyl, gamma, k1, i, j, ...] for one draw of a raw state and the integer in [i, j] it selects.
+        Returns (n, 20) uint32: the float bits of the draws (keyed), or [draw bits, integer, bits of the following draw, 0 ...] (raw)."""
+        entries = np.ascontiguousarray(entries, np.uint32)
+        if entries.ndim != 2 or entries.shape[1] != 8 or len(entries) == 0:
+            raise ValueError("debug_rng_probe: entries must be a non-empty (n, 8) uint32 array")
+        out = np.zeros((len(entries), 20), np.uint32)
+        lib().pt_debug_rng_probe.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
+        self._chk(lib().pt_debug_rng_probe(self._h, _p(entries), len(entries), _p(out)), "pt_debug_rng_probe")
+        return out
 
     def reset_stats(self):
         self._chk(lib().pt_stats_reset(self._h), "pt_stats_reset")

@@ -205,6 +205,17 @@ inline float counterU01(const CounterKey& k, uint32_t depth, uint32_t dim)
     return (float)(x >> 8) * (1.0f / 16777216.0f); // [0,1)
 }
 
+// The most counter-mode draws any one stage (one Rng: one depth of one path) has made in this process since the last
+// orc_counter_stage_draws_reset: a stage owns 16 draw slots (ctr = depth * 16 + dim + 1), and a 17th draw would be the next
+// depth's first.  tests/test_prng_cpu.py holds the mark at <= 16 over every integrator, light choice and camera.
+std::atomic<uint32_t> g_stageDrawsMax { 0 };
+inline void noteStageDraws(uint32_t draws)
+{
+    uint32_t seen = g_stageDrawsMax.load(std::memory_order_relaxed);
+    while (draws > seen && !g_stageDrawsMax.compare_exchange_weak(seen, draws, std::memory_order_relaxed)) {
+    }
+}
+
 struct Rng {
     int mode;
     uint32_t g[4]; // LFSR113 state
@@ -214,7 +225,9 @@ struct Rng {
     {
         if (mode == ORC_RNG_LFSR113) // (float)(z * 2.3283063e-10), the constant is a double literal (lfsr113.c.h:41-42,87-89)
             return (float)((double)lfsrNext(g) * 2.3283063e-10);
-        return counterU01(key, depth, dim++);
+        const float u = counterU01(key, depth, dim++);
+        noteStageDraws(dim);
+        return u;
     }
     // clrngLfsr113RandomInteger (lfsr113.c.h:91-93): i + (int)((j-i+1) * U01); U01 may be 1.0f in
     // LFSR mode -- reproduced; the counter PRNG is < 1 and additionally clamped.
@@ -1037,6 +1050,9 @@ float orc_counter_u01(uint32_t pixel, uint32_t sample, uint32_t depth, uint32_t 
 {
     return counterU01(counterKey(pixel, sample, seed), depth, dim);
 }
+
+void orc_counter_stage_draws_reset(void) { g_stageDrawsMax.store(0, std::memory_order_relaxed); }
+uint32_t orc_counter_stage_draws_max(void) { return g_stageDrawsMax.load(std::memory_order_relaxed); }
 
 // kernel.cl:24-84
 void orc_generatePrimaryRays(size_t global, OrcRayData* outRays, OrcKernelData* kd, void* streams, const OrcParams* p)

@@ -110,6 +110,9 @@ struct OrcCounters {
 void orc_lfsr113_create_streams(uint32_t count, void* streams48); // src/lfsr113.c:183-290
 float orc_lfsr113_u01(void* stream48); // private/lfsr113.c.h:61-89
 float orc_counter_u01(uint32_t pixel, uint32_t sample, uint32_t depth, uint32_t dim, uint32_t seed);
+// high-water mark of counter-mode draws made by one stage (one depth of one path), process-wide, over every render since the reset
+void orc_counter_stage_draws_reset(void);
+uint32_t orc_counter_stage_draws_max(void);
 
 // ---- kernels (serial, gid order) -----------------------------------------------------------
 void orc_generatePrimaryRays(size_t global, OrcRayData* outRays, OrcKernelData* kd, void* streams, const OrcParams* p);

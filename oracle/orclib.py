@@ -80,6 +80,10 @@ def oracle(fast=False):
     lib.orc_lfsr113_u01.restype = C.c_float
     lib.orc_counter_u01.restype = C.c_float
     lib.orc_counter_u01.argtypes = [C.c_uint32] * 5
+    lib.orc_counter_stage_draws_reset.restype = None
+    lib.orc_counter_stage_draws_reset.argtypes = []
+    lib.orc_counter_stage_draws_max.restype = C.c_uint32
+    lib.orc_counter_stage_draws_max.argtypes = []
     return lib
 
 
