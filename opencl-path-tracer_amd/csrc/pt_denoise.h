@@ -155,25 +155,68 @@ __global__ void __launch_bounds__(256) k_guides(SceneDev sc, const float4* __res
 }
 
 // ---- filter -------------------------------------------------------------------------------------
+constexpr uint32_t kInputAccum = 0, kInputTemporal = 1, kInputTemporalVariance = 2; // PT_DENOISE_INPUT_*
+
 __device__ inline float luminance709(float r, float g, float b) { return 0.2126f * r + 0.7152f * g + 0.0722f * b; }
 __device__ inline float albedoOf(float sum, float gspp) { return fmaxf(sum / gspp, kAlbedoFloor); }
 
-// mean, demodulation and guide normalisation in one pass over the three inputs:
-//   colour = (c / max(a, 1e-3), luminance of that)   c = accum.rgb / spp, a = albedo sum / gspp
-//   guide  = (n, z)                                   n = normal sum normalised (zero stays zero), z = distance sum / gspp
-// so that a tap of the filter costs two 16-byte loads.
-__global__ void __launch_bounds__(256) k_denoise_prepare(const float4* __restrict__ accum, const float4* __restrict__ albedoHits,
-    const float4* __restrict__ normalDepth, float4* __restrict__ colour, float4* __restrict__ guide, uint32_t n, float spp, float gspp)
+// d = c / max(a, 1e-3):   c = accum.rgb / spp, a = albedo sum / gspp
+__device__ inline V3 demodulatedMean(float4 s, float4 al, float spp, float gspp)
+{
+    return mk(s.x / spp / albedoOf(al.x, gspp), s.y / spp / albedoOf(al.y, gspp), s.z / spp / albedoOf(al.z, gspp));
+}
+
+// (n, z):   n = normal sum normalised (zero stays zero), z = distance sum / gspp
+__device__ inline float4 guideOf(float4 g, float gspp)
+{
+    const float len = sqrtf(g.x * g.x + g.y * g.y + g.z * g.z);
+    const float inv = len > 0.0f ? 1.0f / len : 0.0f;
+    return make_float4(g.x * inv, g.y * inv, g.z * inv, g.w / gspp);
+}
+
+// e_n + e_z of a tap whose guide is gq, seen from a surface of normal n at distance z (include/ptamd.h has the terms)
+__device__ inline float guideTerms(V3 n, float z, float4 gq, float kNormal, float invSigmaDepth)
+{
+    const float en = kNormal * fmaxf(0.0f, 1.0f - (n.x * gq.x + n.y * gq.y + n.z * gq.z));
+    const float ez = fabsf(z - gq.w) * invSigmaDepth / (fminf(z, gq.w) + 1e-6f);
+    return en + ez;
+}
+
+// the output pixel of a demodulated colour: times the current albedo, linear or through pt_resolve's tone curve
+__device__ inline float4 remodulated(float r, float g, float b, float4 al, float gspp, bool tonemapped, float relativeAperture, float shutterTime, float ISO)
+{
+    r *= albedoOf(al.x, gspp), g *= albedoOf(al.y, gspp), b *= albedoOf(al.z, gspp);
+    if (tonemapped) {
+        const float exposure = resolveExposure(relativeAperture, shutterTime, ISO);
+        r = resolveChannel(r * exposure), g = resolveChannel(g * exposure), b = resolveChannel(b * exposure);
+    }
+    return make_float4(r, g, b, 1.0f);
+}
+
+// d0 and the guide normalisation in one pass over the inputs, so that a tap of the filter costs two 16-byte loads:
+//   colour = (d0, its fourth component)    guide = guideOf(normal_depth)
+//   PT_DENOISE_INPUT_ACCUM              d0 = demodulatedMean(accum, albedo sums),   the luminance of d0
+//   PT_DENOISE_INPUT_TEMPORAL           d0 = the newest history's d,                the luminance of d0
+//   PT_DENOISE_INPUT_TEMPORAL_VARIANCE  the same d0,                                V_0 = v / max(N, 1): the variance of the history's MEAN
+template <uint32_t INPUT>
+__global__ void __launch_bounds__(256) k_denoise_prepare(const float4* __restrict__ source, const float* __restrict__ histVariance,
+    const float4* __restrict__ albedoHits, const float4* __restrict__ normalDepth, float4* __restrict__ colour, float4* __restrict__ guide, uint32_t n,
+    float spp, float gspp)
 {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n)
         return;
-    const float4 s = accum[i], a = albedoHits[i], g = normalDepth[i];
-    const float r = s.x / spp / albedoOf(a.x, gspp), gr = s.y / spp / albedoOf(a.y, gspp), b = s.z / spp / albedoOf(a.z, gspp);
-    colour[i] = make_float4(r, gr, b, luminance709(r, gr, b));
-    const float len = sqrtf(g.x * g.x + g.y * g.y + g.z * g.z);
-    const float inv = len > 0.0f ? 1.0f / len : 0.0f;
-    guide[i] = make_float4(g.x * inv, g.y * inv, g.z * inv, g.w / gspp);
+    const float4 s = source[i], g = normalDepth[i];
+    V3 d = xyz(s);
+    if constexpr (INPUT == kInputAccum)
+        d = demodulatedMean(s, albedoHits[i], spp, gspp);
+    float fourth;
+    if constexpr (INPUT == kInputTemporalVariance)
+        fourth = histVariance[i] / fmaxf(s.w, 1.0f);
+    else
+        fourth = luminance709(d.x, d.y, d.z);
+    colour[i] = make_float4(d.x, d.y, d.z, fourth);
+    guide[i] = guideOf(g, gspp);
 }
 
 // iterations == 0, linear output: the mean radiance as it is
@@ -188,7 +231,7 @@ __global__ void __launch_bounds__(256) k_denoise_mean(const float4* __restrict__
 
 enum : uint32_t { ATROUS_MORE = 0, ATROUS_LAST_HDR = 1, ATROUS_LAST_TONEMAPPED = 2 };
 struct AtrousArgs {
-    const float4* colour; // d_i.rgb, luminance
+    const float4* colour; // (d_i.rgb, luminance); VARIANCE: (d_i.rgb, V_i), the variance of d_i's luminance
     const float4* guide; // n.xyz, z
     float4* out; // d_{i+1} in the same form, or the final image
     const float4* albedoHits; // last iteration: re-modulation
@@ -198,6 +241,10 @@ struct AtrousArgs {
     uint32_t mode; // ATROUS_*
     float gspp;
     float relativeAperture, shutterTime, ISO; // ATROUS_LAST_TONEMAPPED
+    // VARIANCE (pt_set_temporal_variance; include/ptamd.h, "temporal variance")
+    const float4* history; // (d.rgb, N) of the newest history set: s(p) comes from its count
+    float sigmaVariance, relativeFloor;
+    float invFullHistory; // 1 / (full_history - 1)
 };
 
 constexpr int kAtrousTileW = 32, kAtrousTileH = 8; // 256 threads; a wave is two rows of 32 pixels
@@ -211,7 +258,17 @@ constexpr int kAtrousLdsW = kAtrousTileW + 2 * kAtrousMaxHalo, kAtrousLdsH = kAt
 // translates) lie in ONE row of 32 consecutive float4, i.e. on 16 different 16-byte slots of the 256-byte bank row whatever the pitch -- no conflicts,
 // no padding.  Steps >= 4 would need a halo larger than the tile: their taps are global loads (strided gathers over two images of 15-33 MB, served
 // by L2 / the memory-side cache).
-template <bool STEP_IN_LDS>
+// VARIANCE: the filter over the temporal history.  The luminance term moves from the relative one to a variance one as the pixel's history grows,
+// s(p) = clamp((N(p) - 1) / (full_history - 1), 0, 1):
+//   e_l = s e_var + (1 - s) e_plain,   e_var = |L_p - L_q| / (sigma_variance g(p) + relative_floor (max(L_p, L_q) + 1e-3)),   e_plain = the plain e_l
+//   g(p)^2 = the 3 x 3 binomial mean of V_i over the neighbours at distance 1 inside the image, whatever the step
+//   d_{i+1}(p) = sum w d_i(q) / sum w,   V_{i+1}(p) = sum w^2 V_i(q) / (sum w)^2
+// A tap stays two 16-byte loads: the luminance is recomputed per tap (three FMAs), the fourth component carries V.  STEP_IN_LDS: V is staged a second
+// time as a plane of floats, from which the 3 x 3 comes (the halo is at least 2) -- nine ds_read_b32 at [row][x + const], 32 consecutive dwords per lane
+// group and so on 32 different banks; the same reads out of the float4 image would be 16 bytes apart, four lanes to a bank (MI355X_MICROARCH.md, LDS).
+// Steps >= 4: nine adjacent 4-byte global reads beside the 50 16-byte ones.  That plane is the guided instantiation's alone: 23 040 B of LDS against the
+// plain one's 20 480, which is exactly 8 workgroups in a CU's 160 KB.
+template <bool STEP_IN_LDS, bool VARIANCE = false>
 __global__ void __launch_bounds__(256) k_atrous(AtrousArgs a)
 {
     const int tx = threadIdx.x, ty = threadIdx.y;
@@ -219,104 +276,8 @@ __global__ void __launch_bounds__(256) k_atrous(AtrousArgs a)
     const int W = (int)a.width, H = (int)a.height;
     __shared__ float4 ldsC[STEP_IN_LDS ? kAtrousLdsH * kAtrousLdsW : 1];
     __shared__ float4 ldsG[STEP_IN_LDS ? kAtrousLdsH * kAtrousLdsW : 1];
-    const int halo = 2 * a.step, pitch = kAtrousTileW + 2 * halo;
-    if constexpr (STEP_IN_LDS) {
-        const int rows = kAtrousTileH + 2 * halo, x0 = (int)blockIdx.x * kAtrousTileW - halo, y0 = (int)blockIdx.y * kAtrousTileH - halo;
-        for (int e = ty * kAtrousTileW + tx; e < rows * pitch; e += kAtrousTileW * kAtrousTileH) {
-            const int ly = e / pitch, lx = e - ly * pitch;
-            const int gx = x0 + lx, gy = y0 + ly;
-            float4 c = make_float4(0.f, 0.f, 0.f, 0.f), g = c; // outside the image: never read (the tap loop skips those)
-            if (gx >= 0 && gx < W && gy >= 0 && gy < H) {
-                c = a.colour[(size_t)gy * W + gx];
-                g = a.guide[(size_t)gy * W + gx];
-            }
-            ldsC[e] = c;
-            ldsG[e] = g;
-        }
-        __syncthreads();
-    }
-    if (x >= W || y >= H)
-        return;
-    const size_t p = (size_t)y * W + x;
-    float4 cp, gp;
-    if constexpr (STEP_IN_LDS) {
-        cp = ldsC[(ty + halo) * pitch + tx + halo];
-        gp = ldsG[(ty + halo) * pitch + tx + halo];
-    } else {
-        cp = a.colour[p];
-        gp = a.guide[p];
-    }
-    const float kern[5] = { 1.0f / 16.0f, 1.0f / 4.0f, 3.0f / 8.0f, 1.0f / 4.0f, 1.0f / 16.0f };
-    float sr = 0.f, sg = 0.f, sb = 0.f, sw = 0.f;
-#pragma unroll
-    for (int dy = -2; dy <= 2; dy++) {
-        const int qy = y + dy * a.step;
-        if (qy < 0 || qy >= H)
-            continue;
-#pragma unroll
-        for (int dx = -2; dx <= 2; dx++) {
-            const int qx = x + dx * a.step;
-            if (qx < 0 || qx >= W)
-                continue;
-            float4 cq, gq;
-            if constexpr (STEP_IN_LDS) {
-                const int e = (ty + halo + dy * a.step) * pitch + tx + halo + dx * a.step;
-                cq = ldsC[e];
-                gq = ldsG[e];
-            } else {
-                cq = a.colour[(size_t)qy * W + qx];
-                gq = a.guide[(size_t)qy * W + qx];
-            }
-            const float en = a.kNormal * fmaxf(0.0f, 1.0f - (gp.x * gq.x + gp.y * gq.y + gp.z * gq.z));
-            const float ez = fabsf(gp.w - gq.w) * a.invSigmaDepth / (fminf(gp.w, gq.w) + 1e-6f);
-            const float el = fabsf(cp.w - cq.w) * a.invSigmaLum / (fmaxf(cp.w, cq.w) + 1e-3f);
-            const float w = kern[dy + 2] * kern[dx + 2] * __expf(-(en + ez + el));
-            sr += w * cq.x, sg += w * cq.y, sb += w * cq.z, sw += w;
-        }
-    }
-    // (the centre tap has w = k(0): sw >= 9/64)
-    float r = sr / sw, g = sg / sw, b = sb / sw;
-    if (a.mode == ATROUS_MORE) {
-        a.out[p] = make_float4(r, g, b, luminance709(r, g, b));
-        return;
-    }
-    const float4 al = a.albedoHits[p];
-    r *= albedoOf(al.x, a.gspp), g *= albedoOf(al.y, a.gspp), b *= albedoOf(al.z, a.gspp);
-    if (a.mode == ATROUS_LAST_TONEMAPPED) {
-        const float exposure = resolveExposure(a.relativeAperture, a.shutterTime, a.ISO);
-        r = resolveChannel(r * exposure), g = resolveChannel(g * exposure), b = resolveChannel(b * exposure);
-    }
-    a.out[p] = make_float4(r, g, b, 1.0f);
-}
-
-// ---- variance-guided filter (pt_set_temporal_variance; include/ptamd.h, "temporal variance") ------
-struct AtrousVarArgs {
-    AtrousArgs f; // k_atrous' own; colour and out hold (d_i.rgb, V_i): the variance of d_i's luminance where k_atrous keeps the luminance itself
-    const float4* history; // (d.rgb, N) of the newest history set: s(p) comes from its count
-    float sigmaVariance, relativeFloor;
-    float invFullHistory; // 1 / (full_history - 1)
-};
-
-// One iteration of the filter over the temporal history, on k_atrous' tiles and with its taps, kernel and guide terms.  The luminance term moves from
-// k_atrous' relative one to a variance one as the pixel's history grows, s(p) = clamp((N(p) - 1) / (full_history - 1), 0, 1):
-//   e_l = s e_var + (1 - s) e_plain,   e_var = |L_p - L_q| / (sigma_variance g(p) + relative_floor (max(L_p, L_q) + 1e-3)),   e_plain = k_atrous' e_l
-//   g(p)^2 = the 3 x 3 binomial mean of V_i over the neighbours at distance 1 inside the image, whatever the step
-//   d_{i+1}(p) = sum w d_i(q) / sum w,   V_{i+1}(p) = sum w^2 V_i(q) / (sum w)^2
-// A tap stays two 16-byte loads: the luminance is recomputed per tap (three FMAs), the fourth component carries V.  STEP_IN_LDS: V is staged a second
-// time as a plane of floats, from which the 3 x 3 comes (the halo is at least 2) -- nine ds_read_b32 at [row][x + const], 32 consecutive dwords per lane
-// group and so on 32 different banks; the same reads out of the float4 image would be 16 bytes apart, four lanes to a bank (MI355X_MICROARCH.md, LDS).
-// Steps >= 4: nine adjacent 4-byte global reads beside the 50 16-byte ones.
-template <bool STEP_IN_LDS>
-__global__ void __launch_bounds__(256) k_atrous_var(AtrousVarArgs v)
-{
-    const AtrousArgs& a = v.f;
-    const int tx = threadIdx.x, ty = threadIdx.y;
-    const int x = blockIdx.x * kAtrousTileW + tx, y = blockIdx.y * kAtrousTileH + ty;
-    const int W = (int)a.width, H = (int)a.height;
-    __shared__ float4 ldsC[STEP_IN_LDS ? kAtrousLdsH * kAtrousLdsW : 1];
-    __shared__ float4 ldsG[STEP_IN_LDS ? kAtrousLdsH * kAtrousLdsW : 1];
-    __shared__ float ldsV[STEP_IN_LDS ? kAtrousLdsH * kAtrousLdsW : 1];
-    const int halo = 2 * a.step, pitch = kAtrousTileW + 2 * halo; // (the launch keeps halo <= kAtrousMaxHalo for this variant)
+    __shared__ float ldsV[STEP_IN_LDS && VARIANCE ? kAtrousLdsH * kAtrousLdsW : 1];
+    const int halo = 2 * a.step, pitch = kAtrousTileW + 2 * halo; // (the launch keeps halo <= kAtrousMaxHalo for STEP_IN_LDS)
     if constexpr (STEP_IN_LDS) {
         const int rows = kAtrousTileH + 2 * halo, x0 = (int)blockIdx.x * kAtrousTileW - halo, y0 = (int)blockIdx.y * kAtrousTileH - halo;
         for (int e = ty * kAtrousTileW + tx; e < rows * pitch; e += kAtrousTileW * kAtrousTileH) {
@@ -329,14 +290,17 @@ __global__ void __launch_bounds__(256) k_atrous_var(AtrousVarArgs v)
             }
             ldsC[e] = c;
             ldsG[e] = g;
-            ldsV[e] = c.w;
+            if constexpr (VARIANCE)
+                ldsV[e] = c.w;
         }
         __syncthreads();
     }
     if (x >= W || y >= H)
         return;
     const size_t p = (size_t)y * W + x;
-    const float count = v.history[p].w;
+    float count;
+    if constexpr (VARIANCE)
+        count = a.history[p].w;
     float4 cp, gp;
     if constexpr (STEP_IN_LDS) {
         cp = ldsC[(ty + halo) * pitch + tx + halo];
@@ -345,31 +309,34 @@ __global__ void __launch_bounds__(256) k_atrous_var(AtrousVarArgs v)
         cp = a.colour[p];
         gp = a.guide[p];
     }
-    const float bin[3] = { 0.25f, 0.5f, 0.25f };
-    float nv = 0.f, nk = 0.f;
+    float lp = cp.w, sigmaG, s;
+    if constexpr (VARIANCE) {
+        const float bin[3] = { 0.25f, 0.5f, 0.25f };
+        float nv = 0.f, nk = 0.f;
 #pragma unroll
-    for (int dy = -1; dy <= 1; dy++) {
-        const int qy = y + dy;
-        if (qy < 0 || qy >= H)
-            continue;
-#pragma unroll
-        for (int dx = -1; dx <= 1; dx++) {
-            const int qx = x + dx;
-            if (qx < 0 || qx >= W)
+        for (int dy = -1; dy <= 1; dy++) {
+            const int qy = y + dy;
+            if (qy < 0 || qy >= H)
                 continue;
-            float vq;
-            if constexpr (STEP_IN_LDS)
-                vq = ldsV[(ty + halo + dy) * pitch + tx + halo + dx];
-            else
-                vq = a.colour[(size_t)qy * W + qx].w;
-            const float k = bin[dy + 1] * bin[dx + 1];
-            nv += k * vq, nk += k;
+#pragma unroll
+            for (int dx = -1; dx <= 1; dx++) {
+                const int qx = x + dx;
+                if (qx < 0 || qx >= W)
+                    continue;
+                float vq;
+                if constexpr (STEP_IN_LDS)
+                    vq = ldsV[(ty + halo + dy) * pitch + tx + halo + dx];
+                else
+                    vq = a.colour[(size_t)qy * W + qx].w;
+                const float k = bin[dy + 1] * bin[dx + 1];
+                nv += k * vq, nk += k;
+            }
         }
+        // (the centre counts with 1/4: nk >= 1/4)
+        sigmaG = a.sigmaVariance * sqrtf(nv / nk);
+        s = fminf(fmaxf((count - 1.0f) * a.invFullHistory, 0.0f), 1.0f);
+        lp = luminance709(cp.x, cp.y, cp.z);
     }
-    // (the centre counts with 1/4: nk >= 1/4)
-    const float sigmaG = v.sigmaVariance * sqrtf(nv / nk);
-    const float s = fminf(fmaxf((count - 1.0f) * v.invFullHistory, 0.0f), 1.0f);
-    const float lp = luminance709(cp.x, cp.y, cp.z);
     const float kern[5] = { 1.0f / 16.0f, 1.0f / 4.0f, 3.0f / 8.0f, 1.0f / 4.0f, 1.0f / 16.0f };
     float sr = 0.f, sg = 0.f, sb = 0.f, sv = 0.f, sw = 0.f;
 #pragma unroll
@@ -391,30 +358,27 @@ __global__ void __launch_bounds__(256) k_atrous_var(AtrousVarArgs v)
                 cq = a.colour[(size_t)qy * W + qx];
                 gq = a.guide[(size_t)qy * W + qx];
             }
-            const float lq = luminance709(cq.x, cq.y, cq.z);
-            const float en = a.kNormal * fmaxf(0.0f, 1.0f - (gp.x * gq.x + gp.y * gq.y + gp.z * gq.z));
-            const float ez = fabsf(gp.w - gq.w) * a.invSigmaDepth / (fminf(gp.w, gq.w) + 1e-6f);
+            float lq = cq.w;
+            if constexpr (VARIANCE)
+                lq = luminance709(cq.x, cq.y, cq.z);
+            const float eg = guideTerms(xyz(gp), gp.w, gq, a.kNormal, a.invSigmaDepth); // (stated before e_l: the instruction schedule follows this order)
             const float diff = fabsf(lp - lq), top = fmaxf(lp, lq) + 1e-3f;
-            const float ePlain = diff * a.invSigmaLum / top;
-            const float eVar = diff / (sigmaG + v.relativeFloor * top);
-            const float el = s * eVar + (1.0f - s) * ePlain;
-            const float w = kern[dy + 2] * kern[dx + 2] * __expf(-(en + ez + el));
-            sr += w * cq.x, sg += w * cq.y, sb += w * cq.z, sv += w * w * cq.w, sw += w;
+            float el = diff * a.invSigmaLum / top;
+            if constexpr (VARIANCE)
+                el = s * (diff / (sigmaG + a.relativeFloor * top)) + (1.0f - s) * el;
+            const float w = kern[dy + 2] * kern[dx + 2] * __expf(-(eg + el));
+            sr += w * cq.x, sg += w * cq.y, sb += w * cq.z, sw += w;
+            if constexpr (VARIANCE)
+                sv += w * w * cq.w;
         }
     }
     // (the centre tap has w = k(0): sw >= 9/64)
-    float r = sr / sw, g = sg / sw, b = sb / sw;
+    const float r = sr / sw, g = sg / sw, b = sb / sw;
     if (a.mode == ATROUS_MORE) {
-        a.out[p] = make_float4(r, g, b, sv / (sw * sw));
+        a.out[p] = make_float4(r, g, b, VARIANCE ? sv / (sw * sw) : luminance709(r, g, b));
         return;
     }
-    const float4 al = a.albedoHits[p];
-    r *= albedoOf(al.x, a.gspp), g *= albedoOf(al.y, a.gspp), b *= albedoOf(al.z, a.gspp);
-    if (a.mode == ATROUS_LAST_TONEMAPPED) {
-        const float exposure = resolveExposure(a.relativeAperture, a.shutterTime, a.ISO);
-        r = resolveChannel(r * exposure), g = resolveChannel(g * exposure), b = resolveChannel(b * exposure);
-    }
-    a.out[p] = make_float4(r, g, b, 1.0f);
+    a.out[p] = remodulated(r, g, b, a.albedoHits[p], a.gspp, a.mode == ATROUS_LAST_TONEMAPPED, a.relativeAperture, a.shutterTime, a.ISO);
 }
 
 } // namespace ptd

@@ -58,21 +58,15 @@ __global__ void __launch_bounds__(256) k_temporal(TemporalArgs a)
     float4 mv, pn;
     if constexpr (MOTION)
         mv = a.motion[p], pn = a.prevNormal[p];
-    // exactly k_denoise_prepare's quantities
-    const float dr = s.x / a.spp / albedoOf(al.x, a.gspp), dg = s.y / a.spp / albedoOf(al.y, a.gspp), db = s.z / a.spp / albedoOf(al.z, a.gspp);
-    const float len = sqrtf(g.x * g.x + g.y * g.y + g.z * g.z);
-    const float inv = len > 0.0f ? 1.0f / len : 0.0f;
-    const V3 n = mk(g.x * inv, g.y * inv, g.z * inv);
-    const float z = g.w / a.gspp;
-    a.outGuide[p] = make_float4(n.x, n.y, n.z, z);
-    V3 nThen = n; // what the history's normals are compared with
-    if constexpr (MOTION) {
-        const float lenT = sqrtf(pn.x * pn.x + pn.y * pn.y + pn.z * pn.z);
-        const float invT = lenT > 0.0f ? 1.0f / lenT : 0.0f;
-        nThen = mk(pn.x * invT, pn.y * invT, pn.z * invT);
-    }
+    const V3 d = demodulatedMean(s, al, a.spp, a.gspp);
+    const float4 nz = guideOf(g, a.gspp);
+    const float z = nz.w;
+    a.outGuide[p] = nz;
+    V3 nThen = xyz(nz); // what the history's normals are compared with
+    if constexpr (MOTION)
+        nThen = xyz(guideOf(pn, a.gspp));
 
-    float outR = dr, outG = dg, outB = db, outN = 1.0f;
+    float outR = d.x, outG = d.y, outB = d.z, outN = 1.0f;
     float outV = 0.0f;
     if (a.histColour) {
         // world point of the first hit through the pixel centre, then into the history's camera
@@ -116,9 +110,7 @@ __global__ void __launch_bounds__(256) k_temporal(TemporalArgs a)
                 if (counts) {
                     const float4 gh = a.histGuide[(size_t)(y0 + (t >> 1)) * W + (x0 + (t & 1))];
                     const float b = ((t & 1) ? ax : 1.0f - ax) * ((t >> 1) ? ay : 1.0f - ay);
-                    const float en = a.kNormal * fmaxf(0.0f, 1.0f - (nThen.x * gh.x + nThen.y * gh.y + nThen.z * gh.z));
-                    const float ez = fabsf(zq - gh.w) * a.invSigmaDepth / (fminf(zq, gh.w) + 1e-6f);
-                    w = b * __expf(-(en + ez));
+                    w = b * __expf(-guideTerms(nThen, zq, gh, a.kNormal, a.invSigmaDepth));
                 }
                 sr += w * (counts ? ch[t].x : 0.0f), sg += w * (counts ? ch[t].y : 0.0f), sb += w * (counts ? ch[t].z : 0.0f);
                 sn += w * (counts ? ch[t].w : 0.0f), sw += w;
@@ -128,9 +120,9 @@ __global__ void __launch_bounds__(256) k_temporal(TemporalArgs a)
             if (sw >= 1e-12f) {
                 const float hr = sr / sw, hg = sg / sw, hb = sb / sw;
                 outN = fminf(sn + 1.0f, a.maxHistory);
-                outR = hr + (dr - hr) / outN, outG = hg + (dg - hg) / outN, outB = hb + (db - hb) / outN;
+                outR = hr + (d.x - hr) / outN, outG = hg + (d.y - hg) / outN, outB = hb + (d.z - hb) / outN;
                 if constexpr (VARIANCE) {
-                    const float alpha = 1.0f / outN, delta = luminance709(dr, dg, db) - luminance709(hr, hg, hb);
+                    const float alpha = 1.0f / outN, delta = luminance709(d.x, d.y, d.z) - luminance709(hr, hg, hb);
                     outV = (1.0f - alpha) * (sv / sw + alpha * delta * delta);
                 }
             }
@@ -141,50 +133,15 @@ __global__ void __launch_bounds__(256) k_temporal(TemporalArgs a)
         a.outVariance[p] = outV;
 }
 
-// pt_denoise with PT_DENOISE_INPUT_TEMPORAL: k_denoise_prepare with d0 taken from the newest history; the guides are the current frame's
-__global__ void __launch_bounds__(256) k_denoise_prepare_temporal(const float4* __restrict__ histColour, const float4* __restrict__ normalDepth,
-    float4* __restrict__ colour, float4* __restrict__ guide, uint32_t n, float gspp)
-{
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n)
-        return;
-    const float4 h = histColour[i], g = normalDepth[i];
-    colour[i] = make_float4(h.x, h.y, h.z, luminance709(h.x, h.y, h.z));
-    const float len = sqrtf(g.x * g.x + g.y * g.y + g.z * g.z);
-    const float inv = len > 0.0f ? 1.0f / len : 0.0f;
-    guide[i] = make_float4(g.x * inv, g.y * inv, g.z * inv, g.w / gspp);
-}
-
-// pt_denoise with PT_DENOISE_INPUT_TEMPORAL_VARIANCE: the same with the variance of the history's MEAN, V_0 = v / max(N, 1), where the luminance was
-// (k_atrous_var recomputes that per tap)
-__global__ void __launch_bounds__(256) k_denoise_prepare_variance(const float4* __restrict__ histColour, const float* __restrict__ histVariance,
-    const float4* __restrict__ normalDepth, float4* __restrict__ colour, float4* __restrict__ guide, uint32_t n, float gspp)
-{
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n)
-        return;
-    const float4 h = histColour[i], g = normalDepth[i];
-    const float v = histVariance[i];
-    colour[i] = make_float4(h.x, h.y, h.z, v / fmaxf(h.w, 1.0f));
-    const float len = sqrtf(g.x * g.x + g.y * g.y + g.z * g.z);
-    const float inv = len > 0.0f ? 1.0f / len : 0.0f;
-    guide[i] = make_float4(g.x * inv, g.y * inv, g.z * inv, g.w / gspp);
-}
-
-// ... and its iterations == 0: the history re-modulated with the current albedo, linear or through pt_resolve's tone curve
+// pt_denoise over the history (PT_DENOISE_INPUT_TEMPORAL, _VARIANCE) with iterations == 0: the newest d re-modulated with the current albedo
 __global__ void __launch_bounds__(256) k_temporal_resolve(const float4* __restrict__ histColour, const float4* __restrict__ albedoHits,
     float4* __restrict__ out, uint32_t n, float gspp, uint32_t tonemapped, float relativeAperture, float shutterTime, float ISO)
 {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n)
         return;
-    const float4 h = histColour[i], al = albedoHits[i];
-    float r = h.x * albedoOf(al.x, gspp), g = h.y * albedoOf(al.y, gspp), b = h.z * albedoOf(al.z, gspp);
-    if (tonemapped) {
-        const float exposure = resolveExposure(relativeAperture, shutterTime, ISO);
-        r = resolveChannel(r * exposure), g = resolveChannel(g * exposure), b = resolveChannel(b * exposure);
-    }
-    out[i] = make_float4(r, g, b, 1.0f);
+    const float4 h = histColour[i];
+    out[i] = remodulated(h.x, h.y, h.z, albedoHits[i], gspp, tonemapped != 0u, relativeAperture, shutterTime, ISO);
 }
 
 } // namespace ptd

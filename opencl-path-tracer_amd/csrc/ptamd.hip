@@ -1279,6 +1279,33 @@ int pt_write_guides(pt_ctx* c, const float* albedo_hits, const float* normal_dep
 
 void* pt_guides_device_ptr(pt_ctx* c, int which) { return c && (which == 0 || which == 1) ? (void*)c->guides[which] : nullptr; }
 
+namespace {
+
+void resolveGuideSigmas(float k_normal, float sigma_depth, float* kNormal, float* invSigmaDepth) // 0 = the default, for the filter and the history's taps alike
+{
+    *kNormal = k_normal > 0.f ? k_normal : PT_DENOISE_DEFAULT_K_NORMAL;
+    *invSigmaDepth = 1.0f / (sigma_depth > 0.f ? sigma_depth : PT_DENOISE_DEFAULT_SIGMA_DEPTH);
+}
+
+// the run-time switches of a call to the instantiation that has them as template flags
+void launchPrepare(pt_ctx* c, uint32_t input, const float4* source, const float* variance, uint32_t n)
+{
+    const auto k = input == PT_DENOISE_INPUT_ACCUM ? k_denoise_prepare<PT_DENOISE_INPUT_ACCUM>
+        : (input == PT_DENOISE_INPUT_TEMPORAL ? k_denoise_prepare<PT_DENOISE_INPUT_TEMPORAL> : k_denoise_prepare<PT_DENOISE_INPUT_TEMPORAL_VARIANCE>);
+    hipLaunchKernelGGL(k, dim3((n + 255u) / 256u), dim3(256), 0, c->stream, source, variance, c->guides[0], c->guides[1], c->denoiseColour[0].p,
+        c->denoiseGuide.p, n, (float)c->spp, (float)c->guideSpp);
+}
+void launchAtrous(hipStream_t stream, dim3 grid, dim3 block, bool inLds, bool guided, const AtrousArgs& a)
+{
+    hipLaunchKernelGGL(inLds ? (guided ? k_atrous<true, true> : k_atrous<true>) : (guided ? k_atrous<false, true> : k_atrous<false>), grid, block, 0, stream, a);
+}
+void launchTemporal(hipStream_t stream, dim3 grid, dim3 block, bool moved, bool variance, const TemporalArgs& a)
+{
+    hipLaunchKernelGGL(moved ? (variance ? k_temporal<true, true> : k_temporal<true>) : (variance ? k_temporal<false, true> : k_temporal<false>), grid, block, 0, stream, a);
+}
+
+} // namespace
+
 int pt_denoise_device(pt_ctx* c, const pt_denoise_params* prm, void* device_rgba)
 {
     return guarded(c, "pt_denoise_device", [&]() -> int {
@@ -1330,24 +1357,16 @@ int pt_denoise_device(pt_ctx* c, const pt_denoise_params* prm, void* device_rgba
         HIPCHK(c, c->denoiseColour[1].alloc(n));
         HIPCHK(c, c->denoiseGuide.alloc(n));
     }
-    if (guided)
-        hipLaunchKernelGGL(k_denoise_prepare_variance, lin, dim3(256), 0, c->stream, history[0], c->temporalVariance[c->temporalNewest].p, c->guides[1],
-            c->denoiseColour[0].p, c->denoiseGuide.p, n, (float)c->guideSpp);
-    else if (temporal)
-        hipLaunchKernelGGL(k_denoise_prepare_temporal, lin, dim3(256), 0, c->stream, history[0], c->guides[1], c->denoiseColour[0].p, c->denoiseGuide.p, n,
-            (float)c->guideSpp);
-    else
-        hipLaunchKernelGGL(k_denoise_prepare, lin, dim3(256), 0, c->stream, c->accum, c->guides[0], c->guides[1], c->denoiseColour[0].p, c->denoiseGuide.p, n,
-            (float)c->spp, (float)c->guideSpp);
+    launchPrepare(c, prm->input, temporal ? history[0] : c->accum, guided ? c->temporalVariance[c->temporalNewest].p : nullptr, n);
     AtrousArgs a {};
     a.guide = c->denoiseGuide.p;
     a.albedoHits = c->guides[0];
     a.width = W, a.height = H;
-    a.kNormal = prm->k_normal > 0.f ? prm->k_normal : PT_DENOISE_DEFAULT_K_NORMAL;
-    a.invSigmaDepth = 1.0f / (prm->sigma_depth > 0.f ? prm->sigma_depth : PT_DENOISE_DEFAULT_SIGMA_DEPTH);
+    resolveGuideSigmas(prm->k_normal, prm->sigma_depth, &a.kNormal, &a.invSigmaDepth);
     const float sigmaLum = prm->sigma_lum > 0.f ? prm->sigma_lum : PT_DENOISE_DEFAULT_SIGMA_LUM;
     a.gspp = (float)c->guideSpp;
     a.relativeAperture = c->camera.relativeAperture, a.shutterTime = c->camera.shutterTime, a.ISO = c->camera.ISO;
+    a.history = history[0], a.sigmaVariance = c->sigmaVariance, a.relativeFloor = c->relativeFloor, a.invFullHistory = 1.0f / (c->fullHistory - 1.0f); // (guided)
     const dim3 grid((W + kAtrousTileW - 1) / kAtrousTileW, (H + kAtrousTileH - 1) / kAtrousTileH), block(kAtrousTileW, kAtrousTileH);
     for (uint32_t i = 0; i < prm->iterations; i++) {
         const bool last = i + 1u == prm->iterations;
@@ -1356,17 +1375,7 @@ int pt_denoise_device(pt_ctx* c, const pt_denoise_params* prm, void* device_rgba
         a.step = 1 << i;
         a.invSigmaLum = 1.0f / (sigmaLum * std::ldexp(1.0f, -(int)i));
         a.mode = !last ? ATROUS_MORE : (tonemapped ? ATROUS_LAST_TONEMAPPED : ATROUS_LAST_HDR);
-        const bool inLds = 2 * a.step <= kAtrousMaxHalo;
-        if (guided) {
-            const AtrousVarArgs v { a, history[0], c->sigmaVariance, c->relativeFloor, 1.0f / (c->fullHistory - 1.0f) };
-            if (inLds)
-                hipLaunchKernelGGL(k_atrous_var<true>, grid, block, 0, c->stream, v);
-            else
-                hipLaunchKernelGGL(k_atrous_var<false>, grid, block, 0, c->stream, v);
-        } else if (inLds)
-            hipLaunchKernelGGL(k_atrous<true>, grid, block, 0, c->stream, a);
-        else
-            hipLaunchKernelGGL(k_atrous<false>, grid, block, 0, c->stream, a);
+        launchAtrous(c->stream, grid, block, 2 * a.step <= kAtrousMaxHalo, guided, a);
     }
     HIPCHK(c, hipGetLastError());
     return PT_OK;
@@ -1456,8 +1465,7 @@ int pt_temporal_accumulate(pt_ctx* c, const pt_temporal_params* prm)
     a.outColour = c->temporal[to][0], a.outGuide = c->temporal[to][1];
     a.width = c->cfg.width, a.height = c->cfg.height;
     a.spp = (float)c->spp, a.gspp = (float)c->guideSpp;
-    a.kNormal = prm->k_normal > 0.f ? prm->k_normal : PT_DENOISE_DEFAULT_K_NORMAL;
-    a.invSigmaDepth = 1.0f / (prm->sigma_depth > 0.f ? prm->sigma_depth : PT_DENOISE_DEFAULT_SIGMA_DEPTH);
+    resolveGuideSigmas(prm->k_normal, prm->sigma_depth, &a.kNormal, &a.invSigmaDepth);
     a.maxHistory = (float)(prm->max_history ? prm->max_history : 32u);
     a.invW = 1.0f / (float)a.width, a.invH = 1.0f / (float)a.height;
     a.eye = xyz(c->camera.eye), a.screen = xyz(c->camera.screen), a.u = xyz(c->camera.u), a.v = xyz(c->camera.v);
@@ -1477,16 +1485,8 @@ int pt_temporal_accumulate(pt_ctx* c, const pt_temporal_params* prm)
     const bool moved = c->motionSet || c->vertexMotionSet; // the history is met where the surfaces were (the two sums are there: the setters made them)
     if (moved)
         a.motion = c->motionGuides[0], a.prevNormal = c->motionGuides[1];
-    if (c->varianceSet) { // the same arithmetic and one more plane
-        a.histVariance = c->temporalVariance[from].p, a.outVariance = c->temporalVariance[to].p;
-        if (moved)
-            hipLaunchKernelGGL((k_temporal<true, true>), grid, block, 0, c->stream, a);
-        else
-            hipLaunchKernelGGL((k_temporal<false, true>), grid, block, 0, c->stream, a);
-    } else if (moved)
-        hipLaunchKernelGGL(k_temporal<true>, grid, block, 0, c->stream, a);
-    else
-        hipLaunchKernelGGL(k_temporal<false>, grid, block, 0, c->stream, a);
+    a.histVariance = c->temporalVariance[from].p, a.outVariance = c->temporalVariance[to].p; // (varianceSet: the same arithmetic and one more plane)
+    launchTemporal(c->stream, grid, block, moved, c->varianceSet, a);
     HIPCHK(c, hipGetLastError());
     c->temporalCamera = c->camera;
     c->temporalNewest = to;
@@ -1537,7 +1537,7 @@ int pt_write_temporal(pt_ctx* c, const float* colour_count, const float* normal_
 
 void* pt_temporal_device_ptr(pt_ctx* c, int which) { return c && (which == 0 || which == 1) ? (void*)c->temporal[c->temporalNewest][which] : nullptr; }
 
-// ---- temporal variance (k_temporal<., true>, k_atrous_var) --------------------------------------
+// ---- temporal variance (k_temporal<., true>, k_atrous<., true>) ---------------------------------
 
 int pt_set_temporal_variance(pt_ctx* c, const pt_variance_params* prm)
 {

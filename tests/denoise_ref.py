@@ -10,6 +10,9 @@ ALBEDO_FLOOR = 1e-3
 KERNEL = (1.0 / 16.0, 1.0 / 4.0, 3.0 / 8.0, 1.0 / 4.0, 1.0 / 16.0)
 # the defaults of include/ptamd.h (PT_DENOISE_DEFAULT_*)
 K_NORMAL, SIGMA_DEPTH, SIGMA_LUM = 64.0, 0.05, 0.7
+# ... and of pt_variance_params
+SIGMA_VARIANCE, RELATIVE_FLOOR, FULL_HISTORY = 2.0, 0.1, 16.0
+BINOMIAL = (0.25, 0.5, 0.25)
 
 
 # ---------------------------------------------------------------- guide deposits
@@ -98,12 +101,17 @@ def luminance(rgb):
     return dt(0.2126) * rgb[..., 0] + dt(0.7152) * rgb[..., 1] + dt(0.0722) * rgb[..., 2]
 
 
-def tap_weight(n_p, n_q, z_p, z_q, l_p, l_q, i, k_normal, sigma_depth, sigma_lum):
-    """w_i(p, q) = exp(-(e_n + e_z + e_l)) of iteration i; arrays of one dtype, which the arithmetic stays in"""
+def tap_weight(n_p, n_q, z_p, z_q, l_p, l_q, i, k_normal, sigma_depth, sigma_lum, guided=None):
+    """w_i(p, q) = exp(-(e_n + e_z + e_l)) of iteration i; arrays of one dtype, which the arithmetic stays in.  guided: None, or
+    (s_p, sigma_variance g_p, relative_floor) of the variance-guided filter: e_l = s e_var + (1 - s) e_plain"""
     dt = z_p.dtype.type
     e_n = dt(k_normal) * np.maximum(dt(0), dt(1) - (n_p * n_q).sum(-1))
     e_z = np.abs(z_p - z_q) / (dt(sigma_depth) * (np.minimum(z_p, z_q) + dt(1e-6)))
-    e_l = np.abs(l_p - l_q) / (dt(sigma_lum) * dt(2.0 ** -i) * (np.maximum(l_p, l_q) + dt(1e-3)))
+    diff, top = np.abs(l_p - l_q), np.maximum(l_p, l_q) + dt(1e-3)
+    e_l = diff / (dt(sigma_lum) * dt(2.0 ** -i) * top)
+    if guided is not None:
+        s, sigma_g, relative_floor = guided
+        e_l = s * (diff / (sigma_g + relative_floor * top)) + (dt(1) - s) * e_l
     return np.exp(-(e_n + e_z + e_l))
 
 
@@ -120,15 +128,47 @@ def prepare(accum, spp, albedo_hits, normal_depth, gspp, dtype=np.float64):
     return c / a, a, n, z
 
 
-def atrous(d, n, z, iterations, k_normal=0.0, sigma_depth=0.0, sigma_lum=0.0):
-    """`iterations` passes of the 5 x 5 B3-spline filter with step doubling over d (H, W, 3) under the guides n (H, W, 3), z (H, W)"""
+def history_weight(count, full_history=0.0):
+    """s(p) = min((N - 1) / (full_history - 1), 1), and 0 below N = 1 (a count pt_temporal_accumulate never writes)"""
+    dt = count.dtype.type
+    return np.clip((count - dt(1)) / (dt(full_history or FULL_HISTORY) - dt(1)), dt(0), dt(1))
+
+
+def _neighbourhood(V):
+    """g^2: the 3 x 3 binomial mean of V over the neighbours at distance 1 inside the image"""
+    dt = V.dtype.type
+    H, W = V.shape
+    num, den = np.zeros_like(V), np.zeros_like(V)
+    for dy in (-1, 0, 1):
+        for dx in (-1, 0, 1):
+            if abs(dy) >= H or abs(dx) >= W:
+                continue
+            p = (slice(max(0, -dy), H - max(0, dy)), slice(max(0, -dx), W - max(0, dx)))
+            q = (slice(max(0, dy), H - max(0, -dy)), slice(max(0, dx), W - max(0, -dx)))
+            k = dt(BINOMIAL[dy + 1]) * dt(BINOMIAL[dx + 1])
+            num[p] += k * V[q]
+            den[p] += k
+    return num / den
+
+
+def atrous(d, n, z, iterations, k_normal=0.0, sigma_depth=0.0, sigma_lum=0.0, variance=None):
+    """`iterations` passes of the 5 x 5 B3-spline filter with step doubling over d (H, W, 3) under the guides n (H, W, 3), z (H, W).
+    variance: None, or (V, count, sigma_variance, relative_floor, full_history) -- the filter of PT_DENOISE_INPUT_TEMPORAL_VARIANCE, whose luminance
+    term moves from the relative one to the variance one as the history grows; V (H, W) is V_0, count (H, W) the history's N.  Returns (d, V) then."""
     k_normal, sigma_depth, sigma_lum = k_normal or K_NORMAL, sigma_depth or SIGMA_DEPTH, sigma_lum or SIGMA_LUM
     dt = d.dtype.type
     H, W = z.shape
+    guided = None
+    if variance is not None:
+        V, count, sigma_variance, relative_floor, full_history = variance
+        sigma_variance, relative_floor = dt(sigma_variance or SIGMA_VARIANCE), dt(relative_floor or RELATIVE_FLOOR)
+        hw = history_weight(count.astype(d.dtype), full_history)
     for i in range(iterations):
         s = 2 ** i
         lum = luminance(d)
         num, den = np.zeros_like(d), np.zeros_like(z)
+        if variance is not None:
+            g, num_v = np.sqrt(_neighbourhood(V)), np.zeros_like(z)
         for dy in range(-2, 3):
             for dx in range(-2, 3):
                 oy, ox = dy * s, dx * s
@@ -136,11 +176,17 @@ def atrous(d, n, z, iterations, k_normal=0.0, sigma_depth=0.0, sigma_lum=0.0):
                     continue
                 p = (slice(max(0, -oy), H - max(0, oy)), slice(max(0, -ox), W - max(0, ox)))
                 q = (slice(max(0, oy), H - max(0, -oy)), slice(max(0, ox), W - max(0, -ox)))
-                w = dt(KERNEL[dy + 2]) * dt(KERNEL[dx + 2]) * tap_weight(n[p], n[q], z[p], z[q], lum[p], lum[q], i, k_normal, sigma_depth, sigma_lum)
+                if variance is not None:
+                    guided = (hw[p], sigma_variance * g[p], relative_floor)
+                w = dt(KERNEL[dy + 2]) * dt(KERNEL[dx + 2]) * tap_weight(n[p], n[q], z[p], z[q], lum[p], lum[q], i, k_normal, sigma_depth, sigma_lum, guided)
                 num[p] += w[..., None] * d[q]
                 den[p] += w
+                if variance is not None:
+                    num_v[p] += w * w * V[q]
         d = num / den[..., None]
-    return d
+        if variance is not None:
+            V = num_v / (den * den)
+    return d if variance is None else (d, V)
 
 
 def denoise_hdr(accum, spp, albedo_hits, normal_depth, gspp, iterations, dtype=np.float64, **params):

@@ -1,7 +1,11 @@
 """Helpers shared by the GPU parity tests (all calls go through the C-ABI via ptamd.device)."""
+import re
+
 import numpy as np
+import pytest
 
 import orclib as O
+from ptamd import device
 
 
 def make_ctx(D, bundle_or_flat, width, height, camera=None, sky=None, tex=None, **kw):
@@ -304,3 +308,23 @@ def assert_hits_of_the_per_ray_kernel(got, want, what=""):
     assert np.allclose(got["t"][diff], want["t"][diff], rtol=1e-6), what
     for k in ("t", "u", "v"):
         assert np.array_equal(got[k][same].view(np.uint32), want[k][same].view(np.uint32)), (what, k)
+
+
+def status(fn):
+    """the status code of a call that must be refused (ptamd.device.PtError), with a message in pt_last_error"""
+    with pytest.raises(device.PtError) as e:
+        fn()
+    m = re.search(r"failed \((-?\d+)\): (.*)", str(e.value), re.S)
+    assert m and m.group(2).strip(), "a refusal carries a message in pt_last_error"
+    return int(m.group(1))
+
+
+def read_ppm(path):
+    data = open(path, "rb").read()
+    m = re.match(rb"P6\n(\d+) (\d+)\n255\n", data)
+    w, h = int(m.group(1)), int(m.group(2))
+    return np.frombuffer(data[m.end():], np.uint8).reshape(h, w, 3).astype(np.float64)
+
+
+def mean_abs_laplacian(img):
+    return float(np.abs(4 * img[1:-1, 1:-1] - img[:-2, 1:-1] - img[2:, 1:-1] - img[1:-1, :-2] - img[1:-1, 2:]).mean())

@@ -1,5 +1,5 @@
-"""numpy restatement of the instance motion (include/ptamd.h, "instance motion"): the host's record conversion, the two guide deposits and the
-motion-aware pt_temporal_accumulate, parameterised by dtype like temporal_ref -- float64 is the reference the device is held against, float32
+"""numpy restatement of the instance motion (include/ptamd.h, "instance motion"): the host's record conversion and the two guide deposits,
+parameterised by dtype like temporal_ref, whose accumulate takes the two motion sums -- float64 is the reference the device is held against, float32
 measures what single precision costs the same arithmetic on the same input.  Also the synthetic moved-sphere case the motion tests share."""
 import contextlib
 
@@ -12,81 +12,11 @@ SHIFT = np.array([0.25, 0.0, 0.1])  # the sphere's move between the history and 
 TURN = 0.5  # ... and, optionally, its turn about y (radians)
 
 
-# ---------------------------------------------------------------- the restatement of the accumulate
-def accumulate(accum, spp, albedo_hits, normal_depth, gspp, camera, history=None, motion=None, prev_normal=None, max_history=T.MAX_HISTORY,
-               k_normal=0.0, sigma_depth=0.0, dtype=np.float64):
-    """temporal_ref.accumulate with two more inputs, the (H, W, 4) motion and prev_normal sums: q = (X + m / gspp) - E', and the taps' normal term
-    compares with n_then, the prev_normal sum normalised by denoise_ref.prepare's own normalisation.  motion=None stands for zero motion sums and
-    prev_normal = normal_depth.xyz: temporal_ref.accumulate exactly."""
-    dt = dtype
-    k_normal, sigma_depth = dt(k_normal or R.K_NORMAL), dt(sigma_depth or R.SIGMA_DEPTH)
-    d, _, n, z = R.prepare(accum, spp, albedo_hits, normal_depth, gspp, dt)
-    H, W = z.shape
-    out_nd = np.concatenate([n, z[..., None]], -1)
-    if history is None:
-        return np.concatenate([d, np.ones((H, W, 1), dt)], -1), out_nd, np.zeros((H, W), dt)
-    if motion is None:
-        motion = np.zeros((H, W, 4), np.float32)
-        prev_normal = np.asarray(normal_depth, np.float32).reshape(H, W, 4)
-    m = np.asarray(motion).astype(dt).reshape(H, W, 4)[..., :3] / dt(gspp)
-    n_then = R.prepare(accum, spp, albedo_hits, np.asarray(prev_normal).reshape(H, W, 4), gspp, dt)[2]
-    hist_cn, hist_nd, hist_camera = history
-    hist_cn, hist_nd = np.asarray(hist_cn).astype(dt).reshape(H, W, 4), np.asarray(hist_nd).astype(dt).reshape(H, W, 4)
-    E, S, u, v = T.camera_vectors(camera, dt)
-    Eh, Sh, uh, vh = T.camera_vectors(hist_camera, dt)
-    yy, xx = np.mgrid[0:H, 0:W]
-    px = ((xx.astype(dt) + dt(0.5)) / dt(W))[..., None]
-    py = ((yy.astype(dt) + dt(0.5)) / dt(H))[..., None]
-    with np.errstate(all="ignore"):
-        dirv = S + u * px + v * py - E
-        D = dirv / np.sqrt(T._dot(dirv, dirv))[..., None]
-        X = E + z[..., None] * D
-        q = (X + m) - Eh
-        s0 = Sh - Eh
-        uxv = np.cross(uh, vh)
-        det = T._dot(s0, uxv)
-        lam = T._dot(q, uxv) / det
-        alpha = T._dot(s0, np.cross(q, vh)) / det
-        beta = T._dot(s0, np.cross(uh, q)) / det
-        front = lam > 0
-        lam = np.where(front, lam, dt(1))
-        fx = np.clip(dt(W) * alpha / lam - dt(0.5), dt(-2), dt(W + 1))
-        fy = np.clip(dt(H) * beta / lam - dt(0.5), dt(-2), dt(H + 1))
-        zq = np.sqrt(T._dot(q, q))
-        flx, fly = np.floor(fx), np.floor(fy)
-        x0, y0 = flx.astype(np.int64), fly.astype(np.int64)
-        ax, ay = fx - flx, fy - fly
-        sd, sn, sw = np.zeros((H, W, 3), dt), np.zeros((H, W), dt), np.zeros((H, W), dt)
-        for j in (0, 1):
-            for i in (0, 1):
-                tx, ty = x0 + i, y0 + j
-                inside = front & (tx >= 0) & (tx < W) & (ty >= 0) & (ty < H)
-                ch = hist_cn[np.clip(ty, 0, H - 1), np.clip(tx, 0, W - 1)]
-                gh = hist_nd[np.clip(ty, 0, H - 1), np.clip(tx, 0, W - 1)]
-                counts = inside & (ch[..., 3] > 0)
-                b = (ax if i else dt(1) - ax) * (ay if j else dt(1) - ay)
-                e_n = k_normal * np.maximum(dt(0), dt(1) - T._dot(n_then, gh[..., :3]))
-                e_z = np.abs(zq - gh[..., 3]) / (sigma_depth * (np.minimum(zq, gh[..., 3]) + dt(1e-6)))
-                w = np.where(counts, b * np.exp(-(e_n + e_z)), dt(0)).astype(dt)
-                sd += w[..., None] * ch[..., :3]
-                sn += w * ch[..., 3]
-                sw += w
-        use = sw >= dt(1e-12)
-        safe = np.where(use, sw, dt(1))
-        h = sd / safe[..., None]
-        N = np.minimum(sn + dt(1), dt(max_history))
-        d_out = np.where(use[..., None], h + (d - h) / N[..., None], d)
-        N_out = np.where(use, N, dt(1))
-    out = np.concatenate([d_out, N_out[..., None]], -1)
-    assert out.dtype == dt and out_nd.dtype == dt
-    return out, out_nd, sw
-
-
+# ---------------------------------------------------------------- the accumulate: temporal_ref.accumulate with its two motion inputs
 def run_case(case, dtype=np.float64, with_motion=True, **params):
     hist = (case["hist_cn"], case["hist_nd"], case["hist_camera"])
-    mo = (case["motion"], case["prev_normal"]) if with_motion else (None, None)
-    return accumulate(case["accum"], case["spp"], case["albedo_hits"], case["normal_depth"], case["gspp"], case["camera"], hist, mo[0], mo[1],
-                      dtype=dtype, **params)
+    mo = dict(motion=case["motion"], prev_normal=case["prev_normal"]) if with_motion else {}
+    return T.accumulate(case["accum"], case["spp"], case["albedo_hits"], case["normal_depth"], case["gspp"], case["camera"], hist, dtype=dtype, **mo, **params)
 
 
 def bound(case, **params):

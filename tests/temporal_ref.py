@@ -23,9 +23,14 @@ def _dot(a, b):
 
 
 def accumulate(accum, spp, albedo_hits, normal_depth, gspp, camera, history=None, max_history=MAX_HISTORY, k_normal=0.0, sigma_depth=0.0,
-               dtype=np.float64):
+               dtype=np.float64, motion=None, prev_normal=None, variance=False):
     """One pt_temporal_accumulate.  accum, albedo_hits, normal_depth: (H, W, 4) sums; history: None or (colour_count (H, W, 4),
-    normal_depth (H, W, 4), camera it was made under).  Returns (colour_count, normal_depth, Wsum), all of `dtype`."""
+    normal_depth (H, W, 4), camera it was made under).  Returns (colour_count, normal_depth, Wsum), all of `dtype`.
+    motion, prev_normal (include/ptamd.h, "instance motion"): the two (H, W, 4) motion sums -- q = (X + m / gspp) - E', and the taps' normal term
+    compares with n_then, the prev_normal sum normalised by denoise_ref.prepare's own normalisation.
+    variance (pt_set_temporal_variance): the history carries a fourth element, its variance plane (H, W), and the third result is the new plane
+        v_out = (1 - alpha) (v_h + alpha (l - mu)^2),  alpha = 1 / N_out,  l = L(d),  mu = L(h),  v_h = sum w v_tap / Wsum
+    over the colour's own taps and weights, 0 where the pixel found no history."""
     dt = dtype
     k_normal, sigma_depth = dt(k_normal or R.K_NORMAL), dt(sigma_depth or R.SIGMA_DEPTH)
     d, _, n, z = R.prepare(accum, spp, albedo_hits, normal_depth, gspp, dt)
@@ -33,8 +38,13 @@ def accumulate(accum, spp, albedo_hits, normal_depth, gspp, camera, history=None
     out_nd = np.concatenate([n, z[..., None]], -1)
     if history is None:
         return np.concatenate([d, np.ones((H, W, 1), dt)], -1), out_nd, np.zeros((H, W), dt)
-    hist_cn, hist_nd, hist_camera = history
+    hist_cn, hist_nd, hist_camera = history[:3]
     hist_cn, hist_nd = np.asarray(hist_cn).astype(dt).reshape(H, W, 4), np.asarray(hist_nd).astype(dt).reshape(H, W, 4)
+    hist_v = np.asarray(history[3]).astype(dt).reshape(H, W) if variance else np.zeros((H, W), dt)
+    n_then = n  # what the history's normals are compared with
+    if motion is not None:
+        m = np.asarray(motion).astype(dt).reshape(H, W, 4)[..., :3] / dt(gspp)
+        n_then = R.prepare(accum, spp, albedo_hits, np.asarray(prev_normal).reshape(H, W, 4), gspp, dt)[2]
     E, S, u, v = camera_vectors(camera, dt)
     Eh, Sh, uh, vh = camera_vectors(hist_camera, dt)
     yy, xx = np.mgrid[0:H, 0:W]
@@ -44,6 +54,8 @@ def accumulate(accum, spp, albedo_hits, normal_depth, gspp, camera, history=None
         dirv = S + u * px + v * py - E
         D = dirv / np.sqrt(_dot(dirv, dirv))[..., None]
         X = E + z[..., None] * D
+        if motion is not None:
+            X = X + m  # where the surface was
         q = X - Eh
         s0 = Sh - Eh
         uxv = np.cross(uh, vh)
@@ -59,20 +71,21 @@ def accumulate(accum, spp, albedo_hits, normal_depth, gspp, camera, history=None
         flx, fly = np.floor(fx), np.floor(fy)
         x0, y0 = flx.astype(np.int64), fly.astype(np.int64)
         ax, ay = fx - flx, fy - fly
-        sd, sn, sw = np.zeros((H, W, 3), dt), np.zeros((H, W), dt), np.zeros((H, W), dt)
+        sd, sn, sv, sw = np.zeros((H, W, 3), dt), np.zeros((H, W), dt), np.zeros((H, W), dt), np.zeros((H, W), dt)
         for j in (0, 1):
             for i in (0, 1):
                 tx, ty = x0 + i, y0 + j
                 inside = front & (tx >= 0) & (tx < W) & (ty >= 0) & (ty < H)
-                ch = hist_cn[np.clip(ty, 0, H - 1), np.clip(tx, 0, W - 1)]
-                gh = hist_nd[np.clip(ty, 0, H - 1), np.clip(tx, 0, W - 1)]
+                cy, cx = np.clip(ty, 0, H - 1), np.clip(tx, 0, W - 1)
+                ch, gh = hist_cn[cy, cx], hist_nd[cy, cx]
                 counts = inside & (ch[..., 3] > 0)
                 b = (ax if i else dt(1) - ax) * (ay if j else dt(1) - ay)
-                e_n = k_normal * np.maximum(dt(0), dt(1) - _dot(n, gh[..., :3]))
+                e_n = k_normal * np.maximum(dt(0), dt(1) - _dot(n_then, gh[..., :3]))
                 e_z = np.abs(zq - gh[..., 3]) / (sigma_depth * (np.minimum(zq, gh[..., 3]) + dt(1e-6)))
                 w = np.where(counts, b * np.exp(-(e_n + e_z)), dt(0)).astype(dt)
                 sd += w[..., None] * ch[..., :3]
                 sn += w * ch[..., 3]
+                sv += w * hist_v[cy, cx]
                 sw += w
         use = sw >= dt(1e-12)
         safe = np.where(use, sw, dt(1))
@@ -80,9 +93,11 @@ def accumulate(accum, spp, albedo_hits, normal_depth, gspp, camera, history=None
         N = np.minimum(sn + dt(1), dt(max_history))
         d_out = np.where(use[..., None], h + (d - h) / N[..., None], d)
         N_out = np.where(use, N, dt(1))
+        a, delta = dt(1) / N_out, R.luminance(d) - R.luminance(h)
+        v_out = np.where(use, (dt(1) - a) * (sv / safe + a * delta * delta), dt(0))
     out = np.concatenate([d_out, N_out[..., None]], -1)
-    assert out.dtype == dt and out_nd.dtype == dt
-    return out, out_nd, sw
+    assert out.dtype == dt and out_nd.dtype == dt and v_out.dtype == dt
+    return out, out_nd, (v_out if variance else sw)
 
 
 # ---------------------------------------------------------------- the synthetic scene

@@ -1,7 +1,6 @@
 """The edge-avoiding a-trous denoiser on the device (pt_denoise, include/ptamd.h "guides and denoiser") against its numpy restatement
 (tests/denoise_ref.py): synthetic inputs through write_accum / write_guides, a rendered frame, the refusals, the C++ example."""
 import os
-import re
 import subprocess
 
 import numpy as np
@@ -139,28 +138,20 @@ def test_rendered_frame_zero_iterations_is_resolve_and_five_match_the_restatemen
     ctx.close()
 
 
-def _status(fn):
-    with pytest.raises(D.PtError) as e:
-        fn()
-    m = re.search(r"failed \((-?\d+)\): (.*)", str(e.value), re.S)
-    assert m and m.group(2).strip(), "a refusal carries a message in pt_last_error"
-    return int(m.group(1))
-
-
 def test_refusals_and_clear(gpu):
     INVALID, STATE, UNSUPPORTED = -1, -3, -4
     b = scenes.cornell_box(32, 32)
     ctx = U.make_ctx(gpu, b, 32, 32)
     ctx.render(1)
-    assert _status(lambda: ctx.denoise(3)) == STATE  # no guide sample yet
+    assert U.status(lambda: ctx.denoise(3)) == STATE  # no guide sample yet
     ctx.clear()
     ctx.render_guides(1)
-    assert _status(lambda: ctx.denoise(3)) == STATE  # no colour sample yet
+    assert U.status(lambda: ctx.denoise(3)) == STATE  # no colour sample yet
     ctx.render(1)
     assert ctx.denoise(3).shape == (32, 32, 4)
-    assert _status(lambda: ctx.denoise(7)) == INVALID
+    assert U.status(lambda: ctx.denoise(7)) == INVALID
     ctx.set_tiles([(0, 0, 16, 32)])
-    assert _status(lambda: ctx.denoise(3)) == UNSUPPORTED
+    assert U.status(lambda: ctx.denoise(3)) == UNSUPPORTED
     ctx.set_tiles([])
     ctx.clear()
     assert ctx.guide_samples == 0 and ctx.samples_per_pixel == 0
@@ -168,22 +159,11 @@ def test_refusals_and_clear(gpu):
     assert not a.any() and not g.any()
     ctx.close()
     parity = U.make_ctx(gpu, b, 32, 32, rng_mode=D.RNG_LFSR113_PARITY)
-    assert _status(lambda: parity.render_guides(1)) == UNSUPPORTED
+    assert U.status(lambda: parity.render_guides(1)) == UNSUPPORTED
     parity.close()
     bare = gpu.Context(32, 32)
-    assert _status(lambda: bare.render_guides(1)) == STATE  # no scene, no camera
+    assert U.status(lambda: bare.render_guides(1)) == STATE  # no scene, no camera
     bare.close()
-
-
-def _read_ppm(path):
-    data = open(path, "rb").read()
-    m = re.match(rb"P6\n(\d+) (\d+)\n255\n", data)
-    w, h = int(m.group(1)), int(m.group(2))
-    return np.frombuffer(data[m.end():], np.uint8).reshape(h, w, 3).astype(np.float64)
-
-
-def _mean_abs_laplacian(img):
-    return float(np.abs(4 * img[1:-1, 1:-1] - img[:-2, 1:-1] - img[2:, 1:-1] - img[1:-1, :-2] - img[1:-1, 2:]).mean())
 
 
 def test_cpp_denoise_example(gpu, tmp_path):
@@ -194,8 +174,8 @@ def test_cpp_denoise_example(gpu, tmp_path):
     assert r.returncode == 0, r.stderr
     fields = dict(kv.split("=") for kv in r.stdout.split() if "=" in kv)
     assert int(fields["spp"]) == 4 and int(fields["guide_samples"]) == 4 and 0.3 < float(fields["coverage"]) <= 1.0
-    a, b = _read_ppm(raw), _read_ppm(den)
+    a, b = U.read_ppm(raw), U.read_ppm(den)
     assert a.shape == b.shape == (256, 256, 3) and not np.array_equal(a, b)
-    la, lb = _mean_abs_laplacian(a), _mean_abs_laplacian(b)
+    la, lb = U.mean_abs_laplacian(a), U.mean_abs_laplacian(b)
     print(f"mean |Laplacian|: raw {la:.4f}, denoised {lb:.4f}")
     assert lb < la

@@ -3,7 +3,6 @@ restatement (tests/motion_ref.py): the motion-aware accumulate on the synthetic 
 sheared and non-uniformly scaled instances, a rendered moving instance, the refusals, the C++ example."""
 import math
 import os
-import re
 import subprocess
 
 import numpy as np
@@ -271,14 +270,6 @@ def test_a_rendered_moving_instance_keeps_its_history_with_motion(gpu):
 
 
 # ---------------------------------------------------------------- 5. refusals and lifetimes
-def _status(fn):
-    with pytest.raises(D.PtError) as e:
-        fn()
-    m = re.search(r"failed \((-?\d+)\): (.*)", str(e.value), re.S)
-    assert m and m.group(2).strip(), "a refusal carries a message in pt_last_error"
-    return int(m.group(1))
-
-
 def test_refusals_and_lifetimes(gpu):
     INVALID, STATE, UNSUPPORTED = -1, -3, -4
     flat = one_instance_flat()
@@ -286,23 +277,23 @@ def test_refusals_and_lifetimes(gpu):
     assert len(top) == 1
     bare = gpu.Context(16, 16)
     assert bare.instance_motion == (False, 0) and bare.motion_guides_device_ptr(0) == 0
-    assert _status(lambda: bare.set_instance_motion(top)) == STATE  # no dynamic state
+    assert U.status(lambda: bare.set_instance_motion(top)) == STATE  # no dynamic state
     bare.close()
     parity = U.make_ctx(gpu, flat, 16, 16, rng_mode=D.RNG_LFSR113_PARITY)
-    assert _status(lambda: parity.set_instance_motion(top)) == UNSUPPORTED
+    assert U.status(lambda: parity.set_instance_motion(top)) == UNSUPPORTED
     parity.close()
     refill = U.make_ctx(gpu, flat, 64, 64, max_active_rays=1024)
-    assert _status(lambda: refill.set_instance_motion(top)) == UNSUPPORTED
+    assert U.status(lambda: refill.set_instance_motion(top)) == UNSUPPORTED
     refill.close()
 
     ctx = U.make_ctx(gpu, flat, 16, 16, camera=scenes.cornell_box(16, 16).camera)
-    assert _status(lambda: ctx.set_instance_motion(np.zeros((2, 16), np.float32))) == INVALID  # not the state's node count
+    assert U.status(lambda: ctx.set_instance_motion(np.zeros((2, 16), np.float32))) == INVALID  # not the state's node count
     bad = top["invTransform"].copy()
     bad[0, 0:3] = 0.0
-    assert _status(lambda: ctx.set_instance_motion(bad)) == INVALID  # singular
+    assert U.status(lambda: ctx.set_instance_motion(bad)) == INVALID  # singular
     bad = top["invTransform"].copy()
     bad[0, 13] = np.nan
-    assert _status(lambda: ctx.set_instance_motion(bad)) == INVALID  # not finite
+    assert U.status(lambda: ctx.set_instance_motion(bad)) == INVALID  # not finite
     assert ctx.instance_motion == (False, 0)  # a refused call is no call
     was = top["invTransform"].copy()
     was[0, 12] += 0.25  # the box was a quarter to the side (in its own space)
@@ -313,8 +304,8 @@ def test_refusals_and_lifetimes(gpu):
     assert ctx.instance_motion == (True, 0)
     ctx.set_instance_motion(was)
     ctx.render_guides(1)
-    assert _status(lambda: ctx.set_instance_motion(was)) == STATE  # guide samples are in: neither set ...
-    assert _status(lambda: ctx.set_instance_motion(None)) == STATE  # ... nor forgotten
+    assert U.status(lambda: ctx.set_instance_motion(was)) == STATE  # guide samples are in: neither set ...
+    assert U.status(lambda: ctx.set_instance_motion(None)) == STATE  # ... nor forgotten
     m, pn = ctx.read_motion_guides()
     on_box = m[:, 0] != 0  # every hit moved by -0.25 along x, a miss by nothing
     assert on_box.sum() > 128 and np.allclose(m[on_box, 0], -0.25, rtol=0, atol=1e-6) and not m[:, 1:].any()
@@ -338,17 +329,6 @@ def test_refusals_and_lifetimes(gpu):
 
 
 # ---------------------------------------------------------------- 6. the C++ example
-def _read_ppm(path):
-    data = open(path, "rb").read()
-    m = re.match(rb"P6\n(\d+) (\d+)\n255\n", data)
-    w, h = int(m.group(1)), int(m.group(2))
-    return np.frombuffer(data[m.end():], np.uint8).reshape(h, w, 3).astype(np.float64)
-
-
-def _mean_abs_laplacian(img):
-    return float(np.abs(4 * img[1:-1, 1:-1] - img[:-2, 1:-1] - img[2:, 1:-1] - img[1:-1, :-2] - img[1:-1, 2:]).mean())
-
-
 def test_cpp_moving_example(gpu, tmp_path):
     """examples/moving_cornell.cpp: three images of one size that differ; over the blob's final screen rectangle the image filtered over the history
     with motion has less high-frequency energy than the one without."""
@@ -358,10 +338,10 @@ def test_cpp_moving_example(gpu, tmp_path):
     fields = dict(kv.split("=") for kv in r.stdout.split() if "=" in kv)
     assert int(fields["frames"]) == 12 and int(fields["spp"]) == 1 and int(fields["temporal_frames"]) == 12 and int(fields["moving"]) == 1
     x0, y0, x1, y1 = (int(v) for v in fields["blob_rect"].split(","))
-    alone, without, with_motion = (_read_ppm(p) for p in paths)
+    alone, without, with_motion = (U.read_ppm(p) for p in paths)
     assert alone.shape == without.shape == with_motion.shape == (256, 256, 3)
     assert not np.array_equal(without, with_motion) and not np.array_equal(alone, with_motion)
     assert 0 <= x0 < x1 <= 256 and 0 <= y0 < y1 <= 256 and (x1 - x0) * (y1 - y0) > 400
-    lw, lm = (_mean_abs_laplacian(x[y0:y1, x0:x1]) for x in (without, with_motion))
+    lw, lm = (U.mean_abs_laplacian(x[y0:y1, x0:x1]) for x in (without, with_motion))
     print(f"mean |Laplacian| over the blob's rectangle: over the history without motion {lw:.4f}, with motion {lm:.4f}")
     assert lm < lw

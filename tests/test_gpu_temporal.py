@@ -3,7 +3,6 @@ history") against its numpy restatement (tests/temporal_ref.py): synthetic input
 rendered frames, the refusals, the C++ example."""
 import math
 import os
-import re
 import subprocess
 
 import numpy as np
@@ -244,38 +243,30 @@ def test_rendered_orbit_is_closer_to_the_converged_image_over_the_history(gpu):
     ref.close()
 
 
-def _status(fn):
-    with pytest.raises(D.PtError) as e:
-        fn()
-    m = re.search(r"failed \((-?\d+)\): (.*)", str(e.value), re.S)
-    assert m and m.group(2).strip(), "a refusal carries a message in pt_last_error"
-    return int(m.group(1))
-
-
 def test_refusals_and_what_leaves_the_history_alone(gpu):
     INVALID, STATE, UNSUPPORTED = -1, -3, -4
     case = T.make_case("pan", 16, 16)
     bare = gpu.Context(16, 16)
     bare.write_accum(case["accum"], 1)
     bare.write_guides(case["albedo_hits"], case["normal_depth"], 1)
-    assert _status(bare.temporal_accumulate) == STATE  # no camera
-    assert _status(lambda: bare.denoise(3, hdr=True, input_temporal=True)) == STATE  # no history
+    assert U.status(bare.temporal_accumulate) == STATE  # no camera
+    assert U.status(lambda: bare.denoise(3, hdr=True, input_temporal=True)) == STATE  # no history
     bare.set_camera(case["camera"])
     bare.temporal_accumulate()
     bare.close()
     ctx = gpu.Context(16, 16)
     ctx.set_camera(case["camera"])
     ctx.write_guides(case["albedo_hits"], case["normal_depth"], 1)
-    assert _status(ctx.temporal_accumulate) == STATE  # no colour sample
+    assert U.status(ctx.temporal_accumulate) == STATE  # no colour sample
     ctx.write_accum(case["accum"], 1)
     ctx.write_guides(case["albedo_hits"], case["normal_depth"], 0)
-    assert _status(ctx.temporal_accumulate) == STATE  # no guide sample
+    assert U.status(ctx.temporal_accumulate) == STATE  # no guide sample
     ctx.write_guides(case["albedo_hits"], case["normal_depth"], 1)
-    assert _status(lambda: ctx.temporal_accumulate(max_history=4097)) == INVALID
-    assert _status(lambda: ctx.temporal_accumulate(sigma_depth=-1.0)) == INVALID
-    assert _status(lambda: ctx.temporal_accumulate(k_normal=-1.0)) == INVALID
+    assert U.status(lambda: ctx.temporal_accumulate(max_history=4097)) == INVALID
+    assert U.status(lambda: ctx.temporal_accumulate(sigma_depth=-1.0)) == INVALID
+    assert U.status(lambda: ctx.temporal_accumulate(k_normal=-1.0)) == INVALID
     ctx.set_tiles([(0, 0, 8, 16)])
-    assert _status(ctx.temporal_accumulate) == UNSUPPORTED
+    assert U.status(ctx.temporal_accumulate) == UNSUPPORTED
     ctx.set_tiles([])
     assert ctx.temporal_frames == 0  # a refused call is no call
     ctx.temporal_accumulate(max_history=4096)
@@ -286,24 +277,13 @@ def test_refusals_and_what_leaves_the_history_alone(gpu):
     assert ctx.temporal_frames == 1 and ctx.samples_per_pixel == 0
     cn, nd = ctx.read_temporal()
     assert np.array_equal(cn.reshape(16, 16, 4), case["hist_cn"]) and np.array_equal(nd.reshape(16, 16, 4), case["hist_nd"])
-    assert _status(lambda: ctx.denoise(3, input_temporal=True)) == STATE  # a history, but no sample of the current frame
+    assert U.status(lambda: ctx.denoise(3, input_temporal=True)) == STATE  # a history, but no sample of the current frame
     assert ctx.temporal_device_ptr(0) and ctx.temporal_device_ptr(1) and ctx.temporal_device_ptr(0) != ctx.temporal_device_ptr(1)
     ctx.close()
     parity = gpu.Context(16, 16, rng_mode=D.RNG_LFSR113_PARITY)
-    assert _status(lambda: parity.set_sample_base(3)) == UNSUPPORTED
+    assert U.status(lambda: parity.set_sample_base(3)) == UNSUPPORTED
     assert parity.sample_base == 0
     parity.close()
-
-
-def _read_ppm(path):
-    data = open(path, "rb").read()
-    m = re.match(rb"P6\n(\d+) (\d+)\n255\n", data)
-    w, h = int(m.group(1)), int(m.group(2))
-    return np.frombuffer(data[m.end():], np.uint8).reshape(h, w, 3).astype(np.float64)
-
-
-def _mean_abs_laplacian(img):
-    return float(np.abs(4 * img[1:-1, 1:-1] - img[:-2, 1:-1] - img[2:, 1:-1] - img[1:-1, :-2] - img[1:-1, 2:]).mean())
 
 
 def test_cpp_orbit_example(gpu, tmp_path):
@@ -314,9 +294,9 @@ def test_cpp_orbit_example(gpu, tmp_path):
     assert r.returncode == 0, r.stderr
     fields = dict(kv.split("=") for kv in r.stdout.split() if "=" in kv)
     assert int(fields["frames"]) == 12 and int(fields["spp"]) == 1 and int(fields["temporal_frames"]) == 12
-    raw, filtered, temporal = (_read_ppm(p) for p in paths)
+    raw, filtered, temporal = (U.read_ppm(p) for p in paths)
     assert raw.shape == filtered.shape == temporal.shape == (256, 256, 3)
     assert not np.array_equal(filtered, temporal) and not np.array_equal(raw, temporal)
-    lr, lf, lt = (_mean_abs_laplacian(x) for x in (raw, filtered, temporal))
+    lr, lf, lt = (U.mean_abs_laplacian(x) for x in (raw, filtered, temporal))
     print(f"mean |Laplacian|: raw {lr:.4f}, filtered alone {lf:.4f}, filtered over the history {lt:.4f}")
     assert lt < lf

@@ -1,8 +1,7 @@
-"""The temporal luminance variance on the device (pt_set_temporal_variance, k_temporal<., true>, k_atrous_var; include/ptamd.h "temporal
+"""The temporal luminance variance on the device (pt_set_temporal_variance, k_temporal<., true>, k_atrous<., true>; include/ptamd.h "temporal
 variance") against its numpy restatement (tests/variance_ref.py): synthetic inputs through write_accum / write_guides / write_temporal /
 write_temporal_variance, the refusals, the C++ example."""
 import os
-import re
 import subprocess
 
 import numpy as np
@@ -50,7 +49,7 @@ def read(ctx, case):
 
 def restated(case, hist_v, dtype):
     return V.accumulate(case["accum"], case["spp"], case["albedo_hits"], case["normal_depth"], case["gspp"], case["camera"],
-                        (case["hist_cn"], case["hist_nd"], case["hist_camera"], hist_v), case.get("motion"), case.get("prev_normal"), dtype=dtype)
+                        (case["hist_cn"], case["hist_nd"], case["hist_camera"], hist_v), motion=case.get("motion"), prev_normal=case.get("prev_normal"), dtype=dtype)
 
 
 def variance_bound(ref64, ref32):
@@ -264,14 +263,6 @@ def test_three_chained_accumulates(gpu):
     ctx.close()
 
 
-def _status(fn):
-    with pytest.raises(D.PtError) as e:
-        fn()
-    m = re.search(r"failed \((-?\d+)\): (.*)", str(e.value), re.S)
-    assert m and m.group(2).strip(), "a refusal carries a message in pt_last_error"
-    return int(m.group(1))
-
-
 def test_refusals_and_what_they_leave_alone(gpu):
     INVALID, STATE, UNSUPPORTED = -1, -3, -4
     case = T.make_case("pan", 16, 16)
@@ -279,28 +270,28 @@ def test_refusals_and_what_they_leave_alone(gpu):
     ctx = gpu.Context(16, 16)
     for bad in (dict(sigma_variance=-1.0), dict(relative_floor=-0.5), dict(full_history=-3.0), dict(sigma_variance=float("nan")),
                 dict(relative_floor=float("inf")), dict(full_history=1.5), dict(full_history=float("nan"))):
-        assert _status(lambda: ctx.set_temporal_variance(**bad)) == INVALID, bad
+        assert U.status(lambda: ctx.set_temporal_variance(**bad)) == INVALID, bad
         assert ctx.temporal_variance is False
     # mode off: no plane to read or write, no guided filter
     load(ctx, case)
-    assert _status(ctx.read_temporal_variance) == STATE
-    assert _status(lambda: ctx.write_temporal_variance(hist_v)) == STATE
-    assert _status(lambda: ctx.denoise(3, input=GUIDED)) == STATE
-    assert _status(lambda: ctx.denoise(3, input=3)) == INVALID
+    assert U.status(ctx.read_temporal_variance) == STATE
+    assert U.status(lambda: ctx.write_temporal_variance(hist_v)) == STATE
+    assert U.status(lambda: ctx.denoise(3, input=GUIDED)) == STATE
+    assert U.status(lambda: ctx.denoise(3, input=3)) == INVALID
     # a history exists: the mode cannot change, either way
     assert ctx.temporal_frames == 1
-    assert _status(ctx.set_temporal_variance) == STATE
+    assert U.status(ctx.set_temporal_variance) == STATE
     assert ctx.temporal_variance is False
     ctx.temporal_reset()
     ctx.set_temporal_variance(full_history=2.0)
     assert ctx.temporal_variance is True
     # mode on, no history
-    assert _status(ctx.read_temporal_variance) == STATE
-    assert _status(lambda: ctx.write_temporal_variance(hist_v)) == STATE
-    assert _status(lambda: ctx.denoise(3, input=GUIDED)) == STATE
+    assert U.status(ctx.read_temporal_variance) == STATE
+    assert U.status(lambda: ctx.write_temporal_variance(hist_v)) == STATE
+    assert U.status(lambda: ctx.denoise(3, input=GUIDED)) == STATE
     load(ctx, case, variance=hist_v)
-    assert _status(lambda: ctx.set_temporal_variance(False)) == STATE  # forgetting, too
-    assert _status(ctx.set_temporal_variance) == STATE
+    assert U.status(lambda: ctx.set_temporal_variance(False)) == STATE  # forgetting, too
+    assert U.status(ctx.set_temporal_variance) == STATE
     assert ctx.temporal_variance is True and ctx.temporal_frames == 1
     assert np.array_equal(ctx.read_temporal_variance(), hist_v.ravel())  # the refused calls changed nothing
     assert ctx.denoise(3, input=GUIDED).shape == (16, 16, 4)
@@ -310,11 +301,11 @@ def test_refusals_and_what_they_leave_alone(gpu):
     ctx.set_temporal_variance(False)
     assert ctx.temporal_variance is False and ctx.temporal_variance_device_ptr == 0
     ctx.temporal_accumulate()  # the plain kernel again
-    assert _status(ctx.read_temporal_variance) == STATE
+    assert U.status(ctx.read_temporal_variance) == STATE
     ctx.close()
     for kw in (dict(rng_mode=D.RNG_LFSR113_PARITY), dict(max_active_rays=1024)):
         other = gpu.Context(64, 64, **kw)
-        assert _status(other.set_temporal_variance) == UNSUPPORTED
+        assert U.status(other.set_temporal_variance) == UNSUPPORTED
         assert other.temporal_variance is False
         other.close()
 

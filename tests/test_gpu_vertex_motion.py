@@ -2,7 +2,6 @@
 (tests/vertex_motion_ref.py): the two guide deposits of a refitted mesh over both refit routes, both instance routes and two builders, the cases
 where nothing deformed, a pipelined upload, a rendered leaning blob, the refusals, the C++ example."""
 import os
-import re
 import subprocess
 
 import numpy as np
@@ -316,49 +315,41 @@ def test_a_rendered_leaning_blob_keeps_its_history_with_vertex_motion(gpu):
 
 
 # ---------------------------------------------------------------- 5. refusals and lifetimes
-def _status(fn):
-    with pytest.raises(D.PtError) as e:
-        fn()
-    m = re.search(r"failed \((-?\d+)\): (.*)", str(e.value), re.S)
-    assert m and m.group(2).strip(), "a refusal carries a message in pt_last_error"
-    return int(m.group(1))
-
-
 def test_refusals_and_lifetimes(gpu):
     STATE, UNSUPPORTED = -3, -4
     room = V.DeformingRoom(width=16, height=16, fov=40.0)
     flat_a, w, h = room.flat0, 16, 16
     bare = gpu.Context(w, h)
     assert bare.vertex_motion == (False, 0)
-    assert _status(lambda: bare.set_vertex_motion()) == STATE  # no dynamic state
-    assert _status(lambda: bare.set_vertex_motion(False)) == STATE
+    assert U.status(lambda: bare.set_vertex_motion()) == STATE  # no dynamic state
+    assert U.status(lambda: bare.set_vertex_motion(False)) == STATE
     bare.close()
     parity = U.make_ctx(gpu, flat_a, w, h, rng_mode=D.RNG_LFSR113_PARITY)
-    assert _status(lambda: parity.set_vertex_motion()) == UNSUPPORTED
+    assert U.status(lambda: parity.set_vertex_motion()) == UNSUPPORTED
     parity.close()
     refill = U.make_ctx(gpu, flat_a, 64, 64, max_active_rays=1024)
-    assert _status(lambda: refill.set_vertex_motion()) == UNSUPPORTED
+    assert U.status(lambda: refill.set_vertex_motion()) == UNSUPPORTED
     refill.close()
 
     ctx = U.make_ctx(gpu, flat_a, w, h, camera=room.camera)
-    assert _status(lambda: ctx.set_vertex_motion()) == STATE  # one state so far: there is no "then"
+    assert U.status(lambda: ctx.set_vertex_motion()) == STATE  # one state so far: there is no "then"
     ctx.set_vertex_motion(False)  # forgetting what is not set is no error
     flat_b = room.frame(1)
     room.hand_over(ctx, "device", flat_b)
-    assert _status(lambda: ctx.set_vertex_motion()) == STATE  # an upload is pending (and still no previous state)
+    assert U.status(lambda: ctx.set_vertex_motion()) == STATE  # an upload is pending (and still no previous state)
     ctx.frame_tick()
     ctx.clear()
     flat_c = room.frame(2)
     room.hand_over(ctx, "device", flat_c)
-    assert _status(lambda: ctx.set_vertex_motion()) == STATE  # pending: it is overwriting the set that held state A
+    assert U.status(lambda: ctx.set_vertex_motion()) == STATE  # pending: it is overwriting the set that held state A
     assert ctx.vertex_motion == (False, 0)  # a refused call is no call
     ctx.frame_tick()
     ctx.clear()
     ctx.set_vertex_motion()
     assert ctx.vertex_motion == (True, 1)
     ctx.render_guides(1)
-    assert _status(lambda: ctx.set_vertex_motion()) == STATE  # guide samples are in: neither set ...
-    assert _status(lambda: ctx.set_vertex_motion(False)) == STATE  # ... nor forgotten
+    assert U.status(lambda: ctx.set_vertex_motion()) == STATE  # guide samples are in: neither set ...
+    assert U.status(lambda: ctx.set_vertex_motion(False)) == STATE  # ... nor forgotten
     assert ctx.vertex_motion == (True, 1)
     m, pn = ctx.read_motion_guides()
     assert np.abs(m).max() > 0.02 and not m[:, 3].any() and not pn[:, 3].any()
@@ -390,7 +381,7 @@ def test_refusals_and_lifetimes(gpu):
     ctx.upload_static_async(other)
     ctx.upload_dynamic(other)
     ctx.clear()
-    assert _status(lambda: ctx.set_vertex_motion()) == UNSUPPORTED
+    assert U.status(lambda: ctx.set_vertex_motion()) == UNSUPPORTED
     assert ctx.vertex_motion == (False, 0)
     ctx.upload_dynamic(other)  # a second state on the rebuilt scene: vertex motion is back
     ctx.clear()
@@ -400,17 +391,6 @@ def test_refusals_and_lifetimes(gpu):
 
 
 # ---------------------------------------------------------------- 6. the C++ example
-def _read_ppm(path):
-    data = open(path, "rb").read()
-    m = re.match(rb"P6\n(\d+) (\d+)\n255\n", data)
-    w, h = int(m.group(1)), int(m.group(2))
-    return np.frombuffer(data[m.end():], np.uint8).reshape(h, w, 3).astype(np.float64)
-
-
-def _mean_abs_laplacian(img):
-    return float(np.abs(4 * img[1:-1, 1:-1] - img[:-2, 1:-1] - img[2:, 1:-1] - img[1:-1, :-2] - img[1:-1, 2:]).mean())
-
-
 def test_cpp_deforming_example(gpu, tmp_path):
     """examples/deforming_cornell.cpp: three images of one size that differ; over the blob's final screen rectangle the image filtered over the
     history with vertex motion has less high-frequency energy than the one without."""
@@ -420,10 +400,10 @@ def test_cpp_deforming_example(gpu, tmp_path):
     fields = dict(kv.split("=") for kv in r.stdout.split() if "=" in kv)
     assert int(fields["frames"]) == 12 and int(fields["spp"]) == 1 and int(fields["temporal_frames"]) == 12 and int(fields["deformed"]) == 1
     x0, y0, x1, y1 = (int(v) for v in fields["blob_rect"].split(","))
-    alone, without, with_motion = (_read_ppm(p) for p in paths)
+    alone, without, with_motion = (U.read_ppm(p) for p in paths)
     assert alone.shape == without.shape == with_motion.shape == (256, 256, 3)
     assert not np.array_equal(without, with_motion) and not np.array_equal(alone, with_motion)
     assert 0 <= x0 < x1 <= 256 and 0 <= y0 < y1 <= 256 and (x1 - x0) * (y1 - y0) > 400
-    lw, lm = (_mean_abs_laplacian(x[y0:y1, x0:x1]) for x in (without, with_motion))
+    lw, lm = (U.mean_abs_laplacian(x[y0:y1, x0:x1]) for x in (without, with_motion))
     print(f"mean |Laplacian| over the blob's rectangle: over the history without vertex motion {lw:.4f}, with it {lm:.4f}")
     assert lm < lw

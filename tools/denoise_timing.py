@@ -6,7 +6,7 @@ denoise_ms[N]: median `ms_out` of pt_denoise with N iterations (hipEvents around
 iteration costs.  guides_ms: median device ms of pt_render_guides(1), between two events on the stream the context renders on.  frame_ms: the
 same for pt_render(1), the frame the two serve.  bytes: what the filter must move (prepare: 3 reads + 2 writes, every iteration 2 reads + 1
 write of a float4 image); fraction_of_copy: that traffic per second against pt_debug_copy_bandwidth.
---variance: the same six medians for PT_DENOISE_INPUT_TEMPORAL (k_atrous over the history) and PT_DENOISE_INPUT_TEMPORAL_VARIANCE (k_atrous_var) in the
+--variance: the same six medians for PT_DENOISE_INPUT_TEMPORAL (k_atrous over the history) and PT_DENOISE_INPUT_TEMPORAL_VARIANCE (k_atrous<., true>) in the
 same process, and per iteration -- the difference of two consecutive medians -- the ratio of the second to the first."""
 import argparse
 import json
