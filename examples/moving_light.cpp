@@ -1,0 +1,145 @@
+// A light that moves under a static camera, at one sample per pixel and frame: the Cornell room of converge_cornell.cpp with its ceiling light as an
+// instance of its own, which stands at x = -0.5 for a while and then swings to x = +0.5 (one frameTick).  A moving light has no motion vector -- the
+// surfaces its shadows move over stand still -- so the temporal history keeps the old lighting and fades it over max_history frames.  The loop runs
+// twice, without and with the temporal response (RayTracer::setTemporalResponse), and at three frames after the jump the unfiltered history is
+// measured against a converged render of the new state (tone-mapped RMSE, before gamma).  Every frame takes 16 guide samples (first hits alone: cheap next
+// to the frame): how long the history grows is the guides' doing, and with one jittered guide sample per frame the history of this small room stays so
+// short that it forgets the old light by itself.
+//     usage: moving_light [frames before the jump] [reference spp]
+#include "../opencl-path-tracer_amd/host/raytracer.h"
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+
+using namespace raytracer;
+
+static std::shared_ptr<Mesh> quadMesh(vec3 a, vec3 b, vec3 c, vec3 d, const Material& m)
+{
+    const float pos[12] = { a.x, a.y, a.z, b.x, b.y, b.z, c.x, c.y, c.z, d.x, d.y, d.z };
+    const uint32_t idx[6] = { 0, 1, 2, 0, 2, 3 };
+    return std::make_shared<Mesh>(pos, nullptr, nullptr, 4, idx, nullptr, 2, std::vector<Material> { m }, BvhBuilder::BinnedSAH);
+}
+
+// linear radiance -> exposure -> Reinhard, before gamma: the space the image gates of the tests measure in
+static std::vector<double> tonemapped(const std::vector<float>& rgba, double scale, const CameraData& cam)
+{
+    const double ev = std::log2((double)cam.relativeAperture * cam.relativeAperture / cam.shutterTime * 100.0 / cam.ISO);
+    const double exposure = 1.0 / (1.2 * std::exp2(ev));
+    std::vector<double> out(rgba.size() / 4 * 3);
+    for (size_t i = 0; i < rgba.size() / 4; i++)
+        for (int k = 0; k < 3; k++) {
+            const double l = rgba[i * 4 + k] * scale * exposure;
+            out[i * 3 + k] = l / (1.0 + l);
+        }
+    return out;
+}
+
+static double rmse(const std::vector<double>& a, const std::vector<double>& b)
+{
+    double s = 0.0;
+    for (size_t i = 0; i < a.size(); i++)
+        s += (a[i] - b[i]) * (a[i] - b[i]);
+    return std::sqrt(s / (double)a.size());
+}
+
+static const int kAfter[3] = { 4, 16, 32 }; // frames after the jump at which the history is measured
+static const uint32_t kGuideSamples = 16;
+static const float kLightBefore = -0.5f, kLightAfter = 0.5f;
+
+struct Room {
+    std::shared_ptr<Scene> scene = std::make_shared<Scene>();
+    SceneNode* light = nullptr;
+    Room()
+    {
+        const Material white = Material::Diffuse(vec3(0.73f)), green = Material::Diffuse(vec3(0.12f, 0.45f, 0.15f)), red = Material::Diffuse(vec3(0.65f, 0.05f, 0.05f));
+        scene->addNode(quadMesh({ -1, 0, -1 }, { -1, 0, 1 }, { 1, 0, 1 }, { 1, 0, -1 }, white)); // floor
+        scene->addNode(quadMesh({ -1, 2, -1 }, { 1, 2, -1 }, { 1, 2, 1 }, { -1, 2, 1 }, white)); // ceiling
+        scene->addNode(quadMesh({ -1, 0, 1 }, { -1, 2, 1 }, { 1, 2, 1 }, { 1, 0, 1 }, white)); // back
+        scene->addNode(quadMesh({ -1, 0, -1 }, { -1, 2, -1 }, { -1, 2, 1 }, { -1, 0, 1 }, green)); // left
+        scene->addNode(quadMesh({ 1, 0, -1 }, { 1, 0, 1 }, { 1, 2, 1 }, { 1, 2, -1 }, red)); // right
+        auto plate = quadMesh({ -0.3f, 0.6f, -0.3f }, { -0.3f, 0.6f, 0.3f }, { 0.3f, 0.6f, 0.3f }, { 0.3f, 0.6f, -0.3f }, Material::Diffuse(vec3(0.2f, 0.3f, 0.7f)));
+        scene->addNode(plate, Transform(vec3(0.2f, 0.0f, 0.1f)));
+        light = &scene->addNode(quadMesh({ -0.25f, 0.0f, -0.25f }, { 0.25f, 0.0f, -0.25f }, { 0.25f, 0.0f, 0.25f }, { -0.25f, 0.0f, 0.25f },
+                                    Material::Emissive(vec3(1.0f, 0.92f, 0.8f), 12.0f)),
+            Transform(vec3(kLightBefore, 1.98f, 0.0f)));
+    }
+};
+
+// the unfiltered history (the newest d times the current albedo), linear
+static std::vector<float> history(RayTracer& rt, int W, int H)
+{
+    std::vector<float> image((size_t)W * H * 4);
+    pt_denoise_params prm {};
+    prm.iterations = 0u;
+    prm.output = PT_DENOISE_HDR;
+    prm.input = PT_DENOISE_INPUT_TEMPORAL;
+    if (pt_denoise(rt.context(), &prm, image.data(), nullptr) != PT_OK)
+        throw std::runtime_error(pt_last_error(rt.context()));
+    return image;
+}
+
+int main(int argc, char** argv)
+{
+    const int before = argc > 1 ? std::atoi(argv[1]) : 16;
+    const int referenceSpp = argc > 2 ? std::atoi(argv[2]) : 256;
+    const int W = 64, H = 64;
+    if (before < 1 || referenceSpp < 1) {
+        std::fprintf(stderr, "error: frames before the jump and reference spp must be at least 1\n");
+        return 1;
+    }
+    try {
+        Camera camera(Transform(vec3(0.0f, 1.0f, -3.9f)), 40.0f, (float)W / H, 3.9f); // identity orientation looks down +z
+        camera.m_thinLens = false;
+        camera.m_shutterTime = 1.0f;
+        const CameraData cam = camera.get_camera_data();
+        TextureArray noTextures, sky;
+        const float grey[4] = { 0.4f, 0.4f, 0.4f, 1.0f };
+        sky.add(grey, 1, 1);
+
+        std::vector<double> want; // the converged view of the state after the jump, from random numbers no frame below draws
+        {
+            Room room;
+            room.light->transform = Transform(vec3(kLightAfter, 1.98f, 0.0f));
+            RayTracer rt(W, H, room.scene, noTextures, sky);
+            rt.setSampleBase(1000000u);
+            for (int s = 0; s < referenceSpp; s++)
+                rt.rayTrace(camera);
+            want = tonemapped(rt.getAccumulator(), 1.0 / referenceSpp, cam);
+        }
+
+        double e[2][3];
+        unsigned temporalFrames = 0;
+        for (int mode = 0; mode < 2; mode++) {
+            Room room;
+            RayTracer rt(W, H, room.scene, noTextures, sky);
+            rt.setTemporalResponse(mode == 1);
+            const int frames = before + kAfter[2];
+            for (int f = 0; f < frames; f++) {
+                if (f == before) {
+                    room.light->transform = Transform(vec3(kLightAfter, 1.98f, 0.0f)); // the swing: one re-posed instance, one tick
+                    rt.frameTick();
+                }
+                if (pt_clear(rt.context()) != PT_OK) // the camera stands still: rayTrace would go on accumulating
+                    throw std::runtime_error(pt_last_error(rt.context()));
+                rt.setSampleBase((uint32_t)f);
+                rt.rayTrace(camera);
+                if (pt_render_guides(rt.context(), kGuideSamples) != PT_OK) // (getTemporalOutput would take one: as many as the frame has samples)
+                    throw std::runtime_error(pt_last_error(rt.context()));
+                rt.getTemporalOutput(0); // blends this frame into the history (and, with the mode on, into the fast one)
+                for (int k = 0; k < 3; k++)
+                    if (f + 1 == before + kAfter[k])
+                        e[mode][k] = rmse(tonemapped(history(rt, W, H), 1.0, cam), want);
+            }
+            temporalFrames = pt_temporal_frames(rt.context());
+            if (pt_temporal_response(rt.context()) != mode)
+                throw std::runtime_error("the temporal response is not in the mode it was set to");
+        }
+        for (int k = 0; k < 3; k++)
+            std::printf("after=%d plain=%.4e response=%.4e ratio=%.3f\n", kAfter[k], e[0][k], e[1][k], e[1][k] / e[0][k]);
+        std::printf("before=%d temporal_frames=%u\n", before, temporalFrames);
+    } catch (const std::exception& e) {
+        std::fprintf(stderr, "error: %s\n", e.what());
+        return 1;
+    }
+    return 0;
+}

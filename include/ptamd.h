@@ -413,8 +413,8 @@ uint32_t pt_sample_base(const pt_ctx* ctx);
  *   into history    q = (X + m / gspp) - E',  m the pixel's motion sum: the displacement is added to X BEFORE the history's eye is subtracted;  z' = |q| as before
  *   taps            e_n = k_normal max(0, 1 - n_then(p).n_h),  n_then the pixel's prev_normal sum normalised exactly as n is (zero stays zero)
  * and nothing else: the set written out still holds the CURRENT (n, z); blend, clamps and the 1e-12 rule are the same.  Zero motion sums and
- * prev_normal == normal_depth.xyz give the plain output bit for bit.  Still without motion vectors: rebuilt trees (pt_upload_static_async) and
- * moving lights.
+ * prev_normal == normal_depth.xyz give the plain output bit for bit.  Still without motion vectors: rebuilt trees (pt_upload_static_async).
+ * Moving lights have none to give -- their shadows and highlights move over surfaces that stand still --; TEMPORAL RESPONSE below follows them.
  * Refusals: PT_ERR_STATE before a camera is set and when pt_samples_per_pixel or pt_guide_samples is 0; PT_ERR_UNSUPPORTED while tiles are set (as
  * pt_denoise); PT_ERR_INVALID for max_history > 4096 or a negative k_normal / sigma_depth. */
 typedef struct {
@@ -548,6 +548,50 @@ int pt_temporal_variance(const pt_ctx* ctx); /* 1 / 0 */
 int pt_read_temporal_variance(pt_ctx* ctx, float* out); /* host, width*height floats, of the newest set */
 int pt_write_temporal_variance(pt_ctx* ctx, const float* in); /* checkpoint restore: after pt_write_temporal, which zeroes the plane */
 void* pt_temporal_variance_device_ptr(pt_ctx* ctx); /* the newest set's plane; NULL while the mode is off and before the first temporal call with it on */
+
+/* TEMPORAL RESPONSE: a second, short history beside the long one, and a fall-back to it where the lighting changed.  A moving light has no motion
+ * vector: the surface under the pixel stood still, depth and normal accept the whole history, and the history is wrong.  Opt-in: with the mode off,
+ * every entry point launches exactly the kernels it launches without this block and returns the same bits.
+ *
+ * With the mode on each history set holds one more width*height float4 image, fast = (d_f.rgb, N_f), and the context two scratch planes: a float2
+ * plane of luminances and a float plane s.  One pt_temporal_accumulate, per pixel:
+ *   long history    (d_l, N_l) and (n, z) by TEMPORAL HISTORY's arithmetic, the same bits; the variance plane too where that mode is on, unchanged
+ *   fast history    met at the same four taps with the same b exp(-(e_n + e_z)); a tap counts where it lies inside the image and the FAST count is
+ *                   positive.  Wsum_f < 1e-12, or no history: (d, 1).  Otherwise h_f = sum w d_f / Wsum_f,
+ *                   N_f = min(sum w N_f,tap + 1, fast_history),   d_f = h_f + (d - h_f) / N_f   -- the long history's blend, one inline function
+ *   window          l_l = L(d_l), l_f = L(d_f) (Rec.709); over the n_p pixels of the 7 x 7 window that lie inside the image
+ *                   mu_l = sum l_l / n_p,   mu_f = sum l_f / n_p,   sigma_f^2 = sum (l_f - mu_f)^2 / n_p      (two passes, NOT E[x^2] - E[x]^2)
+ *   mix factor      t = |mu_f - mu_l| / (sigma_response sigma_f / sqrt(n_p) + relative_floor (max(mu_f, mu_l) + 1e-3)),   s = clamp(t - 1, 0, 1)
+ *   output          (d_out, N_out) = (d_l, N_l) + s ((d_f, N_f) - (d_l, N_l));   fast keeps (d_f, N_f)
+ * Where the low-passed histories disagree by more than the fast one's own noise explains, colour AND count fall back to the fast history, and the long
+ * history re-converges from there.  Every quantity is a continuous function of the inputs; the one kink is a clamp, there is no accept / reject
+ * decision.  With no history (first call, after pt_temporal_reset) fast = (d, 1), s = 0 and the window is not evaluated.
+ * While pt_temporal_frames() <= fast_history the two histories have the same bits: t = 0, s = 0, and colour_count has the bits of a context with the
+ * mode off (and fast the bits of colour_count).
+ * The motion routes (INSTANCE MOTION, VERTEX MOTION) meet fast at the taps they meet the colour at.  The variance plane stays as TEMPORAL VARIANCE
+ * wrote it; the guided filter's s(p) follows the lowered count and falls back to the plain luminance term there.  pt_denoise is untouched.
+ *
+ * pt_set_temporal_response refuses: PT_ERR_UNSUPPORTED in parity / refill mode; PT_ERR_INVALID for fast_history > 4096 and for a negative or
+ * non-finite float; PT_ERR_STATE while pt_temporal_frames() != 0, for setting and for forgetting alike.  pt_read_temporal_fast,
+ * pt_write_temporal_fast and pt_read_temporal_response: PT_ERR_STATE with the mode off or without a history.  A refused call changes nothing.
+ * pt_temporal_reset keeps the mode set.  pt_write_temporal zeroes the fast image of the set it writes -- the fast history then restarts from the
+ * current frame --; pt_write_temporal_fast restores it.  The buffers are allocated at the first temporal call with the mode on, freed by pt_destroy. */
+#define PT_RESPONSE_RADIUS 3 /* the window is 7 x 7, clipped to the image */
+#define PT_RESPONSE_DEFAULT_FAST_HISTORY 4u
+#define PT_RESPONSE_DEFAULT_SIGMA_RESPONSE 2.0f
+#define PT_RESPONSE_DEFAULT_RELATIVE_FLOOR 0.02f
+typedef struct {
+    uint32_t fast_history; /* 0 = 4; at most 4096 */
+    float sigma_response; /* 0 = 2.0 */
+    float relative_floor; /* 0 = 0.02 */
+    uint32_t _reserved[5];
+} pt_response_params; /* 32 bytes */
+int pt_set_temporal_response(pt_ctx* ctx, const pt_response_params* params); /* NULL: off */
+int pt_temporal_response(const pt_ctx* ctx); /* 1 / 0 */
+int pt_read_temporal_fast(pt_ctx* ctx, float* colour_count); /* host, width*height*4 floats, of the newest set */
+int pt_write_temporal_fast(pt_ctx* ctx, const float* colour_count); /* checkpoint restore: after pt_write_temporal, which zeroes the image */
+int pt_read_temporal_response(pt_ctx* ctx, float* s_out); /* host, width*height floats: the mix factor of the last pt_temporal_accumulate */
+void* pt_temporal_fast_device_ptr(pt_ctx* ctx); /* the newest set's fast image; NULL while the mode is off and before the first temporal call with it on */
 
 /* ---- kernel-granular entry points (parity tests and micro-benchmarks) ------------------
  * Host SoA arrays in, host SoA arrays out; the scene must have been uploaded. */

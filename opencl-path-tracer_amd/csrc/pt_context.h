@@ -380,6 +380,15 @@ struct pt_ctx {
     bool varianceSet = false;
     float sigmaVariance = 0, relativeFloor = 0, fullHistory = 0; // pt_variance_params, defaults resolved
 
+    // temporal response (include/ptamd.h): one more float4 image per history set, the fast history (d_f.rgb, N_f), and two scratch planes -- the
+    // luminance pairs k_temporal<., ., true> leaves for k_temporal_response, and the mix factor s of the last accumulate --, allocated (zeroed) at the
+    // first temporal call with the mode on.  The mode changes only while there is no history.
+    DevBuf<float4> temporalFast[2];
+    DevBuf<float2> responseLuminance;
+    DevBuf<float> responseMix;
+    bool responseSet = false;
+    float fastHistory = 0, sigmaResponse = 0, responseFloor = 0; // pt_response_params, defaults resolved
+
     // instance motion (include/ptamd.h): one record per instance of the ACTIVE dynamic state (indexed like its instance table, which is how the guide
     // pass meets a hit), and the two guide sums made from them -- (displacement.xyz, 0) and (normal then.xyz, 0), width * height float4 each, allocated at
     // the first pt_set_instance_motion / pt_write_motion_guides.  pt_frame_tick forgets the motion; pt_clear zeroes the sums and keeps it.

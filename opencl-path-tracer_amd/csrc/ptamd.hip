@@ -1299,9 +1299,13 @@ void launchAtrous(hipStream_t stream, dim3 grid, dim3 block, bool inLds, bool gu
 {
     hipLaunchKernelGGL(inLds ? (guided ? k_atrous<true, true> : k_atrous<true>) : (guided ? k_atrous<false, true> : k_atrous<false>), grid, block, 0, stream, a);
 }
-void launchTemporal(hipStream_t stream, dim3 grid, dim3 block, bool moved, bool variance, const TemporalArgs& a)
+void launchTemporal(hipStream_t stream, dim3 grid, dim3 block, bool moved, bool variance, bool response, const TemporalArgs& a)
 {
-    hipLaunchKernelGGL(moved ? (variance ? k_temporal<true, true> : k_temporal<true>) : (variance ? k_temporal<false, true> : k_temporal<false>), grid, block, 0, stream, a);
+    if (response)
+        hipLaunchKernelGGL(moved ? (variance ? k_temporal<true, true, true> : k_temporal<true, false, true>)
+                                 : (variance ? k_temporal<false, true, true> : k_temporal<false, false, true>), grid, block, 0, stream, a);
+    else
+        hipLaunchKernelGGL(moved ? (variance ? k_temporal<true, true> : k_temporal<true>) : (variance ? k_temporal<false, true> : k_temporal<false>), grid, block, 0, stream, a);
 }
 
 } // namespace
@@ -1426,6 +1430,17 @@ int ensureTemporal(pt_ctx* c)
             HIPCHK(c, plane.alloc((size_t)c->cfg.width * c->cfg.height));
             HIPCHK(c, hipMemsetAsync(plane.p, 0, plane.n * sizeof(float), c->stream));
         }
+    if (c->responseSet && !c->temporalFast[0].p) {
+        const size_t n = (size_t)c->cfg.width * c->cfg.height;
+        for (DevBuf<float4>& image : c->temporalFast) {
+            HIPCHK(c, image.alloc(n));
+            HIPCHK(c, hipMemsetAsync(image.p, 0, n * sizeof(float4), c->stream));
+        }
+        HIPCHK(c, c->responseLuminance.alloc(n));
+        HIPCHK(c, hipMemsetAsync(c->responseLuminance.p, 0, n * sizeof(float2), c->stream));
+        HIPCHK(c, c->responseMix.alloc(n));
+        HIPCHK(c, hipMemsetAsync(c->responseMix.p, 0, n * sizeof(float), c->stream));
+    }
     return PT_OK;
 }
 
@@ -1486,8 +1501,19 @@ int pt_temporal_accumulate(pt_ctx* c, const pt_temporal_params* prm)
     if (moved)
         a.motion = c->motionGuides[0], a.prevNormal = c->motionGuides[1];
     a.histVariance = c->temporalVariance[from].p, a.outVariance = c->temporalVariance[to].p; // (varianceSet: the same arithmetic and one more plane)
-    launchTemporal(c->stream, grid, block, moved, c->varianceSet, a);
+    a.histFast = c->temporalFast[from].p, a.outFast = c->temporalFast[to].p, a.outLuminance = c->responseLuminance.p, a.fastHistory = c->fastHistory; // (responseSet)
+    launchTemporal(c->stream, grid, block, moved, c->varianceSet, c->responseSet, a);
     HIPCHK(c, hipGetLastError());
+    if (c->responseSet) {
+        if (a.histColour) { // the two histories of every pixel are there: mix them where the window says so
+            ResponseArgs r {};
+            r.luminance = c->responseLuminance.p, r.colour = a.outColour, r.fast = a.outFast, r.mix = c->responseMix.p;
+            r.width = a.width, r.height = a.height, r.sigmaResponse = c->sigmaResponse, r.relativeFloor = c->responseFloor;
+            hipLaunchKernelGGL(k_temporal_response, grid, block, 0, c->stream, r);
+            HIPCHK(c, hipGetLastError());
+        } else // no history: fast = (d, 1) = colour_count, nothing to mix
+            HIPCHK(c, hipMemsetAsync(c->responseMix.p, 0, c->responseMix.n * sizeof(float), c->stream));
+    }
     c->temporalCamera = c->camera;
     c->temporalNewest = to;
     c->temporalFrames++;
@@ -1526,6 +1552,10 @@ int pt_write_temporal(pt_ctx* c, const float* colour_count, const float* normal_
     if (c->varianceSet) { // nothing is known about these colours' spread: pt_write_temporal_variance restores it
         DevBuf<float>& plane = c->temporalVariance[c->temporalNewest];
         HIPCHK(c, hipMemsetAsync(plane.p, 0, plane.n * sizeof(float), c->stream));
+    }
+    if (c->responseSet) { // the fast history restarts from the current frame: pt_write_temporal_fast restores it
+        DevBuf<float4>& image = c->temporalFast[c->temporalNewest];
+        HIPCHK(c, hipMemsetAsync(image.p, 0, image.n * sizeof(float4), c->stream));
     }
     auto f4 = [](const float* p) { return make_float4(p[0], p[1], p[2], 0.f); };
     c->temporalCamera = CameraDev {};
@@ -1611,6 +1641,88 @@ int pt_write_temporal_variance(pt_ctx* c, const float* in)
 }
 
 void* pt_temporal_variance_device_ptr(pt_ctx* c) { return c && c->varianceSet ? (void*)c->temporalVariance[c->temporalNewest].p : nullptr; }
+
+// ---- temporal response (k_temporal<., ., true>, k_temporal_response) ----------------------------
+
+int pt_set_temporal_response(pt_ctx* c, const pt_response_params* prm)
+{
+    if (!c)
+        return PT_ERR_INVALID;
+    if (const int rc = fixedScheduleOnly(c, "pt_set_temporal_response"))
+        return rc;
+    if (prm) {
+        if (prm->fast_history > 4096u)
+            return fail(c, PT_ERR_INVALID, "pt_set_temporal_response: fast_history = %u (1..4096; 0 = %u)", prm->fast_history, PT_RESPONSE_DEFAULT_FAST_HISTORY);
+        const float given[2] = { prm->sigma_response, prm->relative_floor };
+        for (const float f : given)
+            if (!(f >= 0.0f) || !std::isfinite(f))
+                return fail(c, PT_ERR_INVALID, "pt_set_temporal_response: negative or non-finite parameter");
+    }
+    if (c->temporalFrames != 0)
+        return fail(c, PT_ERR_STATE, "pt_set_temporal_response: a history of %u frames exists -- set or forget the mode right after pt_temporal_reset",
+            c->temporalFrames);
+    c->responseSet = prm != nullptr;
+    if (prm) {
+        c->fastHistory = (float)(prm->fast_history ? prm->fast_history : PT_RESPONSE_DEFAULT_FAST_HISTORY);
+        c->sigmaResponse = prm->sigma_response > 0.f ? prm->sigma_response : PT_RESPONSE_DEFAULT_SIGMA_RESPONSE;
+        c->responseFloor = prm->relative_floor > 0.f ? prm->relative_floor : PT_RESPONSE_DEFAULT_RELATIVE_FLOOR;
+    }
+    return PT_OK;
+}
+
+int pt_temporal_response(const pt_ctx* c) { return c && c->responseSet ? 1 : 0; }
+
+namespace {
+
+// what the three transfers share: PT_OK with the mode on, a history there and the buffers allocated
+int responseReady(pt_ctx* c, const char* who)
+{
+    if (!c->responseSet)
+        return fail(c, PT_ERR_STATE, "%s: the temporal response is off (pt_set_temporal_response)", who);
+    if (c->temporalFrames == 0)
+        return fail(c, PT_ERR_STATE, "%s: no history (pt_temporal_accumulate, pt_write_temporal)", who);
+    HIPCHK(c, hipSetDevice(c->device));
+    return ensureTemporal(c);
+}
+
+} // namespace
+
+int pt_read_temporal_fast(pt_ctx* c, float* colour_count)
+{
+    if (!c || !colour_count)
+        return PT_ERR_INVALID;
+    if (const int rc = responseReady(c, "pt_read_temporal_fast"))
+        return rc;
+    const DevBuf<float4>& image = c->temporalFast[c->temporalNewest];
+    HIPCHK(c, hipMemcpyAsync(colour_count, image.p, image.n * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return PT_OK;
+}
+
+int pt_write_temporal_fast(pt_ctx* c, const float* colour_count)
+{
+    if (!c || !colour_count)
+        return PT_ERR_INVALID;
+    if (const int rc = responseReady(c, "pt_write_temporal_fast"))
+        return rc;
+    const DevBuf<float4>& image = c->temporalFast[c->temporalNewest];
+    HIPCHK(c, hipMemcpyAsync(image.p, colour_count, image.n * sizeof(float4), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return PT_OK;
+}
+
+int pt_read_temporal_response(pt_ctx* c, float* s_out)
+{
+    if (!c || !s_out)
+        return PT_ERR_INVALID;
+    if (const int rc = responseReady(c, "pt_read_temporal_response"))
+        return rc;
+    HIPCHK(c, hipMemcpyAsync(s_out, c->responseMix.p, c->responseMix.n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return PT_OK;
+}
+
+void* pt_temporal_fast_device_ptr(pt_ctx* c) { return c && c->responseSet ? (void*)c->temporalFast[c->temporalNewest].p : nullptr; }
 
 // ---- instance motion (k_guides<1>, k_temporal<true>) --------------------------------------------
 

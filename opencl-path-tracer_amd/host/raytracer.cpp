@@ -252,6 +252,13 @@ void RayTracer::setTemporalVariance(bool on)
     m_temporalVariance = on;
 }
 
+void RayTracer::setTemporalResponse(bool on)
+{
+    check(pt_temporal_reset(m_ctx), "pt_temporal_reset");
+    const pt_response_params defaults {};
+    check(pt_set_temporal_response(m_ctx, on ? &defaults : nullptr), "pt_set_temporal_response");
+}
+
 void RayTracer::resetTemporalHistory() { check(pt_temporal_reset(m_ctx), "pt_temporal_reset"); }
 
 void RayTracer::setSampleBase(uint32_t base) { check(pt_set_sample_base(m_ctx, base), "pt_set_sample_base"); }

@@ -108,6 +108,10 @@ public:
     // (the mode changes only while there is none); from then on getTemporalOutput filters with PT_DENOISE_INPUT_TEMPORAL_VARIANCE -- a static camera's
     // image keeps converging where the fixed-strength filter stops at its own blur.  Off by default.
     void setTemporalVariance(bool on);
+    // A short, fast history beside the long one, and a fall-back to it where the lighting changed (include/ptamd.h, "temporal response"): a moving light
+    // has no motion vector, and its old shadows would fade over max_history frames.  Resets the history like setTemporalVariance, of which it is
+    // independent.  Off by default.
+    void setTemporalResponse(bool on);
     void resetTemporalHistory(); // forget the history: after a cut, or when the scene changed beyond what depth and normal can tell
     void setSampleBase(uint32_t base); // pt_set_sample_base: frames that restart at sample 0 draw other random numbers each
     struct Guides {

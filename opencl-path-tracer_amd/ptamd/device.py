@@ -88,6 +88,11 @@ class VarianceParams(C.Structure):
     _fields_ = [("sigma_variance", C.c_float), ("relative_floor", C.c_float), ("full_history", C.c_float), ("_reserved", C.c_uint32 * 5)]
 
 
+class ResponseParams(C.Structure):
+    """pt_response_params (32 bytes); a parameter of 0 selects the default documented in include/ptamd.h"""
+    _fields_ = [("fast_history", C.c_uint32), ("sigma_response", C.c_float), ("relative_floor", C.c_float), ("_reserved", C.c_uint32 * 5)]
+
+
 EXPORTS = ["pt_create", "pt_destroy", "pt_last_error", "pt_set_stream", "pt_upload_static", "pt_upload_static_async", "pt_upload_dynamic",
            "pt_upload_dynamic_async", "pt_frame_tick", "pt_update_geometry", "pt_refit_vertices",
            "pt_upload_texture_array", "pt_set_camera", "pt_set_tiles", "pt_set_accum_buffer", "pt_clear", "pt_render",
@@ -97,7 +102,9 @@ EXPORTS = ["pt_create", "pt_destroy", "pt_last_error", "pt_set_stream", "pt_uplo
            "pt_temporal_frames", "pt_read_temporal", "pt_write_temporal", "pt_temporal_device_ptr", "pt_set_instance_motion", "pt_instance_motion",
            "pt_read_motion_guides", "pt_write_motion_guides", "pt_motion_guides_device_ptr", "pt_debug_motion_records",
            "pt_set_vertex_motion", "pt_vertex_motion", "pt_debug_vertex_motion_rows", "pt_set_temporal_variance", "pt_temporal_variance",
-           "pt_read_temporal_variance", "pt_write_temporal_variance", "pt_temporal_variance_device_ptr", "pt_stats_get", "pt_stats_reset", "pt_profile_kernels", "pt_reduce_accum",
+           "pt_read_temporal_variance", "pt_write_temporal_variance", "pt_temporal_variance_device_ptr",
+           "pt_set_temporal_response", "pt_temporal_response", "pt_read_temporal_fast", "pt_write_temporal_fast", "pt_read_temporal_response",
+           "pt_temporal_fast_device_ptr", "pt_stats_get", "pt_stats_reset", "pt_profile_kernels", "pt_reduce_accum",
            "pt_intersect", "pt_gen_rays", "pt_primary_pass", "pt_shade_batch", "pt_debug_quantise_node", "pt_debug_convert", "pt_debug_copy_bandwidth", "pt_debug_math_probe", "pt_debug_rng_probe", "pt_debug_live_resources",
            "pt_version"]
 
@@ -184,6 +191,13 @@ def lib():
         l.pt_write_temporal_variance.argtypes = [C.c_void_p, C.c_void_p]
         l.pt_temporal_variance_device_ptr.restype = C.c_void_p
         l.pt_temporal_variance_device_ptr.argtypes = [C.c_void_p]
+        l.pt_set_temporal_response.argtypes = [C.c_void_p, C.POINTER(ResponseParams)]
+        l.pt_temporal_response.argtypes = [C.c_void_p]
+        l.pt_read_temporal_fast.argtypes = [C.c_void_p, C.c_void_p]
+        l.pt_write_temporal_fast.argtypes = [C.c_void_p, C.c_void_p]
+        l.pt_read_temporal_response.argtypes = [C.c_void_p, C.c_void_p]
+        l.pt_temporal_fast_device_ptr.restype = C.c_void_p
+        l.pt_temporal_fast_device_ptr.argtypes = [C.c_void_p]
         l.pt_stats_get.argtypes = [C.c_void_p, C.POINTER(Stats)]
         l.pt_stats_reset.argtypes = [C.c_void_p]
         l.pt_profile_kernels.argtypes = [C.c_void_p, C.c_int]
@@ -526,6 +540,40 @@ class Context:
     def temporal_variance_device_ptr(self):
         """Device address of the newest set's variance plane (0 while the mode is off or nothing is allocated yet)."""
         return lib().pt_temporal_variance_device_ptr(self._h) or 0
+
+    # ---- temporal response
+    def set_temporal_response(self, on=True, fast_history=0, sigma_response=0.0, relative_floor=0.0):
+        """Keep a short, fast history beside the long one (temporal_accumulate) and fall back to it where the two disagree over a 7 x 7 window by more
+        than the fast one's noise explains: a lighting change.  False forgets it.  Only while there is no history: right after temporal_reset()."""
+        prm = ResponseParams(fast_history, sigma_response, relative_floor)
+        self._chk(lib().pt_set_temporal_response(self._h, C.byref(prm) if on else None), "pt_set_temporal_response")
+
+    @property
+    def temporal_response(self):
+        return bool(lib().pt_temporal_response(self._h))
+
+    def read_temporal_fast(self):
+        """the fast history (d_f.rgb, N_f) of the newest set: (width*height, 4) float32"""
+        out = np.zeros((self.height * self.width, 4), np.float32)
+        self._chk(lib().pt_read_temporal_fast(self._h, _p(out)), "pt_read_temporal_fast")
+        return out
+
+    def write_temporal_fast(self, colour_count):
+        """Install the fast history of the newest set (after write_temporal, which zeroes it)."""
+        f = np.ascontiguousarray(colour_count, np.float32)
+        assert f.size == self.width * self.height * 4
+        self._chk(lib().pt_write_temporal_fast(self._h, _p(f)), "pt_write_temporal_fast")
+
+    def read_temporal_response(self):
+        """the mix factor s of the last temporal_accumulate: (width*height,) float32"""
+        out = np.zeros(self.height * self.width, np.float32)
+        self._chk(lib().pt_read_temporal_response(self._h, _p(out)), "pt_read_temporal_response")
+        return out
+
+    @property
+    def temporal_fast_device_ptr(self):
+        """Device address of the newest set's fast image (0 while the mode is off or nothing is allocated yet)."""
+        return lib().pt_temporal_fast_device_ptr(self._h) or 0
 
     # ---- instance motion
     def set_instance_motion(self, prev):

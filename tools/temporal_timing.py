@@ -1,13 +1,15 @@
 #!/usr/bin/env python3
 """Device time of pt_temporal_accumulate at 1280 x 720 and 1920 x 1080, one JSON line (EXPERIMENTS.md).
-Not part of bench.py.     usage: python tools/temporal_timing.py [--calls 25] [--batch 20] [--scene cornell|blob] [--motion] [--variance]
+Not part of bench.py.     usage: python tools/temporal_timing.py [--calls 25] [--batch 20] [--scene cornell|blob] [--motion] [--variance] [--response]
 
 temporal_ms.static / .panned: median device ms of ONE pt_temporal_accumulate, measured between two events on the stream the context renders on
 around `batch` calls in a row (one call is tens of microseconds: a pair of events around a single launch would time the events).  static: the camera
 of the history is the current one (every pixel finds its four taps around its own position); panned: the camera alternates between two poses 1.5
 degrees apart about the room's centre, so every call reprojects.  frame_ms: the same measurement of pt_render(1), the 1-spp frame the history serves.
 floor_bytes: what a call must move -- three 16-byte reads of the current frame, two 16-byte writes and the history's two images read once (neighbours
-share their taps): 7 x 16 = 112 bytes per pixel; fraction_of_copy: that traffic per second against pt_debug_copy_bandwidth."""
+share their taps): 7 x 16 = 112 bytes per pixel; fraction_of_copy: that traffic per second against pt_debug_copy_bandwidth.
+--response: the same two figures with pt_set_temporal_response on -- one call is then k_temporal<., ., true> and k_temporal_response behind it, and the
+floor 152 + 44 bytes per pixel (the two kernels' shares come from a kernel trace of this script)."""
 import argparse
 import json
 import math
@@ -20,6 +22,9 @@ sys.path[:0] = [os.path.join(ROOT, "opencl-path-tracer_amd"), ROOT]
 
 FLOOR_BYTES_PER_PIXEL = 7 * 16
 MOTION_FLOOR_BYTES_PER_PIXEL = 9 * 16  # --motion: the two motion sums are read as well
+# --response: k_temporal<., ., true> reads the fast image once more and writes it and the luminance pairs (16 + 16 + 8 = 40 bytes more: 152);
+# k_temporal_response reads the luminance pairs, colour_count and the fast image and writes s (8 + 16 + 16 + 4 = 44 bytes; 16 more where it stores)
+RESPONSE_EXTRA_BYTES_PER_PIXEL, RESPONSE_MIX_BYTES_PER_PIXEL = 40, 44
 VARIANCE_EXTRA_BYTES_PER_PIXEL = 8  # --variance: the history's variance plane read once, the new one written (4 bytes each): 120 and 152
 
 
@@ -31,6 +36,7 @@ def main():
     ap.add_argument("--scene", default="cornell")
     ap.add_argument("--motion", action="store_true", help="also time k_temporal<true> (instance motion set), next to the plain kernel")
     ap.add_argument("--variance", action="store_true", help="also time k_temporal<., true> (pt_set_temporal_variance), next to the plain kernel")
+    ap.add_argument("--response", action="store_true", help="also time k_temporal<., ., true> + k_temporal_response (pt_set_temporal_response), next to the plain kernel")
     args = ap.parse_args()
     import torch
     from ptamd import device as D, scenes
@@ -94,6 +100,25 @@ def main():
                 "fraction_of_copy": {"static": round(v_floor / v_static / 1e6 / copy, 3), "panned": round(v_floor / v_panned / 1e6 / copy, 3)}}
             ctx.temporal_reset()
             ctx.set_temporal_variance(False)
+            ctx.temporal_accumulate()
+        if args.response:
+            # k_temporal<false, false, true> and k_temporal_response behind it, in the same process and the same batches as the plain kernel, against the same
+            # copy rate: one call is the two launches.  The accumulator stays what it is, so s is 0 almost everywhere and the mix stores next to nothing: the
+            # floor is the one without the store.  (The two kernels' shares: a kernel trace of this script.)
+            ctx.set_camera(b.camera)
+            ctx.temporal_reset()
+            ctx.set_temporal_response()
+            ctx.temporal_accumulate()
+            r_static = timed(lambda i: ctx.temporal_accumulate(sync=False), args.batch)
+            r_panned = timed(panned_call, args.batch)
+            r_floor = (FLOOR_BYTES_PER_PIXEL + RESPONSE_EXTRA_BYTES_PER_PIXEL + RESPONSE_MIX_BYTES_PER_PIXEL) * width * height
+            out["sizes"][f"{width}x{height}"]["response"] = {
+                "temporal_ms": {"static": round(r_static, 5), "panned": round(r_panned, 5)}, "floor_bytes": r_floor,
+                "ratio_to_plain": {"static": round(r_static / static, 3), "panned": round(r_panned / panned, 3)},
+                "mean_mix_factor_panned": round(float(ctx.read_temporal_response().mean()), 5),
+                "fraction_of_copy": {"static": round(r_floor / r_static / 1e6 / copy, 3), "panned": round(r_floor / r_panned / 1e6 / copy, 3)}}
+            ctx.temporal_reset()
+            ctx.set_temporal_response(False)
             ctx.temporal_accumulate()
         if args.motion:
             # k_temporal<true> in the same process, against the same copy rate: every instance was a millimetre to the side, so every pixel of it carries
