@@ -377,6 +377,50 @@ int pt_denoise(pt_ctx* ctx, const pt_denoise_params* params, float* rgba_out, fl
  * pt_resolve_device_ptr returns (shared with pt_resolve_device) */
 int pt_denoise_device(pt_ctx* ctx, const pt_denoise_params* params, void* device_rgba);
 
+/* GUIDE CHAIN: the guide pass follows refraction to the first surface that is not glass (the "primary surface replacement" of NRD-style denoisers).
+ * Without it a REFRACTIVE or BASIC_REFRACTIVE first hit deposits albedo (1,1,1) and the glass's own normal and distance: over a pane or a glass body the
+ * guides are flat, the filter blurs every edge seen through the glass, and the history reprojects those pixels at the depth of the glass.  Opt-in, default
+ * off: with max_transmissions == 0 every entry point launches exactly the kernels it launches without this block and returns the same bits.
+ *
+ * With K = max_transmissions > 0, guide sample s of an owned pixel starts as above (the camera ray of sample base + s; a thin lens normalised as above:
+ * D / |D|, t * |D|) with dist = 0 and walks stages j = 0 .. K.  At each stage the closest hit of the current segment (origin O, direction D) is taken.
+ *   The chain CONTINUES when the hit is on a REFRACTIVE or BASIC_REFRACTIVE surface, j < K, and the interface transmits:
+ *     N     the normal the pass would deposit there: interpolated shading normal, world space, normalised, facing the ray
+ *     ior   the material's own: refractiveIndexBasic (BASIC_REFRACTIVE) or refractiveIndexRough (REFRACTIVE)
+ *     n1n2  1 / ior on the side where shading's real normal -- normalize(normalTransform(instance, edge1 x edge2)), so a mirrored instance takes the side
+ *           the path takes -- faces the ray by shading's own compare (real.-D > 1e-4 for BASIC_REFRACTIVE, > 0 for REFRACTIVE); ior on the other side
+ *     cos1 = -N.D,   Kt = 1 - n1n2^2 (1 - cos1^2);   transmitted if and only if Kt > 1e-4 (kEPS, shading's constant)
+ *     T = normalize(n1n2 D + N (n1n2 cos1 - sqrt(Kt)))
+ *     next segment: origin X + 1e-4 T (X = O + t D, as shading offsets a continuation ray), direction T, dist += t
+ *   Rough glass is followed as if it were smooth, along the mean direction.  Absorption and Fresnel are ignored: the guides describe surfaces, not radiance.
+ *   The chain ENDS otherwise -- a hit that is not refractive, a miss, total internal reflection, stage K reached on glass -- and the terminal surface
+ *   deposits exactly the expressions of the GUIDE PASS, with two changes: the distance is dist + t (a miss still deposits PT_GUIDE_SKY_DEPTH, and -D of
+ *   the LAST segment as its normal), and hits is 1 if and only if the terminal is geometry.
+ * A pixel whose first hit is not glass gets the bits it gets with the chain off.  The sums stay bit-reproducible, additive over calls and over
+ * complementary tilings: each pixel has exactly one live entry per sample and one terminal deposit, so the sample order per pixel is kept however later
+ * stages are compacted; no float atomics, no host read-back between stages.  Where the uploaded materials hold no refractive type the pass launches the
+ * kernels of the chain-off pass.  A second scratch queue and two float planes (40 bytes per owned pixel) are allocated at the first guide call with
+ * the chain on over a scene with glass; pt_destroy frees them.
+ *
+ * What it means downstream.  The temporal reprojection's X = E + z D (TEMPORAL HISTORY below) becomes a VIRTUAL point: the eye ray extended to the
+ * length of the bent path.  That is exact where there is no glass, and good for flat panes seen near the normal (the path is displaced sideways by a
+ * fraction of the pane's thickness); behind a lens or a thick curved body it is an approximation -- pt_temporal_accumulate itself does not change.
+ * LIMITATIONS: the silhouette of a thin untinted pane stops being a guide edge (both sides of it now describe what lies behind); motion deposits along a
+ * chain are out of scope -- the chain and an instance or vertex motion refuse each other.
+ *
+ * Refusals: PT_ERR_INVALID above PT_GUIDE_CHAIN_MAX; PT_ERR_STATE when the value CHANGES while pt_guide_samples() > 0 (sums of two definitions must
+ * not mix; pt_clear zeroes them -- setting the value it already has is always accepted); PT_ERR_UNSUPPORTED for a value > 0 while an instance or vertex
+ * motion is set, and from pt_set_instance_motion / pt_set_vertex_motion (setting, not forgetting) while the chain is on; PT_ERR_UNSUPPORTED for a
+ * value > 0 in parity / refill mode (as pt_render_guides). */
+#define PT_GUIDE_CHAIN_MAX 4u
+int pt_set_guide_chain(pt_ctx* ctx, uint32_t max_transmissions); /* 0 = off (default) */
+uint32_t pt_guide_chain(const pt_ctx* ctx);
+/* test hook: while enabled (a width*height buffer of four int32 per pixel, set to -1 at enabling, freed at disabling and by pt_destroy) every chain
+ * pass also records where each owned pixel's chain ended, the LAST guide sample's: (primitive, top-level leaf, stage, 1 if the chain ended in total
+ * internal reflection else 0); primitive = leaf = -1 for a miss.  A pass that runs the chain-off kernels (chain off, no glass) writes nothing. */
+int pt_debug_guide_chain_terminals(pt_ctx* ctx, int enable);
+int pt_debug_read_guide_chain_terminals(pt_ctx* ctx, int32_t* out4); /* host, width*height*4 int32; synchronises */
+
 /* SAMPLE BASE.  pt_render traces the sample indices base + pt_samples_per_pixel ..., pt_render_guides base + pt_guide_samples ...: a frame loop
  * that clears before every frame ("move, pt_clear, pt_render(1)") sets the base to its frame number, so that every frame draws other random
  * numbers -- without it each frame is sample 0 again, with the same counter-PRNG keys, and a history of such frames averages nothing.  Default 0.

@@ -363,6 +363,12 @@ struct pt_ctx {
     DevBuf<float4> guideRayO, guideRayD, guideHit;
     DevBuf<int32_t> guideHitInst;
     DevBuf<Control> guideCtl;
+    // guide chain (pt_set_guide_chain; pt_denoise.h, k_guide_chain): the second scratch queue the stages ping-pong with, and the distance travelled so
+    // far as a float plane per queue -- allocated at the first guide call with the chain on over a scene that holds glass
+    uint32_t guideChain = 0; // max_transmissions; 0 = off
+    DevBuf<float4> guideChainO, guideChainD;
+    DevBuf<float> guideChainDist[2];
+    DevBuf<int4> guideChainTerminals; // pt_debug_guide_chain_terminals (test hook): width * height records, allocated while enabled
     DevBuf<float4> denoiseColour[2], denoiseGuide;
     Event evDenoise[2];
 

@@ -845,6 +845,7 @@ int convertStatic(StaticHost& s, const ConvertOptions& o, uint64_t& versions, co
             std::memcpy(&ty, (const char*)&mats[tris[t].materialIndex] + 32, 4); // the type word of the 48-byte record (Material::typeAndPad.x)
             types |= 1u << std::min(ty, 31u);
         }
+        s.refractive = (types & ((1u << MAT_REFRACTIVE) | (1u << MAT_BASIC_REFRACTIVE))) != 0u;
         types &= ~(1u << MAT_EMISSIVE);
         s.materialBins = (types & (types - 1u)) != 0u && (o.flags & PT_FLAG_MATERIAL_BINS) != 0u; // opt-in: measured slower (pt_shade.h)
     }

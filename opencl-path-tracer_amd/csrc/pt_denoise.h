@@ -64,6 +64,45 @@ __device__ inline V3 guidePoint(const float4 e1e, const float4 e2v, const float4
     return mk(fmaf(e1e.w, v, fmaf(e1e.x, u, e2v.z)), fmaf(e2v.x, v, fmaf(e1e.y, u, e2v.w)), fmaf(e2v.y, v, fmaf(e1e.z, u, v0c.x)));
 }
 
+// The terminal deposit of a guide ray, stated once for k_guides and k_guide_chain: the normal and the albedo of a hit as the comment of k_guides has them.
+// guideShadingNormal: the interpolated shading normal, object space (the motion modes take it through the previous transform as well);
+// guideNormal: that normal to world space, normalised, turned to face the ray of direction D (`flip`: it was turned).  All three hand VALUES back: with
+// the albedo passed by reference k_guides<1> and <2> came out with another schedule (EXPERIMENTS.md, "Guide chain").
+__device__ __forceinline__ V3 guideShadingNormal(const float4 f0, const float4 f1, const float4 f2, float u, float v)
+{
+    const V3 n0 = xyz(f0), n1 = xyz(f1), n2 = xyz(f2);
+    return normalize(n0 + (n1 - n0) * u + (n2 - n0) * v); // object space (shadeHit)
+}
+struct GuideNormal {
+    V3 N;
+    bool flip;
+};
+__device__ __forceinline__ GuideNormal guideNormal(const Instance& in, V3 shadingNormal, V3 D)
+{
+    GuideNormal r;
+    r.N = normalize(normalTransform(in, shadingNormal));
+    r.flip = dot(r.N, D) > 0.0f;
+    if (r.flip)
+        r.N = r.N * -1.0f;
+    return r;
+}
+// guideAlbedo: `albedo` comes in as (1,1,1), what REFRACTIVE / BASIC_REFRACTIVE / EMISSIVE keep
+__device__ __forceinline__ V3 guideAlbedo(const SceneDev& sc, const MatView& mat, const float4 f0, const float4 f1, const float4 f2, const float4 f3, float u, float v,
+    V3 albedo)
+{
+    if (mat.type == MAT_PBR) {
+        albedo = mat.colour;
+    } else if (mat.type == MAT_DIFFUSE) {
+        albedo = mat.colour;
+        if (mat.texId != -1) {
+            albedo = diffuseColourTextured(sc, mat, f0, f1, f2, f3, u, v);
+            if (albedo.x == -1.0f) // alpha-0 texel
+                albedo = mk(1.0f);
+        }
+    }
+    return albedo;
+}
+
 template <int MODE> // 0: no motion; 1: instance motion; 2: instance and vertex motion
 __global__ void __launch_bounds__(256) k_guides(SceneDev sc, const float4* __restrict__ qO, const float4* __restrict__ qD, const float4* __restrict__ hit,
     const int32_t* __restrict__ hitInst, uint32_t n, uint32_t thinLens, float4* __restrict__ albedoHits, float4* __restrict__ normalDepth, GuideMotionArgs mo)
@@ -100,12 +139,10 @@ __global__ void __launch_bounds__(256) k_guides(SceneDev sc, const float4* __res
             t0 = tp->n0u, t1 = tp->n1u, t2 = tp->n2u, t4 = tp->e1e, t5 = tp->e2v, t6 = tp->v0c;
             l0 = lp[0], l1 = lp[1], l2 = lp[2];
         }
-        const V3 n0 = xyz(f0), n1 = xyz(f1), n2 = xyz(f2);
-        const V3 shadingNormal = normalize(n0 + (n1 - n0) * u + (n2 - n0) * v); // object space (shadeHit)
-        N = normalize(normalTransform(in, shadingNormal));
-        const bool flip = dot(N, D) > 0.0f;
-        if (flip)
-            N = N * -1.0f;
+        const V3 shadingNormal = guideShadingNormal(f0, f1, f2, u, v);
+        const GuideNormal facing = guideNormal(in, shadingNormal, D);
+        N = facing.N;
+        const bool flip = facing.flip;
         if constexpr (MODE >= 1) {
             Instance then = in;
             then.r0 = rec.p0, then.r1 = rec.p1, then.r2 = rec.p2;
@@ -126,16 +163,7 @@ __global__ void __launch_bounds__(256) k_guides(SceneDev sc, const float4* __res
             }
         }
         const MatView mat = loadMaterial(f6, f7);
-        if (mat.type == MAT_PBR) {
-            albedo = mat.colour;
-        } else if (mat.type == MAT_DIFFUSE) {
-            albedo = mat.colour;
-            if (mat.texId != -1) {
-                albedo = diffuseColourTextured(sc, mat, f0, f1, f2, f3, u, v);
-                if (albedo.x == -1.0f) // alpha-0 texel
-                    albedo = mk(1.0f);
-            }
-        }
+        albedo = guideAlbedo(sc, mat, f0, f1, f2, f3, u, v, albedo);
         t = h.x * scale;
         hits = 1.0f;
     }
@@ -151,6 +179,136 @@ __global__ void __launch_bounds__(256) k_guides(SceneDev sc, const float4* __res
         pn.x += nThen.x, pn.y += nThen.y, pn.z += nThen.z;
         mo.motion[pixel] = m;
         mo.prevNormal[pixel] = pn;
+    }
+}
+
+// ---- guide chain (include/ptamd.h, "guide chain") ------------------------------------------------
+// With pt_set_guide_chain(K > 0) a guide ray follows refraction to the first surface that is not glass.  Per sample the guide pass launches k_guide_gen and
+// then, for stage j = 0 .. K, the per-ray closest-hit kernel over stage j's queue (pass j of the guide pass's control block) and k_guide_chain(j):
+// one thread per entry of stage j.  An entry whose hit is REFRACTIVE / BASIC_REFRACTIVE, whose interface transmits and whose stage is below K goes on:
+//   N     the normal guideNormal gives (what a terminal hit would deposit)         ior   refractiveIndexBasic / refractiveIndexRough (MatView p0 / p1)
+//   n1n2  1 / ior where shadeHit's real normal faces the ray (its own compare per material: > kEPS for BASIC_REFRACTIVE, > 0 for REFRACTIVE), else ior
+//   cos1 = -N.D,   Kt = 1 - n1n2^2 (1 - cos1^2),   transmitted iff Kt > kEPS,   T = normalize(n1n2 D + N (n1n2 cos1 - sqrt(Kt)))
+//   next entry: origin X + T kEPS (X = O + t D of the queue's own origin and direction, as k_shade forms it), direction T, dist + t
+// (rough glass is followed along its mean direction; absorption and Fresnel are ignored: the guides describe surfaces).  Every other entry is TERMINAL
+// -- a hit that is not glass, a miss, total internal reflection, stage K on glass -- and deposits what k_guides<0> deposits, through the same two
+// functions, with the distance dist + t (a miss: PT_GUIDE_SKY_DEPTH as it is, and -D of this segment).  Stage 0 with dist = 0 adds the bits k_guides<0> adds.
+// A pixel has exactly one live entry per sample and one terminal deposit, and the launches of a sample are ordered on the stream: a plain
+// read-modify-write, sums in sample order whatever order the compaction leaves the later stages in.
+// Compaction as k_shade's: ranks from a wave64 ballot, the waves' counts through LDS, ONE atomicAdd per workgroup on the next stage's count (none where
+// nothing goes on).  The two queues ping-pong (stage j reads queue j & 1); the counts and cursors of stages 1 .. K are zeroed by the host's memset nodes
+// before stage 0.  The entry, its hit, the instance index, the eight quarters of the triangle's record and the instance are issued before the first use.
+struct GuideChainArgs {
+    SceneDev sc;
+    const float4* qO; // stage j: origin.xyz, bits(pixel)
+    const float4* qD; // direction.xyz, bits(state)
+    const float* qDist; // distance travelled before this segment (not read at stage 0)
+    const float4* hit;
+    const int32_t* hitInst;
+    float4* outO; // stage j + 1
+    float4* outD;
+    float* outDist;
+    Control* ctl;
+    uint32_t stage, last; // last: stage == K, glass is terminal
+    uint32_t capacity; // entries a queue holds
+    uint32_t thinLens; // stage 0 of a thin-lens camera: the direction is not normalised
+    float4* albedoHits;
+    float4* normalDepth;
+    int4* terminals; // test hook (pt_debug_guide_chain_terminals), else null: per pixel (prim, top-level leaf, stage, 1: total internal reflection) of the terminal
+};
+
+__global__ void __launch_bounds__(256) k_guide_chain(GuideChainArgs a)
+{
+    __shared__ uint32_t sCount[4], sBase;
+    const uint32_t count = min(a.ctl->extCount[a.stage], a.capacity);
+    if (blockIdx.x * 256u >= count) // the whole workgroup: the grid covers the queue's capacity, the count is a device word
+        return;
+    const uint32_t k = blockIdx.x * 256u + threadIdx.x;
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const bool live = k < count;
+    bool goOn = false;
+    V3 nextO = mk(0.0f), nextD = mk(0.0f);
+    float nextDist = 0.0f;
+    uint32_t pixel = 0u;
+    if (live) {
+        const float4 ro = a.qO[k], rd = a.qD[k], h = a.hit[k];
+        const int32_t hinst = a.hitInst[k];
+        const float before = a.stage ? a.qDist[k] : 0.0f;
+        pixel = asU(ro.w);
+        V3 D = xyz(rd);
+        float scale = 1.0f;
+        if (a.thinLens) {
+            scale = sqrtf(dot(D, D));
+            D = D / scale;
+        }
+        const int32_t prim = (int32_t)asU(h.w);
+        V3 albedo = mk(1.0f), N = D * -1.0f;
+        float t = kGuideSkyDepth, hits = 0.0f;
+        int32_t leaf = -1, reflected = 0;
+        if (prim >= 0) {
+            const TriFat* fp = &a.sc.triFat[prim];
+            const float4 f0 = fp->n0u, f1 = fp->n1u, f2 = fp->n2u, f3 = fp->vvvm, f4 = fp->e1e, f5 = fp->e2v, f6 = fp->v0c, f7 = fp->mat;
+            const float u = h.y, v = h.z;
+            const Instance in = a.sc.instances[hinst];
+            N = guideNormal(in, guideShadingNormal(f0, f1, f2, u, v), D).N;
+            const MatView mat = loadMaterial(f6, f7);
+            t = h.x * scale;
+            leaf = (int32_t)in.topNode;
+            const bool basic = mat.type == MAT_BASIC_REFRACTIVE;
+            if ((basic || mat.type == MAT_REFRACTIVE) && !a.last) {
+                const V3 edge1 = xyz(f4), edge2 = mk(f4.w, f5.x, f5.y);
+                const V3 realNormal = fastNormalize(normalTransform(in, cross(edge1, edge2))); // as shadeHit forms it: mirrored instances take the path's side
+                const float facing = dot(realNormal, D * -1.0f);
+                const float ior = basic ? mat.p0 : mat.p1;
+                const float n1n2 = (basic ? facing > kEPS : facing > 0.0f) ? 1.0f / ior : ior;
+                const float cos1 = -dot(N, D);
+                const float Kt = 1.0f - (n1n2 * n1n2) * (1.0f - cos1 * cos1);
+                if (Kt > kEPS) {
+                    goOn = true;
+                    nextD = normalize(n1n2 * D + N * (n1n2 * cos1 - sqrtf(Kt)));
+                    nextO = xyz(ro) + xyz(rd) * h.x + nextD * kEPS;
+                    nextDist = before + t;
+                } else {
+                    reflected = 1;
+                }
+            }
+            if (!goOn) {
+                albedo = guideAlbedo(a.sc, mat, f0, f1, f2, f3, u, v, albedo);
+                t = before + t;
+                hits = 1.0f;
+            }
+        }
+        if (!goOn) {
+            float4 al = a.albedoHits[pixel], g = a.normalDepth[pixel];
+            al.x += albedo.x, al.y += albedo.y, al.z += albedo.z, al.w += hits;
+            g.x += N.x, g.y += N.y, g.z += N.z, g.w += t;
+            a.albedoHits[pixel] = al;
+            a.normalDepth[pixel] = g;
+            if (a.terminals)
+                a.terminals[pixel] = make_int4(prim, leaf, (int32_t)a.stage, reflected);
+        }
+    }
+    const unsigned long long going = __ballot(goOn);
+    if (lane == 0)
+        sCount[wave] = (uint32_t)__popcll(going);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t sum = 0;
+        for (uint32_t w = 0; w < 4u; w++) {
+            const uint32_t n = sCount[w];
+            sCount[w] = sum;
+            sum += n;
+        }
+        sBase = sum ? atomicAdd(&a.ctl->extCount[a.stage + 1u], sum) : 0u;
+    }
+    __syncthreads();
+    if (goOn) {
+        const uint32_t slot = sBase + sCount[wave] + (uint32_t)__popcll(going & ((1ull << lane) - 1ull));
+        if (slot < a.capacity) { // (always: stage j + 1 holds at most the entries of stage j)
+            a.outO[slot] = make_float4(nextO.x, nextO.y, nextO.z, asF(pixel));
+            a.outD[slot] = make_float4(nextD.x, nextD.y, nextD.z, asF(packState(0u, a.stage + 1u, 0u)));
+            a.outDist[slot] = nextDist;
+        }
     }
 }
 

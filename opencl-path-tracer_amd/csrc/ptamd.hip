@@ -1226,6 +1226,15 @@ int pt_render_guides(pt_ctx* c, uint32_t spp)
         HIPCHK(c, c->guideCtl.alloc(1));
         HIPCHK(c, hipMemsetAsync(c->guideCtl.p, 0, sizeof(Control), c->stream));
     }
+    // the guide chain (pt_set_guide_chain), where the scene holds glass at all -- the conversion knows; without any, today's three kernels per sample
+    const uint32_t chain = c->stat[c->dyn[c->active].staticIndex].host.refractive ? c->guideChain : 0u;
+    if (chain && c->guideChainO.n < c->guideRayO.n) {
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        HIPCHK(c, c->guideChainO.alloc(c->guideRayO.n));
+        HIPCHK(c, c->guideChainD.alloc(c->guideRayO.n));
+        HIPCHK(c, c->guideChainDist[0].alloc(c->guideRayO.n));
+        HIPCHK(c, c->guideChainDist[1].alloc(c->guideRayO.n));
+    }
     // always the per-ray kernel: which kernel traces a launch must not depend on what the last render left in the context (the team kernel is chosen
     // by the previous batch's counters), and the launch is none of pt_stats' business
     const uint32_t batchEntries = c->batchEntries;
@@ -1240,6 +1249,26 @@ int pt_render_guides(pt_ctx* c, uint32_t spp)
         a.rayO = c->guideRayO.p, a.rayD = c->guideRayD.p, a.rayC = nullptr;
         a.hit = c->guideHit.p, a.inst = c->guideHitInst.p, a.accum = AccumView { nullptr, nullptr, nullptr, 0u }, a.occluded = nullptr;
         a.ctl = c->guideCtl.p, a.pass = 0;
+        if (chain) {
+            // stages 1 .. K start empty, with their fetch cursors at zero (k_guide_gen arms stage 0 alone); an error shows in hipGetLastError below,
+            // after the render's bookkeeping is back in place
+            (void)hipMemsetAsync(&c->guideCtl.p->extCount[1], 0, chain * sizeof(uint32_t), c->stream);
+            (void)hipMemsetAsync(&c->guideCtl.p->extCursor[1], 0, chain * sizeof(uint32_t), c->stream);
+            GuideChainArgs g {};
+            g.sc = c->scene, g.hit = c->guideHit.p, g.hitInst = c->guideHitInst.p, g.ctl = c->guideCtl.p;
+            g.capacity = n, g.albedoHits = c->guides[0], g.normalDepth = c->guides[1], g.terminals = c->guideChainTerminals.p;
+            for (uint32_t j = 0; j <= chain; j++) { // the counts of stages >= 1 are device words: every launch covers the queue, empty workgroups leave at once
+                float4* const qO[2] = { c->guideRayO.p, c->guideChainO.p };
+                float4* const qD[2] = { c->guideRayD.p, c->guideChainD.p };
+                a.rayO = qO[j & 1u], a.rayD = qD[j & 1u], a.pass = j;
+                launchTrace(c, false, a);
+                g.qO = qO[j & 1u], g.qD = qD[j & 1u], g.qDist = c->guideChainDist[j & 1u].p;
+                g.outO = qO[(j + 1u) & 1u], g.outD = qD[(j + 1u) & 1u], g.outDist = c->guideChainDist[(j + 1u) & 1u].p;
+                g.stage = j, g.last = j == chain ? 1u : 0u, g.thinLens = j == 0u ? c->camera.thinLens : 0u;
+                hipLaunchKernelGGL(k_guide_chain, dim3((n + 255u) / 256u), dim3(256), 0, c->stream, g);
+            }
+            continue;
+        }
         launchTrace(c, false, a);
         if (c->vertexMotionSet && c->vertexDeformed) // (the snapshot, never the inactive set: the next state may be on its way into that)
             launchGuides<2>(c, n, GuideMotionArgs { c->motionRecords.p, c->motionGuides[0], c->motionGuides[1], c->fatThen.p, c->vertexRows.p });
@@ -1257,6 +1286,65 @@ int pt_render_guides(pt_ctx* c, uint32_t spp)
 }
 
 uint32_t pt_guide_samples(const pt_ctx* c) { return c ? c->guideSpp : 0; }
+
+// ---- guide chain (k_guide_chain) ----------------------------------------------------------------
+int pt_set_guide_chain(pt_ctx* c, uint32_t maxTransmissions)
+{
+    return guarded(c, "pt_set_guide_chain", [&]() -> int {
+    if (!c)
+        return PT_ERR_INVALID;
+    if (maxTransmissions > PT_GUIDE_CHAIN_MAX)
+        return fail(c, PT_ERR_INVALID, "pt_set_guide_chain: %u transmissions, at most PT_GUIDE_CHAIN_MAX = %u are followed", maxTransmissions, PT_GUIDE_CHAIN_MAX);
+    if (maxTransmissions == c->guideChain)
+        return PT_OK;
+    if (maxTransmissions != 0u) {
+        if (const int rc = fixedScheduleOnly(c, "pt_set_guide_chain"))
+            return rc;
+        if (c->motionSet || c->vertexMotionSet)
+            return fail(c, PT_ERR_UNSUPPORTED, "pt_set_guide_chain: an instance or vertex motion is set -- motion deposits along a chain are not supported");
+    }
+    if (c->guideSpp != 0)
+        return fail(c, PT_ERR_STATE, "pt_set_guide_chain: %u guide samples are in the sums already -- sums of two definitions must not mix: change it right after pt_clear", c->guideSpp);
+    c->guideChain = maxTransmissions;
+    return PT_OK;
+    });
+}
+
+uint32_t pt_guide_chain(const pt_ctx* c) { return c ? c->guideChain : 0u; }
+
+// test hook: where the chain of each pixel's LAST guide sample ended
+int pt_debug_guide_chain_terminals(pt_ctx* c, int enable)
+{
+    return guarded(c, "pt_debug_guide_chain_terminals", [&]() -> int {
+    if (!c)
+        return PT_ERR_INVALID;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream)); // (a guide pass in flight may be writing the records)
+    const size_t n = (size_t)c->cfg.width * c->cfg.height;
+    if (!enable) {
+        c->guideChainTerminals.release();
+        return PT_OK;
+    }
+    if (c->guideChainTerminals.n != n)
+        HIPCHK(c, c->guideChainTerminals.alloc(n));
+    HIPCHK(c, hipMemsetAsync(c->guideChainTerminals.p, 0xFF, n * sizeof(int4), c->stream)); // -1: no chain pass has written the pixel
+    return PT_OK;
+    });
+}
+
+int pt_debug_read_guide_chain_terminals(pt_ctx* c, int32_t* out4)
+{
+    return guarded(c, "pt_debug_read_guide_chain_terminals", [&]() -> int {
+    if (!c || !out4)
+        return PT_ERR_INVALID;
+    if (!c->guideChainTerminals.p)
+        return fail(c, PT_ERR_STATE, "pt_debug_read_guide_chain_terminals: the records are not enabled (pt_debug_guide_chain_terminals)");
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipMemcpyAsync(out4, c->guideChainTerminals.p, c->guideChainTerminals.n * sizeof(int4), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return PT_OK;
+    });
+}
 
 int pt_read_guides(pt_ctx* c, float* albedo_hits, float* normal_depth)
 {
@@ -1812,6 +1900,8 @@ int pt_set_instance_motion(pt_ctx* c, const float* prevInv, uint32_t nTop)
         c->motionMoving = 0;
         return PT_OK;
     }
+    if (c->guideChain)
+        return fail(c, PT_ERR_UNSUPPORTED, "pt_set_instance_motion: a guide chain is set (pt_set_guide_chain) -- motion deposits along a chain are not supported");
     const pt_ctx::DynamicSet& d = c->dyn[c->active];
     if (nTop != d.numTopNodes)
         return fail(c, PT_ERR_INVALID, "pt_set_instance_motion: %u previous transforms for an active state of %u top-level nodes", nTop, d.numTopNodes);
@@ -1872,6 +1962,8 @@ int pt_set_vertex_motion(pt_ctx* c, int enable)
         c->vertexMotionSet = c->vertexDeformed = false;
         return PT_OK;
     }
+    if (c->guideChain)
+        return fail(c, PT_ERR_UNSUPPORTED, "pt_set_vertex_motion: a guide chain is set (pt_set_guide_chain) -- motion deposits along a chain are not supported");
     if (c->pending >= 0)
         return fail(c, PT_ERR_STATE, "pt_set_vertex_motion: an upload is pending (pt_upload_dynamic_async without its pt_frame_tick): it is overwriting the set that held the previous state");
     pt_ctx::DynamicSet &cur = c->dyn[c->active], &old = c->dyn[1 - c->active];

@@ -144,7 +144,7 @@ void RayTracer::setMotionAfterTick()
 {
     m_motionDue = false;
     setInstanceMotionAfterTick();
-    const bool deformed = m_vertexMotion && m_vertexDue && pt_temporal_frames(m_ctx) != 0;
+    const bool deformed = m_vertexMotion && !m_guideChain && m_vertexDue && pt_temporal_frames(m_ctx) != 0;
     m_vertexDue = false;
     if (deformed)
         check(pt_set_vertex_motion(m_ctx, 1), "pt_set_vertex_motion");
@@ -158,7 +158,7 @@ void RayTracer::setInstanceMotionAfterTick()
     size_t leaves = 0;
     while (leaves < top.size() && top[leaves].isLeaf)
         leaves++;
-    bool follow = m_instanceMotion && m_prevLeafValid && pt_temporal_frames(m_ctx) != 0 && leaves * 16 == m_prevLeafInv.size();
+    bool follow = m_instanceMotion && !m_guideChain && m_prevLeafValid && pt_temporal_frames(m_ctx) != 0 && leaves * 16 == m_prevLeafInv.size();
     for (size_t i = leaves; i < top.size(); i++)
         follow = follow && !top[i].isLeaf; // (leaves behind an inner node: not the host library's top level, the indices mean something else)
     if (!follow) {
@@ -257,6 +257,19 @@ void RayTracer::setTemporalResponse(bool on)
     check(pt_temporal_reset(m_ctx), "pt_temporal_reset");
     const pt_response_params defaults {};
     check(pt_set_temporal_response(m_ctx, on ? &defaults : nullptr), "pt_set_temporal_response");
+}
+
+void RayTracer::setGuideChain(unsigned maxTransmissions)
+{
+    check(pt_clear(m_ctx), "pt_clear"); // (the chain changes, and a motion is forgotten, only while no guide samples are in the sums)
+    if (maxTransmissions != 0) {
+        if (pt_instance_motion(m_ctx, nullptr))
+            check(pt_set_instance_motion(m_ctx, nullptr, 0), "pt_set_instance_motion");
+        if (pt_vertex_motion(m_ctx, nullptr))
+            check(pt_set_vertex_motion(m_ctx, 0), "pt_set_vertex_motion");
+    }
+    check(pt_set_guide_chain(m_ctx, maxTransmissions), "pt_set_guide_chain");
+    m_guideChain = maxTransmissions;
 }
 
 void RayTracer::resetTemporalHistory() { check(pt_temporal_reset(m_ctx), "pt_temporal_reset"); }

@@ -112,6 +112,11 @@ public:
     // has no motion vector, and its old shadows would fade over max_history frames.  Resets the history like setTemporalVariance, of which it is
     // independent.  Off by default.
     void setTemporalResponse(bool on);
+    // Guide rays follow up to `maxTransmissions` refractions (0..PT_GUIDE_CHAIN_MAX; 0, the default: off) to the first surface that is not glass
+    // (include/ptamd.h, "guide chain"): the filter and the history then see the edges and albedos behind a pane or inside a glass body.  Restarts the
+    // accumulation (pt_clear: guide sums of two definitions must not mix).  While it is on no instance or vertex motion is handed to the device library
+    // (motion deposits along a chain are not supported): moving surfaces keep or lose their history by depth and normal alone.
+    void setGuideChain(unsigned maxTransmissions);
     void resetTemporalHistory(); // forget the history: after a cut, or when the scene changed beyond what depth and normal can tell
     void setSampleBase(uint32_t base); // pt_set_sample_base: frames that restart at sample 0 draw other random numbers each
     struct Guides {
@@ -132,6 +137,7 @@ private:
     CameraData m_prevCamera;
     bool m_haveCamera = false;
     bool m_temporalDirty = false; // samples were traced since the last getTemporalOutput
+    unsigned m_guideChain = 0; // setGuideChain
     bool m_temporalVariance = false; // setTemporalVariance: getTemporalOutput's filter reads the variance plane
     // instance motion: the leaves' invTransform (16 floats each, scene-graph order) of the state the newest history was made under
     bool m_instanceMotion = true;

@@ -148,6 +148,10 @@ def build_raytracer(force=False):
     if force or _newer(exe10, [os.path.join(ex_dir, "moving_light.cpp"), out]):
         subprocess.run(["g++", "-std=c++17", "-O2", "-Wall", "moving_light.cpp", "-o", "moving_light", "-L" + HOST_DIR, "-lptamd_raytracer",
                         "-lptamd_host", "-L" + CSRC_DIR, "-lptamd", "-Wl,-rpath," + HOST_DIR, "-Wl,-rpath," + CSRC_DIR], cwd=ex_dir, check=True)
+    exe11 = os.path.join(ex_dir, "glass_cornell")
+    if force or _newer(exe11, [os.path.join(ex_dir, "glass_cornell.cpp"), out]):
+        subprocess.run(["g++", "-std=c++17", "-O2", "-Wall", "glass_cornell.cpp", "-o", "glass_cornell", "-L" + HOST_DIR, "-lptamd_raytracer",
+                        "-lptamd_host", "-L" + CSRC_DIR, "-lptamd", "-Wl,-rpath," + HOST_DIR, "-Wl,-rpath," + CSRC_DIR], cwd=ex_dir, check=True)
     return out, exe
 
 

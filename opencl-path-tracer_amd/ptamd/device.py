@@ -64,6 +64,7 @@ class ShadeBatchIO(C.Structure):
 
 DENOISE_TONEMAPPED, DENOISE_HDR = 0, 1
 GUIDE_SKY_DEPTH = 1e6
+GUIDE_CHAIN_MAX = 4  # PT_GUIDE_CHAIN_MAX
 
 
 class DenoiseParams(C.Structure):
@@ -98,6 +99,7 @@ EXPORTS = ["pt_create", "pt_destroy", "pt_last_error", "pt_set_stream", "pt_uplo
            "pt_upload_texture_array", "pt_set_camera", "pt_set_tiles", "pt_set_accum_buffer", "pt_clear", "pt_render",
            "pt_synchronize", "pt_resolve", "pt_resolve_device", "pt_resolve_device_ptr", "pt_read_accum", "pt_write_accum", "pt_accum_device_ptr",
            "pt_samples_per_pixel", "pt_render_guides", "pt_guide_samples", "pt_read_guides", "pt_write_guides", "pt_guides_device_ptr",
+           "pt_set_guide_chain", "pt_guide_chain", "pt_debug_guide_chain_terminals", "pt_debug_read_guide_chain_terminals",
            "pt_denoise", "pt_denoise_device", "pt_set_sample_base", "pt_sample_base", "pt_temporal_accumulate", "pt_temporal_reset",
            "pt_temporal_frames", "pt_read_temporal", "pt_write_temporal", "pt_temporal_device_ptr", "pt_set_instance_motion", "pt_instance_motion",
            "pt_read_motion_guides", "pt_write_motion_guides", "pt_motion_guides_device_ptr", "pt_debug_motion_records",
@@ -162,6 +164,11 @@ def lib():
         l.pt_write_guides.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]
         l.pt_guides_device_ptr.restype = C.c_void_p
         l.pt_guides_device_ptr.argtypes = [C.c_void_p, C.c_int]
+        l.pt_set_guide_chain.argtypes = [C.c_void_p, C.c_uint32]
+        l.pt_guide_chain.restype = C.c_uint32
+        l.pt_guide_chain.argtypes = [C.c_void_p]
+        l.pt_debug_guide_chain_terminals.argtypes = [C.c_void_p, C.c_int]
+        l.pt_debug_read_guide_chain_terminals.argtypes = [C.c_void_p, C.c_void_p]
         l.pt_denoise.argtypes = [C.c_void_p, C.POINTER(DenoiseParams), C.c_void_p, C.POINTER(C.c_float)]
         l.pt_denoise_device.argtypes = [C.c_void_p, C.POINTER(DenoiseParams), C.c_void_p]
         l.pt_set_sample_base.argtypes = [C.c_void_p, C.c_uint32]
@@ -452,6 +459,25 @@ class Context:
     def guides_device_ptr(self, which):
         """Device address of the albedo_hits (0) / normal_depth (1) image (0 before the first guide call)."""
         return lib().pt_guides_device_ptr(self._h, which) or 0
+
+    def set_guide_chain(self, max_transmissions):
+        """pt_set_guide_chain: guide rays follow up to `max_transmissions` refractions to the first surface that is not glass (0, the default: off).
+        Right after clear(): a change is refused once guide samples are in."""
+        self._chk(lib().pt_set_guide_chain(self._h, max_transmissions), "pt_set_guide_chain")
+
+    @property
+    def guide_chain(self):
+        return int(lib().pt_guide_chain(self._h))
+
+    def debug_guide_chain_terminals(self, enable=True):
+        """test hook: chain passes record where each pixel's chain ended (read_guide_chain_terminals)"""
+        self._chk(lib().pt_debug_guide_chain_terminals(self._h, 1 if enable else 0), "pt_debug_guide_chain_terminals")
+
+    def read_guide_chain_terminals(self):
+        """(width*height, 4) int32 of the last guide sample: primitive, top-level leaf, stage, 1 = total internal reflection; -1s: a miss / never written"""
+        out = np.zeros((self.height * self.width, 4), np.int32)
+        self._chk(lib().pt_debug_read_guide_chain_terminals(self._h, _p(out)), "pt_debug_read_guide_chain_terminals")
+        return out
 
     def denoise(self, iterations=5, hdr=False, k_normal=0.0, sigma_depth=0.0, sigma_lum=0.0, with_ms=False, input_temporal=False, input=None):
         """The edge-avoiding a-trous filter over the accumulator under the guides: (height, width, 4) tone-mapped like resolve(), or linear

@@ -1,11 +1,15 @@
 #!/usr/bin/env python3
 """Device time of pt_render_guides(4) at 1920 x 1080 on the blob room after a refit of its blob, one JSON line (EXPERIMENTS.md, "Vertex motion"):
 without motion (k_guides<0>), with an instance motion set (k_guides<1>) and with instance and vertex motion (k_guides<2>).  Not part of bench.py.
-     usage: python tools/guides_timing.py [--calls 15] [--warmup 3] [--level 6] [--samples 4]
+     usage: python tools/guides_timing.py [--calls 15] [--warmup 3] [--level 6] [--samples 4] [--chain K]
 
 Each figure is the median over `calls` of the time between two events on the stream the context renders on, around ONE pt_render_guides(samples):
 the camera rays, the closest-hit pass and k_guides, `samples` times.  The three cases run in one process on the same scene state -- the blob leaning
-0.05 at its top against the state before --, so the first two, which are the kernels of before, are the yardstick of the third."""
+0.05 at its top against the state before --, so the first two, which are the kernels of before, are the yardstick of the third.
+
+--chain K (EXPERIMENTS.md, "Guide chain"): the blob room with a GLASS blob (BASIC_REFRACTIVE, index 1.5) instead, no motion: pt_render_guides(samples) with
+pt_set_guide_chain(K) -- K = 0 makes the launches of a library without the chain, and never calls the setter, so that PTAMD_LIB may name such a library --
+next to the 1-spp frame the guides serve (pt_clear + pt_render(1), timed the same way) and the share of guide entries that go through glass."""
 import argparse
 import json
 import os
@@ -16,18 +20,62 @@ ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 sys.path[:0] = [os.path.join(ROOT, "opencl-path-tracer_amd"), ROOT]
 
 
+def chain_timing(args, D, L, scenes, torch, np, width, height):
+    b = scenes.blob_room(width, height, material=L.material_basic_refractive(1.5), level=args.level)
+    ctx = D.Context(width, height)
+    ctx.upload_scene(b.flat, sky=b.sky, material_textures=b.material_textures)
+    ctx.set_camera(b.camera)
+    stream = torch.cuda.Stream()
+    ctx.set_stream(stream.cuda_stream)
+    if args.chain:
+        ctx.set_guide_chain(args.chain)
+
+    def timed(work):
+        ms = []
+        for k in range(args.warmup + args.calls):
+            ctx.clear()
+            ctx.synchronize()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(stream)
+            work()
+            e1.record(stream)
+            ctx.synchronize()
+            if k >= args.warmup:
+                ms.append(e0.elapsed_time(e1))
+        return {"median_ms": round(statistics.median(ms), 4), "min_ms": round(min(ms), 4), "max_ms": round(max(ms), 4)}
+
+    out = {"width": width, "height": height, "triangles": int(len(b.flat.triangles)), "samples": args.samples, "calls": args.calls, "chain": args.chain}
+    out["render_guides"] = timed(lambda: ctx.render_guides(args.samples, sync=False))
+    out["frame_1spp"] = timed(lambda: ctx.render(1, sync=False))
+    ctx.clear()
+    ctx.render_guides(1)
+    a, g = ctx.read_guides()
+    out["mean_distance"] = round(float(g[:, 3][a[:, 3] > 0].mean()), 4)  # (moves behind the blob with the chain on)
+    if args.chain:
+        ctx.debug_guide_chain_terminals(True)
+        ctx.clear()
+        ctx.render_guides(1)
+        stage = ctx.read_guide_chain_terminals()[:, 2]
+        out["entries_per_stage"] = np.bincount(stage[stage >= 0], minlength=args.chain + 1).tolist()
+    ctx.close()
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--calls", type=int, default=15)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--level", type=int, default=6)
     ap.add_argument("--samples", type=int, default=4)
+    ap.add_argument("--chain", type=int, default=None, help="time the guide chain with this many transmissions on the glass blob room instead")
     args = ap.parse_args()
     import numpy as np
     import torch
-    from ptamd import device as D, scenes
+    from ptamd import device as D, layout as L, scenes
 
     width, height = 1920, 1080
+    if args.chain is not None:
+        return chain_timing(args, D, L, scenes, torch, np, width, height)
     b = scenes.blob_room(width, height, level=args.level)
     blob = b.scene._meshes[1]
     flat = b.flat
