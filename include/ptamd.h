@@ -421,6 +421,49 @@ uint32_t pt_guide_chain(const pt_ctx* ctx);
 int pt_debug_guide_chain_terminals(pt_ctx* ctx, int enable);
 int pt_debug_read_guide_chain_terminals(pt_ctx* ctx, int32_t* out4); /* host, width*height*4 int32; synchronises */
 
+/* GUIDE REFLECTIONS: the guide chain also follows mirrors and total internal reflection -- the other half of "primary surface replacement".
+ * Without it a polished metal surface -- a MIRROR: type == PT_MAT_PBR, metallic != 0, smoothness > 0.94f, what the shading itself treats as a specular
+ * bounce, by its own compare on the same float -- deposits its own albedo, normal and the depth of the mirror plane: the filter blurs every edge of the
+ * reflected room, and the history reprojects mirror pixels where the MIRROR was although a reflection moves like the virtual image behind it (the depth
+ * and normal terms accept that wrong history: ghosting under camera motion); and a chain inside a glass body ends at the first total internal
+ * reflection and deposits the glass.  Opt-in, default off: with it off every entry point launches exactly the kernels it launches without this block
+ * and returns the same bits.
+ *
+ * K = pt_guide_chain() stays the number of interfaces a guide ray may follow; reflections spend from the same budget.  With reflections on and K > 0 a
+ * guide entry carries a TINT (three floats, (1,1,1) at the camera) next to dist.  At stage j < K on a hit, with
+ *     N     the normal the pass would deposit there (GUIDE CHAIN above), cos1 = -N.D
+ *     real  shading's real normal, normalize(normalTransform(instance, edge1 x edge2));  G = real if real.-D > 0, else -real
+ *   glass, Kt > 1e-4:  transmitted exactly as in GUIDE CHAIN (the same n1n2, T, offset and dist); the tint stays
+ *   glass, Kt <= 1e-4 (total internal reflection):  reflected (below); the tint stays
+ *   a MIRROR:  reflected (below), and where the reflection is followed tint = tint (.) baseColour -- one float multiply per component, in stage order
+ *   reflected:  R = normalize(D + N (2 cos1)), followed if and only if G.R > 1e-4 (a bent shading normal that would send the reflection through the
+ *     surface is where shading ends such a path); next segment: origin X + 1e-4 R (X = O + t D as the chain forms it), direction R, dist += t (the
+ *     chain's own scaling of t for a thin lens at stage 0).  A reflection that is not followed makes this surface terminal.
+ *   Everything else is TERMINAL -- any hit that is not followed, a miss, stage K -- and deposits the expressions of the GUIDE PASS with the chain's two
+ *   changes and one more: albedo = tint (.) what the terminal would deposit (a miss: tint (.) (1,1,1), hits 0, PT_GUIDE_SKY_DEPTH, -D of the last segment).
+ *   Rough metal of smoothness in (0.94, 1) is followed along the mirror direction, as rough glass is along its mean direction.  Fresnel is ignored: the
+ *   tint is baseColour, not Schlick's.  Glossy dielectrics (metallic == 0) are never followed: they are mostly diffuse.
+ * Bits: a pixel whose chain met neither a MIRROR nor a total internal reflection gets the bits of a context with reflections off and the same K (its
+ * tint is exactly 1).  The sums stay bit-reproducible, additive over calls and complementary tilings and independent of samples_in_flight: one live
+ * entry per sample and pixel, one terminal deposit, no float atomics, no host read-back between stages.
+ * Which kernels run: the reflecting kernel runs only when K > 0, reflections are on and the uploaded materials hold a refractive type OR a MIRROR
+ * (decided per upload) -- so a scene with a mirror and no glass runs the chain.  K == 0 with reflections on is accepted and inert (the chain-off
+ * kernels): the order of the two setters does not matter.  One more float4 plane per scratch queue (32 bytes per owned pixel) is allocated at the
+ * first guide call that runs the reflecting kernel; pt_destroy frees them.
+ *
+ * What it means downstream.  For a PLANAR mirror the virtual point X = E + dist D reprojects exactly: the mirror image of the room is rigid and
+ * |X - E'| is the bent path's length from the other eye.  WHERE IT GAINS: planar mirrors (walls, windows at grazing angles, table tops) and camera
+ * motion in front of them.  WHERE IT DOES NOT: small or curved mirrors (a box face that reflects a plain wall, a polished blob: every pixel sees
+ * another direction, the virtual point is an approximation and the guides turn noisy); glossy dielectrics are not followed; Fresnel is ignored.
+ *
+ * Refusals: PT_ERR_INVALID for a null context; PT_ERR_UNSUPPORTED for enabling in parity / refill mode (as pt_set_guide_chain); PT_ERR_STATE when the
+ * value CHANGES while pt_guide_samples() > 0 (setting the value it has is always accepted; pt_clear zeroes the sums).  The chain and the motions
+ * refuse each other already, and reflections without K > 0 are inert.  A refused call changes nothing.
+ * Test hook: with reflections on, the fourth word of pt_debug_read_guide_chain_terminals is the number of reflections the chain followed (MIRROR or
+ * total internal); with reflections off it keeps its meaning. */
+int pt_set_guide_reflections(pt_ctx* ctx, int enable); /* 0 = off (default) */
+int pt_guide_reflections(const pt_ctx* ctx);           /* 1 / 0 */
+
 /* SAMPLE BASE.  pt_render traces the sample indices base + pt_samples_per_pixel ..., pt_render_guides base + pt_guide_samples ...: a frame loop
  * that clears before every frame ("move, pt_clear, pt_render(1)") sets the base to its frame number, so that every frame draws other random
  * numbers -- without it each frame is sample 0 again, with the same counter-PRNG keys, and a history of such frames averages nothing.  Default 0.

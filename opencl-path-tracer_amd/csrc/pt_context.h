@@ -369,6 +369,10 @@ struct pt_ctx {
     DevBuf<float4> guideChainO, guideChainD;
     DevBuf<float> guideChainDist[2];
     DevBuf<int4> guideChainTerminals; // pt_debug_guide_chain_terminals (test hook): width * height records, allocated while enabled
+    // guide reflections (pt_set_guide_reflections; k_guide_chain<true>): the tint of a chain's entries, a float4 plane per queue -- allocated at the first
+    // guide call that runs the reflecting kernel
+    bool guideReflections = false;
+    DevBuf<float4> guideChainTint[2];
     DevBuf<float4> denoiseColour[2], denoiseGuide;
     Event evDenoise[2];
 

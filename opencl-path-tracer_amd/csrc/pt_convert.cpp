@@ -840,11 +840,19 @@ int convertStatic(StaticHost& s, const ConvertOptions& o, uint64_t& versions, co
     s.hostNodeBoxesStale = false;
     {   // material types in use (emissive surfaces end a path in a few instructions: they do not count)
         uint32_t types = 0;
+        bool mirror = false;
         for (uint32_t t = 0; t < nT; t++) {
+            const char* const record = (const char*)&mats[tris[t].materialIndex];
             uint32_t ty;
-            std::memcpy(&ty, (const char*)&mats[tris[t].materialIndex] + 32, 4); // the type word of the 48-byte record (Material::typeAndPad.x)
+            std::memcpy(&ty, record + 32, 4); // the type word of the 48-byte record (Material::typeAndPad.x)
             types |= 1u << std::min(ty, 31u);
+            if (ty == (uint32_t)MAT_PBR) { // a MIRROR as k_shade and k_guide_chain<true> read the record: the smoothness float, the metallic byte
+                float smoothness;
+                std::memcpy(&smoothness, record + 16, 4);
+                mirror = mirror || (record[24] != 0 && smoothness > 0.94f); // kMaxSmoothness (pt_shade.h)
+            }
         }
+        s.mirror = mirror;
         s.refractive = (types & ((1u << MAT_REFRACTIVE) | (1u << MAT_BASIC_REFRACTIVE))) != 0u;
         types &= ~(1u << MAT_EMISSIVE);
         s.materialBins = (types & (types - 1u)) != 0u && (o.flags & PT_FLAG_MATERIAL_BINS) != 0u; // opt-in: measured slower (pt_shade.h)

@@ -132,6 +132,7 @@ struct StaticHost {
                                 // re-makes the device's copies on the device only; the host's are refreshed if the whole conversion ever runs again)
     bool materialBins = false; // the surfaces are of more than one material type: k_shade shades its tiles in material order
     bool refractive = false; // some triangle is REFRACTIVE or BASIC_REFRACTIVE: a guide chain has something to follow (pt_set_guide_chain)
+    bool mirror = false; // some triangle is a MIRROR -- PBR, metallic, smoothness > 0.94: with pt_set_guide_reflections a guide chain follows those too
 };
 
 // The caller's latest vertices and nodes where they are not rawVerts / hostSubNodes: after a refit on the device (pt_update_geometry) they sit in its

@@ -215,8 +215,22 @@ struct GuideChainArgs {
     float4* albedoHits;
     float4* normalDepth;
     int4* terminals; // test hook (pt_debug_guide_chain_terminals), else null: per pixel (prim, top-level leaf, stage, 1: total internal reflection) of the terminal
+    const float4* qTint; // REFLECT only: the tint of stage j's entries (not read at stage 0) ...
+    float4* outTint; // ... and of stage j + 1's
 };
 
+// REFLECT (include/ptamd.h, "guide reflections"; pt_set_guide_reflections with K > 0 over a scene that holds glass or a MIRROR): an entry also goes on
+//   * from a MIRROR -- MAT_PBR, metallic, smoothness > kMaxSmoothness: what k_shade treats as a specular bounce (dospecular) -- with its tint times the
+//     base colour (one multiply per component, in stage order; Fresnel is ignored, rough metal is followed along the mirror direction), and
+//   * from glass whose interface does not transmit (total internal reflection), tint unchanged,
+// along R = normalize(D + N (2 cos1)) if and only if G.R > kEPS, G the real normal turned to the ray's side (a bent shading normal that would send the
+// reflection through the surface is where k_shade ends such a path: the surface is terminal).  The next entry starts at X + R kEPS with dist + t, as a
+// transmitted one.  The terminal's albedo is tint (.) what it deposits otherwise (a miss: the tint itself), multiplied onto the VALUE guideAlbedo hands
+// back; an entry that met neither a MIRROR nor a total internal reflection has tint exactly 1 and deposits the bits of k_guide_chain<false>.  The tint
+// travels in one more float4 plane per queue, issued with the entry's other loads; the number of reflections followed so far travels in the `plane`
+// field of the state word (the trace kernels read the flags and nothing else of it) and is what the terminal record's fourth word holds.
+// k_guide_chain<false> is the kernel of before, instruction for instruction.
+template <bool REFLECT>
 __global__ void __launch_bounds__(256) k_guide_chain(GuideChainArgs a)
 {
     __shared__ uint32_t sCount[4], sBase;
@@ -230,10 +244,16 @@ __global__ void __launch_bounds__(256) k_guide_chain(GuideChainArgs a)
     V3 nextO = mk(0.0f), nextD = mk(0.0f);
     float nextDist = 0.0f;
     uint32_t pixel = 0u;
+    V3 tint = mk(1.0f); // (REFLECT)
+    uint32_t nextCount = 0u;
     if (live) {
         const float4 ro = a.qO[k], rd = a.qD[k], h = a.hit[k];
         const int32_t hinst = a.hitInst[k];
         const float before = a.stage ? a.qDist[k] : 0.0f;
+        if constexpr (REFLECT) {
+            if (a.stage)
+                tint = xyz(a.qTint[k]);
+        }
         pixel = asU(ro.w);
         V3 D = xyz(rd);
         float scale = 1.0f;
@@ -245,6 +265,8 @@ __global__ void __launch_bounds__(256) k_guide_chain(GuideChainArgs a)
         V3 albedo = mk(1.0f), N = D * -1.0f;
         float t = kGuideSkyDepth, hits = 0.0f;
         int32_t leaf = -1, reflected = 0;
+        if constexpr (REFLECT)
+            reflected = (int32_t)(asU(rd.w) >> 16); // reflections followed so far
         if (prim >= 0) {
             const TriFat* fp = &a.sc.triFat[prim];
             const float4 f0 = fp->n0u, f1 = fp->n1u, f2 = fp->n2u, f3 = fp->vvvm, f4 = fp->e1e, f5 = fp->e2v, f6 = fp->v0c, f7 = fp->mat;
@@ -255,7 +277,44 @@ __global__ void __launch_bounds__(256) k_guide_chain(GuideChainArgs a)
             t = h.x * scale;
             leaf = (int32_t)in.topNode;
             const bool basic = mat.type == MAT_BASIC_REFRACTIVE;
-            if ((basic || mat.type == MAT_REFRACTIVE) && !a.last) {
+            if constexpr (REFLECT) {
+                const bool glass = basic || mat.type == MAT_REFRACTIVE;
+                const bool mirror = mat.type == MAT_PBR && mat.metallic && mat.p0 > kMaxSmoothness;
+                if ((glass || mirror) && !a.last) {
+                    const V3 edge1 = xyz(f4), edge2 = mk(f4.w, f5.x, f5.y);
+                    const V3 realNormal = fastNormalize(normalTransform(in, cross(edge1, edge2)));
+                    const float facing = dot(realNormal, D * -1.0f);
+                    const float cos1 = -dot(N, D);
+                    bool reflect = mirror;
+                    if (glass) {
+                        const float ior = basic ? mat.p0 : mat.p1;
+                        const float n1n2 = (basic ? facing > kEPS : facing > 0.0f) ? 1.0f / ior : ior;
+                        const float Kt = 1.0f - (n1n2 * n1n2) * (1.0f - cos1 * cos1);
+                        if (Kt > kEPS) {
+                            goOn = true;
+                            nextD = normalize(n1n2 * D + N * (n1n2 * cos1 - sqrtf(Kt)));
+                            nextCount = (uint32_t)reflected;
+                        } else {
+                            reflect = true;
+                        }
+                    }
+                    if (reflect) {
+                        const V3 R = normalize(D + N * (2.0f * cos1));
+                        const float side = dot(realNormal, R);
+                        if ((facing > 0.0f ? side : -side) > kEPS) { // G.R, G the real normal on the ray's side
+                            goOn = true;
+                            nextD = R;
+                            nextCount = (uint32_t)reflected + 1u;
+                            if (mirror)
+                                tint = mk(tint.x * mat.colour.x, tint.y * mat.colour.y, tint.z * mat.colour.z);
+                        }
+                    }
+                    if (goOn) {
+                        nextO = xyz(ro) + xyz(rd) * h.x + nextD * kEPS;
+                        nextDist = before + t;
+                    }
+                }
+            } else if ((basic || mat.type == MAT_REFRACTIVE) && !a.last) {
                 const V3 edge1 = xyz(f4), edge2 = mk(f4.w, f5.x, f5.y);
                 const V3 realNormal = fastNormalize(normalTransform(in, cross(edge1, edge2))); // as shadeHit forms it: mirrored instances take the path's side
                 const float facing = dot(realNormal, D * -1.0f);
@@ -279,6 +338,8 @@ __global__ void __launch_bounds__(256) k_guide_chain(GuideChainArgs a)
             }
         }
         if (!goOn) {
+            if constexpr (REFLECT)
+                albedo = mk(tint.x * albedo.x, tint.y * albedo.y, tint.z * albedo.z);
             float4 al = a.albedoHits[pixel], g = a.normalDepth[pixel];
             al.x += albedo.x, al.y += albedo.y, al.z += albedo.z, al.w += hits;
             g.x += N.x, g.y += N.y, g.z += N.z, g.w += t;
@@ -306,8 +367,10 @@ __global__ void __launch_bounds__(256) k_guide_chain(GuideChainArgs a)
         const uint32_t slot = sBase + sCount[wave] + (uint32_t)__popcll(going & ((1ull << lane) - 1ull));
         if (slot < a.capacity) { // (always: stage j + 1 holds at most the entries of stage j)
             a.outO[slot] = make_float4(nextO.x, nextO.y, nextO.z, asF(pixel));
-            a.outD[slot] = make_float4(nextD.x, nextD.y, nextD.z, asF(packState(0u, a.stage + 1u, 0u)));
+            a.outD[slot] = make_float4(nextD.x, nextD.y, nextD.z, asF(packState(0u, a.stage + 1u, REFLECT ? nextCount : 0u)));
             a.outDist[slot] = nextDist;
+            if constexpr (REFLECT)
+                a.outTint[slot] = make_float4(tint.x, tint.y, tint.z, 0.0f);
         }
     }
 }

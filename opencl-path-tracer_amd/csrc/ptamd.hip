@@ -1226,14 +1226,22 @@ int pt_render_guides(pt_ctx* c, uint32_t spp)
         HIPCHK(c, c->guideCtl.alloc(1));
         HIPCHK(c, hipMemsetAsync(c->guideCtl.p, 0, sizeof(Control), c->stream));
     }
-    // the guide chain (pt_set_guide_chain), where the scene holds glass at all -- the conversion knows; without any, today's three kernels per sample
-    const uint32_t chain = c->stat[c->dyn[c->active].staticIndex].host.refractive ? c->guideChain : 0u;
+    // the guide chain (pt_set_guide_chain), where the scene holds glass at all -- the conversion knows; without any, today's three kernels per sample.
+    // With pt_set_guide_reflections a MIRROR is something to follow as well, and the chain's kernel is the reflecting instantiation.
+    const ptconv::StaticHost& materialsOf = c->stat[c->dyn[c->active].staticIndex].host;
+    const bool reflect = c->guideReflections && c->guideChain != 0u && (materialsOf.refractive || materialsOf.mirror);
+    const uint32_t chain = materialsOf.refractive || reflect ? c->guideChain : 0u;
     if (chain && c->guideChainO.n < c->guideRayO.n) {
         HIPCHK(c, hipStreamSynchronize(c->stream));
         HIPCHK(c, c->guideChainO.alloc(c->guideRayO.n));
         HIPCHK(c, c->guideChainD.alloc(c->guideRayO.n));
         HIPCHK(c, c->guideChainDist[0].alloc(c->guideRayO.n));
         HIPCHK(c, c->guideChainDist[1].alloc(c->guideRayO.n));
+    }
+    if (reflect && c->guideChainTint[0].n < c->guideRayO.n) {
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        HIPCHK(c, c->guideChainTint[0].alloc(c->guideRayO.n));
+        HIPCHK(c, c->guideChainTint[1].alloc(c->guideRayO.n));
     }
     // always the per-ray kernel: which kernel traces a launch must not depend on what the last render left in the context (the team kernel is chosen
     // by the previous batch's counters), and the launch is none of pt_stats' business
@@ -1265,7 +1273,12 @@ int pt_render_guides(pt_ctx* c, uint32_t spp)
                 g.qO = qO[j & 1u], g.qD = qD[j & 1u], g.qDist = c->guideChainDist[j & 1u].p;
                 g.outO = qO[(j + 1u) & 1u], g.outD = qD[(j + 1u) & 1u], g.outDist = c->guideChainDist[(j + 1u) & 1u].p;
                 g.stage = j, g.last = j == chain ? 1u : 0u, g.thinLens = j == 0u ? c->camera.thinLens : 0u;
-                hipLaunchKernelGGL(k_guide_chain, dim3((n + 255u) / 256u), dim3(256), 0, c->stream, g);
+                if (reflect) {
+                    g.qTint = c->guideChainTint[j & 1u].p, g.outTint = c->guideChainTint[(j + 1u) & 1u].p;
+                    hipLaunchKernelGGL(k_guide_chain<true>, dim3((n + 255u) / 256u), dim3(256), 0, c->stream, g);
+                } else {
+                    hipLaunchKernelGGL(k_guide_chain<false>, dim3((n + 255u) / 256u), dim3(256), 0, c->stream, g);
+                }
             }
             continue;
         }
@@ -1311,6 +1324,28 @@ int pt_set_guide_chain(pt_ctx* c, uint32_t maxTransmissions)
 }
 
 uint32_t pt_guide_chain(const pt_ctx* c) { return c ? c->guideChain : 0u; }
+
+// ---- guide reflections (k_guide_chain<true>) ----------------------------------------------------
+int pt_set_guide_reflections(pt_ctx* c, int enable)
+{
+    return guarded(c, "pt_set_guide_reflections", [&]() -> int {
+    if (!c)
+        return PT_ERR_INVALID;
+    const bool on = enable != 0;
+    if (on == c->guideReflections)
+        return PT_OK;
+    if (on) {
+        if (const int rc = fixedScheduleOnly(c, "pt_set_guide_reflections"))
+            return rc;
+    }
+    if (c->guideSpp != 0)
+        return fail(c, PT_ERR_STATE, "pt_set_guide_reflections: %u guide samples are in the sums already -- sums of two definitions must not mix: change it right after pt_clear", c->guideSpp);
+    c->guideReflections = on;
+    return PT_OK;
+    });
+}
+
+int pt_guide_reflections(const pt_ctx* c) { return c && c->guideReflections ? 1 : 0; }
 
 // test hook: where the chain of each pixel's LAST guide sample ended
 int pt_debug_guide_chain_terminals(pt_ctx* c, int enable)

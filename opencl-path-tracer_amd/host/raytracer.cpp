@@ -272,6 +272,12 @@ void RayTracer::setGuideChain(unsigned maxTransmissions)
     m_guideChain = maxTransmissions;
 }
 
+void RayTracer::setGuideReflections(bool on)
+{
+    check(pt_clear(m_ctx), "pt_clear"); // (like the chain: it changes only while no guide samples are in the sums)
+    check(pt_set_guide_reflections(m_ctx, on ? 1 : 0), "pt_set_guide_reflections");
+}
+
 void RayTracer::resetTemporalHistory() { check(pt_temporal_reset(m_ctx), "pt_temporal_reset"); }
 
 void RayTracer::setSampleBase(uint32_t base) { check(pt_set_sample_base(m_ctx, base), "pt_set_sample_base"); }

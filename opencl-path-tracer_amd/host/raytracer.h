@@ -117,6 +117,11 @@ public:
     // accumulation (pt_clear: guide sums of two definitions must not mix).  While it is on no instance or vertex motion is handed to the device library
     // (motion deposits along a chain are not supported): moving surfaces keep or lose their history by depth and normal alone.
     void setGuideChain(unsigned maxTransmissions);
+    // The guide chain also follows mirrors -- PBR metal of smoothness > 0.94 -- and total internal reflection, within setGuideChain's budget, and
+    // tints the terminal's albedo by the mirrors on the way (include/ptamd.h, "guide reflections"): a planar mirror then shows the filter the edges
+    // of what it reflects and keeps a history under camera motion that follows the virtual image.  Inert while setGuideChain is 0; small or curved
+    // mirrors gain nothing.  Restarts the accumulation like setGuideChain.  Off by default.
+    void setGuideReflections(bool on);
     void resetTemporalHistory(); // forget the history: after a cut, or when the scene changed beyond what depth and normal can tell
     void setSampleBase(uint32_t base); // pt_set_sample_base: frames that restart at sample 0 draw other random numbers each
     struct Guides {

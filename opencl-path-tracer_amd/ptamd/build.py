@@ -152,6 +152,10 @@ def build_raytracer(force=False):
     if force or _newer(exe11, [os.path.join(ex_dir, "glass_cornell.cpp"), out]):
         subprocess.run(["g++", "-std=c++17", "-O2", "-Wall", "glass_cornell.cpp", "-o", "glass_cornell", "-L" + HOST_DIR, "-lptamd_raytracer",
                         "-lptamd_host", "-L" + CSRC_DIR, "-lptamd", "-Wl,-rpath," + HOST_DIR, "-Wl,-rpath," + CSRC_DIR], cwd=ex_dir, check=True)
+    exe12 = os.path.join(ex_dir, "mirror_cornell")
+    if force or _newer(exe12, [os.path.join(ex_dir, "mirror_cornell.cpp"), out]):
+        subprocess.run(["g++", "-std=c++17", "-O2", "-Wall", "mirror_cornell.cpp", "-o", "mirror_cornell", "-L" + HOST_DIR, "-lptamd_raytracer",
+                        "-lptamd_host", "-L" + CSRC_DIR, "-lptamd", "-Wl,-rpath," + HOST_DIR, "-Wl,-rpath," + CSRC_DIR], cwd=ex_dir, check=True)
     return out, exe
 
 

@@ -100,6 +100,7 @@ EXPORTS = ["pt_create", "pt_destroy", "pt_last_error", "pt_set_stream", "pt_uplo
            "pt_synchronize", "pt_resolve", "pt_resolve_device", "pt_resolve_device_ptr", "pt_read_accum", "pt_write_accum", "pt_accum_device_ptr",
            "pt_samples_per_pixel", "pt_render_guides", "pt_guide_samples", "pt_read_guides", "pt_write_guides", "pt_guides_device_ptr",
            "pt_set_guide_chain", "pt_guide_chain", "pt_debug_guide_chain_terminals", "pt_debug_read_guide_chain_terminals",
+           "pt_set_guide_reflections", "pt_guide_reflections",
            "pt_denoise", "pt_denoise_device", "pt_set_sample_base", "pt_sample_base", "pt_temporal_accumulate", "pt_temporal_reset",
            "pt_temporal_frames", "pt_read_temporal", "pt_write_temporal", "pt_temporal_device_ptr", "pt_set_instance_motion", "pt_instance_motion",
            "pt_read_motion_guides", "pt_write_motion_guides", "pt_motion_guides_device_ptr", "pt_debug_motion_records",
@@ -169,6 +170,9 @@ def lib():
         l.pt_guide_chain.argtypes = [C.c_void_p]
         l.pt_debug_guide_chain_terminals.argtypes = [C.c_void_p, C.c_int]
         l.pt_debug_read_guide_chain_terminals.argtypes = [C.c_void_p, C.c_void_p]
+        l.pt_set_guide_reflections.argtypes = [C.c_void_p, C.c_int]
+        l.pt_guide_reflections.restype = C.c_int
+        l.pt_guide_reflections.argtypes = [C.c_void_p]
         l.pt_denoise.argtypes = [C.c_void_p, C.POINTER(DenoiseParams), C.c_void_p, C.POINTER(C.c_float)]
         l.pt_denoise_device.argtypes = [C.c_void_p, C.POINTER(DenoiseParams), C.c_void_p]
         l.pt_set_sample_base.argtypes = [C.c_void_p, C.c_uint32]
@@ -469,12 +473,22 @@ class Context:
     def guide_chain(self):
         return int(lib().pt_guide_chain(self._h))
 
+    def set_guide_reflections(self, enable=True):
+        """pt_set_guide_reflections: the guide chain also follows mirrors (PBR metal of smoothness > 0.94) and total internal reflection, and the
+        terminal's albedo is tinted by the mirrors on the way.  Inert without set_guide_chain(K > 0).  Right after clear(), like set_guide_chain."""
+        self._chk(lib().pt_set_guide_reflections(self._h, 1 if enable else 0), "pt_set_guide_reflections")
+
+    @property
+    def guide_reflections(self):
+        return bool(lib().pt_guide_reflections(self._h))
+
     def debug_guide_chain_terminals(self, enable=True):
         """test hook: chain passes record where each pixel's chain ended (read_guide_chain_terminals)"""
         self._chk(lib().pt_debug_guide_chain_terminals(self._h, 1 if enable else 0), "pt_debug_guide_chain_terminals")
 
     def read_guide_chain_terminals(self):
-        """(width*height, 4) int32 of the last guide sample: primitive, top-level leaf, stage, 1 = total internal reflection; -1s: a miss / never written"""
+        """(width*height, 4) int32 of the last guide sample: primitive, top-level leaf, stage, 1 = total internal reflection (with guide reflections
+        on: the number of reflections the chain followed); -1s: a miss / never written"""
         out = np.zeros((self.height * self.width, 4), np.int32)
         self._chk(lib().pt_debug_read_guide_chain_terminals(self._h, _p(out)), "pt_debug_read_guide_chain_terminals")
         return out

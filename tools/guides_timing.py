@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Device time of pt_render_guides(4) at 1920 x 1080 on the blob room after a refit of its blob, one JSON line (EXPERIMENTS.md, "Vertex motion"):
 without motion (k_guides<0>), with an instance motion set (k_guides<1>) and with instance and vertex motion (k_guides<2>).  Not part of bench.py.
-     usage: python tools/guides_timing.py [--calls 15] [--warmup 3] [--level 6] [--samples 4] [--chain K]
+     usage: python tools/guides_timing.py [--calls 15] [--warmup 3] [--level 6] [--samples 4] [--chain K [--reflections] [--scene S]]
 
 Each figure is the median over `calls` of the time between two events on the stream the context renders on, around ONE pt_render_guides(samples):
 the camera rays, the closest-hit pass and k_guides, `samples` times.  The three cases run in one process on the same scene state -- the blob leaning
@@ -9,7 +9,11 @@ the camera rays, the closest-hit pass and k_guides, `samples` times.  The three 
 
 --chain K (EXPERIMENTS.md, "Guide chain"): the blob room with a GLASS blob (BASIC_REFRACTIVE, index 1.5) instead, no motion: pt_render_guides(samples) with
 pt_set_guide_chain(K) -- K = 0 makes the launches of a library without the chain, and never calls the setter, so that PTAMD_LIB may name such a library --
-next to the 1-spp frame the guides serve (pt_clear + pt_render(1), timed the same way) and the share of guide entries that go through glass."""
+next to the 1-spp frame the guides serve (pt_clear + pt_render(1), timed the same way) and the share of guide entries that go through glass.
+
+--reflections (EXPERIMENTS.md, "Guide reflections"; with --chain K): pt_set_guide_reflections(1) as well, and --scene names what the chain runs over:
+glass_blob (the default: the reflecting kernel over glass), mirror_blob (the blob room with a polished metal blob) or mirror_wall (cornell_mirror_wall).
+Without --reflections the setter is never called, and a scene without glass then runs the chain-off kernels whatever K."""
 import argparse
 import json
 import os
@@ -21,7 +25,11 @@ sys.path[:0] = [os.path.join(ROOT, "opencl-path-tracer_amd"), ROOT]
 
 
 def chain_timing(args, D, L, scenes, torch, np, width, height):
-    b = scenes.blob_room(width, height, material=L.material_basic_refractive(1.5), level=args.level)
+    if args.scene == "mirror_wall":
+        b = scenes.cornell_mirror_wall(width, height)
+    else:
+        blob = L.material_pbr_metal((0.95, 0.8, 0.5), 1.0) if args.scene == "mirror_blob" else L.material_basic_refractive(1.5)
+        b = scenes.blob_room(width, height, material=blob, level=args.level)
     ctx = D.Context(width, height)
     ctx.upload_scene(b.flat, sky=b.sky, material_textures=b.material_textures)
     ctx.set_camera(b.camera)
@@ -29,6 +37,8 @@ def chain_timing(args, D, L, scenes, torch, np, width, height):
     ctx.set_stream(stream.cuda_stream)
     if args.chain:
         ctx.set_guide_chain(args.chain)
+    if args.reflections:
+        ctx.set_guide_reflections(True)
 
     def timed(work):
         ms = []
@@ -44,7 +54,8 @@ def chain_timing(args, D, L, scenes, torch, np, width, height):
                 ms.append(e0.elapsed_time(e1))
         return {"median_ms": round(statistics.median(ms), 4), "min_ms": round(min(ms), 4), "max_ms": round(max(ms), 4)}
 
-    out = {"width": width, "height": height, "triangles": int(len(b.flat.triangles)), "samples": args.samples, "calls": args.calls, "chain": args.chain}
+    out = {"width": width, "height": height, "triangles": int(len(b.flat.triangles)), "samples": args.samples, "calls": args.calls, "chain": args.chain,
+           "scene": args.scene, "reflections": bool(args.reflections)}
     out["render_guides"] = timed(lambda: ctx.render_guides(args.samples, sync=False))
     out["frame_1spp"] = timed(lambda: ctx.render(1, sync=False))
     ctx.clear()
@@ -56,7 +67,7 @@ def chain_timing(args, D, L, scenes, torch, np, width, height):
         ctx.clear()
         ctx.render_guides(1)
         stage = ctx.read_guide_chain_terminals()[:, 2]
-        out["entries_per_stage"] = np.bincount(stage[stage >= 0], minlength=args.chain + 1).tolist()
+        out["entries_per_stage"] = np.bincount(stage[stage >= 0], minlength=args.chain + 1).tolist()  # (all zero: the chain-off kernels ran)
     ctx.close()
     print(json.dumps(out))
 
@@ -68,6 +79,8 @@ def main():
     ap.add_argument("--level", type=int, default=6)
     ap.add_argument("--samples", type=int, default=4)
     ap.add_argument("--chain", type=int, default=None, help="time the guide chain with this many transmissions on the glass blob room instead")
+    ap.add_argument("--reflections", action="store_true", help="with --chain: pt_set_guide_reflections(1) as well")
+    ap.add_argument("--scene", choices=["glass_blob", "mirror_blob", "mirror_wall"], default="glass_blob", help="with --chain: what the chain runs over")
     args = ap.parse_args()
     import numpy as np
     import torch
