@@ -3,7 +3,7 @@
 // bottom-up, topology kept), RayTracer::updateGeometry (pt_update_geometry), RayTracer::frameTick (lights + top level, pt_upload_dynamic_async +
 // pt_frame_tick), then one sample per pixel.  Prints the median milliseconds of every stage: the tick without any binding in between.
 //      usage: deform_loop [nu nv] [frames]        (2 * nu * nv triangles on a lumpy torus; 135 x 135 = 36 450, the lab report's mesh size)
-#include "../opencl-path-tracer_amd/host/raytracer.h"
+#include "cornell.h"
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -11,6 +11,7 @@
 #include <cstdlib>
 
 using namespace raytracer;
+using namespace cornell;
 using Clock = std::chrono::steady_clock;
 
 static double ms(Clock::time_point a, Clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); }
@@ -18,13 +19,6 @@ static double median(std::vector<double> v)
 {
     std::sort(v.begin(), v.end());
     return v.empty() ? 0.0 : v[v.size() / 2];
-}
-
-static std::shared_ptr<Mesh> quadMesh(vec3 a, vec3 b, vec3 c, vec3 d, const Material& m)
-{
-    const float pos[12] = { a.x, a.y, a.z, b.x, b.y, b.z, c.x, c.y, c.z, d.x, d.y, d.z };
-    const uint32_t idx[6] = { 0, 1, 2, 0, 2, 3 };
-    return std::make_shared<Mesh>(pos, nullptr, nullptr, 4, idx, nullptr, 2, std::vector<Material> { m }, BvhBuilder::BinnedSAH);
 }
 
 static void torus(int nu, int nv, float phase, std::vector<float>& pos)
@@ -50,8 +44,7 @@ int main(int argc, char** argv)
         const Material white = Material::Diffuse(vec3(0.73f));
         scene->addNode(quadMesh({ -1, 0, -1 }, { -1, 0, 1 }, { 1, 0, 1 }, { 1, 0, -1 }, white));
         scene->addNode(quadMesh({ -1, 0, 1 }, { -1, 2, 1 }, { 1, 2, 1 }, { 1, 0, 1 }, white));
-        scene->addNode(quadMesh({ -0.25f, 1.98f, -0.25f }, { 0.25f, 1.98f, -0.25f }, { 0.25f, 1.98f, 0.25f }, { -0.25f, 1.98f, 0.25f },
-            Material::Emissive(vec3(1.0f, 0.92f, 0.8f), 12.0f)));
+        scene->addNode(ceilingLight());
         std::vector<float> pos;
         torus(nu, nv, 0.0f, pos);
         std::vector<uint32_t> idx;
@@ -68,9 +61,7 @@ int main(int argc, char** argv)
         t.location = vec3(0.0f, 0.8f, 0.1f);
         scene->addNode(mesh, t);
 
-        TextureArray noTextures, sky;
-        const float grey[4] = { 0.4f, 0.4f, 0.4f, 1.0f };
-        sky.add(grey, 1, 1);
+        const TextureArray noTextures, sky = greySky();
         RayTracer rt(W, H, scene, noTextures, sky);
         Transform camT(vec3(0.0f, 1.0f, -3.9f));
         Camera camera(camT, 50.0f, (float)W / H, 3.9f);

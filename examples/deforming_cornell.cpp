@@ -5,32 +5,14 @@
 // (RayTracer::setVertexMotion, the default), where the history follows the surface.  The last frame is written three times as a PPM: filtered alone
 // (getDenoisedOutput), filtered over the history without vertex motion, and with it.
 //     usage: deforming_cornell [frames] [filtered.ppm] [temporal_plain.ppm] [temporal_motion.ppm]
-#include "../opencl-path-tracer_amd/host/raytracer.h"
+#include "cornell.h"
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 
 using namespace raytracer;
-
-static std::shared_ptr<Mesh> quadMesh(vec3 a, vec3 b, vec3 c, vec3 d, const Material& m)
-{
-    const float pos[12] = { a.x, a.y, a.z, b.x, b.y, b.z, c.x, c.y, c.z, d.x, d.y, d.z };
-    const uint32_t idx[6] = { 0, 1, 2, 0, 2, 3 };
-    return std::make_shared<Mesh>(pos, nullptr, nullptr, 4, idx, nullptr, 2, std::vector<Material> { m }, BvhBuilder::BinnedSAH);
-}
-
-static void writePPM(const char* path, const std::vector<float>& img, int W, int H)
-{
-    FILE* f = std::fopen(path, "wb");
-    if (!f)
-        throw std::runtime_error("cannot write output");
-    std::fprintf(f, "P6\n%d %d\n255\n", W, H);
-    for (int i = 0; i < W * H; i++)
-        for (int k = 0; k < 3; k++)
-            std::fputc((int)(std::fmin(1.0f, std::fmax(0.0f, img[i * 4 + k])) * 255.0f + 0.5f), f);
-    std::fclose(f);
-}
+using namespace cornell;
 
 // a lumpy sphere of radius ~0.45 about the origin: kLat x kLon quads, one vertex per pole and ring position
 static const int kLat = 24, kLon = 48;
@@ -70,14 +52,8 @@ struct Result {
 static Result run(int frames, bool vertexMotion, const Camera& camera, int W, int H)
 {
     auto scene = std::make_shared<Scene>();
-    const Material white = Material::Diffuse(vec3(0.73f)), green = Material::Diffuse(vec3(0.12f, 0.45f, 0.15f)), red = Material::Diffuse(vec3(0.65f, 0.05f, 0.05f));
-    scene->addNode(quadMesh({ -1, 0, -1 }, { -1, 0, 1 }, { 1, 0, 1 }, { 1, 0, -1 }, white)); // floor
-    scene->addNode(quadMesh({ -1, 2, -1 }, { 1, 2, -1 }, { 1, 2, 1 }, { -1, 2, 1 }, white)); // ceiling
-    scene->addNode(quadMesh({ -1, 0, 1 }, { -1, 2, 1 }, { 1, 2, 1 }, { 1, 0, 1 }, white)); // back
-    scene->addNode(quadMesh({ -1, 0, -1 }, { -1, 2, -1 }, { -1, 2, 1 }, { -1, 0, 1 }, green)); // left
-    scene->addNode(quadMesh({ 1, 0, -1 }, { 1, 0, 1 }, { 1, 2, 1 }, { 1, 2, -1 }, red)); // right
-    scene->addNode(quadMesh({ -0.25f, 1.98f, -0.25f }, { 0.25f, 1.98f, -0.25f }, { 0.25f, 1.98f, 0.25f }, { -0.25f, 1.98f, 0.25f },
-        Material::Emissive(vec3(1.0f, 0.92f, 0.8f), 12.0f)));
+    addWalls(*scene); // floor, ceiling, back, left, right
+    scene->addNode(ceilingLight());
     std::vector<float> rest, pos;
     blobRest(rest);
     std::vector<uint32_t> idx;
@@ -94,9 +70,7 @@ static Result run(int frames, bool vertexMotion, const Camera& camera, int W, in
         std::vector<Material> { Material::Diffuse(vec3(0.2f, 0.3f, 0.7f)) }, BvhBuilder::BinnedSAH);
     scene->addNode(blob, Transform(kBlobAt));
 
-    TextureArray noTextures, sky;
-    const float grey[4] = { 0.4f, 0.4f, 0.4f, 1.0f };
-    sky.add(grey, 1, 1);
+    const TextureArray noTextures, sky = greySky();
     RayTracer rt(W, H, scene, noTextures, sky);
     rt.setVertexMotion(vertexMotion);
     Result r;
@@ -134,9 +108,7 @@ int main(int argc, char** argv)
         return 1;
     }
     try {
-        Camera camera(Transform(vec3(0.0f, 1.0f, -3.9f)), 40.0f, (float)W / H, 3.9f); // identity orientation looks down +z
-        camera.m_thinLens = false;
-        camera.m_shutterTime = 1.0f;
+        const Camera camera = frontCamera(W, H);
         const Result plain = run(frames, false, camera, W, H), motion = run(frames, true, camera, W, H);
         writePPM(filteredPath, motion.filtered, W, H);
         writePPM(plainPath, plain.temporal, W, H);

@@ -4,20 +4,14 @@
 // history, or blend in the wall that used to be there -- and with it (RayTracer::setInstanceMotion, the default), where the history follows the box.
 // The last frame is written three times as a PPM: filtered alone (getDenoisedOutput), filtered over the history without motion, and with motion.
 //     usage: moving_cornell [frames] [filtered.ppm] [temporal_plain.ppm] [temporal_motion.ppm]
-#include "../opencl-path-tracer_amd/host/raytracer.h"
+#include "cornell.h"
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 
 using namespace raytracer;
-
-static std::shared_ptr<Mesh> quadMesh(vec3 a, vec3 b, vec3 c, vec3 d, const Material& m)
-{
-    const float pos[12] = { a.x, a.y, a.z, b.x, b.y, b.z, c.x, c.y, c.z, d.x, d.y, d.z };
-    const uint32_t idx[6] = { 0, 1, 2, 0, 2, 3 };
-    return std::make_shared<Mesh>(pos, nullptr, nullptr, 4, idx, nullptr, 2, std::vector<Material> { m }, BvhBuilder::BinnedSAH);
-}
+using namespace cornell;
 
 // a box about the origin, four vertices of its own per face (flat normals), wound outwards
 static std::shared_ptr<Mesh> boxMesh(vec3 h, const Material& m)
@@ -40,18 +34,6 @@ static std::shared_ptr<Mesh> boxMesh(vec3 h, const Material& m)
     return std::make_shared<Mesh>(pos.data(), nullptr, nullptr, 24, idx.data(), nullptr, 12, std::vector<Material> { m }, BvhBuilder::BinnedSAH);
 }
 
-static void writePPM(const char* path, const std::vector<float>& img, int W, int H)
-{
-    FILE* f = std::fopen(path, "wb");
-    if (!f)
-        throw std::runtime_error("cannot write output");
-    std::fprintf(f, "P6\n%d %d\n255\n", W, H);
-    for (int i = 0; i < W * H; i++)
-        for (int k = 0; k < 3; k++)
-            std::fputc((int)(std::fmin(1.0f, std::fmax(0.0f, img[i * 4 + k])) * 255.0f + 0.5f), f);
-    std::fclose(f);
-}
-
 static const vec3 kHalf(0.28f, 0.45f, 0.28f);
 
 static Transform boxPose(int frame)
@@ -69,19 +51,11 @@ struct Result {
 static Result run(int frames, bool instanceMotion, const Camera& camera, int W, int H)
 {
     auto scene = std::make_shared<Scene>();
-    const Material white = Material::Diffuse(vec3(0.73f)), green = Material::Diffuse(vec3(0.12f, 0.45f, 0.15f)), red = Material::Diffuse(vec3(0.65f, 0.05f, 0.05f));
-    scene->addNode(quadMesh({ -1, 0, -1 }, { -1, 0, 1 }, { 1, 0, 1 }, { 1, 0, -1 }, white)); // floor
-    scene->addNode(quadMesh({ -1, 2, -1 }, { 1, 2, -1 }, { 1, 2, 1 }, { -1, 2, 1 }, white)); // ceiling
-    scene->addNode(quadMesh({ -1, 0, 1 }, { -1, 2, 1 }, { 1, 2, 1 }, { 1, 0, 1 }, white)); // back
-    scene->addNode(quadMesh({ -1, 0, -1 }, { -1, 2, -1 }, { -1, 2, 1 }, { -1, 0, 1 }, green)); // left
-    scene->addNode(quadMesh({ 1, 0, -1 }, { 1, 0, 1 }, { 1, 2, 1 }, { 1, 2, -1 }, red)); // right
-    scene->addNode(quadMesh({ -0.25f, 1.98f, -0.25f }, { 0.25f, 1.98f, -0.25f }, { 0.25f, 1.98f, 0.25f }, { -0.25f, 1.98f, 0.25f },
-        Material::Emissive(vec3(1.0f, 0.92f, 0.8f), 12.0f)));
+    addWalls(*scene); // floor, ceiling, back, left, right
+    scene->addNode(ceilingLight());
     SceneNode& box = scene->addNode(boxMesh(kHalf, Material::Diffuse(vec3(0.2f, 0.3f, 0.7f))), boxPose(0));
 
-    TextureArray noTextures, sky;
-    const float grey[4] = { 0.4f, 0.4f, 0.4f, 1.0f };
-    sky.add(grey, 1, 1);
+    const TextureArray noTextures, sky = greySky();
     RayTracer rt(W, H, scene, noTextures, sky);
     rt.setInstanceMotion(instanceMotion);
     Result r;
@@ -117,9 +91,7 @@ int main(int argc, char** argv)
         return 1;
     }
     try {
-        Camera camera(Transform(vec3(0.0f, 1.0f, -3.9f)), 40.0f, (float)W / H, 3.9f); // identity orientation looks down +z
-        camera.m_thinLens = false;
-        camera.m_shutterTime = 1.0f;
+        const Camera camera = frontCamera(W, H);
         const Result plain = run(frames, false, camera, W, H), motion = run(frames, true, camera, W, H);
         writePPM(filteredPath, motion.filtered, W, H);
         writePPM(plainPath, plain.temporal, W, H);

@@ -6,41 +6,12 @@
 // to the frame): how long the history grows is the guides' doing, and with one jittered guide sample per frame the history of this small room stays so
 // short that it forgets the old light by itself.
 //     usage: moving_light [frames before the jump] [reference spp]
-#include "../opencl-path-tracer_amd/host/raytracer.h"
-#include <cmath>
+#include "cornell.h"
 #include <cstdio>
 #include <cstdlib>
 
 using namespace raytracer;
-
-static std::shared_ptr<Mesh> quadMesh(vec3 a, vec3 b, vec3 c, vec3 d, const Material& m)
-{
-    const float pos[12] = { a.x, a.y, a.z, b.x, b.y, b.z, c.x, c.y, c.z, d.x, d.y, d.z };
-    const uint32_t idx[6] = { 0, 1, 2, 0, 2, 3 };
-    return std::make_shared<Mesh>(pos, nullptr, nullptr, 4, idx, nullptr, 2, std::vector<Material> { m }, BvhBuilder::BinnedSAH);
-}
-
-// linear radiance -> exposure -> Reinhard, before gamma: the space the image gates of the tests measure in
-static std::vector<double> tonemapped(const std::vector<float>& rgba, double scale, const CameraData& cam)
-{
-    const double ev = std::log2((double)cam.relativeAperture * cam.relativeAperture / cam.shutterTime * 100.0 / cam.ISO);
-    const double exposure = 1.0 / (1.2 * std::exp2(ev));
-    std::vector<double> out(rgba.size() / 4 * 3);
-    for (size_t i = 0; i < rgba.size() / 4; i++)
-        for (int k = 0; k < 3; k++) {
-            const double l = rgba[i * 4 + k] * scale * exposure;
-            out[i * 3 + k] = l / (1.0 + l);
-        }
-    return out;
-}
-
-static double rmse(const std::vector<double>& a, const std::vector<double>& b)
-{
-    double s = 0.0;
-    for (size_t i = 0; i < a.size(); i++)
-        s += (a[i] - b[i]) * (a[i] - b[i]);
-    return std::sqrt(s / (double)a.size());
-}
+using namespace cornell;
 
 static const int kAfter[3] = { 4, 16, 32 }; // frames after the jump at which the history is measured
 static const uint32_t kGuideSamples = 16;
@@ -51,14 +22,8 @@ struct Room {
     SceneNode* light = nullptr;
     Room()
     {
-        const Material white = Material::Diffuse(vec3(0.73f)), green = Material::Diffuse(vec3(0.12f, 0.45f, 0.15f)), red = Material::Diffuse(vec3(0.65f, 0.05f, 0.05f));
-        scene->addNode(quadMesh({ -1, 0, -1 }, { -1, 0, 1 }, { 1, 0, 1 }, { 1, 0, -1 }, white)); // floor
-        scene->addNode(quadMesh({ -1, 2, -1 }, { 1, 2, -1 }, { 1, 2, 1 }, { -1, 2, 1 }, white)); // ceiling
-        scene->addNode(quadMesh({ -1, 0, 1 }, { -1, 2, 1 }, { 1, 2, 1 }, { 1, 0, 1 }, white)); // back
-        scene->addNode(quadMesh({ -1, 0, -1 }, { -1, 2, -1 }, { -1, 2, 1 }, { -1, 0, 1 }, green)); // left
-        scene->addNode(quadMesh({ 1, 0, -1 }, { 1, 0, 1 }, { 1, 2, 1 }, { 1, 2, -1 }, red)); // right
-        auto plate = quadMesh({ -0.3f, 0.6f, -0.3f }, { -0.3f, 0.6f, 0.3f }, { 0.3f, 0.6f, 0.3f }, { 0.3f, 0.6f, -0.3f }, Material::Diffuse(vec3(0.2f, 0.3f, 0.7f)));
-        scene->addNode(plate, Transform(vec3(0.2f, 0.0f, 0.1f)));
+        addWalls(*scene); // floor, ceiling, back, left, right
+        scene->addNode(bluePlate(), Transform(vec3(0.2f, 0.0f, 0.1f)));
         light = &scene->addNode(quadMesh({ -0.25f, 0.0f, -0.25f }, { 0.25f, 0.0f, -0.25f }, { 0.25f, 0.0f, 0.25f }, { -0.25f, 0.0f, 0.25f },
                                     Material::Emissive(vec3(1.0f, 0.92f, 0.8f), 12.0f)),
             Transform(vec3(kLightBefore, 1.98f, 0.0f)));
@@ -88,13 +53,9 @@ int main(int argc, char** argv)
         return 1;
     }
     try {
-        Camera camera(Transform(vec3(0.0f, 1.0f, -3.9f)), 40.0f, (float)W / H, 3.9f); // identity orientation looks down +z
-        camera.m_thinLens = false;
-        camera.m_shutterTime = 1.0f;
+        const Camera camera = frontCamera(W, H);
         const CameraData cam = camera.get_camera_data();
-        TextureArray noTextures, sky;
-        const float grey[4] = { 0.4f, 0.4f, 0.4f, 1.0f };
-        sky.add(grey, 1, 1);
+        const TextureArray noTextures, sky = greySky();
 
         std::vector<double> want; // the converged view of the state after the jump, from random numbers no frame below draws
         {

@@ -5,7 +5,7 @@
 // top level, frames keep rendering meanwhile.  Prints the median milliseconds of every stage and checks the last frame against a RayTracer that only ever
 // saw that frame: the two accumulators must be identical.
 //      usage: rebuild_loop [level] [frames]        (icosphere level: 5 = 20 480 triangles, bench.py's `rebuild_20k`)
-#include "../opencl-path-tracer_amd/host/raytracer.h"
+#include "cornell.h"
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -15,6 +15,7 @@
 #include <map>
 
 using namespace raytracer;
+using namespace cornell;
 using Clock = std::chrono::steady_clock;
 
 static double ms(Clock::time_point a, Clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); }
@@ -53,13 +54,6 @@ private:
     Material m_material;
     std::shared_ptr<Mesh> m_mesh;
 };
-
-static std::shared_ptr<Mesh> quadMesh(vec3 a, vec3 b, vec3 c, vec3 d, const Material& m)
-{
-    const float pos[12] = { a.x, a.y, a.z, b.x, b.y, b.z, c.x, c.y, c.z, d.x, d.y, d.z };
-    const uint32_t idx[6] = { 0, 1, 2, 0, 2, 3 };
-    return std::make_shared<Mesh>(pos, nullptr, nullptr, 4, idx, nullptr, 2, std::vector<Material> { m }, BvhBuilder::BinnedSAH);
-}
 
 // unit icosphere, `level` subdivisions (20 * 4^level triangles)
 static void icosphere(int level, std::vector<float>& pos, std::vector<uint32_t>& idx)
@@ -121,8 +115,7 @@ int main(int argc, char** argv)
             auto scene = std::make_shared<Scene>();
             scene->addNode(quadMesh({ -1, 0, -1 }, { -1, 0, 1 }, { 1, 0, 1 }, { 1, 0, -1 }, white));
             scene->addNode(quadMesh({ -1, 0, 1 }, { -1, 2, 1 }, { 1, 2, 1 }, { 1, 0, 1 }, white));
-            scene->addNode(quadMesh({ -0.25f, 1.98f, -0.25f }, { 0.25f, 1.98f, -0.25f }, { 0.25f, 1.98f, 0.25f }, { -0.25f, 1.98f, 0.25f },
-                Material::Emissive(vec3(1.0f, 0.92f, 0.8f), 12.0f)));
+            scene->addNode(ceilingLight());
             auto seq = std::make_shared<RebuiltMesh>(idx, blobMaterial);
             deformed(unit, frame, pos);
             seq->goToFrame(pos);
@@ -133,9 +126,7 @@ int main(int argc, char** argv)
             *out = seq;
             return scene;
         };
-        TextureArray noTextures, sky;
-        const float grey[4] = { 0.4f, 0.4f, 0.4f, 1.0f };
-        sky.add(grey, 1, 1);
+        const TextureArray noTextures, sky = greySky();
         Transform camT(vec3(0.0f, 1.0f, -3.9f));
         Camera camera(camT, 50.0f, (float)W / H, 3.9f);
         camera.m_thinLens = false;

@@ -4,12 +4,13 @@
 // transferDynamicData src/raytracer.cpp:510-568); ADVICE r5: it was skipped silently and the next frame showed stale geometry.
 // Renders the deformed state through updateGeometry + frameTick and through a fresh RayTracer: the two accumulators must be identical.
 //      usage: untracked_mesh          prints stale_differs=<0|1> same_as_fresh=<0|1>
-#include "../opencl-path-tracer_amd/host/raytracer.h"
+#include "cornell.h"
 #include <cmath>
 #include <cstdio>
 #include <cstring>
 
 using namespace raytracer;
+using namespace cornell;
 
 // a sequence-like mesh: forwards everything to a Mesh it owns, deforms through it, reports no generation
 class SequenceLikeMesh : public IMesh {
@@ -34,13 +35,6 @@ public:
 private:
     std::shared_ptr<Mesh> m_mesh;
 };
-
-static std::shared_ptr<Mesh> quadMesh(vec3 a, vec3 b, vec3 c, vec3 d, const Material& m)
-{
-    const float pos[12] = { a.x, a.y, a.z, b.x, b.y, b.z, c.x, c.y, c.z, d.x, d.y, d.z };
-    const uint32_t idx[6] = { 0, 1, 2, 0, 2, 3 };
-    return std::make_shared<Mesh>(pos, nullptr, nullptr, 4, idx, nullptr, 2, std::vector<Material> { m }, BvhBuilder::BinnedSAH);
-}
 
 static void blob(int n, float phase, std::vector<float>& pos, std::vector<uint32_t>* idx)
 {
@@ -73,8 +67,7 @@ int main()
         auto makeScene = [&](const std::vector<float>& pos, std::shared_ptr<SequenceLikeMesh>* out) {
             auto scene = std::make_shared<Scene>();
             scene->addNode(quadMesh({ -1, 0, -1 }, { -1, 0, 1 }, { 1, 0, 1 }, { 1, 0, -1 }, Material::Diffuse(vec3(0.73f))));
-            scene->addNode(quadMesh({ -0.25f, 1.98f, -0.25f }, { 0.25f, 1.98f, -0.25f }, { 0.25f, 1.98f, 0.25f }, { -0.25f, 1.98f, 0.25f },
-                Material::Emissive(vec3(1.0f, 0.92f, 0.8f), 12.0f)));
+            scene->addNode(ceilingLight());
             auto inner = std::make_shared<Mesh>(pos.data(), nullptr, nullptr, (size_t)N * N, idx.data(), nullptr, idx.size() / 3,
                 std::vector<Material> { Material::Diffuse(vec3(0.8f, 0.3f, 0.2f)) }, BvhBuilder::BinnedSAH);
             auto seq = std::make_shared<SequenceLikeMesh>(inner);
@@ -85,9 +78,7 @@ int main()
                 *out = seq;
             return scene;
         };
-        TextureArray noTextures, sky;
-        const float grey[4] = { 0.4f, 0.4f, 0.4f, 1.0f };
-        sky.add(grey, 1, 1);
+        const TextureArray noTextures, sky = greySky();
         Transform camT(vec3(0.0f, 1.0f, -3.9f));
         Camera camera(camT, 50.0f, (float)W / H, 3.9f);
         camera.m_thinLens = false;

@@ -101,62 +101,20 @@ def build_device(force=False):
 
 def build_raytracer(force=False):
     """libptamd_raytracer.so: the C++ RayTracer class (host/raytracer.cpp) on top of both libraries,
-    and the examples/render_cornell demo that drives it."""
+    and the programs under examples/ that drive it (returned: render_cornell)."""
     out = os.path.join(HOST_DIR, "libptamd_raytracer.so")
     deps = _all_files(HOST_DIR, (".cpp", ".h")) + _all_files(os.path.join(ROOT, "..", "include"), (".h",))  # pt_stats etc. are part of its ABI
     if force or _newer(out, deps):
         subprocess.run(["g++", "-std=c++17", "-O2", "-Wall", "-fPIC", "-shared", "raytracer.cpp", "-o", out, "-L.", "-lptamd_host",
                         "-L../csrc", "-lptamd", "-Wl,-rpath,$ORIGIN", "-Wl,-rpath,$ORIGIN/../csrc"], cwd=HOST_DIR, check=True)
     ex_dir = os.path.abspath(os.path.join(ROOT, "..", "examples"))
-    exe = os.path.join(ex_dir, "render_cornell")
-    if force or _newer(exe, [os.path.join(ex_dir, "render_cornell.cpp"), out]):
-        subprocess.run(["g++", "-std=c++17", "-O2", "-Wall", "render_cornell.cpp", "-o", "render_cornell", "-L" + HOST_DIR, "-lptamd_raytracer",
-                        "-lptamd_host", "-L" + CSRC_DIR, "-lptamd", "-Wl,-rpath," + HOST_DIR, "-Wl,-rpath," + CSRC_DIR], cwd=ex_dir, check=True)
-    exe2 = os.path.join(ex_dir, "deform_loop")
-    if force or _newer(exe2, [os.path.join(ex_dir, "deform_loop.cpp"), out]):
-        subprocess.run(["g++", "-std=c++17", "-O2", "-Wall", "deform_loop.cpp", "-o", "deform_loop", "-L" + HOST_DIR, "-lptamd_raytracer",
-                        "-lptamd_host", "-L" + CSRC_DIR, "-lptamd", "-Wl,-rpath," + HOST_DIR, "-Wl,-rpath," + CSRC_DIR], cwd=ex_dir, check=True)
-    exe3 = os.path.join(ex_dir, "untracked_mesh")
-    if force or _newer(exe3, [os.path.join(ex_dir, "untracked_mesh.cpp"), out]):
-        subprocess.run(["g++", "-std=c++17", "-O2", "-Wall", "untracked_mesh.cpp", "-o", "untracked_mesh", "-L" + HOST_DIR, "-lptamd_raytracer",
-                        "-lptamd_host", "-L" + CSRC_DIR, "-lptamd", "-Wl,-rpath," + HOST_DIR, "-Wl,-rpath," + CSRC_DIR], cwd=ex_dir, check=True)
-    exe4 = os.path.join(ex_dir, "rebuild_loop")
-    if force or _newer(exe4, [os.path.join(ex_dir, "rebuild_loop.cpp"), out]):
-        subprocess.run(["g++", "-std=c++17", "-O2", "-Wall", "rebuild_loop.cpp", "-o", "rebuild_loop", "-L" + HOST_DIR, "-lptamd_raytracer",
-                        "-lptamd_host", "-L" + CSRC_DIR, "-lptamd", "-Wl,-rpath," + HOST_DIR, "-Wl,-rpath," + CSRC_DIR], cwd=ex_dir, check=True)
-    exe5 = os.path.join(ex_dir, "denoise_cornell")
-    if force or _newer(exe5, [os.path.join(ex_dir, "denoise_cornell.cpp"), out]):
-        subprocess.run(["g++", "-std=c++17", "-O2", "-Wall", "denoise_cornell.cpp", "-o", "denoise_cornell", "-L" + HOST_DIR, "-lptamd_raytracer",
-                        "-lptamd_host", "-L" + CSRC_DIR, "-lptamd", "-Wl,-rpath," + HOST_DIR, "-Wl,-rpath," + CSRC_DIR], cwd=ex_dir, check=True)
-    exe6 = os.path.join(ex_dir, "orbit_cornell")
-    if force or _newer(exe6, [os.path.join(ex_dir, "orbit_cornell.cpp"), out]):
-        subprocess.run(["g++", "-std=c++17", "-O2", "-Wall", "orbit_cornell.cpp", "-o", "orbit_cornell", "-L" + HOST_DIR, "-lptamd_raytracer",
-                        "-lptamd_host", "-L" + CSRC_DIR, "-lptamd", "-Wl,-rpath," + HOST_DIR, "-Wl,-rpath," + CSRC_DIR], cwd=ex_dir, check=True)
-    exe7 = os.path.join(ex_dir, "moving_cornell")
-    if force or _newer(exe7, [os.path.join(ex_dir, "moving_cornell.cpp"), out]):
-        subprocess.run(["g++", "-std=c++17", "-O2", "-Wall", "moving_cornell.cpp", "-o", "moving_cornell", "-L" + HOST_DIR, "-lptamd_raytracer",
-                        "-lptamd_host", "-L" + CSRC_DIR, "-lptamd", "-Wl,-rpath," + HOST_DIR, "-Wl,-rpath," + CSRC_DIR], cwd=ex_dir, check=True)
-    exe8 = os.path.join(ex_dir, "deforming_cornell")
-    if force or _newer(exe8, [os.path.join(ex_dir, "deforming_cornell.cpp"), out]):
-        subprocess.run(["g++", "-std=c++17", "-O2", "-Wall", "deforming_cornell.cpp", "-o", "deforming_cornell", "-L" + HOST_DIR, "-lptamd_raytracer",
-                        "-lptamd_host", "-L" + CSRC_DIR, "-lptamd", "-Wl,-rpath," + HOST_DIR, "-Wl,-rpath," + CSRC_DIR], cwd=ex_dir, check=True)
-    exe9 = os.path.join(ex_dir, "converge_cornell")
-    if force or _newer(exe9, [os.path.join(ex_dir, "converge_cornell.cpp"), out]):
-        subprocess.run(["g++", "-std=c++17", "-O2", "-Wall", "converge_cornell.cpp", "-o", "converge_cornell", "-L" + HOST_DIR, "-lptamd_raytracer",
-                        "-lptamd_host", "-L" + CSRC_DIR, "-lptamd", "-Wl,-rpath," + HOST_DIR, "-Wl,-rpath," + CSRC_DIR], cwd=ex_dir, check=True)
-    exe10 = os.path.join(ex_dir, "moving_light")
-    if force or _newer(exe10, [os.path.join(ex_dir, "moving_light.cpp"), out]):
-        subprocess.run(["g++", "-std=c++17", "-O2", "-Wall", "moving_light.cpp", "-o", "moving_light", "-L" + HOST_DIR, "-lptamd_raytracer",
-                        "-lptamd_host", "-L" + CSRC_DIR, "-lptamd", "-Wl,-rpath," + HOST_DIR, "-Wl,-rpath," + CSRC_DIR], cwd=ex_dir, check=True)
-    exe11 = os.path.join(ex_dir, "glass_cornell")
-    if force or _newer(exe11, [os.path.join(ex_dir, "glass_cornell.cpp"), out]):
-        subprocess.run(["g++", "-std=c++17", "-O2", "-Wall", "glass_cornell.cpp", "-o", "glass_cornell", "-L" + HOST_DIR, "-lptamd_raytracer",
-                        "-lptamd_host", "-L" + CSRC_DIR, "-lptamd", "-Wl,-rpath," + HOST_DIR, "-Wl,-rpath," + CSRC_DIR], cwd=ex_dir, check=True)
-    exe12 = os.path.join(ex_dir, "mirror_cornell")
-    if force or _newer(exe12, [os.path.join(ex_dir, "mirror_cornell.cpp"), out]):
-        subprocess.run(["g++", "-std=c++17", "-O2", "-Wall", "mirror_cornell.cpp", "-o", "mirror_cornell", "-L" + HOST_DIR, "-lptamd_raytracer",
-                        "-lptamd_host", "-L" + CSRC_DIR, "-lptamd", "-Wl,-rpath," + HOST_DIR, "-Wl,-rpath," + CSRC_DIR], cwd=ex_dir, check=True)
-    return out, exe
+    headers = _all_files(ex_dir, (".h",))
+    for src in sorted(f for f in os.listdir(ex_dir) if f.endswith(".cpp")):  # every example: its own source, the shared headers, the library
+        name = src[:-len(".cpp")]
+        if force or _newer(os.path.join(ex_dir, name), [os.path.join(ex_dir, src), out] + headers):
+            subprocess.run(["g++", "-std=c++17", "-O2", "-Wall", src, "-o", name, "-L" + HOST_DIR, "-lptamd_raytracer",
+                            "-lptamd_host", "-L" + CSRC_DIR, "-lptamd", "-Wl,-rpath," + HOST_DIR, "-Wl,-rpath," + CSRC_DIR], cwd=ex_dir, check=True)
+    return out, os.path.join(ex_dir, "render_cornell")
 
 
 def build_all(force=False):
