@@ -734,6 +734,12 @@ typedef struct {
     uint32_t* nflags;
     uint32_t* shadow_alive;
     float *sox, *soy, *soz, *sdx, *sdy, *sdz, *slen, *sc_r, *sc_g, *sc_b;
+    /* The path's density word (RayData.pdf, neeMisShading shading.cl:35-349): the solid-angle density with which the previous bounce sampled the
+     * direction of this ray.  k_shade reads it only for bounce != 0 (primary rays carry LASTSPECULAR and density 0) and only under the MIS
+     * integrator, where an emissive hit after a non-specular bounce weighs its deposit with it; it writes the density of the direction it sampled
+     * into the continuation ray (0 for glass and for the alpha-0 pass-through; 0 from the default kernel, which carries none). */
+    const float* in_pdf; /* in, n; NULL: 0 for every entry */
+    float* npdf; /* out, n: written for live continuation rays; NULL: not returned */
 } pt_shade_batch_io;
 int pt_shade_batch(pt_ctx* ctx, pt_shade_batch_io* io);
 

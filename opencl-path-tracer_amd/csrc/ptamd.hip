@@ -2408,7 +2408,7 @@ int pt_shade_batch(pt_ctx* c, pt_shade_batch_io* io)
         std::memcpy(&fp, &px, 4), std::memcpy(&ff, &fl, 4), std::memcpy(&fprim, &prim, 4);
         hO[i] = make_float4(io->ox[i], io->oy[i], io->oz[i], fp);
         hD[i] = make_float4(io->dx[i], io->dy[i], io->dz[i], ff);
-        hT[i] = make_float4(io->thr_r[i], io->thr_g[i], io->thr_b[i], 0.f);
+        hT[i] = make_float4(io->thr_r[i], io->thr_g[i], io->thr_b[i], io->in_pdf ? io->in_pdf[i] : 0.f);
         hH[i] = make_float4(prim >= 0 ? io->t[i] : INFINITY, io->u[i], io->v[i], fprim);
         int32_t ti = io->inst[i];
         hI[i] = (ti >= 0 && (size_t)ti < topToInst.size()) ? topToInst[ti] : -1;
@@ -2477,6 +2477,8 @@ int pt_shade_batch(pt_ctx* c, pt_shade_batch_io* io)
             uint32_t fl;
             std::memcpy(&fl, &d[i].w, 4);
             io->nflags[i] = fl & 0xFFu;
+            if (io->npdf)
+                io->npdf[i] = t[i].w;
         }
         if (io->shadow_alive[i]) {
             io->sox[i] = so[i].x, io->soy[i] = so[i].y, io->soz[i] = so[i].z, io->slen[i] = so[i].w;

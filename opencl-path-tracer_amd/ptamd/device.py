@@ -59,7 +59,8 @@ class ShadeBatchIO(C.Structure):
                 + [("sample", C.c_uint32)]
                 + [(n, C.c_void_p) for n in ("radiance", "out_alive", "nox", "noy", "noz", "ndx", "ndy", "ndz",
                                              "nthr_r", "nthr_g", "nthr_b", "nflags", "shadow_alive", "sox", "soy",
-                                             "soz", "sdx", "sdy", "sdz", "slen", "sc_r", "sc_g", "sc_b")])
+                                             "soz", "sdx", "sdy", "sdz", "slen", "sc_r", "sc_g", "sc_b",
+                                             "in_pdf", "npdf")])
 
 
 DENOISE_TONEMAPPED, DENOISE_HDR = 0, 1
@@ -735,7 +736,8 @@ class Context:
         self._chk(lib().pt_primary_pass(self._h, sample, batch, n, *[_p(a) for a in arrs], _p(pixel), C.byref(hits)), "pt_primary_pass")
         return np.stack(arrs[:3], 1), np.stack(arrs[3:], 1), pixel, dict(t=t, u=u, v=v, prim=prim, inst=inst)
 
-    def shade_batch(self, o, d, thr, pixel, flags, bounce, t, u, v, prim, inst, sample=0):
+    def shade_batch(self, o, d, thr, pixel, flags, bounce, t, u, v, prim, inst, sample=0, in_pdf=None):
+        """in_pdf: the density with which the previous bounce sampled each ray (None: 0); out["npdf"]: the density k_shade wrote for the next bounce"""
         n = len(o)
         f32 = lambda a: np.ascontiguousarray(a, np.float32)
         u32 = lambda a: np.ascontiguousarray(a, np.uint32)
@@ -752,6 +754,10 @@ class Context:
             out[k] = np.zeros(n, np.float32)
         order = ["radiance", "out_alive", "nox", "noy", "noz", "ndx", "ndy", "ndz", "nthr_r", "nthr_g", "nthr_b",
                  "nflags", "shadow_alive", "sox", "soy", "soz", "sdx", "sdy", "sdz", "slen", "sc_r", "sc_g", "sc_b"]
-        io = ShadeBatchIO(n, *[_p(a).value for a in ins], sample, *[_p(out[k]).value for k in order])
+        out["npdf"] = np.zeros(n, np.float32)
+        in_pdf = None if in_pdf is None else f32(in_pdf)
+        assert in_pdf is None or in_pdf.shape == (n,)
+        io = ShadeBatchIO(n, *[_p(a).value for a in ins], sample, *[_p(out[k]).value for k in order],
+                          None if in_pdf is None else _p(in_pdf).value, _p(out["npdf"]).value)
         self._chk(lib().pt_shade_batch(self._h, C.byref(io)), "pt_shade_batch")
         return out

@@ -790,12 +790,16 @@ inline LightSample weightedRandomPointOnLight(const Scene& sc, V3 X, Rng& rng)
 //   kept   -- its DIFFUSE light sample divides diffuseColour by pi without the alpha-0 check of the IS variant (:150);
 //   FIXED  -- its DIFFUSE continuation stores outData->pdf = dot(shadingNormal, reflection) / pi BEFORE `reflection` is
 //             assigned (:590-592): an uninitialised read, whatever the compiler makes of it.  In oracle/_ref (ROCm clang -O1
-//             for x86-64) it evaluates to 0: a light found by a diffuse bounce then contributes nothing (pdf2 < EPSILON, :87)
-//             although next event estimation was already weighted down by 1 / (pdf1 + pdf2) -- a biased (darker) estimator.
-//             `in.misAsCompiled` reproduces exactly that (ORC_INTEGRATOR_*_AS_COMPILED) and is bit-exact with the reference's
-//             COMPARE_SHADING build on whole queue loops (tests/test_oracle_vs_ref.py); the default takes the density from
-//             the direction that is then sampled, which is what the comment next to it asks for ("MIS needs unsimplified
-//             PDF") and what makes the two estimators agree.
+//             for x86-64) the variable holds what the other arm of that branch, the alpha-0 pass-through, assigns to it: the
+//             ray's own direction.  The density stored is dot(shadingNormal, rayDirection) / pi -- negative wherever the shading
+//             normal faces the ray, so that a light found by a diffuse bounce contributes nothing (pdf2 < EPSILON, :87)
+//             although next event estimation was already weighted down by 1 / (pdf1 + pdf2): a biased (darker) estimator; a
+//             diffuse surface met from behind, or under an instance whose rotation the object-space shading normal ignores,
+//             hands on a positive, meaningless density instead.  `in.misAsCompiled` reproduces exactly that
+//             (ORC_INTEGRATOR_*_AS_COMPILED) and is bit-exact with the reference's COMPARE_SHADING build on whole queue loops
+//             (tests/test_oracle_vs_ref.py) and entry by entry, this word included (tests/test_shade_grid_cpu.py); the default
+//             takes the density from the direction that is then sampled, which is what the comment next to it asks for ("MIS
+//             needs unsimplified PDF") and what makes the two estimators agree.
 V3 neeShading(const Scene& sc, const ShadeIn& in, Rng& rng, ShadeOut& out)
 {
     const Triangle& tri = sc.triangles[in.tri];
@@ -999,8 +1003,8 @@ V3 neeShading(const Scene& sc, const ShadeIn& in, Rng& rng, ShadeOut& out)
             BRDF = mk(1.0f);
         } else {
             reflection = cosineWeightedDiffuseReflection(realNormal, edge1, in.invT, rng);
-            if (in.mis)
-                out.pdf = in.misAsCompiled ? 0.0f : dot(shadingNormal, reflection) * kINVPI; // FIXED: after sampling, not before (see above; :590-592)
+            if (in.mis) // FIXED: after sampling, not before; as compiled: the pass-through branch's `reflection` (see above; :590-592)
+                out.pdf = dot(shadingNormal, in.misAsCompiled ? in.D : reflection) * kINVPI;
             BRDF = c;
         }
     }

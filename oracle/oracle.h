@@ -81,7 +81,7 @@ enum {
     ORC_INTEGRATOR_IS = 0,
     ORC_INTEGRATOR_MIS = 1,
     ORC_INTEGRATOR_COMPARE = 2,
-    // the same two with neeMisShading's uninitialised read (shading.cl:590-592) evaluating to 0, as it does in oracle/_ref
+    // the same two with neeMisShading's uninitialised read (shading.cl:590-592) evaluating to the ray's direction, as it does in oracle/_ref
     ORC_INTEGRATOR_MIS_AS_COMPILED = 3,
     ORC_INTEGRATOR_COMPARE_AS_COMPILED = 4
 };

@@ -38,7 +38,7 @@ class SceneStruct(C.Structure):  # OrcScene == RefScene
 
 
 INTEGRATOR_IS, INTEGRATOR_MIS, INTEGRATOR_COMPARE = 0, 1, 2  # neeIsShading | neeMisShading | COMPARE_SHADING's half-and-half
-INTEGRATOR_MIS_AS_COMPILED, INTEGRATOR_COMPARE_AS_COMPILED = 3, 4  # ... with the reference's uninitialised pdf read as 0 (oracle/_ref)
+INTEGRATOR_MIS_AS_COMPILED, INTEGRATOR_COMPARE_AS_COMPILED = 3, 4  # ... with the reference's uninitialised read as oracle/_ref compiles it
 LIGHTS_UNIFORM, LIGHTS_SOLID_ANGLE = 0, 1  # randomPointOnLight | weightedRandomPointOnLight
 
 

@@ -13,7 +13,11 @@ from the cosine LADDER against the WORLD-space geometric normal with a random az
 
 Labels per entry (the strata of the tests are the values of each label, at least 64 entries each): family, corner (the material's parameters), incidence
 (the rung), placement (mesh/placement); `degenerate` marks the entries whose object-space shading normal is exactly +-x under a sampler seeded with
-(1,0,0) -- PBR and rough glass on the x walls of `axis`, under every placement: the reference's tangent frame is NaN there (oracle.cpp, orient)."""
+(1,0,0) -- PBR and rough glass on the x walls of `axis`, under every placement: the reference's tangent frame is NaN there (oracle.cpp, orient).
+
+The family "emissive mis" (emissive_mis_grid) is the input space of the one branch only neeMisShading has (shading.cl:69-90): hits on the light after a
+non-specular bounce, over a ladder of incoming densities, a ladder of solid angles and both sides of the light; its entries carry two more labels,
+in_pdf and solid_angle.  Every entry of every family carries the incoming density in rays["pdf"] (0 unless a test seeds it: seed_in_pdf)."""
 import numpy as np
 
 from ptamd import host as H
@@ -127,10 +131,17 @@ def mesh_arrays(tilted, materials=None, light_material=None):
             np.concatenate(I).astype(np.uint32), np.asarray(M, np.uint32))
 
 
+# The emissive-under-MIS family alone sees one more instance of either mesh: a pure uniform scale that is not 1.  neeMisShading takes the light's area
+# in OBJECT space and the distance in WORLD space (shading.cl:75-80); only a scaled placement tells a kernel that "fixes" this apart, and a scale of
+# 1/2 moves its solid angle by a factor 4.  The other families keep the scene they were measured on: a ninth and tenth instance would add lights.
+EXTRA_PLACEMENTS = {"scaled 0.5": ((0.1, -0.2, 0.3), None, 0.0, (0.5, 0.5, 0.5))}
+
+
 class Scene:
     """The flattened scene and, per (mesh, placement): the top-level leaf, the float64 matrices, the triangles by material"""
 
-    def __init__(self):
+    def __init__(self, extra=False):
+        placements = {**PLACEMENTS, **EXTRA_PLACEMENTS} if extra else PLACEMENTS
         recs = [m[2] for m in MATERIALS]
         self.scene = H.Scene()
         meshes = {}
@@ -139,7 +150,7 @@ class Scene:
             meshes[name] = H.Mesh(p, i, recs, material_index=m, normals=n, tex_coords=uv, builder=H.BVH_BINNED_SAH)
         expect = []
         for mname, mesh in meshes.items():
-            for pname, (loc, axis, ang, scale) in PLACEMENTS.items():
+            for pname, (loc, axis, ang, scale) in placements.items():
                 self.scene.add_node(mesh, location=loc, orientation_wxyz=_quat(axis, ang), scale=scale)
                 Rm = np.eye(3) if axis is None else _rotation(axis, ang)
                 fwd = np.eye(4)
@@ -165,7 +176,8 @@ class Scene:
                 by_mat.setdefault(int(self.material_label[flat.triangles["materialIndex"][t]]), []).append(int(t))
             self.where[(mn, pn)] = dict(leaf=int(leaf), A=A, M=np.linalg.inv(A), tris={k: np.array(sorted(set(v))) for k, v in by_mat.items()})
             axis_normals[mn] = is_axis
-        assert len(self.where) == 8 and axis_normals == {"axis": True, "tilt": False}, "every (mesh, placement) found once; only `axis` has exact normals"
+        assert len(self.where) == 2 * len(placements), "every (mesh, placement) found once"
+        assert axis_normals == {"axis": True, "tilt": False}, "only `axis` has exact normals"
 
     def _leaf_triangles(self, root):
         out, stack = [], [root]
@@ -178,14 +190,14 @@ class Scene:
         return np.array(out)
 
 
-_scene = None
+_scenes = {}
 
 
-def scene():
-    global _scene
-    if _scene is None:
-        _scene = Scene()
-    return _scene
+def scene(extra=False):
+    """the grid's scene; extra: with EXTRA_PLACEMENTS (the emissive-under-MIS family's)"""
+    if extra not in _scenes:
+        _scenes[extra] = Scene(extra)
+    return _scenes[extra]
 
 
 class Grid:
@@ -235,6 +247,9 @@ def grid(family, seed=1, exact_rungs=False):
     """The entries of `family` (one of FAMILIES); "diffuse" also carries the sky misses and the emissive hits.
     exact_rungs: every rung holds the value LADDER names -- 0 is 0, +-1 is +-1 for rough glass too.  Such a grid is NOT conditioned (see ZERO_RUNG and
     NORMAL_RUNG_ROUGH_GLASS above): it serves the comparison with the reference's own kernel, which is bit for bit and needs no conditioning."""
+    if family == "emissive mis":
+        assert not exact_rungs
+        return emissive_mis_grid(seed)
     S = scene()
     flat = S.flat
     rng = np.random.default_rng([seed, FAMILIES.index(family)])
@@ -323,10 +338,115 @@ def grid(family, seed=1, exact_rungs=False):
     return g
 
 
+# ---------------------------------------------------------------- emissive hits under neeMisShading
+K_EPS = np.float32(1e-4)  # EPSILON, shading.cl
+
+
+def d_ggx(n_dot_h, alpha):
+    """D_GGX (pbr_brdf.cl:96-105) in float64"""
+    a2 = alpha * alpha
+    f = n_dot_h * n_dot_h * (a2 - 1) + 1
+    return a2 / (np.pi * f * f) if f > 1e-4 else 1.0
+
+
+# The incoming density (RayData.pdf): INPUTS, handed over as these very floats -- the neighbours of kEPS are exact.  The peak of the sharpest GGX lobe
+# that is not treated as a mirror, D_GGX(1, 1 - kMaxSmoothness), is 1 / (pi 0.06^2) = 88.4 (alpha is the roughness itself in this renderer, not its square).
+IN_PDF_LADDER = (("0", np.float32(0)), ("kEPS-", np.nextafter(K_EPS, np.float32(0))), ("kEPS+", np.nextafter(K_EPS, np.float32(1))),
+                 ("1/pi", np.float32(1 / np.pi)), ("1", np.float32(1)), ("GGX peak of s=0.94", np.float32(d_ggx(1.0, 1 - 0.94))), ("1e7", np.float32(1e7)))
+# The solid angle cos * area / t^2 the branch computes, set through t.  Its kEPS neighbours are COMPUTED from an area (Heron, three roots), a normalised
+# normal, a dot product and a squared distance, each good to some 1e-6 relative (1e-3 for the cosine at the 2e-4 rung): they sit a factor 1.02 either
+# side, twenty times that round-off, where a wrong constant, a wrong comparison or an area off by any scale still flips the whole rung.
+SOLID_ANGLE_LADDER = (("1e-6", 1e-6), ("kEPS/1.02", 1e-4 / 1.02), ("kEPS*1.02", 1e-4 * 1.02), ("0.05", 0.05), ("20, clamped to 2 pi", 20.0))
+EMISSIVE_MIS_COSINES = (1.0, 0.5, 1e-2, 2e-4, -1e-2, -0.5)  # against the world-space geometric normal: head-on, oblique, grazing; the back side
+BACK_SIDE = "negative (back side)"
+N_EMISSIVE_MIS, N_EMISSIVE_MIS_CONTROL = 2816, 128
+
+
+def emissive_mis_grid(seed=1):
+    """Hits on the light of either mesh under every placement of PLACEMENTS and EXTRA_PLACEMENTS, LASTSPECULAR clear: N_EMISSIVE_MIS entries at bounce 1,
+    throughput U(0.1, 1), over IN_PDF_LADDER x SOLID_ANGLE_LADDER x EMISSIVE_MIS_COSINES x placement (each axis balanced and permuted on its own), and
+    N_EMISSIVE_MIS_CONTROL entries at bounce 0 with density 0 and throughput 1 (a primary ray's word is never loaded), front side, solid angle above
+    kEPS.  The ray origin is X - t d to fp32 rounding: the branch measures the distance |X - origin| with X = origin + t d.
+    g.solid_angle is the solid angle of each entry in float64 from the fp32 inputs (negative on the back side, not clamped)."""
+    S = scene(extra=True)
+    flat = S.flat
+    rng = np.random.default_rng([seed, 977])
+    n_main, n = N_EMISSIVE_MIS, N_EMISSIVE_MIS + N_EMISSIVE_MIS_CONTROL
+    control = np.arange(n) >= n_main
+    light = len(MATERIALS) - 1
+    keys = list(S.where)
+    place = rng.permutation(np.arange(n) % len(keys))
+    pdf_rung = np.where(control, 0, rng.permutation(np.arange(n) % len(IN_PDF_LADDER)))
+    front = [k for k, c in enumerate(EMISSIVE_MIS_COSINES) if c > 0]
+    cos_rung = np.where(control, rng.choice(front, n), rng.permutation(np.arange(n) % len(EMISSIVE_MIS_COSINES)))
+    sa_rung = np.where(control, rng.integers(2, len(SOLID_ANGLE_LADDER), n), rng.permutation(np.arange(n) % len(SOLID_ANGLE_LADDER)))
+    c = np.array(EMISSIVE_MIS_COSINES)[cos_rung]
+    want_sa = np.array([v for _, v in SOLID_ANGLE_LADDER])[sa_rung]
+    r1, r2 = np.sqrt(rng.random(n)), rng.random(n)
+    u, v = (r1 * (1 - r2)).astype(np.float32), (r1 * r2).astype(np.float32)
+    thr = np.where(control[:, None], 1.0, rng.uniform(0.1, 1.0, (n, 3))).astype(np.float32)
+
+    prim, inst = np.zeros(n, np.int32), np.zeros(n, np.int32)
+    X, Nw, area = np.zeros((n, 3)), np.zeros((n, 3)), np.zeros(n)
+    for k, key in enumerate(keys):
+        w = S.where[key]
+        sel = np.flatnonzero(place == k)
+        tri = rng.choice(w["tris"][light], len(sel))
+        p = flat.vertices["vertex"][flat.triangles["indices"][tri].astype(np.int64), :3].astype(np.float64)
+        e1, e2 = p[:, 1] - p[:, 0], p[:, 2] - p[:, 0]
+        obj = p[:, 0] + u[sel, None] * e1 + v[sel, None] * e2
+        X[sel] = obj @ w["M"][:3, :3].T + w["M"][:3, 3]
+        gn = np.cross(e1, e2) @ w["A"][:3, :3]
+        Nw[sel] = gn / np.linalg.norm(gn, axis=1, keepdims=True)
+        area[sel] = 0.5 * np.linalg.norm(np.cross(e1, e2), axis=1)  # OBJECT space, as the reference takes it
+        prim[sel], inst[sel] = tri, w["leaf"]
+    D = -(c[:, None] * Nw + np.sqrt(1 - c[:, None] ** 2) * _perp(Nw, rng))
+    t = np.sqrt(np.abs(c) * area / want_sa).astype(np.float32)
+    o = X - t[:, None].astype(np.float64) * D
+
+    g = Grid()
+    g.family, g.scene, g.n = "emissive mis", S, n
+    g.rays = np.zeros(n, L.RAY_DATA)
+    g.rays["origin"][:, :3], g.rays["direction"][:, :3], g.rays["multiplier"][:, :3] = o, D, thr
+    g.rays["numBounces"] = np.where(control, 0, 1)
+    g.rays["pdf"] = np.array([val for _, val in IN_PDF_LADDER], np.float32)[pdf_rung]
+    g.rays["outputPixel"] = np.arange(n)
+    g.hit = np.ones(n, bool)
+    g.t, g.uv, g.prim, g.inst = t, np.stack([u, v], 1), prim, inst
+    d32 = g.rays["direction"][:, :3].astype(np.float64)
+    unit = d32 / np.linalg.norm(d32, axis=1, keepdims=True)
+    g.solid_angle = -(Nw * unit).sum(1) * area / (t.astype(np.float64) ** 2 * (d32 * d32).sum(1))
+    back = c < 0
+    g.labels = dict(family=np.full(n, "emissive"), corner=np.where(control, "bounce 0 (control)", "bounce 1"),
+                    incidence=np.array([f"cos={x:g}" for x in c]), placement=np.array([f"{keys[k][0]}/{keys[k][1]}" for k in place]),
+                    in_pdf=np.where(control, "0 at bounce 0 (control)", np.array([name for name, _ in IN_PDF_LADDER])[pdf_rung]),
+                    solid_angle=np.where(back, BACK_SIDE, np.array([name for name, _ in SOLID_ANGLE_LADDER])[sa_rung]))
+    g.alpha0, g.degenerate = np.zeros(n, bool), np.zeros(n, bool)
+    g.shading_normal = flat.vertices["normal"][flat.triangles["indices"][prim, 0].astype(np.int64), :3].astype(np.float32)
+    g.colour = np.tile(np.asarray(MATERIALS[light][2]["colour"][:3], np.float32), (n, 1))
+    return g
+
+
+def seed_in_pdf(g, seed=5):
+    """A copy of `g` whose bounce-1 entries carry an incoming density U(0, 10) (bounce 0 keeps 0: a primary ray's word is never loaded).
+    Conditioning: under MIS an emissive hit after a diffuse bounce deposits a weight that goes with its solid angle, hence with the cosine of incidence;
+    at the rungs +-5e-5 and the zero rung (+-2e-6) the round-off of that cosine (1e-7) is 0.2 % and 5 % of it -- the strict and the -march=native
+    oracle deposited 7.428 and 7.475 on one such entry.  Those emissive entries keep density 0 (they deposit nothing under either integrator); the
+    emissive-under-MIS family holds the grazing hits, at cosines whose round-off stays a quarter of the comparison's 2e-3."""
+    s = take(g, np.arange(g.n))
+    rng = np.random.default_rng([seed, g.n])
+    inc = g.labels["incidence"]
+    ill = (g.labels["family"] == "emissive") & (np.isin(inc, (f"cos={5e-5:g}", f"cos={-5e-5:g}")) | np.char.endswith(inc, "(the zero rung)"))
+    s.rays["pdf"] = np.where((s.rays["numBounces"] != 0) & ~ill, rng.uniform(0.0, 10.0, g.n), 0.0).astype(np.float32)
+    return s
+
+
 def strata(g):
     """[(label, indices)]: per label dimension, the entries of each of its values -- the strata the gates are asserted on"""
     out = []
-    for dim in ("family", "corner", "incidence", "placement"):
+    for dim in ("family", "corner", "incidence", "placement", "in_pdf", "solid_angle"):
+        if dim not in g.labels:
+            continue
         for val in sorted(set(g.labels[dim])):
             idx = np.flatnonzero(g.labels[dim] == val)
             if dim != "family" and val == "miss":
@@ -354,11 +474,15 @@ class Shaded:
     ray / shadow: RAY_DATA records (zero where the entry was a miss), ray_alive / shadow_alive, radiance (n, 3), streams (LFSR113 mode)"""
 
 
-def shade(g, which="oracle", rng_mode=None, sample=2, seed=4, fast=False, light_sampling=None, width=64, height=48):
-    """orc_shade (which = "oracle"; counter PRNG keyed by (entry = pixel, sample, seed) unless rng_mode says LFSR113) or the reference's own shade
-    kernel compiled for the host (which = "ref": LFSR113, stream k for slot k) over the queue of `g`."""
+def shade(g, which="oracle", rng_mode=None, sample=2, seed=4, fast=False, light_sampling=None, width=64, height=48, integrator=None,
+          compare_build=False):
+    """orc_shade (which = "oracle"; counter PRNG keyed by (entry = pixel, sample, seed) unless rng_mode says LFSR113; integrator: one of orclib's
+    INTEGRATOR_*, neeIsShading by default) or the reference's own shade kernel compiled for the host (which = "ref": LFSR113, stream k for slot k;
+    compare_build: its COMPARE_SHADING build, neeMisShading where outputPixel % width < width / 2) over the queue of `g`.  The incoming density is
+    rays["pdf"], the one written for the next bounce comes back as Shaded.ray["pdf"]."""
     import ctypes as C
     import orclib as O
+    assert which == "ref" or not compare_build
     rng_mode = O.RNG_COUNTER if rng_mode is None else rng_mode
     S = g.scene
     sc = O.BoundScene(S.flat, sky=S.sky, material_textures=S.tex)
@@ -369,9 +493,11 @@ def shade(g, which="oracle", rng_mode=None, sample=2, seed=4, fast=False, light_
     acc = np.zeros((max(N, width * height), 4), np.float32)
     streams = O.create_streams(N) if (which == "ref" or rng_mode == O.RNG_LFSR113) else None
     if which == "ref":
-        O.ref_kernels().ref_shade(C.c_size_t(N), O._p(acc), O._p(out_r), O._p(out_s), O._p(qr), O._p(sd), O._p(kd), C.byref(sc.struct), O._p(streams))
+        O.ref_kernels(compare_shading=compare_build).ref_shade(C.c_size_t(N), O._p(acc), O._p(out_r), O._p(out_s), O._p(qr), O._p(sd), O._p(kd),
+                                                               C.byref(sc.struct), O._p(streams))
     else:
-        prm = O.Params(rng_mode, sample, seed, 0, O.INTEGRATOR_IS, O.LIGHTS_UNIFORM if light_sampling is None else light_sampling)
+        prm = O.Params(rng_mode, sample, seed, 0, O.INTEGRATOR_IS if integrator is None else integrator,
+                       O.LIGHTS_UNIFORM if light_sampling is None else light_sampling)
         O.oracle(fast).orc_shade(C.c_size_t(N), O._p(acc), O._p(out_r), O._p(out_s), O._p(qr), O._p(sd), O._p(kd), C.byref(sc.struct), O._p(streams),
                                  C.byref(prm), None)
     shaded = np.flatnonzero(g.hit)
@@ -431,4 +557,6 @@ def take(g, idx):
     s.hit, s.t, s.uv, s.prim, s.inst = g.hit[idx], g.t[idx], g.uv[idx], g.prim[idx], g.inst[idx]
     s.alpha0, s.degenerate, s.colour, s.shading_normal = g.alpha0[idx], g.degenerate[idx], g.colour[idx], g.shading_normal[idx]
     s.labels = {k: v[idx] for k, v in g.labels.items()}
+    if hasattr(g, "solid_angle"):
+        s.solid_angle = g.solid_angle[idx]
     return s

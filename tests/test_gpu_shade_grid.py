@@ -4,6 +4,9 @@ incidence either side of kEPS and of the 0.05 cutoff, hits at vertices and edge 
 axis-aligned normals on which the reference's tangent frame is NaN.  tests/test_shade_grid_cpu.py holds the oracle to the reference on the same entries and
 shows that the grid is conditioned: a disagreement beyond the gates here is not round-off.
 
+Under neeMisShading (k_shade<false, true> with FLAG_INTEGRATOR_MIS) the hook carries the path's density word both ways: the same families with a seeded
+incoming density, the density written for the next bounce held to the oracle's, the emissive-under-MIS family of the grid, the COMPARE_SHADING split.
+
 The gates per stratum are those of test_gpu_gen_shade.py::test_shade_batch_matches_oracle_per_material; the measured fractions are read from
 profiles/round6/parity_margins.json (gpu_util.fraction_gate: 0.98 x measured, never below 0.97)."""
 import json
@@ -34,20 +37,22 @@ SHADOW = (("sox", "origin", 0), ("soy", "origin", 1), ("soz", "origin", 2), ("sd
           ("sc_r", "multiplier", 0), ("sc_g", "multiplier", 1), ("sc_b", "multiplier", 2))
 
 
-def _shade_on_gpu(gpu, g, flags=0):
+def _shade_on_gpu(gpu, g, flags=0, in_pdf=None):
+    """in_pdf: the incoming density handed to the hook (None: the hook's own default, 0 for every entry)"""
     S = g.scene
     assert g.n <= W * H and int(g.rays["outputPixel"].max()) < W * H and g.prim.max() < len(S.flat.triangles)
     ctx = U.make_ctx(gpu, S.flat, W, H, camera=S.camera, sky=S.sky, tex=S.tex, seed=4, flags=flags)
     t0 = time.time()
     got = ctx.shade_batch(g.rays["origin"][:, :3], g.rays["direction"][:, :3], g.rays["multiplier"][:, :3], g.rays["outputPixel"], g.rays["flags"],
-                          g.rays["numBounces"], g.t, g.uv[:, 0], g.uv[:, 1], g.prim, g.inst, sample=2)
+                          g.rays["numBounces"], g.t, g.uv[:, 0], g.uv[:, 1], g.prim, g.inst, sample=2, **({} if in_pdf is None else dict(in_pdf=in_pdf)))
     dt = time.time() - t0
     ctx.close()
     return got, dt
 
 
-def _compare(tag, g, got, want):
-    """the stratum gates; returns (flips, worst continuation fraction, worst shadow fraction) over the strata"""
+def _compare(tag, g, got, want, npdf=False):
+    """the stratum gates; returns (flips, worst continuation fraction, worst shadow fraction) over the strata.
+    npdf: the density written for the next bounce is held to the oracle's too, on the entries alive on both sides, at the fields' tolerance"""
     g_o, g_s = got["out_alive"].astype(bool), got["shadow_alive"].astype(bool)
     # every live output is finite, the axis-aligned strata included
     for names, alive in ((RAY, g_o), (SHADOW + (("slen", None, None),), g_s)):
@@ -74,6 +79,12 @@ def _compare(tag, g, got, want):
                 for k in both[~np.isclose(got[a][both], want.ray[f][both, c], rtol=2e-3, atol=2e-4)]:
                     print(f"  off: {tag} entry {k} {[g.labels[d][k] for d in g.labels]} {a}: {got[a][k]!r} against {want.ray[f][k, c]!r}")
         assert np.array_equal(got["nflags"][both] & 2, want.ray["flags"][both] & 2), (tag, label, "LASTSPECULAR")
+        if npdf:
+            close = np.isclose(got["npdf"][both], want.ray["pdf"][both], rtol=2e-3, atol=2e-4)
+            U.fraction_gate(f"shade grid {tag}/{label}: density for the next bounce", close, MEASURED, legacy=0.97)
+            if not close.all() and label.startswith("family"):
+                for k in both[~close]:
+                    print(f"  off: {tag} entry {k} {[g.labels[d][k] for d in g.labels]} npdf: {got['npdf'][k]!r} against {want.ray['pdf'][k]!r}")
         sb = sl[want.shadow_alive[sl] & g_s[sl]]
         worst = 1.0
         for a, f, c in SHADOW:
@@ -88,8 +99,8 @@ def _compare(tag, g, got, want):
     return worst_flips, worst_ray, worst_shadow
 
 
-def _structure(g, got):
-    """what must hold per family whatever the numbers are"""
+def _structure(g, got, mis=False):
+    """what must hold per family whatever the numbers are (mis: under neeMisShading an emissive hit after a non-specular bounce may deposit)"""
     g_o, g_s = got["out_alive"].astype(bool), got["shadow_alive"].astype(bool)
     fam, corner = g.labels["family"], g.labels["corner"]
     glass = np.isin(fam, ("rough glass", "basic glass"))
@@ -101,7 +112,14 @@ def _structure(g, got):
     em = fam == "emissive"
     assert not g_o[em].any() and not g_s[em].any(), "an emissive hit ends the path (shading.cl:387-397)"
     spec = em & (corner == "after a specular bounce")
-    assert np.allclose(got["radiance"][spec], g.rays["multiplier"][spec, :3] * g.colour[spec], rtol=1e-6) and (got["radiance"][em & ~spec] == 0).all()
+    assert np.allclose(got["radiance"][spec], g.rays["multiplier"][spec, :3] * g.colour[spec], rtol=1e-6)
+    if mis:  # a balance-heuristic weight in [0, 1) of throughput x colour; nothing without a density of at least kEPS, nothing at bounce 0
+        cap = np.where((g.rays["numBounces"] == 0)[:, None], 1.0, g.rays["multiplier"][:, :3]) * g.colour
+        rad = got["radiance"][em & ~spec]
+        assert (rad >= 0).all() and (rad <= cap[em & ~spec] * (1 + 1e-6)).all()
+        assert (got["radiance"][em & ~spec & ((g.rays["numBounces"] == 0) | (g.rays["pdf"] < G.K_EPS))] == 0).all()
+    else:
+        assert (got["radiance"][em & ~spec] == 0).all()
     assert (got["radiance"][~em & ~miss] == 0).all(), "only emissive hits and sky misses deposit in shade"
     pbr = np.isin(fam, ("pbr dielectric", "pbr metal"))
     rough = pbr & np.array([c.startswith(("s=0 ", "s=0.3", "s=0.94-")) or c in ("s=0", "s=0.94-") for c in corner])
@@ -146,6 +164,144 @@ def test_shade_grid_general_kernel_weighted_lights(gpu, family):
     flips, worst_ray, worst_shadow = _compare(tag, g, got, want)
     _structure(g, got)
     print(f"shade grid {tag}: {g.n} entries in {dt:.2f} s, worst stratum flips {flips}, worst field fraction {worst_ray:.4f} / {worst_shadow:.4f}")
+
+
+def _density_structure(g, got, want, mis_entries=None):
+    """The density k_shade writes for the next bounce, whatever its value: 0 on glass and on the alpha-0 pass-through (materials that take no part in MIS,
+    shading.cl:175); finite on every other live continuation; positive wherever the instance leaves the shading normal alone (the identity placement),
+    outside the degenerate tangent frames.  It is NOT positive everywhere, in the reference either: the shading normal stays in object space, so under
+    a turned instance a DIFFUSE bounce's dot(shadingNormal, reflection) / pi is negative for some directions, and a perfect mirror's D_GGX (alpha = 0) is
+    0 wherever the turned halfway vector leaves f above kEPS (tests/test_shade_grid_cpu.py pins both bit for bit against the reference's own build).
+    There the sign is the oracle's.  mis_entries: the entries shaded by neeMisShading (all by default); the others carry density 0."""
+    mis_entries = np.ones(g.n, bool) if mis_entries is None else mis_entries
+    g_o = got["out_alive"].astype(bool)
+    fam = g.labels["family"]
+    passive = np.isin(fam, ("rough glass", "basic glass")) | g.alpha0 | ~mis_entries
+    assert (got["npdf"][g_o & passive] == 0).all(), "glass, the alpha-0 pass-through and neeIsShading carry no density"
+    other = g_o & ~passive
+    assert np.isfinite(got["npdf"][other]).all()
+    sound = other & ~g.degenerate
+    identity = sound & np.char.endswith(g.labels["placement"], "/identity")
+    assert (got["npdf"][identity] > 0).all(), sorted(set(g.labels["corner"][identity & ~(got["npdf"] > 0)]))
+    both = sound & want.ray_alive & (np.abs(want.ray["pdf"]) > 1e-3)  # (five times the comparison's atol: round-off does not carry a density across 0)
+    assert np.array_equal(got["npdf"][both] > 0, want.ray["pdf"][both] > 0)
+    assert not sound.any() or (identity.sum() >= 16 and (got["npdf"][sound] > 0).sum() >= 64), (int(identity.sum()), int((got["npdf"][sound] > 0).sum()))
+    return int(sound.sum()), int((got["npdf"][sound] <= 0).sum())
+
+
+@pytest.mark.parametrize("family", G.FAMILIES)
+def test_shade_grid_mis_matches_oracle(gpu, family):
+    """k_shade<false, true> under FLAG_INTEGRATOR_MIS over one material family, the bounce-1 entries carrying a seeded incoming density in [0, 10]
+    (shade_grid.seed_in_pdf) through the hook: the stratum gates of the default kernel's test, unchanged, plus the density written for the next bounce
+    against the oracle's on the entries alive on both sides; finiteness; the structural facts, those of the density among them."""
+    g = G.seed_in_pdf(G.grid(family))
+    want = G.shade(g, sample=2, seed=4, integrator=O.INTEGRATOR_MIS, width=W, height=H)
+    got, dt = _shade_on_gpu(gpu, g, flags=gpu.FLAG_INTEGRATOR_MIS, in_pdf=g.rays["pdf"])
+    tag = "mis " + family
+    flips, worst_ray, worst_shadow = _compare(tag, g, got, want, npdf=True)
+    _structure(g, got, mis=True)
+    n_density, n_not_positive = _density_structure(g, got, want)
+    if family == "diffuse":  # the seeded density reaches the emissive branch: this family's emissive hits after a diffuse bounce deposit
+        em = g.labels["corner"] == "after a diffuse bounce"
+        assert np.array_equal((got["radiance"][em] != 0).any(1), (want.radiance[em] != 0).any(1)) and (got["radiance"][em] != 0).any(1).sum() >= 16
+    print(f"shade grid {tag}: {g.n} entries in {dt:.2f} s, worst stratum flips {flips}, worst field fraction {worst_ray:.4f} (continuation) "
+          f"{worst_shadow:.4f} (shadow), {n_density} densities for the next bounce, {n_not_positive} of them not positive")
+
+
+def test_shade_grid_mis_pbr_light_sample_draws_once_more(gpu):
+    """neeMisShading draws one more number per PBR light sample (shading.cl:131) than neeIsShading: on a PBR entry with a live shadow ray every later
+    draw moves, so the continuation ray of the MIS kernel leaves in another direction than the default kernel's on the SAME entry and keys -- except off a
+    perfect mirror (smoothness 1: the GGX halfway vector is the normal whatever was drawn), which is left out.  Without a shadow ray there is no extra
+    draw: there both kernels sample the same direction."""
+    moved = 0
+    for family in ("pbr dielectric", "pbr metal"):
+        g = G.seed_in_pdf(G.grid(family))
+        mis, _ = _shade_on_gpu(gpu, g, flags=gpu.FLAG_INTEGRATOR_MIS, in_pdf=g.rays["pdf"])
+        plain, _ = _shade_on_gpu(gpu, g)
+        assert np.array_equal(mis["shadow_alive"], plain["shadow_alive"]), "the light sample's three cosine tests see the same draws"
+        assert (plain["npdf"] == 0).all(), "the default kernel carries no density"
+        rough = ~np.char.startswith(g.labels["corner"], "s=1")
+        d_mis, d_plain = (np.stack([r["ndx"], r["ndy"], r["ndz"]], 1) for r in (mis, plain))
+        live = mis["out_alive"].astype(bool) & plain["out_alive"].astype(bool) & rough & ~g.degenerate
+        drew = live & mis["shadow_alive"].astype(bool)
+        assert drew.sum() >= 32 and (np.abs(d_mis[drew] - d_plain[drew]).max(1) > 1e-4).all(), (family, int(drew.sum()))
+        moved += int(drew.sum())
+        same = live & ~mis["shadow_alive"].astype(bool)
+        unmoved = np.isclose(d_mis[same], d_plain[same], rtol=2e-3, atol=2e-4).all(1)  # (two instantiations of one source: the fields' tolerance)
+        assert same.sum() >= 64 and unmoved.mean() >= 0.97, (family, int(same.sum()), float(unmoved.mean()))
+        print(f"shade grid mis {family}: {int(drew.sum())} continuation rays moved by the extra draw, {int(same.sum())} without one unmoved")
+    assert moved >= 64, moved  # (a live shadow ray AND a live continuation ray off a rough PBR corner: some 3 % of a family)
+
+
+def test_shade_grid_mis_emissive(gpu):
+    """The one branch only neeMisShading has (shading.cl:69-90, pt_shade.h shadeHit), over the emissive-under-MIS family: incoming densities 0, either
+    neighbour of kEPS, 1/pi, 1, a GGX peak, 1e7; solid angles far below kEPS, 2 % either side of it, mid-range and clamped at 2 pi; head-on, oblique,
+    grazing and back-side hits; every placement and a uniformly scaled one (area in object space, distance in world space); a bounce-0 control.
+    The deposit per stratum against the oracle at the radiance tolerance of the other tests; deposit-or-not equal to the oracle's on EVERY entry (the
+    grid is conditioned: tests/test_shade_grid_cpu.py); never above throughput x colour; exactly 0 behind the light, below kEPS of density and at
+    bounce 0; and nothing at all from the default kernel on the same entries."""
+    g = G.grid("emissive mis")
+    want = G.shade(g, sample=2, seed=4, integrator=O.INTEGRATOR_MIS, width=W, height=H)
+    got, dt = _shade_on_gpu(gpu, g, flags=gpu.FLAG_INTEGRATOR_MIS, in_pdf=g.rays["pdf"])
+    rad, lab = got["radiance"], g.labels
+    assert np.isfinite(rad).all() and not got["out_alive"].any() and not got["shadow_alive"].any(), "an emissive hit ends the path"
+    dep, dep_want = (rad != 0).any(1), (want.radiance != 0).any(1)
+    wrong = np.flatnonzero(dep != dep_want)
+    for k in wrong[:16]:
+        print(f"  off: entry {k} {[lab[d][k] for d in lab]} solid angle {g.solid_angle[k]:.6g} deposit {rad[k]} against {want.radiance[k]}")
+    assert wrong.size == 0, f"{wrong.size} entries decide deposit / no deposit unlike the oracle"
+    assert dep.sum() >= 512
+    cap = g.rays["multiplier"][:, :3] * g.colour
+    assert (rad >= 0).all() and (rad <= cap * (1 + 1e-6)).all(), "a balance-heuristic weight lies in [0, 1]"
+    for name, stratum in (("behind the light", lab["solid_angle"] == G.BACK_SIDE), ("density kEPS-", lab["in_pdf"] == "kEPS-"),
+                          ("density 0", lab["in_pdf"] == "0"), ("bounce 0", lab["in_pdf"] == "0 at bounce 0 (control)"),
+                          ("solid angle below kEPS", np.isin(lab["solid_angle"], ("1e-6", "kEPS/1.02")))):
+        assert stratum.sum() >= 64 and (rad[stratum] == 0).all(), name
+    worst = 1.0
+    for label, sl in G.strata(g):
+        assert len(sl) >= 64, (label, len(sl))
+        close = np.isclose(rad[sl], want.radiance[sl], rtol=2e-3, atol=1e-4).all(axis=1)
+        worst = min(worst, U.fraction_gate(f"shade grid mis emissive/{label}: radiance deposited by shade", close, MEASURED, legacy=0.98))
+        if label.startswith("family"):
+            for k in sl[~close]:
+                print(f"  off: entry {k} {[lab[d][k] for d in lab]} radiance {rad[k]} against {want.radiance[k]}")
+    plain, _ = _shade_on_gpu(gpu, g, in_pdf=g.rays["pdf"])
+    assert (plain["radiance"] == 0).all() and not plain["out_alive"].any(), "neeIsShading: next event estimation has counted this light already"
+    print(f"shade grid mis emissive: {g.n} entries in {dt:.2f} s, {int(dep.sum())} deposits, worst stratum fraction {worst:.4f}")
+
+
+def test_shade_grid_compare_shading_splits_on_the_pixel(gpu):
+    """FLAG_COMPARE_SHADING over the PBR dielectric family against the oracle's INTEGRATOR_COMPARE: neeMisShading where pixel % width < width / 2,
+    neeIsShading elsewhere.  The reference's COMPARE_SHADING build remaps only the CAMERA ray's x at generation, so that both halves look at the left
+    half's view (kernel.cl:48-51); the queue entry keeps the true outputPixel, and shade selects on outputPixel % scrWidth (kernel.cl:249).  The hook's
+    pixel IS that outputPixel -- it keys the PRNG, addresses the accumulator and makes this selection -- so the hook expresses both halves faithfully.
+    The grid numbers its entries' pixels 0 .. n-1 (take() renumbers them likewise): at width 64 the entries alternate between the halves in runs of 32,
+    half of the family in each, every stratum in both."""
+    g = G.seed_in_pdf(G.grid("pbr dielectric"))
+    left = (g.rays["outputPixel"] % W) < W // 2
+    assert abs(int(left.sum()) - g.n // 2) <= 32
+    for label, sl in G.strata(g):
+        assert min(left[sl].sum(), (~left[sl]).sum()) >= 16, label
+    want = G.shade(g, sample=2, seed=4, integrator=O.INTEGRATOR_COMPARE, width=W, height=H)
+    got, dt = _shade_on_gpu(gpu, g, flags=gpu.FLAG_COMPARE_SHADING, in_pdf=g.rays["pdf"])
+    flips, worst_ray, worst_shadow = _compare("compare pbr dielectric", g, got, want, npdf=True)
+    _structure(g, got, mis=True)
+    _density_structure(g, got, want, mis_entries=left)
+    g_o = got["out_alive"].astype(bool)
+    assert (want.ray["pdf"][want.ray_alive & ~left] == 0).all() and (got["npdf"][g_o & left & ~g.degenerate] != 0).sum() >= 64
+    print(f"shade grid compare pbr dielectric: {g.n} entries in {dt:.2f} s, {int(left.sum())} in the MIS half, worst stratum flips {flips}, "
+          f"worst field fraction {worst_ray:.4f} / {worst_shadow:.4f}")
+
+
+def test_shade_grid_mis_with_weighted_lights(gpu):
+    """FLAG_INTEGRATOR_MIS | FLAG_SOLID_ANGLE_LIGHTS over the PBR metal family against the oracle under INTEGRATOR_MIS and LIGHTS_SOLID_ANGLE: the same gates"""
+    g = G.seed_in_pdf(G.grid("pbr metal"))
+    want = G.shade(g, sample=2, seed=4, integrator=O.INTEGRATOR_MIS, light_sampling=O.LIGHTS_SOLID_ANGLE, width=W, height=H)
+    got, dt = _shade_on_gpu(gpu, g, flags=gpu.FLAG_INTEGRATOR_MIS | gpu.FLAG_SOLID_ANGLE_LIGHTS, in_pdf=g.rays["pdf"])
+    flips, worst_ray, worst_shadow = _compare("mis general pbr metal", g, got, want, npdf=True)
+    _structure(g, got, mis=True)
+    _density_structure(g, got, want)
+    print(f"shade grid mis general pbr metal: {g.n} entries in {dt:.2f} s, worst stratum flips {flips}, worst field fraction {worst_ray:.4f} / {worst_shadow:.4f}")
 
 
 def test_axis_aligned_room_renders_like_the_oracle(gpu):

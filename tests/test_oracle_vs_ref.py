@@ -80,7 +80,7 @@ MIS_CASES = dict(CASES, cornell=lambda: scenes.cornell_box(48, 27), textured=lam
 def test_compare_shading_build_bit_exact(case):
     """kernel.cl built with -DCOMPARE_SHADING: neeMisShading on the left half of the image, neeIsShading on the right, both
     halves showing the left half's view (kernel.cl:48-51,248-265).  The oracle's restatement, with the reference's
-    uninitialised read evaluating to 0 as it does in this build, reproduces whole queue loops bit for bit -- counters, stream
+    uninitialised read evaluating as it does in this build (oracle.cpp, neeShading), reproduces whole queue loops bit for bit -- counters, stream
     states (= draw counts: MIS draws once more per PBR light sample) and sums of both halves."""
     (ra, rs, rt), (oa, os_, ot) = _compare_shading(MIS_CASES[case](), 48, 27, 5, O.INTEGRATOR_COMPARE_AS_COMPILED)
     assert np.array_equal(rt, ot), "per-pass queue counters differ"
@@ -93,7 +93,7 @@ def test_compare_shading_build_bit_exact(case):
 @pytest.mark.skipif(not O.have_ref_mis(), reason="oracle/_ref COMPARE_SHADING build missing")
 def test_the_fixed_mis_density_only_changes_light_hits_after_diffuse_bounces():
     """What the fix changes (oracle.cpp neeShading, 'FIXED'): with the density of a diffuse continuation taken from the sampled
-    direction instead of read as 0, the same queue loop keeps its counters and draw counts -- the fix touches no decision --
+    direction instead of the uninitialised read, the same queue loop keeps its counters and draw counts -- the fix touches no decision --
     and only gains radiance: lights found by a diffuse bounce now contribute with their MIS weight."""
     b = scenes.cornell_box(48, 27)
     (ra, rs, rt), (oa, os_, ot) = _compare_shading(b, 48, 27, 8, O.INTEGRATOR_COMPARE)
