@@ -320,7 +320,7 @@ struct pt_ctx {
     bool identityPixels = true;
     DevBuf<float4> accumOwn, accumPlanes;
     uint32_t packetBlocks[2] = { 0, 0 };
-    uint32_t multiBlocks[4] = { 0, 0, 0, 0 }; // persistent grid of k_trace_multi [without | with instance references in the tree], [2], [3]: the same for a thin-lens camera's converging bundles
+    uint32_t multiBlocks[2][2] = {}; // persistent grid of k_trace_multi [pinhole | a thin lens's converging bundles][without | with instance references in the tree]
     // live entries per pass of the most recent batch whose counters have come back (a HINT for the next batch's k_shade launches:
     // copied to pinned memory by the stream at the end of every batch, never waited for)
     Pinned<uint32_t> passCountsPinned; // as many words as passCountsHint

@@ -49,16 +49,51 @@ int resetStreams(pt_ctx* c)
     return uploadVec(c, c->streams, host);
 }
 
-#ifndef PT_SPLIT_SHADOW_ACCUM
-#define PT_SPLIT_SHADOW_ACCUM 1 // one sample in flight: shadow rays deposit into an accumulator of their own, a shadow queue per bounce (renderSampleFixed)
-#endif
-// does a context with queues of `cap` entries render with the shadow rays' own accumulator and a shadow queue per bounce (renderSampleFixed)?
+// One table per kernel family: every instantiation the library launches, stated once.  ensureSpill walks the traversal tables for the occupancy queries that
+// size the persistent grids, the launchers index the same tables and launch through the pointer -- a row added here is sized and launched, or neither.
+using TraceKernel = void (*)(TraceArgs);
+using ShadeKernel = void (*)(ShadeArgs);
+constexpr TraceKernel kTraceKernels[2][3] = { { k_trace<false, 0>, k_trace<false, 1>, k_trace<false, 2> }, { k_trace<true, 0>, k_trace<true, 1>, k_trace<true, 2> } }; // [anyHit][traceKind]
+constexpr TraceKernel kPacketKernels[2][2] = { { k_trace_packet<false, false>, k_trace_packet<false, true> }, { k_trace_packet<true, false>, k_trace_packet<true, true> } }; // [anyHit][sceneKind]
+constexpr TraceKernel kBundleKernels[2][2] = { { k_trace_multi<PT_MULTI_RAYS, false>, k_trace_multi<PT_MULTI_RAYS, true> },
+    { k_trace_multi<PT_MULTI_RAYS, false, true>, k_trace_multi<PT_MULTI_RAYS, true, true> } }; // [thin lens][sceneKind]
+constexpr TraceKernel kTeamKernels[2] = { k_trace_team<false>, k_trace_team<true> }; // [anyHit]
+// [parity][general shading][variant]: one tile per workgroup, the tile-walking kernel behind a split launch, one tile per workgroup over material bins
+// (nullptr: not built -- parity mode launches whole queues, the general kernel knows no bins)
+enum ShadeVariant { kShadeTile = 0, kShadeLoop = 1, kShadeBinned = 2 };
+constexpr ShadeKernel kShadeKernels[2][2][3] = { { { k_shade<false, false>, k_shade<false, false, true>, k_shade<false, false, false, true> }, { k_shade<false, true>, k_shade<false, true, true>, nullptr } },
+    { { k_shade<true, false>, nullptr, nullptr }, { k_shade<true, true>, nullptr, nullptr } } };
+
+// does a context with queues of `cap` entries render with the shadow rays' own accumulator and a shadow queue per bounce (one sample in flight: planBatch's `split`)?
 inline bool splitShadowAccum(const pt_ctx* c, uint64_t cap)
 {
-    return PT_SPLIT_SHADOW_ACCUM && c->planes == 1u && !parityMode(c) && c->cfg.max_active_rays == 0 && cap <= (4u << 20) && !(c->packetUse & 2u) && maxBounces(c) <= (uint32_t)kMaxPasses;
+    return c->planes == 1u && !parityMode(c) && c->cfg.max_active_rays == 0 && cap <= (4u << 20) && !(c->packetUse & 2u) && maxBounces(c) <= (uint32_t)kMaxPasses;
 }
 
-bool derivedPrimariesCapable(const pt_ctx* c); // (defined with renderSampleFixed's choice of kernels, below)
+#ifndef PT_PACKET_USE
+#define PT_PACKET_USE 1 // primary rays only: shadow rays towards random light points are not coherent enough (2.6x slower)
+#endif
+constexpr uint32_t kPacketUseDefault = PT_PACKET_USE;
+
+// What a coherent first pass -- consecutive entries of the first queue are samples of one pixel -- does with its camera rays: the three questions planBatch asks
+// of the context, each stated here only.
+// May they be generated inside k_trace_multi and walk the tree as bundles?  A pinhole camera's always; a thin-lens camera's too since round 6: converging
+// bundles, pt_packet_multi.h LENS (PTAMD_LENS_BUNDLES=0: packets of 64 as in rounds 3-5).
+inline bool lensBundles()
+{
+    static const bool on = !(getenv("PTAMD_LENS_BUNDLES") && atoi(getenv("PTAMD_LENS_BUNDLES")) == 0);
+    return on;
+}
+inline bool primaryPackets(const pt_ctx* c) { return c->dyn[c->active].packetOk && (c->packetUse & 1u); }
+inline bool primaryBundles(const pt_ctx* c) { return PT_MULTI_RAYS > 1 && (!c->camera.thinLens || lensBundles()) && !(c->packetUse & 8u) && primaryPackets(c); }
+// Are they regenerated by the packet / bundle kernel, from the entry index, and queued there for k_shade, instead of queued by k_gen?
+inline bool primariesFused(const pt_ctx* c) { return primaryPackets(c) && !(c->cfg.flags & PT_FLAG_QUEUE_PRIMARY_RAYS); }
+// ... and queued as (direction, pixel) only?  The bundles of a pinhole camera (a thin lens: every ray has an origin of its own, which stays in the queue).
+inline bool primariesDerived(const pt_ctx* c) { return primariesFused(c) && primaryBundles(c) && !c->camera.thinLens; }
+// The last question asked before a batch exists (ensureQueues, which sizes the first queue by the answer; pt_render, which re-makes the queues when it changes):
+// can the camera rays of a large batch be queued as (direction, pixel) only?
+inline bool derivedPrimariesCapable(const pt_ctx* c) { return c->haveCamera && c->haveDynamic && primariesDerived(c); }
+
 // a new camera, scene state, texture or tiling (or ratios learned from counts cut at a queue's end): what a batch emits is no longer known
 inline void newEpoch(pt_ctx* c)
 {
@@ -168,7 +203,7 @@ int ensureQueues(pt_ctx* c)
             const uint64_t floorEntries = std::min<uint64_t>(cap, ((16ull * c->numOwned + 63u) & ~63ull));
             c->capExt = (uint32_t)std::max<uint64_t>(c->capExt, floorEntries);
             c->capShadow = (uint32_t)std::max<uint64_t>(c->capShadow, floorEntries);
-            // camera rays queued as (direction, pixel) only -- a pinhole's bundles, renderSampleFixed `derived` -- leave the first queue's other planes to the later passes
+            // camera rays queued as (direction, pixel) only -- a pinhole's bundles, BatchPlan::derived -- leave the first queue's other planes to the later passes
             c->q0Small = c->capExt < cap && derivedPrimariesCapable(c);
         }
         newEpoch(c);
@@ -220,64 +255,60 @@ int ensureQueues(pt_ctx* c)
     return PT_OK;
 }
 
+// the fewest workgroups per CU that the GPU keeps resident of any of `n` kernels (one persistent grid serves them all), at least 1
+int residentBlocks(pt_ctx* c, const TraceKernel* fns, int n, int block, int* out)
+{
+    int least = INT_MAX;
+    for (int i = 0; i < n; i++) {
+        int b = 0;
+        HIPCHK(c, hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, (const void*)fns[i], block, 0));
+        least = std::min(least, b);
+    }
+    *out = std::max(1, least);
+    return PT_OK;
+}
+
 int ensureSpill(pt_ctx* c)
 {
     if (c->spill.p)
         return PT_OK;
-    // persistent grids sized to the machine, per instantiation pair ([0]: scenes that are one world-space tree, [1]: scenes with
-    // instance references -- pt_trace.h, TWO_LEVEL)
-    const void* variants[3][2] = { { (const void*)k_trace<false, 0>, (const void*)k_trace<true, 0> }, { (const void*)k_trace<false, 1>, (const void*)k_trace<true, 1> },
-        { (const void*)k_trace<false, 2>, (const void*)k_trace<true, 2> } };
-    const void* packetVariants[2][2] = { { (const void*)k_trace_packet<false, false>, (const void*)k_trace_packet<true, false> },
-        { (const void*)k_trace_packet<false, true>, (const void*)k_trace_packet<true, true> } };
-    for (int tl = 0; tl < 3; tl++) {
-        int blocksPerCU = 8;
-        for (const void* fn : variants[tl]) {
-            int b = 0;
-            HIPCHK(c, hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, fn, kTraceBlock, 0));
-            blocksPerCU = std::min(blocksPerCU, b);
-        }
-        blocksPerCU = std::max(1, blocksPerCU);
+    // persistent grids sized to the machine, per kind of scene -- the any-hit and the closest-hit instantiation of a kind share one ([0]: scenes that are one
+    // world-space tree, [1]: scenes with instance references, pt_trace.h TWO_LEVEL, [2]: the general route; the packet kernels know two kinds of scene)
+    int rc, b;
+    for (int kind = 0; kind < 3; kind++) {
+        const TraceKernel pair[2] = { kTraceKernels[0][kind], kTraceKernels[1][kind] };
+        if ((rc = residentBlocks(c, pair, 2, kTraceBlock, &b)))
+            return rc;
+        b = std::min(b, 8);
         if (const char* e = getenv("PTAMD_TRACE_BLOCKS_PER_CU")) // diagnostics: a smaller persistent grid leaves wave slots to kernels of other streams / processes
-            blocksPerCU = std::max(1, std::min(blocksPerCU, atoi(e)));
-        c->traceBlocks[tl] = (uint32_t)(blocksPerCU * c->numCUs);
-        if (tl >= 2)
-            continue; // (the packet kernels know two kinds of scene)
-        int pb = 8;
-        for (const void* fn : packetVariants[tl]) {
-            int b = 0;
-            HIPCHK(c, hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, fn, kPacketBlock, 0));
-            pb = std::min(pb, b);
-        }
-        pb = std::max(1, pb);
+            b = std::max(1, std::min(b, atoi(e)));
+        c->traceBlocks[kind] = (uint32_t)(b * c->numCUs);
+    }
+    for (int kind = 0; kind < 2; kind++) {
+        const TraceKernel pair[2] = { kPacketKernels[0][kind], kPacketKernels[1][kind] };
+        if ((rc = residentBlocks(c, pair, 2, kPacketBlock, &b)))
+            return rc;
+        b = std::min(b, 8);
         if (const char* e = getenv("PTAMD_PACKET_BLOCKS_PER_CU"))
-            pb = std::max(1, std::min(pb, atoi(e)));
-        c->packetBlocks[tl] = (uint32_t)(pb * c->numCUs);
+            b = std::max(1, std::min(b, atoi(e)));
+        c->packetBlocks[kind] = (uint32_t)(b * c->numCUs);
     }
-    {
-        int b = 0;
-        HIPCHK(c, hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, (const void*)k_trace_multi<PT_MULTI_RAYS, false>, kPacketBlock, 0));
-        c->multiBlocks[0] = (uint32_t)(std::max(1, b) * c->numCUs);
-        HIPCHK(c, hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, (const void*)k_trace_multi<PT_MULTI_RAYS, true>, kPacketBlock, 0));
-        c->multiBlocks[1] = (uint32_t)(std::max(1, b) * c->numCUs);
-        HIPCHK(c, hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, (const void*)k_trace_multi<PT_MULTI_RAYS, false, true>, kPacketBlock, 0));
-        c->multiBlocks[2] = (uint32_t)(std::max(1, b) * c->numCUs);
-        HIPCHK(c, hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, (const void*)k_trace_multi<PT_MULTI_RAYS, true, true>, kPacketBlock, 0));
-        c->multiBlocks[3] = (uint32_t)(std::max(1, b) * c->numCUs);
-        if (const char* e = getenv("PTAMD_PACKET_BLOCKS_PER_CU")) // the documented knob reaches the bundle kernel too
-            for (uint32_t& mb : c->multiBlocks)
+    for (int lens = 0; lens < 2; lens++)
+        for (int kind = 0; kind < 2; kind++) { // (no any-hit bundles: every instantiation a grid of its own)
+            if ((rc = residentBlocks(c, &kBundleKernels[lens][kind], 1, kPacketBlock, &b)))
+                return rc;
+            uint32_t& mb = c->multiBlocks[lens][kind];
+            mb = (uint32_t)(b * c->numCUs);
+            if (const char* e = getenv("PTAMD_PACKET_BLOCKS_PER_CU")) // the documented knob reaches the bundle kernel too
                 mb = std::max(1u, std::min(mb, (uint32_t)std::max(1, atoi(e)) * (uint32_t)c->numCUs));
-    }
-    {
-        int t0 = 0, t1 = 0;
-        HIPCHK(c, hipOccupancyMaxActiveBlocksPerMultiprocessor(&t0, (const void*)k_trace_team<false>, kTeamBlock, 0));
-        HIPCHK(c, hipOccupancyMaxActiveBlocksPerMultiprocessor(&t1, (const void*)k_trace_team<true>, kTeamBlock, 0));
-        c->teamBlocks = (uint32_t)(std::max(1, std::min(t0, t1)) * c->numCUs);
-        if (const char* e = getenv("PTAMD_TEAM_ROUNDS")) // diagnostics: 0 = never use the team kernel
-            c->teamRounds = std::max(0.f, (float)atof(e));
-        if (const char* e = getenv("PTAMD_TEAM_USE"))
-            c->teamUse = (uint32_t)atoi(e);
-    }
+        }
+    if ((rc = residentBlocks(c, kTeamKernels, 2, kTeamBlock, &b)))
+        return rc;
+    c->teamBlocks = (uint32_t)(b * c->numCUs);
+    if (const char* e = getenv("PTAMD_TEAM_ROUNDS")) // diagnostics: 0 = never use the team kernel
+        c->teamRounds = std::max(0.f, (float)atof(e));
+    if (const char* e = getenv("PTAMD_TEAM_USE"))
+        c->teamUse = (uint32_t)atoi(e);
     const size_t threads = (size_t)std::max(std::max(c->traceBlocks[0], c->traceBlocks[1]), c->traceBlocks[2]) * kTraceBlock;
     HIPCHK(c, c->spill.alloc(3 * threads * kSpillStack)); // second and third part: the traversal kernels that run beside another one (the two side streams)
     c->spillHalf = threads * kSpillStack;
@@ -316,40 +347,28 @@ bool teamLaunch(const pt_ctx* c, uint32_t pass, bool anyHit = false)
 
 void launchTrace(pt_ctx* c, bool anyHit, const TraceArgs& args, hipStream_t stream = nullptr)
 {
+    if (!stream)
+        stream = c->stream;
     if (teamLaunch(c, args.pass, anyHit)) {
         c->teamLaunches++;
-        if (anyHit)
-            hipLaunchKernelGGL(k_trace_team<true>, dim3(c->teamBlocks), dim3(kTeamBlock), 0, stream ? stream : c->stream, args);
-        else
-            hipLaunchKernelGGL(k_trace_team<false>, dim3(c->teamBlocks), dim3(kTeamBlock), 0, stream ? stream : c->stream, args);
+        hipLaunchKernelGGL(kTeamKernels[anyHit], dim3(c->teamBlocks), dim3(kTeamBlock), 0, stream, args);
         return;
     }
     // the instantiation that can enter instances only where the tree holds instance references (pt_trace.h)
-    const bool twoLevel = sceneKind(c) != 0;
     const int kind = traceKind(c);
     TraceArgs a = args;
-    if (twoLevel) { // the per-ray kernels walk the top level in which folded instances are plain inner references (the packet kernels: the one with instance references)
+    if (kind != 0) { // the per-ray kernels walk the top level in which folded instances are plain inner references (the packet kernels: the one with instance references)
         a.sc.rootRef = c->dyn[c->active].rootRefFolded;
         a.instFold = c->dyn[c->active].instFold.p, a.instFoldCount = c->dyn[c->active].instFoldCount;
     }
-    const dim3 grid(c->traceBlocks[kind]), block(kTraceBlock);
-    if (!stream)
-        stream = c->stream;
-    if (anyHit) {
-        if (kind == 2)
-            hipLaunchKernelGGL((k_trace<true, 2>), grid, block, 0, stream, a);
-        else if (kind == 1)
-            hipLaunchKernelGGL((k_trace<true, 1>), grid, block, 0, stream, a);
-        else
-            hipLaunchKernelGGL((k_trace<true, 0>), grid, block, 0, stream, a);
-    } else {
-        if (kind == 2)
-            hipLaunchKernelGGL((k_trace<false, 2>), grid, block, 0, stream, a);
-        else if (kind == 1)
-            hipLaunchKernelGGL((k_trace<false, 1>), grid, block, 0, stream, a);
-        else
-            hipLaunchKernelGGL((k_trace<false, 0>), grid, block, 0, stream, a);
-    }
+    hipLaunchKernelGGL(kTraceKernels[anyHit][kind], dim3(c->traceBlocks[kind]), dim3(kTraceBlock), 0, stream, a);
+}
+
+void launchPacket(pt_ctx* c, bool anyHit, const TraceArgs& a)
+{
+    const int kind = sceneKind(c);
+    c->packetLaunches++;
+    hipLaunchKernelGGL(kPacketKernels[anyHit][kind], dim3(c->packetBlocks[kind]), dim3(kPacketBlock), 0, c->stream, a);
 }
 
 TraceArgs traceArgsBase(pt_ctx* c)
@@ -419,134 +438,133 @@ void launchGen(pt_ctx* c, const FrameParams& fp, int q, uint32_t first, uint32_t
         first, n, slotBase, c->streams.p, &ctl->extCount[pass], &ctl->generated);
 }
 
-#ifndef PT_FRAME_BUNDLES
-#define PT_FRAME_BUNDLES 0 // 1: the camera rays of a 1-spp frame (pinhole) as bundles of 256 neighbouring pixels through k_trace_multi.  Measured (1280 x 720,
-                           // one bundle per wave): 1.39 instead of 1.02 ms per frame -- 3 600 walks of a 32 x 8-pixel beam, each a chain of > 100 dependent leaf visits
-#endif
-#ifndef PT_FUSED_PRIMARY
-#define PT_FUSED_PRIMARY 1 // primary rays regenerated by the packet kernel and the first k_shade instead of queued by k_gen
-#endif
-#ifndef PT_SHADE_SPLIT
-#define PT_SHADE_SPLIT 1
-#endif
-#ifndef PT_LAST_SHADOW_ON_MAIN
-#define PT_LAST_SHADOW_ON_MAIN 1
-#endif
-#ifndef PT_DERIVED_PRIMARIES
-#define PT_DERIVED_PRIMARIES 1
-#endif
-#ifndef PT_OVERLAP_SMALL
-#define PT_OVERLAP_SMALL 1 // small launches: shadow rays of bounce b beside the extension rays of bounce b + 1 (side stream)
-#endif
-#ifndef PT_PACKET_USE
-#define PT_PACKET_USE 1 // primary rays only: shadow rays towards random light points are not coherent enough (2.6x slower)
-#endif
-constexpr uint32_t kPacketUseDefault = PT_PACKET_USE;
-
-void launchPacket(pt_ctx* c, bool anyHit, const TraceArgs& a)
+// frame parameters of a batch of `batch` samples per owned pixel: how many of a pixel's samples sit next to each other in the queue
+FrameParams batchFrameParams(pt_ctx* c, uint32_t sample, uint32_t batch)
 {
-    const bool twoLevel = sceneKind(c) != 0;
-    const dim3 grid(c->packetBlocks[twoLevel ? 1 : 0]), block(kPacketBlock);
-    c->packetLaunches++;
-    if (anyHit) {
-        if (twoLevel)
-            hipLaunchKernelGGL((k_trace_packet<true, true>), grid, block, 0, c->stream, a);
-        else
-            hipLaunchKernelGGL((k_trace_packet<true, false>), grid, block, 0, c->stream, a);
-    } else {
-        if (twoLevel)
-            hipLaunchKernelGGL((k_trace_packet<false, true>), grid, block, 0, c->stream, a);
-        else
-            hipLaunchKernelGGL((k_trace_packet<false, false>), grid, block, 0, c->stream, a);
-    }
+    FrameParams fp = frameParams(c, sample);
+    fp.planes = batch;
+    fp.interleave = 1;
+    while (fp.interleave < kGenInterleave && batch % (fp.interleave * 2u) == 0u)
+        fp.interleave *= 2u, fp.interleaveShift++;
+    fp.invSpan = 1.0f / (float)((uint64_t)c->numOwned << fp.interleaveShift);
+    return fp;
 }
 
-// first pass of a batch: may the camera rays be generated inside k_trace_multi and walk the tree as bundles (pinhole camera)?
-// (thin-lens cameras too since round 6: converging bundles, pt_packet_multi.h LENS; PTAMD_LENS_BUNDLES=0: packets of 64 as in rounds 3-5)
-inline bool lensBundles()
+// What one batch launches, decided once (planBatch) and read by everything that issues or describes its passes: renderSampleFixed, the launchers below,
+// pt_primary_pass.  A value-initialised plan with plainPlan's capacities is the schedule of a pass that is nothing special: the refill loop's.
+struct BatchPlan {
+    enum Route { PerRay, Packet, Bundle };
+    bool coherent = false; // consecutive entries of the first queue are samples of one pixel
+    Route first = PerRay; // the kernel that walks the camera rays: k_trace / k_trace_team, k_trace_packet, k_trace_multi (... for a thin lens where the camera has one)
+    bool shadowPackets = false; // the first pass's shadow rays through k_trace_packet (PTAMD_PACKET bit 1: diagnostics)
+    bool fused = false; // the camera rays are generated in that kernel, not queued by k_gen
+    bool derived = false; // ... and queued as (direction, pixel) only: k_shade derives the rest
+    bool overlap = false; // shadow passes on side streams, beside the next bounce's extension pass
+    bool split = false; // the shadow rays' own accumulator plane and queue per bounce (one sample in flight)
+    uint32_t outCap[2] = { 0, 0 }; // entries queue 0 / 1 holds when a pass writes it (pt_shade.h)
+    uint32_t shadowCap = 0; // entries of the shadow queue a pass writes
+};
+
+// the second queue holds capExt entries; the first `capacity`, or capExt where its origin / throughput planes are small; a bounce's own shadow queue `capacity`
+BatchPlan plainPlan(const pt_ctx* c, bool split = false)
 {
-    static const bool on = !(getenv("PTAMD_LENS_BUNDLES") && atoi(getenv("PTAMD_LENS_BUNDLES")) == 0);
-    return on;
-}
-inline bool primaryBundles(const pt_ctx* c)
-{
-    return PT_MULTI_RAYS > 1 && (!c->camera.thinLens || lensBundles()) && !(c->packetUse & 8u) && c->dyn[c->active].packetOk && (c->packetUse & 1u);
-}
-// are consecutive entries of the first queue of a batch rays of one pixel or of neighbouring pixels?  >= 16 samples of a pixel next to each other, or the
-// can the camera rays of a large batch be queued as (direction, pixel) only?  (renderSampleFixed's `derived`, asked before the batch exists: ensureQueues)
-bool derivedPrimariesCapable(const pt_ctx* c)
-{
-    return c->haveCamera && c->haveDynamic && !c->camera.thinLens && primaryBundles(c) && PT_FUSED_PRIMARY && PT_DERIVED_PRIMARIES && !(c->cfg.flags & PT_FLAG_QUEUE_PRIMARY_RAYS);
+    BatchPlan p;
+    p.split = split;
+    p.outCap[0] = c->q0Small ? c->capExt : c->capacity;
+    p.outCap[1] = c->capExt;
+    p.shadowCap = split ? c->capacity : c->capShadow;
+    return p;
 }
 
-// pixels of a 1-spp frame in the order of the pixel list (8 x 8 blocks unless the caller chose otherwise) where bundles of 256 serve them
-inline bool firstPassCoherent(const pt_ctx* c, const FrameParams& fp, uint32_t batch) { return fp.interleave >= 16u || (PT_FRAME_BUNDLES && batch == 1u && primaryBundles(c)); }
-
-// `coherent`: consecutive queue entries are samples of one pixel (first pass of the fixed schedule)
-void launchIntersect(pt_ctx* c, int q, uint32_t pass, bool coherent = false, const FrameParams* fused = nullptr, bool noOrigins = false)
+BatchPlan planBatch(const pt_ctx* c, const FrameParams& fp, uint32_t batch)
 {
-    Control* ctl = c->control.p;
+    BatchPlan p = plainPlan(c, splitShadowAccum(c, c->capacity));
+    // Where the packet kernel serves the primary rays it generates them itself, from the entry index, and queues them for
+    // k_shade: no k_gen launch (3.3 ms of a 121 ms batch, HBM-write-bound) and no read of 32 B per ray in a kernel that has
+    // bandwidth to spare for the two stores instead.  (k_shade regenerating the rays as well, so that they are never stored,
+    // was measured too: its 70 extra instructions per entry cost 2.3 ms per batch, more than the reads they replace.)
+    // The packet kernel serves the first pass when consecutive queue entries are >= 16 samples of one pixel.  (Packets of 8x8 pixel
+    // blocks -- what the default pixel order would give a 1-spp frame -- were measured too: the beam test handles them, but a
+    // 1280x720 frame is 14 k packets for 8 k persistent waves claiming 16 at a time: 2.2-2.4 ms per frame instead of 1.4-1.6.)
+    // (8x8-pixel packets for a 1-spp frame were measured again in round 3 with one packet per claim: 271 us for the 14 400 packets of
+    // a 1280 x 720 frame against 251 us through the per-ray kernel -- 1.8 rounds of latency-bound packet walks on 8 192 waves)
+    // (... and the camera rays of a 1-spp pinhole frame as bundles of 256 neighbouring pixels through k_trace_multi -- the pixel list's 8 x 8 blocks, one bundle
+    // per wave: 1.39 instead of 1.02 ms per 1280 x 720 frame -- 3 600 walks of a 32 x 8-pixel beam, each a chain of > 100 dependent leaf visits)
+    p.coherent = fp.interleave >= 16u;
+    p.fused = p.coherent && primariesFused(c);
+    // ... and where those are the bundles of a pinhole camera, only (direction, pixel) is queued: k_shade takes the eye as the origin and the sample from the
+    // entry index (12 instructions; the full regeneration the paragraph above dismissed is 70) -- 16 B per camera ray less written and 16 B less read
+    p.derived = p.coherent && primariesDerived(c);
+    // camera rays generated in the kernel: PT_MULTI_RAYS x 64 consecutive entries -- the samples of one pixel -- are ONE bundle and are walked as one
+    // (pt_packet_multi.h); queued ones, or those of a lens the bundle kernel is not to take, in packets of 64
+    if (p.coherent && primaryPackets(c))
+        p.first = p.fused && primaryBundles(c) ? BatchPlan::Bundle : BatchPlan::Packet;
+    p.shadowPackets = p.coherent && c->dyn[c->active].packetOk && (c->packetUse & 2u);
+    // Small launches are latency-bound (every traversal launch of a 1-spp 1280 x 720 frame takes 0.1-0.25 ms whatever it holds): the
+    // shadow rays of bounce b then run on a side stream BESIDE the extension rays of bounce b + 1.  Both need only shade b; shade
+    // b + 1 waits for both, so the accumulator sees its deposits in the same order as in the serial schedule (bit-identical images).
+    // Large batches fill the machine with one kernel; two traversal kernels side by side only evict each other's nodes (measured: slower).
+    p.overlap = c->numOwned * batch <= (4u << 20) && !c->profile && !(c->packetUse & 2u);
+    // One sample in flight (RayTracer::rayTrace's frames): every entry deposits into the accumulator proper, so the shade launch of bounce b + 1 had to wait
+    // for the shadow rays of bounce b (same words, same order as the serial schedule) -- and the shadow passes, the longer ones, were the frame's critical path.
+    // There the shadow rays get an accumulator of their own (added to the other at the end of pt_render, in either schedule: the images stay bit-identical
+    // between them) and a queue per bounce: a shadow pass then waits for its own shade launch only.  That is p.split (splitShadowAccum, above).
+    return p;
+}
+
+// the extension rays of queue `q`; pass 0 by the plan's route, with its camera rays generated in the kernel where the plan says so
+void launchIntersect(pt_ctx* c, int q, uint32_t pass, const BatchPlan& plan, const FrameParams& fp)
+{
     TraceArgs a = traceArgsBase(c);
-    if (fused) {
+    const bool first = pass == 0u;
+    if (first && plan.fused) {
         a.fused = 1u;
-        a.fp = *fused;
+        a.fp = fp;
         a.pixelList = c->identityPixels ? nullptr : c->pixelList.p;
     }
     a.rayO = c->rays[q].o.p;
     a.rayD = c->rays[q].d.p;
     a.hit = c->hitH.p;
     a.inst = c->hitInst.p;
-    a.ctl = ctl;
+    a.ctl = c->control.p;
     a.pass = pass;
-    if (coherent && c->dyn[c->active].packetOk && (c->packetUse & 1u)) {
-        // camera rays of a pinhole generated in the kernel: PT_MULTI_RAYS x 64 consecutive entries -- the samples of
-        // one pixel, or of neighbouring pixels -- are ONE bundle and are walked as one (pt_packet_multi.h)
-        if (fused && primaryBundles(c)) {
-            a.noOrigins = noOrigins ? 1u : 0u;
-            c->packetLaunches++;
-            c->bundleLaunches++;
-            if (c->camera.thinLens) { // converging bundles: every ray its own origin (which stays in the queue: k_shade cannot derive it)
-                a.noOrigins = 0u;
-                if (sceneKind(c) != 0)
-                    hipLaunchKernelGGL((k_trace_multi<PT_MULTI_RAYS, true, true>), dim3(c->multiBlocks[3]), dim3(kPacketBlock), 0, c->stream, a);
-                else
-                    hipLaunchKernelGGL((k_trace_multi<PT_MULTI_RAYS, false, true>), dim3(c->multiBlocks[2]), dim3(kPacketBlock), 0, c->stream, a);
-            } else if (sceneKind(c) != 0)
-                hipLaunchKernelGGL((k_trace_multi<PT_MULTI_RAYS, true>), dim3(c->multiBlocks[1]), dim3(kPacketBlock), 0, c->stream, a);
-            else
-                hipLaunchKernelGGL((k_trace_multi<PT_MULTI_RAYS, false>), dim3(c->multiBlocks[0]), dim3(kPacketBlock), 0, c->stream, a);
-        } else {
-            launchPacket(c, false, a);
-        }
+    if (first && plan.first == BatchPlan::Bundle) {
+        const int lens = c->camera.thinLens ? 1 : 0, kind = sceneKind(c);
+        a.noOrigins = plan.derived ? 1u : 0u; // (never a thin lens's converging bundles: every ray its own origin, which k_shade cannot derive)
+        c->packetLaunches++;
+        c->bundleLaunches++;
+        hipLaunchKernelGGL(kBundleKernels[lens][kind], dim3(c->multiBlocks[lens][kind]), dim3(kPacketBlock), 0, c->stream, a);
+    } else if (first && plan.first == BatchPlan::Packet) {
+        launchPacket(c, false, a);
     } else {
         launchTrace(c, false, a);
     }
 }
 
-// `own`: the pass's own shadow queue and the shadow rays' own accumulator (one sample in flight, renderSampleFixed)
-void launchShadow(pt_ctx* c, uint32_t pass, bool coherent = false, hipStream_t side = nullptr, const ShadowQueueBuf* own = nullptr)
+// the shadow rays of `pass`, on `side` where given; from the pass's own queue into its own accumulator plane where the plan is split
+void launchShadow(pt_ctx* c, uint32_t pass, const BatchPlan& plan, hipStream_t side = nullptr)
 {
-    Control* ctl = c->control.p;
     TraceArgs a = traceArgsBase(c);
     if (side) // runs beside the closest-hit traversal of the next bounce (and, with two side streams, beside another shadow pass): a spill region of its own
         a.spill = c->spill.p + c->spillHalf * (side == c->sideStream2 ? 2u : 1u);
-    const ShadowQueueBuf& q = own ? *own : c->shadow;
+    const ShadowQueueBuf& q = plan.split ? c->shadowQ[pass] : c->shadow;
     a.rayO = q.o.p;
     a.rayD = q.d.p;
     a.rayC = q.c.p;
-    a.accum = own ? AccumView { c->accumShadow.p + (size_t)pass * c->cfg.width * c->cfg.height, nullptr, nullptr, 0u } : accumView(c); // (own: this bounce's plane)
-    a.ctl = ctl;
+    a.accum = plan.split ? AccumView { c->accumShadow.p + (size_t)pass * c->cfg.width * c->cfg.height, nullptr, nullptr, 0u } : accumView(c); // (split: this bounce's plane)
+    a.ctl = c->control.p;
     a.pass = pass;
-    if (coherent && c->dyn[c->active].packetOk && (c->packetUse & 2u))
+    if (pass == 0u && plan.shadowPackets)
         launchPacket(c, true, a);
     else
         launchTrace(c, true, a, side);
 }
 
 // shade over `launchEntries` slots (upper bound of the live count) of queue `in` -> queue `out` + shadow queue
-void launchShade(pt_ctx* c, const FrameParams& fp, int in, int out, uint32_t pass, uint32_t launchEntries, const ShadowQueueBuf* ownShadow = nullptr, bool derivedPrimaries = false)
+void launchShade(pt_ctx* c, const FrameParams& fp, int in, int out, uint32_t pass, uint32_t launchEntries, const BatchPlan& plan)
 {
     Control* ctl = c->control.p;
+    const ShadeKernel* kernels = kShadeKernels[parityMode(c) ? 1 : 0][generalShading(c) ? 1 : 0];
     ShadeArgs a {};
     a.sc = c->scene;
     a.fp = fp;
@@ -559,19 +577,15 @@ void launchShade(pt_ctx* c, const FrameParams& fp, int in, int out, uint32_t pas
     a.shadeHits = &ctl->shadeHits[pass];
     a.deposits = parityMode(c) ? &ctl->depositsShade : &ctl->depositSlots[0][0]; // the production kernel spreads its count over the slots (pt_device.h)
     a.streams = c->streams.p;
-    a.derivedPrimaries = derivedPrimaries ? 1u : 0u;
-    // what the queues written here hold (pt_shade.h): the second queue capExt; the first queue capacity, or capExt where its origin / throughput planes are small
-    a.outCap = out == 1 ? c->capExt : (c->q0Small ? c->capExt : c->capacity);
-    a.shadowCap = ownShadow ? c->capacity : c->capShadow;
+    a.derivedPrimaries = pass == 0u && plan.derived ? 1u : 0u;
+    a.outCap = plan.outCap[out]; // what the queues written here hold (pt_shade.h)
+    a.shadowCap = plan.shadowCap;
     const uint32_t blocks = (std::max(launchEntries, 1u) + kShadeBlock - 1u) / kShadeBlock; // those beyond the live count leave at once
     if (parityMode(c)) {
         a.out = c->stagedRays.view();
         a.shadow = c->stagedShadow.view();
         a.activeFlag = c->activeFlag.p;
-        if (generalShading(c))
-            hipLaunchKernelGGL((k_shade<true, true>), dim3(blocks), dim3(kShadeBlock), 0, c->stream, a);
-        else
-            hipLaunchKernelGGL((k_shade<true, false>), dim3(blocks), dim3(kShadeBlock), 0, c->stream, a);
+        hipLaunchKernelGGL(kernels[kShadeTile], dim3(blocks), dim3(kShadeBlock), 0, c->stream, a);
         CompactArgs ca {};
         ca.staged = c->stagedRays.view();
         ca.out = c->rays[out].view();
@@ -585,14 +599,14 @@ void launchShade(pt_ctx* c, const FrameParams& fp, int in, int out, uint32_t pas
         hipLaunchKernelGGL(k_compact_stable, dim3(1), dim3(1024), 0, c->stream, ca);
     } else {
         a.out = c->rays[out].view();
-        a.shadow = ownShadow ? ownShadow->view() : c->shadow.view();
+        a.shadow = plan.split ? c->shadowQ[pass].view() : c->shadow.view();
         // The queue of pass b holds what survived b bounces -- 23 / 6 / 1.3 % of the capacity on the benchmark scene, more than half per
         // bounce behind glass -- but how much is a device word, and a million workgroups that leave at once cost 0.6 ms per launch to
         // dispatch.  So pass b >= 1 launches the one-tile kernel over as many tiles as the same pass of the previous batch filled (its
         // counters come back through pinned memory, unwaited-for; the first batch of a context assumes a half per bounce) and, behind
         // it, a 512-workgroup grid of the tile-walking kernel for whatever lies beyond -- a safety net that normally finds nothing.
         uint32_t head = blocks;
-        if (PT_SHADE_SPLIT && pass > 0) {
+        if (pass > 0) {
             if (c->passCountsEntries && !c->shadeHeadShift) {
                 // what the same pass of the last finished batch held, scaled to this batch's size, + 3 % + 8 tiles
                 const double scale = (double)launchEntries / (double)c->passCountsEntries;
@@ -602,34 +616,15 @@ void launchShade(pt_ctx* c, const FrameParams& fp, int in, int out, uint32_t pas
                 head = std::max(1u, blocks >> std::min(pass + c->shadeHeadShift, 24u)); // no history yet: half per bounce
             }
         }
-        if (generalShading(c))
-            hipLaunchKernelGGL((k_shade<false, true>), dim3(head), dim3(kShadeBlock), 0, c->stream, a);
-        else if (c->st->host.materialBins)
-            hipLaunchKernelGGL((k_shade<false, false, false, true>), dim3(head), dim3(kShadeBlock), 0, c->stream, a);
-        else
-            hipLaunchKernelGGL((k_shade<false, false>), dim3(head), dim3(kShadeBlock), 0, c->stream, a);
+        const bool binned = !generalShading(c) && c->st->host.materialBins;
+        hipLaunchKernelGGL(kernels[binned ? kShadeBinned : kShadeTile], dim3(head), dim3(kShadeBlock), 0, c->stream, a);
         if (head < blocks) {
             a.firstTile = head;
             // (a 1-spp frame's passes: 64 workgroups -- launching 512 that find nothing took 4-5 us of a ~700 us frame three times over)
             const uint32_t rest = std::min(blocks - head, launchEntries <= (4u << 20) ? 64u : 512u);
-            if (generalShading(c))
-                hipLaunchKernelGGL((k_shade<false, true, true>), dim3(rest), dim3(kShadeBlock), 0, c->stream, a);
-            else
-                hipLaunchKernelGGL((k_shade<false, false, true>), dim3(rest), dim3(kShadeBlock), 0, c->stream, a);
+            hipLaunchKernelGGL(kernels[kShadeLoop], dim3(rest), dim3(kShadeBlock), 0, c->stream, a);
         }
     }
-}
-
-// frame parameters of a batch of `batch` samples per owned pixel: how many of a pixel's samples sit next to each other in the queue
-FrameParams batchFrameParams(pt_ctx* c, uint32_t sample, uint32_t batch)
-{
-    FrameParams fp = frameParams(c, sample);
-    fp.planes = batch;
-    fp.interleave = 1;
-    while (fp.interleave < kGenInterleave && batch % (fp.interleave * 2u) == 0u)
-        fp.interleave *= 2u, fp.interleaveShift++;
-    fp.invSpan = 1.0f / (float)((uint64_t)c->numOwned << fp.interleaveShift);
-    return fp;
 }
 
 // Fixed launch schedule for one sample when every owned pixel has its own queue slot: gen, then
@@ -648,42 +643,18 @@ int renderSampleFixed(pt_ctx* c, uint32_t sample, uint32_t batch, Prof& prof)
     const uint32_t bounces = maxBounces(c);
     const uint32_t entries = c->numOwned * batch;
     c->batchEntries = entries;
-    // Where the packet kernel serves the primary rays it generates them itself, from the entry index, and queues them for
-    // k_shade: no k_gen launch (3.3 ms of a 121 ms batch, HBM-write-bound) and no read of 32 B per ray in a kernel that has
-    // bandwidth to spare for the two stores instead.  (k_shade regenerating the rays as well, so that they are never stored,
-    // was measured too: its 70 extra instructions per entry cost 2.3 ms per batch, more than the reads they replace.)
-    // The packet kernel serves the first pass when consecutive queue entries are >= 16 samples of one pixel.  (Packets of 8x8 pixel
-    // blocks -- what the default pixel order would give a 1-spp frame -- were measured too: the beam test handles them, but a
-    // 1280x720 frame is 14 k packets for 8 k persistent waves claiming 16 at a time: 2.2-2.4 ms per frame instead of 1.4-1.6.)
-    // (8x8-pixel packets for a 1-spp frame were measured again in round 3 with one packet per claim: 271 us for the 14 400 packets of
-    // a 1280 x 720 frame against 251 us through the per-ray kernel -- 1.8 rounds of latency-bound packet walks on 8 192 waves)
-    const bool coherentFirst = firstPassCoherent(c, fp, batch);
-    const bool packetsFirst = coherentFirst && c->dyn[c->active].packetOk && (c->packetUse & 1u);
-    const bool fused = packetsFirst && PT_FUSED_PRIMARY && !(c->cfg.flags & PT_FLAG_QUEUE_PRIMARY_RAYS);
-    // ... and where those are the bundles of a pinhole camera, only (direction, pixel) is queued: k_shade takes the eye as the origin and the sample from the
-    // entry index (12 instructions; the full regeneration the paragraph above dismissed is 70) -- 16 B per camera ray less written and 16 B less read
-    const bool derived = fused && primaryBundles(c) && !c->camera.thinLens && PT_DERIVED_PRIMARIES; // (a thin lens: every ray has an origin of its own, which stays in the queue)
+    const BatchPlan plan = planBatch(c, fp, batch);
     // (the first queue's origin / throughput planes hold capExt >= 16 samples' worth of entries: a batch that queues whole camera rays -- fewer than 16 samples
     // per pixel: no bundles -- fits them; a larger one that does so all the same is a change of camera or scene state pt_render has re-made the queues for)
-    if (c->q0Small && !derived && entries > c->capExt)
+    if (c->q0Small && !plan.derived && entries > c->capExt)
         return fail(c, PT_ERR_STATE, "the first queue was sized for camera rays queued as directions only, and this batch queues their origins");
     prof.begin(0);
-    if (fused)
+    if (plan.fused)
         hipLaunchKernelGGL(k_begin_batch, dim3(1), dim3(64), 0, c->stream, &c->control.p->extCount[0], &c->control.p->generated, entries);
     else
         launchGen(c, fp, 0, 0, entries, 0, 0);
     prof.end();
-    // Small launches are latency-bound (every traversal launch of a 1-spp 1280 x 720 frame takes 0.1-0.25 ms whatever it holds): the
-    // shadow rays of bounce b then run on a side stream BESIDE the extension rays of bounce b + 1.  Both need only shade b; shade
-    // b + 1 waits for both, so the accumulator sees its deposits in the same order as in the serial schedule (bit-identical images).
-    // Large batches fill the machine with one kernel; two traversal kernels side by side only evict each other's nodes (measured: slower).
-    const bool overlap = PT_OVERLAP_SMALL && entries <= (4u << 20) && !c->profile && !(c->packetUse & 2u);
-    // One sample in flight (RayTracer::rayTrace's frames): every entry deposits into the accumulator proper, so the shade launch of bounce b + 1 had to wait
-    // for the shadow rays of bounce b (same words, same order as the serial schedule) -- and the shadow passes, the longer ones, were the frame's critical path.
-    // There the shadow rays get an accumulator of their own (added to the other at the end of pt_render, in either schedule: the images stay bit-identical
-    // between them) and a queue per bounce: a shadow pass then waits for its own shade launch only.
-    const bool split = splitShadowAccum(c, c->capacity);
-    if (split) { // (its buffers were set aside with the queues: ensureQueues)
+    if (plan.split) { // (its buffers were set aside with the queues: ensureQueues)
         if (!c->accumShadow.p || !c->shadowQ[bounces - 1].o.p)
             return fail(c, PT_ERR_STATE, "the buffers of the one-sample-in-flight schedule are missing");
         c->mergePending = true;
@@ -691,53 +662,44 @@ int renderSampleFixed(pt_ctx* c, uint32_t sample, uint32_t batch, Prof& prof)
     int in = 0, out = 1;
     for (uint32_t b = 0; b < bounces; b++) {
         prof.begin(1);
-        const bool coherent = b == 0 && coherentFirst;
-        if (c->profile && coherent && c->dyn[c->active].packetOk && (c->packetUse & 1u))
+        if (c->profile && b == 0 && plan.first != BatchPlan::PerRay)
             prof.marks.back().first = 4; // timed apart from the per-ray kernel (ms_packet)
-        launchIntersect(c, in, b, coherent, fused && b == 0 ? &fp : nullptr, derived && b == 0);
+        launchIntersect(c, in, b, plan, fp);
         prof.end();
-        if (overlap && !split && b > 0)
+        if (plan.overlap && !plan.split && b > 0)
             HIPCHK(c, hipStreamWaitEvent(c->stream, c->evShadowed[b - 1], 0)); // the deposits of bounce b - 1's shadow rays come first
         prof.begin(2);
-        launchShade(c, fp, in, out, b, entries, split ? &c->shadowQ[b] : nullptr, derived && b == 0);
+        launchShade(c, fp, in, out, b, entries, plan);
         // A pass emits at most one extension and one shadow ray per entry it was handed.  Pass 0 is handed the whole batch: the only pass that can outgrow the
         // extension queues, and it may outgrow the shadow queue.  A later pass is handed at most capExt entries: where the shadow queue is the smaller one, it may
-        // outgrow that too (the batch was sized by the counts of earlier batches: a guess).  k_trace<true> reads as many shadow entries as the count says -- cut it.
-        if (b == 0 ? smallQueues(c) : c->capShadow < c->capExt) {
-            const uint32_t outCap = out == 1 ? c->capExt : (c->q0Small ? c->capExt : c->capacity); // (the queue pass b writes: launchShade's a.outCap)
-            hipLaunchKernelGGL(k_clamp_counts, dim3(1), dim3(64), 0, c->stream, c->control.p, b, outCap, c->capShadow, c->overflowPinned.p);
-        }
+        // outgrow that too (the batch was sized by the counts of earlier batches: a guess).  The any-hit kernel reads as many shadow entries as the count says --
+        // cut it.  (Never with a queue per bounce: those hold `capacity` entries, and small queues and the split schedule exclude each other, ensureQueues.)
+        if (b == 0 ? smallQueues(c) : c->capShadow < c->capExt)
+            hipLaunchKernelGGL(k_clamp_counts, dim3(1), dim3(64), 0, c->stream, c->control.p, b, plan.outCap[out], plan.shadowCap, c->overflowPinned.p);
         prof.end();
         prof.begin(3);
-        if (overlap && b + 1u == bounces && PT_LAST_SHADOW_ON_MAIN) {
-            // the last bounce's shadow rays have no extension pass to run beside: on the render stream itself, behind their shade launch -- the wait for a
-            // side stream's event that has only just fired was a 17 us hole in front of k_end_sample in every frame's trace
-            launchShadow(c, b, coherent, nullptr, split ? &c->shadowQ[b] : nullptr);
-        } else if (overlap) {
+        if (!plan.overlap || b + 1u == bounces) {
+            // the serial schedule -- and the last bounce's shadow rays, which have no extension pass to run beside: on the render stream itself, behind their
+            // shade launch -- the wait for a side stream's event that has only just fired was a 17 us hole in front of k_end_sample in every frame's trace
+            launchShadow(c, b, plan);
+        } else {
             // (with a plane and a queue per bounce the shadow passes depend on nothing but their own shade launch: two side streams take them in turn, so
             // that the pass of bounce b does not queue behind the longer one of bounce b - 1 -- the side stream had become a frame's critical path)
-            hipStream_t side = split && (b & 1u) ? c->sideStream2 : c->sideStream;
+            hipStream_t side = plan.split && (b & 1u) ? c->sideStream2 : c->sideStream;
             HIPCHK(c, hipEventRecord(c->evShaded[b], c->stream));
             HIPCHK(c, hipStreamWaitEvent(side, c->evShaded[b], 0));
-            launchShadow(c, b, coherent, side, split ? &c->shadowQ[b] : nullptr);
+            launchShadow(c, b, plan, side);
             HIPCHK(c, hipEventRecord(c->evShadowed[b], side));
-        } else {
-            launchShadow(c, b, coherent, nullptr, split ? &c->shadowQ[b] : nullptr);
         }
         prof.end();
         std::swap(in, out);
     }
-    if (overlap && PT_LAST_SHADOW_ON_MAIN) { // the side streams' last passes (long done, as a rule)
-        if (split && bounces > 1)
+    if (plan.overlap && plan.split) { // the side streams' last passes (long done, as a rule)
+        if (bounces > 1)
             HIPCHK(c, hipStreamWaitEvent(c->stream, c->evShadowed[bounces - 2], 0));
-        if (split && bounces > 2)
+        if (bounces > 2)
             HIPCHK(c, hipStreamWaitEvent(c->stream, c->evShadowed[bounces - 3], 0));
-        // (one accumulator: the shade launch of the last bounce has waited for the shadow rays of the bounce before it already)
-    } else if (overlap) {
-        HIPCHK(c, hipStreamWaitEvent(c->stream, c->evShadowed[bounces - 1], 0));
-        if (split && bounces > 1)
-            HIPCHK(c, hipStreamWaitEvent(c->stream, c->evShadowed[bounces - 2], 0)); // the other side stream's last pass
-    }
+    } // (one accumulator: the shade launch of the last bounce has waited for the shadow rays of the bounce before it already)
     // the pass counters go to pinned memory from inside k_end_sample (a report still unread keeps its slot: the host reads it only once its event has fired)
     const bool report = c->passCountsPinned.p && !c->passCountsPending;
     hipLaunchKernelGGL(k_end_sample, dim3(1), dim3(64), 0, c->stream, c->control.p, c->totals.p, bounces, report ? c->passCountsPinned.p : nullptr);
@@ -782,7 +744,7 @@ int renderSampleRefill(pt_ctx* c, uint32_t sample)
     const uint32_t cap = c->capacity;
     uint32_t issued = 0, surviving = 0, pass = 0;
     int in = 0, out = 1;
-    Control zero {};
+    const BatchPlan plan = plainPlan(c); // no pass of this loop is a coherent first pass: nothing fused, nothing beside anything else
     while (true) {
         // every pass reuses index 0/1 of the control block
         hipLaunchKernelGGL(k_set_word, dim3(1), dim3(64), 0, c->stream, &ctl->extCount[0], surviving);
@@ -797,8 +759,8 @@ int renderSampleRefill(pt_ctx* c, uint32_t sample)
                 launchGen(c, fp, in, issued, newRays, surviving, 0);
         }
         const uint32_t entries = surviving + newRays;
-        launchIntersect(c, in, 0);
-        launchShade(c, fp, in, out, 0, entries);
+        launchIntersect(c, in, 0, plan, fp);
+        launchShade(c, fp, in, out, 0, entries, plan);
         uint32_t counts[2] = { 0, 0 };
         HIPCHK(c, hipMemcpyAsync(&counts[0], &ctl->extCount[1], sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipMemcpyAsync(&counts[1], &ctl->shadowCount[0], sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
@@ -807,7 +769,7 @@ int renderSampleRefill(pt_ctx* c, uint32_t sample)
         surviving = counts[0];
         pass++;
         if (counts[1] != 0)
-            launchShadow(c, 0);
+            launchShadow(c, 0, plan);
         // fold this pass into the totals (entries/ shadow counted on the host side of the loop)
         hipLaunchKernelGGL(k_end_sample, dim3(1), dim3(64), 0, c->stream, c->control.p, c->totals.p, 0u, (uint32_t*)nullptr);
         if (surviving == 0 && issued >= c->numOwned)
@@ -816,7 +778,6 @@ int renderSampleRefill(pt_ctx* c, uint32_t sample)
         if (pass > 100000)
             return fail(c, PT_ERR_STATE, "refill loop did not terminate");
     }
-    (void)zero;
     HIPCHK(c, hipGetLastError());
     return PT_OK;
 }

@@ -2357,14 +2357,13 @@ int pt_primary_pass(pt_ctx* c, uint32_t sample, uint32_t batch, uint32_t n, floa
     if (n > (1u << 26)) // every entry comes back to the host (68 B each): a hook for tests, not for 531 M-entry batches
         return fail(c, PT_ERR_INVALID, "pt_primary_pass: %u entries -- the hook reads everything back, use it on small frames (<= 64 M entries)", n);
     FrameParams fp = batchFrameParams(c, sample, batch);
-    const bool coherentFirst = firstPassCoherent(c, fp, batch);
-    const bool packetsFirst = coherentFirst && c->dyn[c->active].packetOk && (c->packetUse & 1u);
-    const bool fused = packetsFirst && PT_FUSED_PRIMARY && !(c->cfg.flags & PT_FLAG_QUEUE_PRIMARY_RAYS);
-    if (fused)
+    BatchPlan plan = planBatch(c, fp, batch);
+    plan.derived = false; // (the origins are read back below: the one thing that differs from pt_render's first pass)
+    if (plan.fused)
         hipLaunchKernelGGL(k_begin_batch, dim3(1), dim3(64), 0, c->stream, &c->control.p->extCount[0], &c->control.p->generated, n);
     else
         launchGen(c, fp, 0, 0, n, 0, 0);
-    launchIntersect(c, 0, 0, coherentFirst, fused ? &fp : nullptr);
+    launchIntersect(c, 0, 0, plan, fp);
     std::vector<float4> o(n), d(n), h(n);
     std::vector<int32_t> in(n);
     HIPCHK(c, hipMemcpyAsync(o.data(), c->rays[0].o.p, n * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
@@ -2449,10 +2448,7 @@ int pt_shade_batch(pt_ctx* c, pt_shade_batch_io* io)
         a.accum = AccumView { dAcc.p, nullptr, nullptr, 0u };
         a.inCount = dCtl.p, a.outCount = dCtl.p + 1, a.shadowCount = dCtl.p + 2, a.shadeHits = dCtl.p + 3, a.deposits = dCtl.p + 4;
         a.outCap = a.shadowCap = 0xFFFFFFFFu; // (the hook's own queues: one slot per entry)
-        if (generalShading(c))
-            hipLaunchKernelGGL((k_shade<false, true>), dim3(1), dim3(64), 0, c->stream, a);
-        else
-            hipLaunchKernelGGL((k_shade<false, false>), dim3(1), dim3(64), 0, c->stream, a);
+        hipLaunchKernelGGL(kShadeKernels[0][generalShading(c) ? 1 : 0][kShadeTile], dim3(1), dim3(64), 0, c->stream, a);
         uint32_t back[4];
         float4 px;
         HIPCHK(c, hipMemcpyAsync(back, dCtl.p, sizeof(back), hipMemcpyDeviceToHost, c->stream));
