@@ -6,6 +6,7 @@
 // (getDenoisedOutput), filtered over the history without vertex motion, and with it.
 //     usage: deforming_cornell [frames] [filtered.ppm] [temporal_plain.ppm] [temporal_motion.ppm]
 #include "cornell.h"
+#include "meshes.h"
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -13,35 +14,7 @@
 
 using namespace raytracer;
 using namespace cornell;
-
-// a lumpy sphere of radius ~0.45 about the origin: kLat x kLon quads, one vertex per pole and ring position
-static const int kLat = 24, kLon = 48;
-static const vec3 kBlobAt(-0.15f, 0.55f, 0.0f);
-
-static void blobRest(std::vector<float>& pos)
-{
-    const float pi = 3.14159265f;
-    pos.clear();
-    for (int i = 0; i <= kLat; i++)
-        for (int j = 0; j < kLon; j++) {
-            const float th = pi * (float)i / kLat, ph = 2.0f * pi * (float)j / kLon;
-            const float r = 0.45f * (1.0f + 0.12f * std::sin(3.0f * th) * std::cos(4.0f * ph));
-            pos.push_back(r * std::sin(th) * std::cos(ph));
-            pos.push_back(r * std::cos(th));
-            pos.push_back(r * std::sin(th) * std::sin(ph));
-        }
-}
-
-// frame f: the blob leans along x by 0.05 per frame at its top and sways along z -- a shear that grows with the square of the height above its foot
-static void blobShape(const std::vector<float>& rest, int frame, std::vector<float>& pos)
-{
-    pos = rest;
-    for (size_t k = 0; k < rest.size(); k += 3) {
-        const float h = rest[k + 1] + 0.5f;
-        pos[k] += 0.05f * (float)frame * h * h;
-        pos[k + 2] += 0.12f * std::sin(0.5f * (float)frame) * h * h;
-    }
-}
+using namespace meshes;
 
 struct Result {
     std::vector<float> temporal, filtered;
@@ -56,16 +29,7 @@ static Result run(int frames, bool vertexMotion, const Camera& camera, int W, in
     scene->addNode(ceilingLight());
     std::vector<float> rest, pos;
     blobRest(rest);
-    std::vector<uint32_t> idx;
-    for (int i = 0; i < kLat; i++)
-        for (int j = 0; j < kLon; j++) {
-            const uint32_t a = (uint32_t)(i * kLon + j), b = (uint32_t)((i + 1) * kLon + j), c = (uint32_t)((i + 1) * kLon + (j + 1) % kLon),
-                           d = (uint32_t)(i * kLon + (j + 1) % kLon);
-            if (i + 1 < kLat) // (at the poles a ring has shrunk to a point: one triangle per quad)
-                idx.insert(idx.end(), { a, c, b });
-            if (i > 0)
-                idx.insert(idx.end(), { a, d, c });
-        }
+    const std::vector<uint32_t> idx = blobIndices();
     auto blob = std::make_shared<Mesh>(rest.data(), nullptr, nullptr, rest.size() / 3, idx.data(), nullptr, idx.size() / 3,
         std::vector<Material> { Material::Diffuse(vec3(0.2f, 0.3f, 0.7f)) }, BvhBuilder::BinnedSAH);
     scene->addNode(blob, Transform(kBlobAt));

@@ -6,16 +6,17 @@
 // saw that frame: the two accumulators must be identical.
 //      usage: rebuild_loop [level] [frames]        (icosphere level: 5 = 20 480 triangles, bench.py's `rebuild_20k`)
 #include "cornell.h"
+#include "meshes.h"
 #include <algorithm>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <map>
 
 using namespace raytracer;
 using namespace cornell;
+using namespace meshes;
 using Clock = std::chrono::steady_clock;
 
 static double ms(Clock::time_point a, Clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); }
@@ -23,74 +24,6 @@ static double median(std::vector<double> v)
 {
     std::sort(v.begin(), v.end());
     return v.empty() ? 0.0 : v[v.size() / 2];
-}
-
-// what the reference's MeshSequence is to its RayTracer: an IMesh whose arrays are another frame's after goToFrame
-class RebuiltMesh : public IMesh {
-public:
-    RebuiltMesh(std::vector<uint32_t> indices, Material material)
-        : m_indices(std::move(indices)), m_material(material) {}
-    void goToFrame(const std::vector<float>& positions)
-    {
-        m_mesh = std::make_shared<Mesh>(positions.data(), nullptr, nullptr, positions.size() / 3, m_indices.data(), nullptr, m_indices.size() / 3,
-            std::vector<Material> { m_material }, BvhBuilder::BinnedFast);
-    }
-    const std::vector<VertexSceneData>& getVertices() const override { return m_mesh->getVertices(); }
-    const std::vector<TriangleSceneData>& getTriangles() const override { return m_mesh->getTriangles(); }
-    const std::vector<Material>& getMaterials() const override { return m_mesh->getMaterials(); }
-    const std::vector<SubBVHNode>& getBvhNodes() const override { return m_mesh->getBvhNodes(); }
-    const std::vector<uint32_t>& getEmissiveTriangles() const override { return m_mesh->getEmissiveTriangles(); }
-    AABB getBounds() const override { return m_mesh->getBounds(); }
-    bool isDynamic() const override { return true; }
-    uint32_t maxNumVertices() const override { return m_mesh->maxNumVertices(); }
-    uint32_t maxNumTriangles() const override { return m_mesh->maxNumTriangles(); }
-    uint32_t maxNumMaterials() const override { return m_mesh->maxNumMaterials(); }
-    uint32_t maxNumBvhNodes() const override { return m_mesh->maxNumBvhNodes(); }
-    void buildBvh() override {}
-    uint32_t getBvhRootNode() const override { return m_mesh->getBvhRootNode(); }
-
-private:
-    std::vector<uint32_t> m_indices;
-    Material m_material;
-    std::shared_ptr<Mesh> m_mesh;
-};
-
-// unit icosphere, `level` subdivisions (20 * 4^level triangles)
-static void icosphere(int level, std::vector<float>& pos, std::vector<uint32_t>& idx)
-{
-    const float t = (1.0f + std::sqrt(5.0f)) / 2.0f;
-    const float v[12][3] = { { -1, t, 0 }, { 1, t, 0 }, { -1, -t, 0 }, { 1, -t, 0 }, { 0, -1, t }, { 0, 1, t }, { 0, -1, -t }, { 0, 1, -t }, { t, 0, -1 }, { t, 0, 1 }, { -t, 0, -1 }, { -t, 0, 1 } };
-    const uint32_t f[20][3] = { { 0, 11, 5 }, { 0, 5, 1 }, { 0, 1, 7 }, { 0, 7, 10 }, { 0, 10, 11 }, { 1, 5, 9 }, { 5, 11, 4 }, { 11, 10, 2 }, { 10, 7, 6 }, { 7, 1, 8 },
-        { 3, 9, 4 }, { 3, 4, 2 }, { 3, 2, 6 }, { 3, 6, 8 }, { 3, 8, 9 }, { 4, 9, 5 }, { 2, 4, 11 }, { 6, 2, 10 }, { 8, 6, 7 }, { 9, 8, 1 } };
-    auto push = [&](float x, float y, float z) {
-        const float n = std::sqrt(x * x + y * y + z * z);
-        pos.push_back(x / n), pos.push_back(y / n), pos.push_back(z / n);
-        return (uint32_t)(pos.size() / 3 - 1);
-    };
-    pos.clear(), idx.clear();
-    for (const auto& p : v)
-        push(p[0], p[1], p[2]);
-    for (const auto& tri : f)
-        idx.insert(idx.end(), tri, tri + 3);
-    for (int l = 0; l < level; l++) {
-        std::map<std::pair<uint32_t, uint32_t>, uint32_t> mid;
-        auto middle = [&](uint32_t a, uint32_t b) {
-            const auto key = std::make_pair(std::min(a, b), std::max(a, b));
-            auto it = mid.find(key);
-            if (it != mid.end())
-                return it->second;
-            const uint32_t m = push(pos[3 * a] + pos[3 * b], pos[3 * a + 1] + pos[3 * b + 1], pos[3 * a + 2] + pos[3 * b + 2]);
-            mid.emplace(key, m);
-            return m;
-        };
-        std::vector<uint32_t> next;
-        for (size_t i = 0; i < idx.size(); i += 3) {
-            const uint32_t a = idx[i], b = idx[i + 1], c = idx[i + 2], ab = middle(a, b), bc = middle(b, c), ca = middle(c, a);
-            const uint32_t t4[12] = { a, ab, ca, b, bc, ab, c, ca, bc, ab, bc, ca };
-            next.insert(next.end(), t4, t4 + 12);
-        }
-        idx.swap(next);
-    }
 }
 
 static void deformed(const std::vector<float>& unit, int k, std::vector<float>& pos)

@@ -496,11 +496,11 @@ uint32_t pt_sample_base(const pt_ctx* ctx);
  *                   continuous function of the inputs -- there is no accept / reject threshold that round-off could flip.
  * (d_out, N_out) and the current (n, z) go into the other set, the current camera is remembered, the sets flip.  Bit-reproducible run to run.
  * A pixel of a dynamic scene whose surface moved keeps or loses its history by the depth and normal terms alone, unless the motion of its instance was set
- * (INSTANCE MOTION below) or its mesh's deformation was (VERTEX MOTION below), which changes two lines of the above:
+ * (INSTANCE MOTION below) or its mesh's deformation was (VERTEX MOTION, REBUILT MOTION below), which changes two lines of the above:
  *   into history    q = (X + m / gspp) - E',  m the pixel's motion sum: the displacement is added to X BEFORE the history's eye is subtracted;  z' = |q| as before
  *   taps            e_n = k_normal max(0, 1 - n_then(p).n_h),  n_then the pixel's prev_normal sum normalised exactly as n is (zero stays zero)
  * and nothing else: the set written out still holds the CURRENT (n, z); blend, clamps and the 1e-12 rule are the same.  Zero motion sums and
- * prev_normal == normal_depth.xyz give the plain output bit for bit.  Still without motion vectors: rebuilt trees (pt_upload_static_async).
+ * prev_normal == normal_depth.xyz give the plain output bit for bit.  Rebuilt trees (pt_upload_static_async) take a triangle map: REBUILT MOTION below.
  * Moving lights have none to give -- their shadows and highlights move over surfaces that stand still --; TEMPORAL RESPONSE below follows them.
  * Refusals: PT_ERR_STATE before a camera is set and when pt_samples_per_pixel or pt_guide_samples is 0; PT_ERR_UNSUPPORTED while tiles are set (as
  * pt_denoise); PT_ERR_INVALID for max_history > 4096 or a negative k_normal / sigma_depth. */
@@ -580,7 +580,7 @@ int pt_debug_motion_records(const float* prev_inv, const float* cur_inv, uint32_
  * pt_set_vertex_motion refuses: PT_ERR_UNSUPPORTED in parity / refill mode; PT_ERR_STATE before a dynamic state is active and while
  * pt_guide_samples() != 0 (setting and forgetting alike); enabling: PT_ERR_STATE when there is no previous state (the other set never held an adopted one)
  * and while an upload is pending (pt_upload_dynamic_async without its pt_frame_tick: it is overwriting the set that held "then"); PT_ERR_UNSUPPORTED when
- * the previous state was built on the other static scene (a pt_upload_static_async rebuild) or has another triangle count; PT_ERR_INVALID when a
+ * the previous state was built on the other static scene (a pt_upload_static_async rebuild: pt_set_rebuilt_motion) or has another triangle count; PT_ERR_INVALID when a
  * transform L is made from is singular.  A refused call changes nothing.  pt_frame_tick (and with it pt_upload_dynamic) forgets the vertex motion as it
  * forgets the instance motion; pt_clear zeroes the sums and keeps it set; pt_set_instance_motion(NULL) forgets the instance part alone. */
 int pt_set_vertex_motion(pt_ctx* ctx, int enable);            /* 1: take the previous state's geometry as "then"; 0: forget */
@@ -589,6 +589,39 @@ int pt_vertex_motion(const pt_ctx* ctx, uint32_t* deformed_out); /* 1 / 0: set o
 /* test hook, no device needed: the rows L for n invTransforms of 16 floats (column-major); out12: n x 12 floats.  A singular or non-finite matrix is
  * PT_ERR_INVALID, through pt_last_error(NULL). */
 int pt_debug_vertex_motion_rows(const float* inv_transforms, uint32_t n, float* out12);
+
+/* REBUILT MOTION: motion vectors for meshes whose tree was REBUILT (pt_upload_static_async) between the previous dynamic state and the active one -- the
+ * second way to fill the "then" records of VERTEX MOTION, for states whose triangle numbering differs: a builder re-emits the triangles in leaf order
+ * and spatial splits duplicate them, so triangle i of the new arrays is not triangle i of the old ones.  Opt-in like the blocks above: with the call
+ * never made, every entry point launches exactly the kernels it launches without this block and returns the same bits.
+ *
+ * The caller hands in the correspondence: prev_triangle[i] is the index of triangle i of the ACTIVE state in the triangle array of the PREVIOUS dynamic
+ * state (the one before the last pt_frame_tick), whichever of the two static scenes either state was built on and whatever their triangle counts;
+ * PT_NO_PREVIOUS_TRIANGLE says that the triangle is new.  The map is validated on the host (one pass, before anything is enqueued), copied into a device
+ * buffer of the context's own (grow-only, freed by pt_destroy), and k_gather_then (csrc/pt_denoise.h) makes the snapshot on the render stream:
+ *   then'[i] = prev_triangle[i] == PT_NO_PREVIOUS_TRIANGLE ? now[i] : then[prev_triangle[i]]      (128-byte shading records, a copy: the bits survive)
+ * into the buffer pt_set_vertex_motion(ctx, 1) copies into.  Everything downstream is VERTEX MOTION's: the same state (pt_vertex_motion reports (1, 1)), the
+ * same rows L, the same deposits, the same order-independence with pt_set_instance_motion, the motion route of pt_temporal_accumulate.  A triangle without
+ * a predecessor takes its own current record as "then": delta == 0 exactly and n_then has the bits of N, like an undeformed triangle -- it keeps or loses
+ * its history by depth and normal.  The guide pass reads the snapshot alone, so a pipelined caller may start the next pt_upload_static_async /
+ * pt_upload_dynamic_async before the frame's pt_render_guides.  The host library makes such a map for meshes whose frames share an input numbering
+ * (pth_triangle_history); the C ABI takes any.
+ * A frame loop: pt_upload_static_async, pt_upload_dynamic_async, pt_frame_tick, pt_clear, pt_set_instance_motion / pt_set_rebuilt_motion, pt_render,
+ * pt_render_guides, pt_temporal_accumulate, pt_denoise.
+ *
+ * pt_set_rebuilt_motion refuses what pt_set_vertex_motion refuses, in its order: PT_ERR_UNSUPPORTED in parity / refill mode; PT_ERR_STATE before a dynamic
+ * state is active and while pt_guide_samples() != 0 (setting and forgetting alike); setting: PT_ERR_UNSUPPORTED while a guide chain is set, PT_ERR_STATE
+ * while an upload is pending, when there is no previous state, and when a set holds no shading records for its own triangle count; then PT_ERR_INVALID when
+ * n_tris is not the active state's triangle count and for an entry that is neither PT_NO_PREVIOUS_TRIANGLE nor below the previous state's count
+ * (pt_last_error names the first one); PT_ERR_INVALID when a transform L is made from is singular.  A refused call changes nothing.  pt_frame_tick forgets
+ * the motion, pt_clear keeps it; pt_set_vertex_motion(ctx, 0) and pt_set_rebuilt_motion(ctx, NULL, 0) both forget it, whichever call set it. */
+#define PT_NO_PREVIOUS_TRIANGLE 0xFFFFFFFFu
+int pt_set_rebuilt_motion(pt_ctx* ctx, const uint32_t* prev_triangle, uint32_t n_tris); /* NULL / 0: forget */
+int pt_rebuilt_motion(const pt_ctx* ctx, uint32_t* followed_out); /* 1 / 0: set by pt_set_rebuilt_motion or not; followed_out (optional): entries of the map
+                                                                     that are not PT_NO_PREVIOUS_TRIANGLE */
+/* test hook: k_gather_then over host arrays -- n_then and n_now records of 128 bytes, n_now map entries, n_now records out.  An entry that is not below
+ * n_then gives the current record (the kernel's own guard: an index out of range never becomes an address). */
+int pt_debug_gather_records(pt_ctx* ctx, const void* then128, uint32_t n_then, const void* now128, uint32_t n_now, const uint32_t* map, void* out128);
 
 /* TEMPORAL VARIANCE: how noisy each pixel of the history still is, and a filter that is guided by it (SVGF's second half).  Opt-in: with the mode off,
  * every entry point launches exactly the kernels it launches without this block and returns the same bits.

@@ -94,6 +94,15 @@ int pth_scene_mesh_offsets(const pth_scene* s, const pth_mesh* m, uint32_t* firs
 /* the mesh's vertex array in place (num_vertices records of 48 bytes; valid until the mesh is destroyed, contents change with pth_mesh_refit) */
 const pt_vertex* pth_mesh_vertices(const pth_mesh* m, uint32_t* count);
 int pth_scene_copy(const pth_scene* s, pt_vertex* v, pt_triangle* t, pt_material* m, pt_sub_bvh_node* n, pt_emissive_triangle* l, pt_top_bvh_node* top);
+/* Where each triangle of the last pth_scene_flatten comes from, num_triangles entries each: the index of its mesh among the scene's meshes (in the order
+ * they were first added) and its input triangle in that mesh -- what the builder's leaf order and spatial splits made of the caller's numbering;
+ * 0xFFFFFFFF (PT_NO_PREVIOUS_TRIANGLE) where the mesh does not say. */
+int pth_scene_copy_triangle_origins(const pth_scene* s, uint32_t* mesh, uint32_t* original);
+/* The map pt_set_rebuilt_motion takes (include/ptamd.h, "rebuilt motion"), from the origins of two flattened scenes whose meshes keep their places and
+ * their input numbering: map[i], i < n_now, is the lowest j < n_then with (then_mesh[j], then_original[j]) == (now_mesh[i], now_original[i]), else
+ * 0xFFFFFFFF; an original of 0xFFFFFFFF matches nothing.  O(n_now + n_then).  A pure function. */
+int pth_triangle_history(const uint32_t* now_mesh, const uint32_t* now_original, uint32_t n_now, const uint32_t* then_mesh, const uint32_t* then_original,
+    uint32_t n_then, uint32_t* map);
 
 int pth_camera_data(const pth_camera_params* p, pt_camera* out);
 

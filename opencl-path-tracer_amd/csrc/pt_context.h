@@ -418,6 +418,14 @@ struct pt_ctx {
     bool vertexMotionSet = false;
     bool vertexDeformed = false; // the previous state held another version of the static arrays: k_guides<2> runs
 
+    // rebuilt motion (include/ptamd.h): the second way to fill fatThen, for a state whose tree was rebuilt -- the caller's map (active triangle -> triangle
+    // of the previous state) on the device, where k_gather_then reads it, and the pinned copy the asynchronous upload reads from (its event: created at the
+    // first call, recorded on the render stream).  Grow-only.  Set: the vertex motion above (set, deformed) came from pt_set_rebuilt_motion.
+    DevBuf<uint32_t> rebuiltMap;
+    Staging rebuiltStage;
+    bool rebuiltMotionSet = false;
+    uint32_t rebuiltFollowed = 0;
+
     double msLastRender = 0, msIntersect = 0, msShade = 0, msShadow = 0, msGen = 0, msPacket = 0;
 };
 

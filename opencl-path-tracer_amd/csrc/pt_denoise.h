@@ -182,6 +182,23 @@ __global__ void __launch_bounds__(256) k_guides(SceneDev sc, const float4* __res
     }
 }
 
+// The snapshot k_guides<2> reads, for a state whose tree was REBUILT since the previous one (pt_set_rebuilt_motion; include/ptamd.h, "rebuilt motion"): the
+// triangles are numbered anew, so "then" is gathered through the caller's map --
+//   out[i] = map[i] == PT_NO_PREVIOUS_TRIANGLE ? now[i] : then[map[i]]
+// a copy of 128-byte records, bits untouched.  Eight lanes move one record, a float4 each: a wave64 moves eight whole 128-byte lines per load and per
+// store, no line is split, the stores are consecutive.  The compare against nThen is the only guard there is: an index that is not below it (the marker
+// is the largest) never becomes an address, whatever the host validated; it gives the current record.
+__global__ void __launch_bounds__(256) k_gather_then(const TriFat* __restrict__ then, uint32_t nThen, const TriFat* __restrict__ now,
+    const uint32_t* __restrict__ map, TriFat* __restrict__ out, uint32_t nNow)
+{
+    const uint32_t i = blockIdx.x * 32u + (threadIdx.x >> 3), piece = threadIdx.x & 7u;
+    if (i >= nNow)
+        return;
+    const uint32_t j = map[i];
+    const float4* src = j < nThen ? (const float4*)(then + j) : (const float4*)(now + i);
+    ((float4*)(out + i))[piece] = src[piece];
+}
+
 // ---- guide chain (include/ptamd.h, "guide chain") ------------------------------------------------
 // With pt_set_guide_chain(K > 0) a guide ray follows refraction to the first surface that is not glass.  Per sample the guide pass launches k_guide_gen and
 // then, for stage j = 0 .. K, the per-ray closest-hit kernel over stage j's queue (pass j of the guide pass's control block) and k_guide_chain(j):

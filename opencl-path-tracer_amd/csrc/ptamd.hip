@@ -840,7 +840,7 @@ int pt_frame_tick(pt_ctx* c)
     c->haveDynamic = true;
     c->motionSet = false; // (its records are indexed by the state that was just replaced)
     c->motionMoving = 0;
-    c->vertexMotionSet = c->vertexDeformed = false; // (its "then" is the state before the one that was just replaced)
+    c->vertexMotionSet = c->vertexDeformed = c->rebuiltMotionSet = false; // (its "then" is the state before the one that was just replaced)
     if (next.staticIndex != c->statCur) { // the state was built on a rebuilt scene (pt_upload_static_async): that scene is the current one from here on
         c->statCur = next.staticIndex;
         c->st = &c->stat[c->statCur];
@@ -1994,7 +1994,7 @@ int pt_set_vertex_motion(pt_ctx* c, int enable)
     if (c->guideSpp != 0)
         return fail(c, PT_ERR_STATE, "pt_set_vertex_motion: %u guide samples are in the sums already -- set or forget the motion right after pt_clear", c->guideSpp);
     if (!enable) {
-        c->vertexMotionSet = c->vertexDeformed = false;
+        c->vertexMotionSet = c->vertexDeformed = c->rebuiltMotionSet = false;
         return PT_OK;
     }
     if (c->guideChain)
@@ -2005,7 +2005,7 @@ int pt_set_vertex_motion(pt_ctx* c, int enable)
     if (!old.used)
         return fail(c, PT_ERR_STATE, "pt_set_vertex_motion: there is no previous state (one pt_frame_tick adopted the only state so far)");
     if (old.staticIndex != cur.staticIndex)
-        return fail(c, PT_ERR_UNSUPPORTED, "pt_set_vertex_motion: the previous state was built on another static scene (pt_upload_static_async): rebuilt trees have no vertex motion");
+        return fail(c, PT_ERR_UNSUPPORTED, "pt_set_vertex_motion: the previous state was built on another static scene (pt_upload_static_async): a rebuilt tree numbers its triangles anew -- hand the correspondence to pt_set_rebuilt_motion");
     if (old.numTris != cur.numTris)
         return fail(c, PT_ERR_UNSUPPORTED, "pt_set_vertex_motion: the previous state has %u triangles, the active one %u", old.numTris, cur.numTris);
     HIPCHK(c, hipSetDevice(c->device));
@@ -2033,6 +2033,7 @@ int pt_set_vertex_motion(pt_ctx* c, int enable)
         return rc;
     c->vertexMotionSet = true;
     c->vertexDeformed = deformed;
+    c->rebuiltMotionSet = false;
     return PT_OK;
     });
 }
@@ -2056,6 +2057,123 @@ int pt_debug_vertex_motion_rows(const float* invTransforms, uint32_t n, float* o
     if (rc)
         return fail(nullptr, rc, "pt_debug_vertex_motion_rows: %s", why.c_str());
     std::memcpy(out12, rows.data(), (size_t)n * 3 * sizeof(float4));
+    return PT_OK;
+    });
+}
+
+// ---- rebuilt motion (k_gather_then, then k_guides<2>) ---------------------------------------------
+namespace {
+
+void launchGatherThen(hipStream_t s, const TriFat* then, uint32_t nThen, const TriFat* now, const uint32_t* map, TriFat* out, uint32_t nNow)
+{
+    hipLaunchKernelGGL(ptd::k_gather_then, dim3((nNow + 31u) / 32u), dim3(256), 0, s, then, nThen, now, map, out, nNow); // (eight lanes per record)
+}
+
+} // namespace
+
+int pt_set_rebuilt_motion(pt_ctx* c, const uint32_t* prevTriangle, uint32_t nTris)
+{
+    return guarded(c, "pt_set_rebuilt_motion", [&]() -> int {
+    if (!c)
+        return PT_ERR_INVALID;
+    if (const int rc = fixedScheduleOnly(c, "pt_set_rebuilt_motion"))
+        return rc;
+    if (!c->haveDynamic)
+        return fail(c, PT_ERR_STATE, "pt_set_rebuilt_motion: no dynamic state is active yet (pt_upload_dynamic)");
+    if (c->guideSpp != 0)
+        return fail(c, PT_ERR_STATE, "pt_set_rebuilt_motion: %u guide samples are in the sums already -- set or forget the motion right after pt_clear", c->guideSpp);
+    if (!prevTriangle || nTris == 0) {
+        c->vertexMotionSet = c->vertexDeformed = c->rebuiltMotionSet = false;
+        return PT_OK;
+    }
+    if (c->guideChain)
+        return fail(c, PT_ERR_UNSUPPORTED, "pt_set_rebuilt_motion: a guide chain is set (pt_set_guide_chain) -- motion deposits along a chain are not supported");
+    if (c->pending >= 0)
+        return fail(c, PT_ERR_STATE, "pt_set_rebuilt_motion: an upload is pending (pt_upload_dynamic_async without its pt_frame_tick): it is overwriting the set that held the previous state");
+    pt_ctx::DynamicSet &cur = c->dyn[c->active], &old = c->dyn[1 - c->active];
+    if (!old.used)
+        return fail(c, PT_ERR_STATE, "pt_set_rebuilt_motion: there is no previous state (one pt_frame_tick adopted the only state so far)");
+    if (old.fat.n < old.numTris || cur.fat.n < cur.numTris)
+        return fail(c, PT_ERR_STATE, "pt_set_rebuilt_motion: the states hold no shading records for their %u and %u triangles", old.numTris, cur.numTris);
+    if (nTris != cur.numTris)
+        return fail(c, PT_ERR_INVALID, "pt_set_rebuilt_motion: a map of %u entries for an active state of %u triangles", nTris, cur.numTris);
+    HIPCHK(c, hipSetDevice(c->device));
+    // the one pass over the map: validated, counted and copied into pinned memory of the context's own, which the asynchronous upload reads (the caller's
+    // array is free again when the call returns; the previous call's upload out of that memory has long been read)
+    HIPCHK(c, c->rebuiltStage.read.create());
+    HIPCHK(c, c->rebuiltStage.wait());
+    HIPCHK(c, c->rebuiltStage.reserve((size_t)nTris * sizeof(uint32_t), ((size_t)nTris + nTris / 8) * sizeof(uint32_t)));
+    uint32_t* const map = (uint32_t*)c->rebuiltStage.mem.p;
+    uint32_t followed = 0;
+    for (uint32_t i = 0; i < nTris; i++) {
+        const uint32_t j = prevTriangle[i];
+        if (j != PT_NO_PREVIOUS_TRIANGLE) {
+            if (j >= old.numTris)
+                return fail(c, PT_ERR_INVALID, "pt_set_rebuilt_motion: entry %u names triangle %u of a previous state of %u triangles", i, j, old.numTris);
+            followed++;
+        }
+        map[i] = j;
+    }
+    std::vector<MotionRecord> records;
+    std::vector<float4> rows;
+    if (c->motionSet)
+        records = c->motionHost;
+    int rc = makeVertexTables(c, c->motionSet, records, rows, "pt_set_rebuilt_motion");
+    if (rc || (rc = c->motionGuides.ensure(c)))
+        return rc;
+    if (c->fatThen.n < nTris || c->rebuiltMap.n < nTris) {
+        HIPCHK(c, hipStreamSynchronize(c->stream)); // (growing frees what an earlier guide pass or gather may still read)
+        if (c->fatThen.n < nTris)
+            HIPCHK(c, c->fatThen.alloc(nTris));
+        if (c->rebuiltMap.n < nTris)
+            HIPCHK(c, c->rebuiltMap.alloc(nTris));
+    }
+    // "then", through the map: the inactive set still holds the previous state's records, the active set the current ones.  On the render stream, which has
+    // waited for both sets' uploads at their ticks and on which every earlier gather has read the map; the inactive set's lastUse moves behind the
+    // gather as it moves behind pt_set_vertex_motion's copy, so the next upload into that set may be started at once.
+    HIPCHK(c, hipMemcpyAsync(c->rebuiltMap.p, map, (size_t)nTris * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, c->rebuiltStage.recordRead(c->stream));
+    launchGatherThen(c->stream, old.fat.p, old.numTris, cur.fat.p, c->rebuiltMap.p, c->fatThen.p, nTris);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipEventRecord(old.lastUse, c->stream));
+    if ((rc = commitVertexTables(c, c->motionSet, records, rows)))
+        return rc;
+    c->vertexMotionSet = c->vertexDeformed = c->rebuiltMotionSet = true;
+    c->rebuiltFollowed = followed;
+    return PT_OK;
+    });
+}
+
+int pt_rebuilt_motion(const pt_ctx* c, uint32_t* followedOut)
+{
+    const bool set = c && c->vertexMotionSet && c->rebuiltMotionSet;
+    if (followedOut)
+        *followedOut = set ? c->rebuiltFollowed : 0u;
+    return set ? 1 : 0;
+}
+
+// test hook (tests/test_gpu_rebuilt_motion.py): k_gather_then over host arrays
+int pt_debug_gather_records(pt_ctx* c, const void* then128, uint32_t nThen, const void* now128, uint32_t nNow, const uint32_t* map, void* out128)
+{
+    return guarded(c, "pt_debug_gather_records", [&]() -> int {
+    if (!c || !now128 || !map || !out128 || nNow == 0 || (nThen != 0 && !then128))
+        return PT_ERR_INVALID;
+    HIPCHK(c, hipSetDevice(c->device));
+    DevBuf<TriFat> dThen, dNow, dOut;
+    DevBuf<uint32_t> dMap;
+    HIPCHK(c, dThen.alloc(std::max<uint32_t>(nThen, 1)));
+    HIPCHK(c, dNow.alloc(nNow));
+    HIPCHK(c, dOut.alloc(nNow));
+    HIPCHK(c, dMap.alloc(nNow));
+    if (nThen)
+        HIPCHK(c, hipMemcpy(dThen.p, then128, (size_t)nThen * sizeof(TriFat), hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(dNow.p, now128, (size_t)nNow * sizeof(TriFat), hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(dMap.p, map, (size_t)nNow * sizeof(uint32_t), hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemsetAsync(dOut.p, 0, (size_t)nNow * sizeof(TriFat), c->stream));
+    launchGatherThen(c->stream, dThen.p, nThen, dNow.p, dMap.p, dOut.p, nNow);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpy(out128, dOut.p, (size_t)nNow * sizeof(TriFat), hipMemcpyDeviceToHost));
     return PT_OK;
     });
 }

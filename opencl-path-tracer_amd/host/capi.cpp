@@ -395,6 +395,31 @@ int pth_scene_copy(const pth_scene* s, pt_vertex* v, pt_triangle* t, pt_material
     });
 }
 
+int pth_scene_copy_triangle_origins(const pth_scene* s, uint32_t* mesh, uint32_t* original)
+{
+    return guarded([&] {
+        const SceneHandle& h = *(const SceneHandle*)s;
+        if (!h.staticFlattened)
+            throw std::logic_error("pth_scene_copy_triangle_origins: call pth_scene_flatten first");
+        if (mesh && !h.flat.triangleMesh.empty())
+            std::memcpy(mesh, h.flat.triangleMesh.data(), h.flat.triangleMesh.size() * sizeof(uint32_t));
+        if (original && !h.flat.triangleOriginal.empty())
+            std::memcpy(original, h.flat.triangleOriginal.data(), h.flat.triangleOriginal.size() * sizeof(uint32_t));
+    });
+}
+
+int pth_triangle_history(const uint32_t* nowMesh, const uint32_t* nowOriginal, uint32_t nNow, const uint32_t* thenMesh, const uint32_t* thenOriginal,
+    uint32_t nThen, uint32_t* map)
+{
+    return guarded([&] {
+        if ((nNow && (!nowMesh || !nowOriginal || !map)) || (nThen && (!thenMesh || !thenOriginal)))
+            throw std::invalid_argument("pth_triangle_history: null argument");
+        const std::vector<uint32_t> m = triangleHistory(nowMesh, nowOriginal, nNow, thenMesh, thenOriginal, nThen);
+        if (nNow)
+            std::memcpy(map, m.data(), (size_t)nNow * sizeof(uint32_t));
+    });
+}
+
 int pth_camera_data(const pth_camera_params* p, pt_camera* out)
 {
     return guarded([&] {

@@ -34,6 +34,9 @@ public:
     // a class: its arrays change under goToNextFrame, src/model/mesh_sequence.cpp:81-97) and hands the re-flattened arrays over as the reference does.
     static constexpr uint64_t kUntracked = ~0ull;
     virtual uint64_t generation() const { return kUntracked; }
+    // getTriangles()[i] is input triangle (*getOriginalTriangles())[i] -- what a builder's leaf order and its spatial splits made of the caller's numbering,
+    // and what follows a triangle from one rebuilt tree to the next (triangleHistory, scene.h).  nullptr: the mesh does not know.
+    virtual const std::vector<uint32_t>* getOriginalTriangles() const { return nullptr; }
 };
 
 class Mesh : public IMesh {
@@ -89,6 +92,7 @@ public:
     size_t numInputTriangles() const { return m_inputTriangles.size(); }
     BvhBuilder builder() const { return m_builder; }
     uint64_t generation() const override { return m_generation; }
+    const std::vector<uint32_t>* getOriginalTriangles() const override { return &m_bvh.originalTriangle; } // (of a tree loaded from a cache file too: loadBvh reconstructs them)
 
 private:
     void generateSmoothNormals();

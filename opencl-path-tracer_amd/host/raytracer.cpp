@@ -61,9 +61,9 @@ void RayTracer::frameTick()
     // instance motion: the state about to be replaced is the one the newest history was made under if getTemporalOutput blended a frame of it; if not
     // (several ticks without a blend) the transforms kept before stay: the oldest.  The leaves of the top level are nodes [0, instances) in scene-graph
     // order (buildTopBVHOver), so index i names the same instance across ticks while the graph's structure is unchanged.
-    if (m_rebuilt) {
+    if (m_rebuilt && !m_rebuiltMotion) {
         m_prevLeafValid = false; // other meshes: nothing to follow
-    } else if (m_blendedThisState) {
+    } else if (m_blendedThisState) { // (rebuilt meshes that are followed: setInstanceMotionAfterTick's leaf count decides)
         size_t leaves = 0;
         while (leaves < m_flat.topBvhNodes.size() && m_flat.topBvhNodes[leaves].isLeaf)
             leaves++;
@@ -74,6 +74,14 @@ void RayTracer::frameTick()
     }
     // vertex motion: the device library takes the state about to be replaced as "then", which is the history's only under the same condition
     m_vertexDue = m_refitted && m_blendedThisState && !m_rebuilt;
+    // rebuilt motion, under the same condition: the map rebuildGeometry made leads from the scene this tick adopts to the one it replaces.  The origins kept
+    // are those of the ADOPTED flat scene -- of two rebuildGeometry calls before one tick the second replaced the first on the device too, and its map.
+    m_rebuiltDue = m_rebuiltMotion && m_rebuilt && m_blendedThisState && m_rebuiltMapValid;
+    if (m_rebuiltDue)
+        m_rebuiltMapDue.swap(m_rebuiltMap);
+    m_rebuiltMapValid = false;
+    if (m_rebuiltMotion && (m_rebuilt || !m_adoptedValid))
+        keepAdoptedOrigins();
     m_refitted = false;
     m_blendedThisState = false;
     m_rebuilt = false;
@@ -135,19 +143,42 @@ void RayTracer::rebuildGeometry()
               m_flat.materials.data(), (uint32_t)m_flat.materials.size(), m_flat.subBvhNodes.data(), (uint32_t)m_flat.subBvhNodes.size()),
         "pt_upload_static_async");
     m_rebuilt = true;
+    m_rebuiltMapValid = m_rebuiltMotion && m_adoptedValid;
+    if (m_rebuiltMapValid)
+        m_rebuiltMap = triangleHistory(m_flat.triangleMesh.data(), m_flat.triangleOriginal.data(), m_flat.triangleMesh.size(), m_adoptedMesh.data(),
+            m_adoptedOriginal.data(), m_adoptedMesh.size());
+}
+
+void RayTracer::keepAdoptedOrigins()
+{
+    m_adoptedMesh = m_flat.triangleMesh;
+    m_adoptedOriginal = m_flat.triangleOriginal;
+    m_adoptedValid = true;
+}
+
+void RayTracer::setRebuiltMotion(bool on)
+{
+    m_rebuiltMotion = on;
+    m_rebuiltDue = m_rebuiltMapValid = m_adoptedValid = false;
+    if (on && !m_rebuilt) // (a rebuilt scene that waits for its tick: m_flat is no longer the adopted one, the origins are kept from that tick on)
+        keepAdoptedOrigins();
 }
 
 // The first rayTrace on a cleared accumulator after a tick: hand the device library the transforms the leaves had when the newest history was made
 // (pt_set_instance_motion wants them before the first guide sample).  Nothing is set without a history, with another number of leaves, or when switched off.
-// Next to it the vertex motion, when a mesh was refitted (updateGeometry) since the previous tick and the history is of the state that tick replaced.
+// Next to it the vertex motion, when a mesh was refitted (updateGeometry) since the previous tick and the history is of the state that tick replaced; or,
+// under the same condition, the map of a scene that was rebuilt (rebuildGeometry, setRebuiltMotion).
 void RayTracer::setMotionAfterTick()
 {
     m_motionDue = false;
     setInstanceMotionAfterTick();
     const bool deformed = m_vertexMotion && !m_guideChain && m_vertexDue && pt_temporal_frames(m_ctx) != 0;
-    m_vertexDue = false;
+    const bool rebuilt = m_rebuiltMotion && !m_guideChain && m_rebuiltDue && !m_rebuiltMapDue.empty() && pt_temporal_frames(m_ctx) != 0;
+    m_vertexDue = m_rebuiltDue = false;
     if (deformed)
         check(pt_set_vertex_motion(m_ctx, 1), "pt_set_vertex_motion");
+    else if (rebuilt)
+        check(pt_set_rebuilt_motion(m_ctx, m_rebuiltMapDue.data(), (uint32_t)m_rebuiltMapDue.size()), "pt_set_rebuilt_motion");
     else if (pt_vertex_motion(m_ctx, nullptr)) // set for an earlier frame of this state: the history has caught up since
         check(pt_set_vertex_motion(m_ctx, 0), "pt_set_vertex_motion");
 }

@@ -96,14 +96,23 @@ public:
     // Motion vectors for instances re-posed by frameTick (include/ptamd.h, "instance motion"): frameTick keeps the leaves' transforms of the state the last
     // getTemporalOutput blended (the oldest, if several ticks passed since), and the first rayTrace on a cleared accumulator after the tick hands them to
     // the device library -- so the guide samples getTemporalOutput renders carry the motion, and the history follows the instances.  Only while the scene
-    // graph's structure is unchanged (same number of leaves: index i then names the same instance), never across rebuildGeometry.  On by default; it acts
+    // graph's structure is unchanged (same number of leaves: index i then names the same instance), and across rebuildGeometry only with setRebuiltMotion.  On by default; it acts
     // for getTemporalOutput users alone (without a history nothing is set): getOutput / getDenoisedOutput are what they were.  A frame loop with a static
     // camera clears by itself (pt_clear(context())) after its frameTick: rayTrace only clears when the camera changed.
     void setInstanceMotion(bool on) { m_instanceMotion = on; }
     // Motion vectors for meshes refitted between two ticks (include/ptamd.h, "vertex motion"): when updateGeometry handed a refitted mesh over since the
     // previous frameTick, and getTemporalOutput blended a frame of the state that tick replaced, the first rayTrace on a cleared accumulator after the tick
-    // sets pt_set_vertex_motion next to the instance motion -- the history follows the deforming surface.  Never across rebuildGeometry.  On by default.
+    // sets pt_set_vertex_motion next to the instance motion -- the history follows the deforming surface.  Not across rebuildGeometry (setRebuiltMotion).  On by
+    // default.
     void setVertexMotion(bool on) { m_vertexMotion = on; }
+    // Motion vectors across rebuildGeometry (include/ptamd.h, "rebuilt motion"): frameTick keeps where every triangle of the flat scene it adopts comes
+    // from (its mesh's place in the scene, its input triangle: IMesh::getOriginalTriangles), rebuildGeometry maps the new scene's triangles onto those
+    // (triangleHistory, scene.h), and the first rayTrace on a cleared accumulator after the tick hands the map to pt_set_rebuilt_motion -- under
+    // setVertexMotion's condition: getTemporalOutput blended a frame of the state the tick replaced.  For meshes that keep their place in the scene and
+    // their input numbering from frame to frame (a deforming surface rebuilt every frame); a triangle without a predecessor, and every triangle of a
+    // mesh that does not report its origins, keeps or loses its history by depth and normal.  The instance motion then survives a rebuild as well, while
+    // the number of leaves stays.  Off by default: the class then does what it did without this call.
+    void setRebuiltMotion(bool on);
     // The luminance variance of every pixel's history beside it, and the filter guided by it (include/ptamd.h, "temporal variance"): resets the history
     // (the mode changes only while there is none); from then on getTemporalOutput filters with PT_DENOISE_INPUT_TEMPORAL_VARIANCE -- a static camera's
     // image keeps converging where the fixed-strength filter stops at its own blur.  Off by default.
@@ -147,13 +156,21 @@ private:
     // instance motion: the leaves' invTransform (16 floats each, scene-graph order) of the state the newest history was made under
     bool m_instanceMotion = true;
     std::vector<float> m_prevLeafInv;
-    bool m_prevLeafValid = false; // m_prevLeafInv is that state's (false: no history yet, or the geometry was rebuilt since)
+    bool m_prevLeafValid = false; // m_prevLeafInv is that state's (false: no history yet, or the geometry was rebuilt since without setRebuiltMotion)
     bool m_blendedThisState = false; // getTemporalOutput blended a frame of the current scene state
     bool m_motionDue = false; // a tick happened: the next rayTrace on a cleared accumulator sets (or leaves unset) the motion
     bool m_rebuilt = false; // rebuildGeometry since the last frameTick
     bool m_vertexMotion = true;
     bool m_refitted = false; // updateGeometry handed a refitted mesh to the device library since the last frameTick
     bool m_vertexDue = false; // ... and that tick replaced the state the newest history was made under: the device library's "then" is the history's
+    // rebuilt motion: the triangle origins of the flat scene the last tick adopted, the map rebuildGeometry made against them, the map the last tick owes
+    bool m_rebuiltMotion = false;
+    std::vector<uint32_t> m_adoptedMesh, m_adoptedOriginal;
+    bool m_adoptedValid = false;
+    std::vector<uint32_t> m_rebuiltMap, m_rebuiltMapDue;
+    bool m_rebuiltMapValid = false; // m_rebuiltMap leads from m_flat to the adopted scene
+    bool m_rebuiltDue = false; // ... and the last tick replaced the state the newest history was made under: m_rebuiltMapDue goes to the device library
+    void keepAdoptedOrigins();
     void setMotionAfterTick();
     void setInstanceMotionAfterTick();
     int m_width, m_height;

@@ -305,7 +305,9 @@ void flattenStatic(Scene& scene, FlattenedScene& out)
     out.materials.resize(numM);
     out.triangles.resize(numT);
     out.subBvhNodes.resize(numN);
-    uint32_t v0 = 0, m0 = 0, t0 = 0, n0 = 0;
+    out.triangleMesh.resize(numT);
+    out.triangleOriginal.resize(numT);
+    uint32_t v0 = 0, m0 = 0, t0 = 0, n0 = 0, meshIndex = 0;
     for (MeshBvhPair& pair : scene.getMeshes()) {
         const IMesh& mesh = *pair.meshPtr;
         std::copy(mesh.getVertices().begin(), mesh.getVertices().end(), out.vertices.begin() + v0);
@@ -318,6 +320,12 @@ void flattenStatic(Scene& scene, FlattenedScene& out)
             t.materialIndex += m0;
             out.triangles[i++] = t;
         }
+        const std::vector<uint32_t>* original = mesh.getOriginalTriangles();
+        const size_t nT = mesh.getTriangles().size();
+        const bool known = original && original->size() == nT;
+        for (size_t k = 0; k < nT; k++)
+            out.triangleMesh[t0 + k] = meshIndex, out.triangleOriginal[t0 + k] = known ? (*original)[k] : kNoTriangle;
+        meshIndex++;
         i = n0;
         for (SubBVHNode n : mesh.getBvhNodes()) {
             n.leftChildOrFirstTriangle += (n.triangleCount > 0) ? t0 : n0;
@@ -342,6 +350,38 @@ void flattenStatic(Scene& scene, FlattenedScene& out)
         }
     };
     Refresh::walk(scene.getRootNode(), scene.getMeshes());
+}
+
+std::vector<uint32_t> triangleHistory(const uint32_t* nowMesh, const uint32_t* nowOriginal, size_t nNow, const uint32_t* thenMesh, const uint32_t* thenOriginal,
+    size_t nThen)
+{
+    // per mesh of `then`: how many input triangles it names (largest original + 1), then one table of all meshes' entries, filled from the back so that the
+    // lowest j stays
+    std::vector<size_t> base;
+    for (size_t j = 0; j < nThen; j++) {
+        if (thenOriginal[j] == kNoTriangle)
+            continue;
+        if (thenMesh[j] > nThen + nNow || thenOriginal[j] > 16 * (nThen + nNow)) // (the tables are sized by these: arrays that are no triangle origins)
+            throw std::invalid_argument("triangleHistory: a mesh index or an input triangle far beyond the number of triangles");
+        if (thenMesh[j] >= base.size())
+            base.resize((size_t)thenMesh[j] + 1, 0);
+        base[thenMesh[j]] = std::max(base[thenMesh[j]], (size_t)thenOriginal[j] + 1);
+    }
+    std::vector<size_t> count = base;
+    size_t total = 0;
+    for (size_t m = 0; m < base.size(); m++)
+        base[m] = total, total += count[m];
+    if (total > 16 * (nThen + nNow + 1))
+        throw std::invalid_argument("triangleHistory: the meshes name far more input triangles than there are triangles");
+    std::vector<uint32_t> first(total, kNoTriangle);
+    for (size_t j = nThen; j-- > 0;)
+        if (thenOriginal[j] != kNoTriangle)
+            first[base[thenMesh[j]] + thenOriginal[j]] = (uint32_t)j;
+    std::vector<uint32_t> map(nNow, kNoTriangle);
+    for (size_t i = 0; i < nNow; i++)
+        if (nowOriginal[i] != kNoTriangle && nowMesh[i] < base.size() && nowOriginal[i] < count[nowMesh[i]])
+            map[i] = first[base[nowMesh[i]] + nowOriginal[i]];
+    return map;
 }
 
 void flattenDynamic(const Scene& scene, FlattenedScene& out)

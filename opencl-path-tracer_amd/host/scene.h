@@ -64,11 +64,26 @@ struct FlattenedScene {
     std::vector<pt_emissive_triangle> emissiveTriangles; // world space
     std::vector<TopBVHNode> topBvhNodes;
     uint32_t topBvhRoot = 0;
+    // where each triangle comes from (flattenStatic): its mesh's index in Scene::getMeshes() and its input triangle there (IMesh::getOriginalTriangles;
+    // kNoTriangle where the mesh does not say)
+    std::vector<uint32_t> triangleMesh, triangleOriginal;
 };
+constexpr uint32_t kNoTriangle = 0xFFFFFFFFu; // PT_NO_PREVIOUS_TRIANGLE
 constexpr uint32_t kMaxNumLights = 256; // MAX_NUM_LIGHTS, src/raytracer.cpp:39
 
 void flattenStatic(Scene& scene, FlattenedScene& out); // also records MeshBvhPair::bvhIndexOffset
 void flattenDynamic(const Scene& scene, FlattenedScene& out); // lights + top-level BVH
+// Rebuilt motion (include/ptamd.h, "rebuilt motion"): the map pt_set_rebuilt_motion takes, from the origins of two flattened scenes whose meshes keep their
+// places in Scene::getMeshes() and their input numbering.  map[i] is the lowest j of `then` whose (mesh, original) is that of triangle i of `now`, else
+// kNoTriangle (a new triangle, a mesh without origins).  The duplicates a spatial split makes carry the same vertex indices, so any of them holds the same
+// record; the lowest makes the map deterministic.  O(n): one table per mesh, no sorting.  The four arrays: FlattenedScene::triangleMesh / triangleOriginal.
+std::vector<uint32_t> triangleHistory(const uint32_t* nowMesh, const uint32_t* nowOriginal, size_t nNow, const uint32_t* thenMesh, const uint32_t* thenOriginal,
+    size_t nThen);
+inline std::vector<uint32_t> triangleHistory(const FlattenedScene& now, const FlattenedScene& then)
+{
+    return triangleHistory(now.triangleMesh.data(), now.triangleOriginal.data(), now.triangleMesh.size(), then.triangleMesh.data(), then.triangleOriginal.data(),
+        then.triangleMesh.size());
+}
 inline FlattenedScene flattenScene(Scene& scene)
 {
     FlattenedScene f;

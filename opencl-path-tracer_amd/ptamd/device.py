@@ -66,6 +66,7 @@ class ShadeBatchIO(C.Structure):
 DENOISE_TONEMAPPED, DENOISE_HDR = 0, 1
 GUIDE_SKY_DEPTH = 1e6
 GUIDE_CHAIN_MAX = 4  # PT_GUIDE_CHAIN_MAX
+NO_PREVIOUS_TRIANGLE = 0xFFFFFFFF  # PT_NO_PREVIOUS_TRIANGLE
 
 
 class DenoiseParams(C.Structure):
@@ -105,7 +106,8 @@ EXPORTS = ["pt_create", "pt_destroy", "pt_last_error", "pt_set_stream", "pt_uplo
            "pt_denoise", "pt_denoise_device", "pt_set_sample_base", "pt_sample_base", "pt_temporal_accumulate", "pt_temporal_reset",
            "pt_temporal_frames", "pt_read_temporal", "pt_write_temporal", "pt_temporal_device_ptr", "pt_set_instance_motion", "pt_instance_motion",
            "pt_read_motion_guides", "pt_write_motion_guides", "pt_motion_guides_device_ptr", "pt_debug_motion_records",
-           "pt_set_vertex_motion", "pt_vertex_motion", "pt_debug_vertex_motion_rows", "pt_set_temporal_variance", "pt_temporal_variance",
+           "pt_set_vertex_motion", "pt_vertex_motion", "pt_debug_vertex_motion_rows",
+           "pt_set_rebuilt_motion", "pt_rebuilt_motion", "pt_debug_gather_records", "pt_set_temporal_variance", "pt_temporal_variance",
            "pt_read_temporal_variance", "pt_write_temporal_variance", "pt_temporal_variance_device_ptr",
            "pt_set_temporal_response", "pt_temporal_response", "pt_read_temporal_fast", "pt_write_temporal_fast", "pt_read_temporal_response",
            "pt_temporal_fast_device_ptr", "pt_stats_get", "pt_stats_reset", "pt_profile_kernels", "pt_reduce_accum",
@@ -197,6 +199,9 @@ def lib():
         l.pt_set_vertex_motion.argtypes = [C.c_void_p, C.c_int]
         l.pt_vertex_motion.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
         l.pt_debug_vertex_motion_rows.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
+        l.pt_set_rebuilt_motion.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
+        l.pt_rebuilt_motion.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
+        l.pt_debug_gather_records.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
         l.pt_set_temporal_variance.argtypes = [C.c_void_p, C.POINTER(VarianceParams)]
         l.pt_temporal_variance.argtypes = [C.c_void_p]
         l.pt_read_temporal_variance.argtypes = [C.c_void_p, C.c_void_p]
@@ -660,6 +665,38 @@ class Context:
         """(set, deformed): whether a vertex motion is set, and 1 when a refit came between the previous state and the active one (else 0)"""
         deformed = C.c_uint32(0)
         return bool(lib().pt_vertex_motion(self._h, C.byref(deformed))), int(deformed.value)
+
+    # ---- rebuilt motion
+    def set_rebuilt_motion(self, prev_triangle):
+        """The vertex motion of a state whose tree was REBUILT since the previous one (upload_static_async): prev_triangle[i] is the index triangle i of
+        the active state had in the previous dynamic state's triangle array, NO_PREVIOUS_TRIANGLE where it is new (host.triangle_history makes such a
+        map).  None forgets the motion.  Right after clear(), like set_vertex_motion, whose state it sets."""
+        if prev_triangle is None:
+            self._chk(lib().pt_set_rebuilt_motion(self._h, None, 0), "pt_set_rebuilt_motion")
+            return
+        m = np.ascontiguousarray(prev_triangle, np.uint32)
+        if m.ndim != 1:
+            raise ValueError("set_rebuilt_motion: the map is one-dimensional, an entry per triangle of the active state")
+        self._chk(lib().pt_set_rebuilt_motion(self._h, _p(m), len(m)), "pt_set_rebuilt_motion")
+
+    @property
+    def rebuilt_motion(self):
+        """(set, followed): whether a rebuilt motion is set, and how many entries of its map name a previous triangle"""
+        followed = C.c_uint32(0)
+        return bool(lib().pt_rebuilt_motion(self._h, C.byref(followed))), int(followed.value)
+
+    def debug_gather_records(self, then, now, prev_triangle):
+        """k_gather_then on the device (pt_debug_gather_records): then (n_then, 32) and now (n_now, 32) uint32 -- 128-byte records --, prev_triangle
+        (n_now) uint32; returns the (n_now, 32) uint32 records out[i] = then[prev_triangle[i]] where that entry is below n_then, else now[i]."""
+        then = np.ascontiguousarray(then, np.uint32).reshape(-1, 32)
+        now = np.ascontiguousarray(now, np.uint32).reshape(-1, 32)
+        m = np.ascontiguousarray(prev_triangle, np.uint32)
+        if m.shape != (len(now),):
+            raise ValueError("debug_gather_records: one map entry per current record")
+        out = np.zeros_like(now)
+        self._chk(lib().pt_debug_gather_records(self._h, _p(then) if len(then) else None, len(then), _p(now), len(now), _p(m), _p(out)),
+                  "pt_debug_gather_records")
+        return out
 
     def stats(self):
         s = Stats()

@@ -72,6 +72,8 @@ def lib():
         _lib.pth_scene_flatten.argtypes = [C.c_void_p, C.POINTER(SceneCounts)]
         _lib.pth_scene_flatten_dynamic.argtypes = [C.c_void_p, C.POINTER(SceneCounts)]
         _lib.pth_scene_copy.argtypes = [C.c_void_p] * 7
+        _lib.pth_scene_copy_triangle_origins.argtypes = [C.c_void_p] * 3
+        _lib.pth_triangle_history.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
         _lib.pth_scene_flatten_dynamic_only.argtypes = [C.c_void_p, C.POINTER(SceneCounts)]
         _lib.pth_scene_mesh_offsets.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
         _lib.pth_mesh_vertices.restype = C.c_void_p
@@ -264,6 +266,7 @@ class Scene:
         top = np.zeros(c.num_top_nodes, L.TOP_BVH_NODE)
         if lib().pth_scene_copy(self._h, _ptr(v), _ptr(t), _ptr(m), _ptr(n), _ptr(l), _ptr(top)):
             _err("pth_scene_copy")
+        self._num_triangles = int(c.num_triangles)  # (triangle_origins)
         return FlatScene(v, t, m, n, l, top, c.top_root, c.num_instances)
 
     def flatten_dynamic(self, flat):
@@ -296,6 +299,17 @@ class Scene:
             _err("pth_scene_copy")
         return FlatScene(None, None, None, None, l, top, c.top_root, c.num_instances), dt
 
+    def triangle_origins(self):
+        """Where each triangle of the last flatten() comes from: (mesh, original) uint32 arrays of num_triangles entries -- the index of its mesh among the
+        scene's meshes and its input triangle there (NO_PREVIOUS_TRIANGLE where the mesh does not say).  What triangle_history follows a rebuilt tree by."""
+        n = getattr(self, "_num_triangles", None)
+        if n is None:
+            raise RuntimeError("triangle_origins: call flatten() first")
+        mesh, original = np.zeros(n, np.uint32), np.zeros(n, np.uint32)
+        if lib().pth_scene_copy_triangle_origins(self._h, _ptr(mesh), _ptr(original)):
+            _err("pth_scene_copy_triangle_origins")
+        return mesh, original
+
     def mesh_offsets(self, mesh):
         """(first vertex, first sub-BVH node) of `mesh` in the arrays of the last flatten()."""
         v, n = C.c_uint32(0), C.c_uint32(0)
@@ -309,7 +323,24 @@ class Scene:
             self._h = None
 
 
-def camera_data(location, orientation_wxyz, horizontal_fov_deg, aspect_ratio, focal_distance=1.0, thin_lens=False,
+NO_PREVIOUS_TRIANGLE = 0xFFFFFFFF  # PT_NO_PREVIOUS_TRIANGLE
+
+
+def triangle_history(now, then):
+    """pth_triangle_history: the map Context.set_rebuilt_motion takes.  now, then: the (mesh, original) pairs Scene.triangle_origins() gave for the
+    active and the previous flattened scene.  map[i] is the lowest j of `then` with the (mesh, original) of triangle i of `now`, NO_PREVIOUS_TRIANGLE
+    where there is none."""
+    nm, no = (np.ascontiguousarray(a, np.uint32) for a in now)
+    tm, to = (np.ascontiguousarray(a, np.uint32) for a in then)
+    if nm.shape != no.shape or tm.shape != to.shape or nm.ndim != 1 or tm.ndim != 1:
+        raise ValueError("triangle_history: (mesh, original) are two one-dimensional arrays of one length")
+    out = np.zeros(len(nm), np.uint32)
+    if lib().pth_triangle_history(_ptr(nm), _ptr(no), len(nm), _ptr(tm), _ptr(to), len(tm), _ptr(out)):
+        _err("pth_triangle_history")
+    return out
+
+
+def camera_data(location,orientation_wxyz, horizontal_fov_deg, aspect_ratio, focal_distance=1.0, thin_lens=False,
                 focal_length_mm=0.0, aperture_fstops=0.0, shutter_time=0.0, iso=0.0):
     p = CameraParams()
     p.location[:] = [float(x) for x in location]
