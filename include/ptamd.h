@@ -713,6 +713,51 @@ int pt_write_temporal_fast(pt_ctx* ctx, const float* colour_count); /* checkpoin
 int pt_read_temporal_response(pt_ctx* ctx, float* s_out); /* host, width*height floats: the mix factor of the last pt_temporal_accumulate */
 void* pt_temporal_fast_device_ptr(pt_ctx* ctx); /* the newest set's fast image; NULL while the mode is off and before the first temporal call with it on */
 
+/* FIREFLY CLAMP: a bounded copy of the current frame's demodulated colour, made before the history and the filter see it.  One outlier of a 1-spp frame
+ * is otherwise blended into the history at full weight, and a non-finite accumulator pixel stays in h + (d - h) / N for ever.  Opt-in: with the mode
+ * off, every entry point launches exactly the kernels it launches without this block and returns the same bits.  With the mode on pt_render,
+ * pt_resolve, pt_read_accum and the accumulator are exactly as before: the stage writes a plane of its own.  The clamp trades energy for variance --
+ * what it removes from a single-pixel highlight or a caustic is real light (DESIGN.md section 9 has the figures).
+ *
+ * Per pixel p of the width x height image, with the current pt_samples_per_pixel and pt_guide_samples:
+ *   d(p)     the demodulated mean c / max(a, 1e-3) of GUIDES AND DENOISER, L(p) its Rec.709 luminance; p is FINITE when the three components of d(p)
+ *            and L(p) are all finite
+ *   R(p)     the rank-th largest L(q) among the up to 24 pixels q != p with |qx - px| <= 2 and |qy - py| <= 2 that lie inside the image and are
+ *            finite; n_q is their number; ties are ordinary values
+ *   Cap(p)   scale (R(p) + 1e-3) -- the luminance floor of the filter's e_l --, and +infinity when n_q < rank
+ *   output   width*height float4 (d_out.rgb, s):   p not finite: (0, 0, 0, 0), counter `nonfinite` + 1
+ *                                                  L(p) > Cap(p): s = Cap / L(p), d_out = d s (one multiply per component), counter `clamped` + 1
+ *                                                  otherwise: (d, 1), with d's bits
+ * An order statistic is a continuous function of its inputs and so is min(1, Cap / L): there is no accept / reject decision round-off could flip, the
+ * exact finiteness test apart.  A feature of rank + 1 or more pixels survives -- each of its pixels has `rank` neighbours like it --, a smaller one
+ * that stands more than `scale` times above its surround does not: a single-pixel highlight at any rank.  That is the stated bias.
+ *
+ * The plane is computed afresh by every call that consumes it -- one launch, nothing to go stale --: pt_temporal_accumulate, which blends the
+ * plane's d where it formed d itself; pt_denoise / pt_denoise_device with PT_DENOISE_INPUT_ACCUM and iterations > 0, whose d_0 it is; and
+ * pt_read_firefly.  iterations == 0 over the accumulator stays pt_resolve's image bit for bit; the two temporal inputs read the history, which was
+ * fed clamped frames already.  Where nothing is clamped every consumer returns the bits of the mode off.  The mode may change at any time: a history
+ * that mixes clamped and unclamped frames is a history with a firefly in it.
+ *
+ * pt_set_firefly_clamp refuses: PT_ERR_UNSUPPORTED in parity / refill mode; PT_ERR_INVALID for rank > PT_FIREFLY_MAX_RANK and for a scale that is
+ * not finite, negative, or in (0, 1).  pt_read_firefly: PT_ERR_STATE with the mode off, or while pt_samples_per_pixel or pt_guide_samples is 0;
+ * PT_ERR_UNSUPPORTED while tiles are set, as pt_denoise.  pt_firefly_counts: PT_ERR_STATE before the first evaluation.  A refused call changes
+ * nothing.  The plane and its two counters are allocated at the first evaluation and freed by pt_destroy. */
+#define PT_FIREFLY_RADIUS 2 /* the window is 5 x 5, clipped to the image, centre excluded */
+#define PT_FIREFLY_MAX_RANK 4u
+#define PT_FIREFLY_DEFAULT_RANK 1u /* the scan of tests/test_firefly_ref.py over five rooms chose the pair (EXPERIMENTS.md, "Firefly clamp") */
+#define PT_FIREFLY_DEFAULT_SCALE 8.0f
+typedef struct {
+    uint32_t rank; /* 0 = 1; 1 .. PT_FIREFLY_MAX_RANK */
+    float scale; /* 0 = 8.0; otherwise >= 1 */
+    uint32_t _reserved[6];
+} pt_firefly_params; /* 32 bytes */
+int pt_set_firefly_clamp(pt_ctx* ctx, const pt_firefly_params* params); /* NULL: off */
+int pt_firefly_clamp(const pt_ctx* ctx); /* 1 / 0 */
+int pt_read_firefly(pt_ctx* ctx, float* d_s, uint32_t counts[2]); /* evaluates the stage on the current accumulator and guides; host, width*height*4
+                                                                     floats; counts = (clamped, nonfinite); either pointer may be NULL; synchronises */
+int pt_firefly_counts(pt_ctx* ctx, uint32_t counts[2]); /* of the LAST evaluation, whichever entry point made it; synchronises */
+void* pt_firefly_device_ptr(pt_ctx* ctx); /* the plane; NULL while the mode is off and before the first evaluation */
+
 /* ---- kernel-granular entry points (parity tests and micro-benchmarks) ------------------
  * Host SoA arrays in, host SoA arrays out; the scene must have been uploaded. */
 typedef struct {

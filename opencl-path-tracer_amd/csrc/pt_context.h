@@ -399,6 +399,15 @@ struct pt_ctx {
     bool responseSet = false;
     float fastHistory = 0, sigmaResponse = 0, responseFloor = 0; // pt_response_params, defaults resolved
 
+    // firefly clamp (include/ptamd.h; pt_firefly.h): the clamped plane (d.rgb, s), width * height float4, and its two counters (clamped, nonfinite) --
+    // allocated at the first evaluation with the mode on, made afresh by every call that consumes the plane.  The mode may change at any time.
+    DevBuf<float4> fireflyPlane;
+    DevBuf<uint32_t> fireflyCounts;
+    bool fireflySet = false;
+    bool fireflyEvaluated = false; // the plane and the counters hold an evaluation
+    uint32_t fireflyRank = 0;
+    float fireflyScale = 0; // pt_firefly_params, defaults resolved
+
     // instance motion (include/ptamd.h): one record per instance of the ACTIVE dynamic state (indexed like its instance table, which is how the guide
     // pass meets a hit), and the two guide sums made from them -- (displacement.xyz, 0) and (normal then.xyz, 0), width * height float4 each, allocated at
     // the first pt_set_instance_motion / pt_write_motion_guides.  pt_frame_tick forgets the motion; pt_clear zeroes the sums and keeps it.

@@ -436,7 +436,9 @@ __device__ inline float4 remodulated(float r, float g, float b, float4 al, float
 //   PT_DENOISE_INPUT_ACCUM              d0 = demodulatedMean(accum, albedo sums),   the luminance of d0
 //   PT_DENOISE_INPUT_TEMPORAL           d0 = the newest history's d,                the luminance of d0
 //   PT_DENOISE_INPUT_TEMPORAL_VARIANCE  the same d0,                                V_0 = v / max(N, 1): the variance of the history's MEAN
-template <uint32_t INPUT>
+// FIREFLY (pt_set_firefly_clamp, PT_DENOISE_INPUT_ACCUM alone): `source` is the clamped plane (d.rgb, s) k_firefly made of the accumulator, d0 is its
+// rgb and the albedo sums are not read.  The FIREFLY-less instantiations are the kernels of before.
+template <uint32_t INPUT, bool FIREFLY = false>
 __global__ void __launch_bounds__(256) k_denoise_prepare(const float4* __restrict__ source, const float* __restrict__ histVariance,
     const float4* __restrict__ albedoHits, const float4* __restrict__ normalDepth, float4* __restrict__ colour, float4* __restrict__ guide, uint32_t n,
     float spp, float gspp)
@@ -446,7 +448,7 @@ __global__ void __launch_bounds__(256) k_denoise_prepare(const float4* __restric
         return;
     const float4 s = source[i], g = normalDepth[i];
     V3 d = xyz(s);
-    if constexpr (INPUT == kInputAccum)
+    if constexpr (INPUT == kInputAccum && !FIREFLY)
         d = demodulatedMean(s, albedoHits[i], spp, gspp);
     float fourth;
     if constexpr (INPUT == kInputTemporalVariance)

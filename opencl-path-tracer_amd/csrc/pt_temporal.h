@@ -2,7 +2,7 @@
 // with the current frame -- include/ptamd.h, "temporal history"; DESIGN.md section 9.  Nothing here is on the render path: k_temporal reads the
 // accumulator and the guide sums like k_denoise_prepare does, and the two history sets the context keeps for it.
 #pragma once
-#include "pt_denoise.h"
+#include "pt_firefly.h"
 
 namespace ptd {
 
@@ -34,6 +34,8 @@ struct TemporalArgs {
     float4* outFast;
     float2* outLuminance;
     float fastHistory;
+    // k_temporal<., ., ., true> (pt_set_firefly_clamp): the clamped plane (d.rgb, s) k_firefly made of this frame; accum and albedoHits are not read
+    const float4* firefly;
 };
 
 // The blend both histories go through: h = sum w d_h / Wsum, N = min(sum w N_h + 1, cap), d_out = h + (d - h) / N.  One function, so equal sums give
@@ -71,7 +73,10 @@ constexpr int kTemporalTileW = kAtrousTileW, kTemporalTileH = kAtrousTileH; // t
 // tap counting where ITS count is positive, capped at fast_history instead of max_history.  Four more gathered 16-byte reads, issued with the colour
 // taps, one 16-byte write and one 8-byte write of (L(d_f), L(d_l)) for k_temporal_response -- 152 bytes per pixel against 112; the other modes add
 // what they add above.  outColour is written UN-mixed, with the bits of the RESPONSE-less kernel: k_temporal_response mixes it in place.
-template <bool MOTION, bool VARIANCE = false, bool RESPONSE = false>
+// FIREFLY (pt_set_firefly_clamp): d is read from the clamped plane instead of being formed here -- one 16-byte read in place of two, 96 bytes per pixel
+// against 112 --, and everything downstream (the blends, l of the variance, the luminance pairs) takes the clamped d because it takes d.  Where the
+// plane holds d's own bits the outputs have the bits of the FIREFLY-less kernel, which is the kernel of before.
+template <bool MOTION, bool VARIANCE = false, bool RESPONSE = false, bool FIREFLY = false>
 __global__ void __launch_bounds__(256) k_temporal(TemporalArgs a)
 {
     const int x = blockIdx.x * kTemporalTileW + threadIdx.x, y = blockIdx.y * kTemporalTileH + threadIdx.y;
@@ -79,11 +84,18 @@ __global__ void __launch_bounds__(256) k_temporal(TemporalArgs a)
     if (x >= W || y >= H)
         return;
     const size_t p = (size_t)y * W + x;
-    const float4 s = a.accum[p], al = a.albedoHits[p], g = a.normalDepth[p];
+    float4 s, al;
+    if constexpr (FIREFLY)
+        s = a.firefly[p];
+    else
+        s = a.accum[p], al = a.albedoHits[p];
+    const float4 g = a.normalDepth[p];
     float4 mv, pn;
     if constexpr (MOTION)
         mv = a.motion[p], pn = a.prevNormal[p];
-    const V3 d = demodulatedMean(s, al, a.spp, a.gspp);
+    V3 d = xyz(s);
+    if constexpr (!FIREFLY)
+        d = demodulatedMean(s, al, a.spp, a.gspp);
     const float4 nz = guideOf(g, a.gspp);
     const float z = nz.w;
     a.outGuide[p] = nz;

@@ -1411,9 +1411,10 @@ void resolveGuideSigmas(float k_normal, float sigma_depth, float* kNormal, float
 }
 
 // the run-time switches of a call to the instantiation that has them as template flags
-void launchPrepare(pt_ctx* c, uint32_t input, const float4* source, const float* variance, uint32_t n)
+// (clamped: `source` is the firefly plane, PT_DENOISE_INPUT_ACCUM alone)
+void launchPrepare(pt_ctx* c, uint32_t input, bool clamped, const float4* source, const float* variance, uint32_t n)
 {
-    const auto k = input == PT_DENOISE_INPUT_ACCUM ? k_denoise_prepare<PT_DENOISE_INPUT_ACCUM>
+    const auto k = input == PT_DENOISE_INPUT_ACCUM ? (clamped ? k_denoise_prepare<PT_DENOISE_INPUT_ACCUM, true> : k_denoise_prepare<PT_DENOISE_INPUT_ACCUM>)
         : (input == PT_DENOISE_INPUT_TEMPORAL ? k_denoise_prepare<PT_DENOISE_INPUT_TEMPORAL> : k_denoise_prepare<PT_DENOISE_INPUT_TEMPORAL_VARIANCE>);
     hipLaunchKernelGGL(k, dim3((n + 255u) / 256u), dim3(256), 0, c->stream, source, variance, c->guides[0], c->guides[1], c->denoiseColour[0].p,
         c->denoiseGuide.p, n, (float)c->spp, (float)c->guideSpp);
@@ -1424,11 +1425,41 @@ void launchAtrous(hipStream_t stream, dim3 grid, dim3 block, bool inLds, bool gu
 }
 void launchTemporal(hipStream_t stream, dim3 grid, dim3 block, bool moved, bool variance, bool response, const TemporalArgs& a)
 {
+    if (a.firefly) { // (pt_set_firefly_clamp: d comes from the clamped plane)
+        if (response)
+            hipLaunchKernelGGL(moved ? (variance ? k_temporal<true, true, true, true> : k_temporal<true, false, true, true>)
+                                     : (variance ? k_temporal<false, true, true, true> : k_temporal<false, false, true, true>), grid, block, 0, stream, a);
+        else
+            hipLaunchKernelGGL(moved ? (variance ? k_temporal<true, true, false, true> : k_temporal<true, false, false, true>)
+                                     : (variance ? k_temporal<false, true, false, true> : k_temporal<false, false, false, true>), grid, block, 0, stream, a);
+        return;
+    }
     if (response)
         hipLaunchKernelGGL(moved ? (variance ? k_temporal<true, true, true> : k_temporal<true, false, true>)
                                  : (variance ? k_temporal<false, true, true> : k_temporal<false, false, true>), grid, block, 0, stream, a);
     else
         hipLaunchKernelGGL(moved ? (variance ? k_temporal<true, true> : k_temporal<true>) : (variance ? k_temporal<false, true> : k_temporal<false>), grid, block, 0, stream, a);
+}
+
+// The firefly clamp's one launch (pt_firefly.h): the plane and the counters of the current accumulator and albedo sums, on the render stream.  The
+// caller has checked that colour and guide samples exist and that no tiles are set.
+int evaluateFirefly(pt_ctx* c)
+{
+    const uint32_t W = c->cfg.width, H = c->cfg.height;
+    const size_t n = (size_t)W * H;
+    if (c->fireflyPlane.n != n) {
+        HIPCHK(c, c->fireflyPlane.alloc(n));
+        HIPCHK(c, c->fireflyCounts.alloc(2));
+    }
+    HIPCHK(c, hipMemsetAsync(c->fireflyCounts.p, 0, 2 * sizeof(uint32_t), c->stream));
+    FireflyArgs f {};
+    f.accum = c->accum, f.albedoHits = c->guides[0], f.plane = c->fireflyPlane.p, f.counts = c->fireflyCounts.p;
+    f.width = W, f.height = H, f.spp = (float)c->spp, f.gspp = (float)c->guideSpp;
+    f.rank = c->fireflyRank, f.scale = c->fireflyScale;
+    hipLaunchKernelGGL(k_firefly, dim3((W + kAtrousTileW - 1) / kAtrousTileW, (H + kAtrousTileH - 1) / kAtrousTileH), dim3(kAtrousTileW, kAtrousTileH), 0, c->stream, f);
+    HIPCHK(c, hipGetLastError());
+    c->fireflyEvaluated = true;
+    return PT_OK;
 }
 
 } // namespace
@@ -1484,7 +1515,11 @@ int pt_denoise_device(pt_ctx* c, const pt_denoise_params* prm, void* device_rgba
         HIPCHK(c, c->denoiseColour[1].alloc(n));
         HIPCHK(c, c->denoiseGuide.alloc(n));
     }
-    launchPrepare(c, prm->input, temporal ? history[0] : c->accum, guided ? c->temporalVariance[c->temporalNewest].p : nullptr, n);
+    const bool clamped = c->fireflySet && !temporal; // d_0 is the clamped plane, made afresh (the history was fed clamped frames already)
+    if (clamped)
+        if (const int rc = evaluateFirefly(c))
+            return rc;
+    launchPrepare(c, prm->input, clamped, temporal ? history[0] : (clamped ? c->fireflyPlane.p : c->accum), guided ? c->temporalVariance[c->temporalNewest].p : nullptr, n);
     AtrousArgs a {};
     a.guide = c->denoiseGuide.p;
     a.albedoHits = c->guides[0];
@@ -1625,6 +1660,11 @@ int pt_temporal_accumulate(pt_ctx* c, const pt_temporal_params* prm)
         a.motion = c->motionGuides[0], a.prevNormal = c->motionGuides[1];
     a.histVariance = c->temporalVariance[from].p, a.outVariance = c->temporalVariance[to].p; // (varianceSet: the same arithmetic and one more plane)
     a.histFast = c->temporalFast[from].p, a.outFast = c->temporalFast[to].p, a.outLuminance = c->responseLuminance.p, a.fastHistory = c->fastHistory; // (responseSet)
+    if (c->fireflySet) { // the current frame's d comes clamped, from a plane made afresh
+        if ((rc = evaluateFirefly(c)))
+            return rc;
+        a.firefly = c->fireflyPlane.p;
+    }
     launchTemporal(c->stream, grid, block, moved, c->varianceSet, c->responseSet, a);
     HIPCHK(c, hipGetLastError());
     if (c->responseSet) {
@@ -1846,6 +1886,75 @@ int pt_read_temporal_response(pt_ctx* c, float* s_out)
 }
 
 void* pt_temporal_fast_device_ptr(pt_ctx* c) { return c && c->responseSet ? (void*)c->temporalFast[c->temporalNewest].p : nullptr; }
+
+// ---- firefly clamp (k_firefly, k_temporal<., ., ., true>, k_denoise_prepare<., true>) ------------
+
+int pt_set_firefly_clamp(pt_ctx* c, const pt_firefly_params* prm)
+{
+    if (!c)
+        return PT_ERR_INVALID;
+    if (const int rc = fixedScheduleOnly(c, "pt_set_firefly_clamp"))
+        return rc;
+    if (prm) {
+        if (prm->rank > PT_FIREFLY_MAX_RANK)
+            return fail(c, PT_ERR_INVALID, "pt_set_firefly_clamp: rank = %u (1..%u; 0 = %u)", prm->rank, PT_FIREFLY_MAX_RANK, PT_FIREFLY_DEFAULT_RANK);
+        if (!std::isfinite(prm->scale) || prm->scale < 0.0f || (prm->scale > 0.0f && prm->scale < 1.0f))
+            return fail(c, PT_ERR_INVALID, "pt_set_firefly_clamp: scale = %g (at least 1; 0 = %g)", (double)prm->scale, (double)PT_FIREFLY_DEFAULT_SCALE);
+    }
+    c->fireflySet = prm != nullptr;
+    if (prm) {
+        c->fireflyRank = prm->rank ? prm->rank : PT_FIREFLY_DEFAULT_RANK;
+        c->fireflyScale = prm->scale > 0.f ? prm->scale : PT_FIREFLY_DEFAULT_SCALE;
+    }
+    return PT_OK;
+}
+
+int pt_firefly_clamp(const pt_ctx* c) { return c && c->fireflySet ? 1 : 0; }
+
+namespace {
+
+// the plane and / or the counters of the last evaluation to the host, behind a synchronisation
+int readFirefly(pt_ctx* c, float* d_s, uint32_t counts[2])
+{
+    if (d_s)
+        HIPCHK(c, hipMemcpyAsync(d_s, c->fireflyPlane.p, c->fireflyPlane.n * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
+    if (counts)
+        HIPCHK(c, hipMemcpyAsync(counts, c->fireflyCounts.p, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return PT_OK;
+}
+
+} // namespace
+
+int pt_read_firefly(pt_ctx* c, float* d_s, uint32_t counts[2])
+{
+    if (!c)
+        return PT_ERR_INVALID;
+    if (!c->fireflySet)
+        return fail(c, PT_ERR_STATE, "pt_read_firefly: the firefly clamp is off (pt_set_firefly_clamp)");
+    if (tilesSet(c))
+        return fail(c, PT_ERR_UNSUPPORTED, "pt_read_firefly: tiles are set -- the clamp needs every pixel's neighbours; evaluate after the reduce, on a context that owns the frame");
+    if (c->spp == 0)
+        return fail(c, PT_ERR_STATE, "pt_read_firefly: no colour samples yet (pt_render)");
+    if (c->guideSpp == 0)
+        return fail(c, PT_ERR_STATE, "pt_read_firefly: no guide samples yet (pt_render_guides)");
+    HIPCHK(c, hipSetDevice(c->device));
+    if (const int rc = evaluateFirefly(c))
+        return rc;
+    return readFirefly(c, d_s, counts);
+}
+
+int pt_firefly_counts(pt_ctx* c, uint32_t counts[2])
+{
+    if (!c || !counts)
+        return PT_ERR_INVALID;
+    if (!c->fireflyEvaluated)
+        return fail(c, PT_ERR_STATE, "pt_firefly_counts: the stage has not been evaluated yet (pt_temporal_accumulate, pt_denoise, pt_read_firefly with the mode on)");
+    HIPCHK(c, hipSetDevice(c->device));
+    return readFirefly(c, nullptr, counts);
+}
+
+void* pt_firefly_device_ptr(pt_ctx* c) { return c && c->fireflySet && c->fireflyEvaluated ? (void*)c->fireflyPlane.p : nullptr; }
 
 // ---- instance motion (k_guides<1>, k_temporal<true>) --------------------------------------------
 

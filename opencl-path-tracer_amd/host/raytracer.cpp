@@ -290,6 +290,12 @@ void RayTracer::setTemporalResponse(bool on)
     check(pt_set_temporal_response(m_ctx, on ? &defaults : nullptr), "pt_set_temporal_response");
 }
 
+void RayTracer::setFireflyClamp(bool on)
+{
+    const pt_firefly_params defaults {};
+    check(pt_set_firefly_clamp(m_ctx, on ? &defaults : nullptr), "pt_set_firefly_clamp");
+}
+
 void RayTracer::setGuideChain(unsigned maxTransmissions)
 {
     check(pt_clear(m_ctx), "pt_clear"); // (the chain changes, and a motion is forgotten, only while no guide samples are in the sums)

@@ -121,6 +121,11 @@ public:
     // has no motion vector, and its old shadows would fade over max_history frames.  Resets the history like setTemporalVariance, of which it is
     // independent.  Off by default.
     void setTemporalResponse(bool on);
+    // Every frame's demodulated colour bounded by its 5 x 5 neighbourhood before the history and the filter see it (include/ptamd.h, "firefly clamp"):
+    // one outlier of a 1-spp frame no longer enters the history at full weight, and a non-finite pixel no longer stays in it.  Acts on getTemporalOutput
+    // and getDenoisedOutput (iterations > 0); getOutput and the accumulator are what they were.  Trades energy for variance: single-pixel highlights
+    // and caustics lose light.  May change at any time, the history is kept.  Off by default.
+    void setFireflyClamp(bool on);
     // Guide rays follow up to `maxTransmissions` refractions (0..PT_GUIDE_CHAIN_MAX; 0, the default: off) to the first surface that is not glass
     // (include/ptamd.h, "guide chain"): the filter and the history then see the edges and albedos behind a pane or inside a glass body.  Restarts the
     // accumulation (pt_clear: guide sums of two definitions must not mix).  While it is on no instance or vertex motion is handed to the device library

@@ -96,6 +96,13 @@ class ResponseParams(C.Structure):
     _fields_ = [("fast_history", C.c_uint32), ("sigma_response", C.c_float), ("relative_floor", C.c_float), ("_reserved", C.c_uint32 * 5)]
 
 
+class FireflyParams(C.Structure):
+    """pt_firefly_params (32 bytes); a parameter of 0 selects the default documented in include/ptamd.h"""
+    _fields_ = [("rank", C.c_uint32), ("scale", C.c_float), ("_reserved", C.c_uint32 * 6)]
+
+
+FIREFLY_RADIUS, FIREFLY_MAX_RANK = 2, 4  # PT_FIREFLY_RADIUS, PT_FIREFLY_MAX_RANK
+
 EXPORTS = ["pt_create", "pt_destroy", "pt_last_error", "pt_set_stream", "pt_upload_static", "pt_upload_static_async", "pt_upload_dynamic",
            "pt_upload_dynamic_async", "pt_frame_tick", "pt_update_geometry", "pt_refit_vertices",
            "pt_upload_texture_array", "pt_set_camera", "pt_set_tiles", "pt_set_accum_buffer", "pt_clear", "pt_render",
@@ -110,7 +117,8 @@ EXPORTS = ["pt_create", "pt_destroy", "pt_last_error", "pt_set_stream", "pt_uplo
            "pt_set_rebuilt_motion", "pt_rebuilt_motion", "pt_debug_gather_records", "pt_set_temporal_variance", "pt_temporal_variance",
            "pt_read_temporal_variance", "pt_write_temporal_variance", "pt_temporal_variance_device_ptr",
            "pt_set_temporal_response", "pt_temporal_response", "pt_read_temporal_fast", "pt_write_temporal_fast", "pt_read_temporal_response",
-           "pt_temporal_fast_device_ptr", "pt_stats_get", "pt_stats_reset", "pt_profile_kernels", "pt_reduce_accum",
+           "pt_temporal_fast_device_ptr", "pt_set_firefly_clamp", "pt_firefly_clamp", "pt_read_firefly", "pt_firefly_counts", "pt_firefly_device_ptr",
+           "pt_stats_get", "pt_stats_reset", "pt_profile_kernels", "pt_reduce_accum",
            "pt_intersect", "pt_gen_rays", "pt_primary_pass", "pt_shade_batch", "pt_debug_quantise_node", "pt_debug_convert", "pt_debug_copy_bandwidth", "pt_debug_math_probe", "pt_debug_rng_probe", "pt_debug_live_resources",
            "pt_version"]
 
@@ -215,6 +223,12 @@ def lib():
         l.pt_read_temporal_response.argtypes = [C.c_void_p, C.c_void_p]
         l.pt_temporal_fast_device_ptr.restype = C.c_void_p
         l.pt_temporal_fast_device_ptr.argtypes = [C.c_void_p]
+        l.pt_set_firefly_clamp.argtypes = [C.c_void_p, C.POINTER(FireflyParams)]
+        l.pt_firefly_clamp.argtypes = [C.c_void_p]
+        l.pt_read_firefly.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32)]
+        l.pt_firefly_counts.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
+        l.pt_firefly_device_ptr.restype = C.c_void_p
+        l.pt_firefly_device_ptr.argtypes = [C.c_void_p]
         l.pt_stats_get.argtypes = [C.c_void_p, C.POINTER(Stats)]
         l.pt_stats_reset.argtypes = [C.c_void_p]
         l.pt_profile_kernels.argtypes = [C.c_void_p, C.c_int]
@@ -620,6 +634,36 @@ class Context:
     def temporal_fast_device_ptr(self):
         """Device address of the newest set's fast image (0 while the mode is off or nothing is allocated yet)."""
         return lib().pt_temporal_fast_device_ptr(self._h) or 0
+
+    # ---- firefly clamp
+    def set_firefly_clamp(self, enable=True, rank=0, scale=0.0):
+        """Bound every pixel's demodulated colour by `scale` x the `rank`-th largest luminance of its 5 x 5 neighbours before temporal_accumulate and
+        denoise (accumulator input, iterations > 0) see it; the accumulator, render and resolve are untouched.  False turns it off.  At any time."""
+        prm = FireflyParams(rank, scale)
+        self._chk(lib().pt_set_firefly_clamp(self._h, C.byref(prm) if enable else None), "pt_set_firefly_clamp")
+
+    @property
+    def firefly_clamp(self):
+        return bool(lib().pt_firefly_clamp(self._h))
+
+    def read_firefly(self):
+        """Evaluates the stage on the current accumulator and guides: ((width*height, 4) float32 plane (d_out.rgb, s), (clamped, nonfinite))"""
+        out = np.zeros((self.height * self.width, 4), np.float32)
+        counts = (C.c_uint32 * 2)()
+        self._chk(lib().pt_read_firefly(self._h, _p(out), counts), "pt_read_firefly")
+        return out, (int(counts[0]), int(counts[1]))
+
+    @property
+    def firefly_counts(self):
+        """(clamped, nonfinite) of the last evaluation, whichever call made it"""
+        counts = (C.c_uint32 * 2)()
+        self._chk(lib().pt_firefly_counts(self._h, counts), "pt_firefly_counts")
+        return int(counts[0]), int(counts[1])
+
+    @property
+    def firefly_device_ptr(self):
+        """Device address of the clamped plane (0 while the mode is off or before the first evaluation)."""
+        return lib().pt_firefly_device_ptr(self._h) or 0
 
     # ---- instance motion
     def set_instance_motion(self, prev):

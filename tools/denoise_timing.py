@@ -1,13 +1,15 @@
 #!/usr/bin/env python3
 """Device time of the guide pass and of the a-trous denoiser at 1280 x 720 and 1920 x 1080, one JSON line (EXPERIMENTS.md).
-Not part of bench.py.     usage: python tools/denoise_timing.py [--calls 25] [--scene cornell|blob] [--variance]
+Not part of bench.py.     usage: python tools/denoise_timing.py [--calls 25] [--scene cornell|blob] [--variance] [--firefly]
 
 denoise_ms[N]: median `ms_out` of pt_denoise with N iterations (hipEvents around the filter's kernels); their differences say what each
 iteration costs.  guides_ms: median device ms of pt_render_guides(1), between two events on the stream the context renders on.  frame_ms: the
 same for pt_render(1), the frame the two serve.  bytes: what the filter must move (prepare: 3 reads + 2 writes, every iteration 2 reads + 1
 write of a float4 image); fraction_of_copy: that traffic per second against pt_debug_copy_bandwidth.
 --variance: the same six medians for PT_DENOISE_INPUT_TEMPORAL (k_atrous over the history) and PT_DENOISE_INPUT_TEMPORAL_VARIANCE (k_atrous<., true>) in the
-same process, and per iteration -- the difference of two consecutive medians -- the ratio of the second to the first."""
+same process, and per iteration -- the difference of two consecutive medians -- the ratio of the second to the first.
+--firefly: median / min / max of pt_denoise with 1 and 5 iterations over the accumulator with pt_set_firefly_clamp off and on in the same process (on: a
+memset and k_firefly before a prepare that reads the plane): the spread of the mode-off figures is the margin the two are told apart by."""
 import argparse
 import json
 import os
@@ -24,6 +26,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--scene", default="cornell")
     ap.add_argument("--variance", action="store_true", help="also time the variance-guided filter against the plain one over the same history")
+    ap.add_argument("--firefly", action="store_true", help="also time the filter over the accumulator with the firefly clamp on, next to the mode off, with min / max")
     args = ap.parse_args()
     import torch
     from ptamd import device as D, scenes
@@ -62,6 +65,21 @@ def main():
             "frame_ms": round(frame, 4), "guides_ms": round(guides, 4), "denoise_ms": {str(k): round(v, 4) for k, v in den.items()},
             "bytes_5_iterations": moved, "gbps_5_iterations": round(moved / den[5] / 1e6, 1), "copy_gbps": round(copy, 1),
             "fraction_of_copy": round(moved / den[5] / 1e6 / copy, 3)}
+        if args.firefly:
+            per = {}
+            have = hasattr(ctx, "set_firefly_clamp")  # (a build from before the mode: the mode-off figures and their spread alone)
+            for name, clamp in (("off", False), ("on", True), ("off_again", False)) if have else (("off", False),):
+                if have:
+                    ctx.set_firefly_clamp(clamp)
+                per[name] = {}
+                for n in (1, 5):
+                    ms = [ctx.denoise(n, with_ms=True)[1] for _ in range(args.warmup + args.calls)][args.warmup:]
+                    per[name][str(n)] = {"median": round(statistics.median(ms), 4), "min": round(min(ms), 4), "max": round(max(ms), 4)}
+                if clamp:
+                    per["counts"] = list(ctx.firefly_counts)
+            if have:
+                per["on_minus_off_ms"] = {n: round(per["on"][n]["median"] - per["off"][n]["median"], 4) for n in ("1", "5")}
+            out["sizes"][f"{width}x{height}"]["firefly"] = per
         if args.variance:
             ctx.clear()
             ctx.render(1)

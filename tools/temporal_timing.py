@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Device time of pt_temporal_accumulate at 1280 x 720 and 1920 x 1080, one JSON line (EXPERIMENTS.md).
-Not part of bench.py.     usage: python tools/temporal_timing.py [--calls 25] [--batch 20] [--scene cornell|blob] [--motion] [--variance] [--response]
+Not part of bench.py.     usage: python tools/temporal_timing.py [--calls 25] [--batch 20] [--scene cornell|blob] [--motion] [--variance] [--response] [--firefly]
 
 temporal_ms.static / .panned: median device ms of ONE pt_temporal_accumulate, measured between two events on the stream the context renders on
 around `batch` calls in a row (one call is tens of microseconds: a pair of events around a single launch would time the events).  static: the camera
@@ -9,7 +9,10 @@ degrees apart about the room's centre, so every call reprojects.  frame_ms: the 
 floor_bytes: what a call must move -- three 16-byte reads of the current frame, two 16-byte writes and the history's two images read once (neighbours
 share their taps): 7 x 16 = 112 bytes per pixel; fraction_of_copy: that traffic per second against pt_debug_copy_bandwidth.
 --response: the same two figures with pt_set_temporal_response on -- one call is then k_temporal<., ., true> and k_temporal_response behind it, and the
-floor 152 + 44 bytes per pixel (the two kernels' shares come from a kernel trace of this script)."""
+floor 152 + 44 bytes per pixel (the two kernels' shares come from a kernel trace of this script).
+--firefly: the same two figures with pt_set_firefly_clamp on -- one call is then a 8-byte memset, k_firefly (32 bytes read, 16 written per pixel) and
+k_temporal<., ., ., true> (one 16-byte read of the current frame in place of two: 96 bytes) --, each as median / min / max over the calls next to the
+plain kernel's own median / min / max in the same process: the spread of the plain figures is the margin the two are told apart by."""
 import argparse
 import json
 import math
@@ -26,6 +29,7 @@ MOTION_FLOOR_BYTES_PER_PIXEL = 9 * 16  # --motion: the two motion sums are read 
 # k_temporal_response reads the luminance pairs, colour_count and the fast image and writes s (8 + 16 + 16 + 4 = 44 bytes; 16 more where it stores)
 RESPONSE_EXTRA_BYTES_PER_PIXEL, RESPONSE_MIX_BYTES_PER_PIXEL = 40, 44
 VARIANCE_EXTRA_BYTES_PER_PIXEL = 8  # --variance: the history's variance plane read once, the new one written (4 bytes each): 120 and 152
+FIREFLY_BYTES_PER_PIXEL = 48 + 6 * 16  # --firefly: k_firefly's 32 + 16, and a k_temporal that reads the plane in place of the accumulator and the albedo sums
 
 
 def main():
@@ -37,6 +41,7 @@ def main():
     ap.add_argument("--motion", action="store_true", help="also time k_temporal<true> (instance motion set), next to the plain kernel")
     ap.add_argument("--variance", action="store_true", help="also time k_temporal<., true> (pt_set_temporal_variance), next to the plain kernel")
     ap.add_argument("--response", action="store_true", help="also time k_temporal<., ., true> + k_temporal_response (pt_set_temporal_response), next to the plain kernel")
+    ap.add_argument("--firefly", action="store_true", help="also time k_firefly + k_temporal<., ., ., true> (pt_set_firefly_clamp), next to the plain kernel, with min / max")
     args = ap.parse_args()
     import torch
     from ptamd import device as D, scenes
@@ -52,7 +57,7 @@ def main():
         t = math.radians(1.5)
         turned = scenes._camera(width, height, (-3.9 * math.sin(t), 1.0, -3.9 * math.cos(t)), (0.0, 1.0, 0.0), 40.0)
 
-        def timed(fn, per=1):
+        def timed(fn, per=1, spread=False):
             ms = []
             for k in range(args.warmup + args.calls):
                 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -63,6 +68,8 @@ def main():
                 ctx.synchronize()
                 if k >= args.warmup:
                     ms.append(e0.elapsed_time(e1) / per)
+            if spread:
+                return {"median": round(statistics.median(ms), 5), "min": round(min(ms), 5), "max": round(max(ms), 5)}
             return statistics.median(ms)
 
         frame = timed(lambda i: ctx.render(1, sync=False))
@@ -120,6 +127,27 @@ def main():
             ctx.temporal_reset()
             ctx.set_temporal_response(False)
             ctx.temporal_accumulate()
+        if args.firefly:
+            # the memset, k_firefly and k_temporal<false, false, false, true> in the same process and the same batches as the plain kernel, which is timed
+            # again right before: median / min / max of both
+            ctx.set_camera(b.camera)
+            ctx.temporal_reset()
+            ctx.temporal_accumulate()
+            off = {"static": timed(lambda i: ctx.temporal_accumulate(sync=False), args.batch, spread=True), "panned": timed(panned_call, args.batch, spread=True)}
+            if not hasattr(ctx, "set_firefly_clamp"):  # a build from before the mode: the plain figures and their spread, to hold the mode off against
+                out["sizes"][f"{width}x{height}"]["firefly"] = {"plain_ms": off}
+                ctx.close()
+                continue
+            ctx.set_firefly_clamp()
+            ctx.temporal_accumulate()
+            on = {"static": timed(lambda i: ctx.temporal_accumulate(sync=False), args.batch, spread=True), "panned": timed(panned_call, args.batch, spread=True)}
+            f_floor = FIREFLY_BYTES_PER_PIXEL * width * height
+            out["sizes"][f"{width}x{height}"]["firefly"] = {
+                "plain_ms": off, "temporal_ms": on, "floor_bytes": f_floor, "counts": list(ctx.firefly_counts),
+                "ratio_to_plain": {k: round(on[k]["median"] / off[k]["median"], 3) for k in on},
+                "fraction_of_copy": {k: round(f_floor / on[k]["median"] / 1e6 / copy, 3) for k in on}}
+            ctx.set_firefly_clamp(False)
+            ctx.set_camera(b.camera)
         if args.motion:
             # k_temporal<true> in the same process, against the same copy rate: every instance was a millimetre to the side, so every pixel of it carries
             # a displacement; two more 16-byte reads per pixel, 9 x 16 = 144 bytes
