@@ -758,6 +758,74 @@ int pt_read_firefly(pt_ctx* ctx, float* d_s, uint32_t counts[2]); /* evaluates t
 int pt_firefly_counts(pt_ctx* ctx, uint32_t counts[2]); /* of the LAST evaluation, whichever entry point made it; synchronises */
 void* pt_firefly_device_ptr(pt_ctx* ctx); /* the plane; NULL while the mode is off and before the first evaluation */
 
+/* ADAPTIVE SAMPLING: a converging render that stops where it has converged.  pt_render gives every owned pixel the same number of samples;
+ * pt_render_adaptive renders in rounds, judges every 8 x 8 block of the image by the difference between two independent halves of its samples, and
+ * gives the next round's samples only to the blocks that are still noisy.  Opt-in: with the mode never set, every entry point launches exactly the
+ * kernels it launches without this block and returns the same bits.  No render kernel knows of the mode: a round is two plain pt_render runs over a
+ * pixel list.  Whole-frame contexts on the fixed schedule only.
+ *
+ * State, allocated at the first pt_render_adaptive / pt_write_adaptive and freed when the mode is turned off and by pt_destroy: two half accumulators
+ * A and B (width*height float4 sums, like the accumulator), counts (uint32 per pixel), error (float per pixel), and one float E_b and one active flag
+ * per block, for ceil(width / 8) x ceil(height / 8) blocks in row-major order.  Block b = (x / 8, y / 8); blocks on the right and bottom edges hold
+ * n_b < 64 pixels.  Counts are constant over a block.
+ *
+ * One round, with S = pt_samples_per_pixel before it (the most-sampled pixel always holds S):
+ *   size      2h = min(S == 0 ? min_samples : round_samples, max_samples - S); all three are even, so the halves hold equally many samples
+ *   active    block b is active iff count_b < min_samples || (count_b < max_samples && !(E_b < threshold)): a pure function of the state and the
+ *             parameters, with no memory of earlier decisions; the compare is strict, so threshold == 0 never stops a block by its error
+ *   render    the pixels of the active blocks, as pt_set_tiles orders the 8 x 8 rects of those blocks given in block-row-major order: h samples
+ *             with indices base + S .. base + S + h - 1 into A, then h with indices base + S + h .. base + S + 2h - 1 into B (base:
+ *             pt_set_sample_base) -- each a complete pt_render, bit for bit what a context with those tiles renders; pt_stats counts the rays
+ *   evaluate  pixels of active blocks: counts += 2h.  Per pixel with n = counts > 0, in float32 and in this order:
+ *               hn = n / 2;  mA = A.rgb / hn;  mB = B.rgb / hn;  m = (A.rgb + B.rgb) / n
+ *               e = (|mA.r - mB.r| + |mA.g - mB.g| + |mA.b - mB.b|) / (2 sqrt(max(m.r + m.g + m.b, 0) + 1e-3))
+ *             n == 0: e = 0.  e not finite: e = 0, and the pixel is counted in `nonfinite` -- more samples never cure it, and it does not keep its
+ *             block alive.  E_b = (sum of e over the block's pixels) / n_b.
+ *   publish   every pixel of the frame: accum.rgb = (A.rgb + B.rgb) * ((float)S' / (float)n) with S' = S + 2h, accum.w = 0; the scale is exactly 1
+ *             where n == S' (the bits of A + B); 0 where n == 0
+ * So with the mode on the accumulator holds EACH PIXEL'S MEAN RADIANCE TIMES pt_samples_per_pixel: pt_resolve, pt_read_accum, pt_denoise,
+ * pt_temporal_accumulate, the firefly clamp and pt_reduce_accum divide by the global count as ever and need not know.  A round ends synchronised:
+ * the flags and counters are read back, the next round's pixel list is made from them.  When pt_render_adaptive returns the context owns the whole
+ * frame again, whatever the last round rendered.
+ *
+ * Known bias: a block is stopped on an estimate made from the very samples it is about to keep, which favours blocks that looked converged by luck
+ * -- their error is under-estimated and so is, slightly, the energy of rare bright paths in them.  min_samples is the guard: nothing is judged before
+ * every pixel holds that many.  There is no default threshold (0 = uniform sampling to max_samples); DESIGN.md section 10 and EXPERIMENTS.md have
+ * the measured threshold / samples / error table.  Halves of 256 samples or a multiple (min_samples, round_samples = 512, 1024 ...) keep the bundle
+ * kernels at full rate at 1080p.
+ *
+ * pt_set_adaptive on a context whose mode is on changes the parameters, keeps the state and, if S > 0, re-evaluates the flags.  Turning the mode on
+ * or off while pt_samples_per_pixel != 0 is PT_ERR_STATE: pt_clear first.  pt_clear zeroes A, B, counts, errors and the round count and keeps the
+ * mode.  Refusals: pt_set_adaptive -- PT_ERR_UNSUPPORTED in parity / refill mode and while tiles are set, PT_ERR_INVALID for an odd, out-of-range,
+ * negative or non-finite parameter; pt_set_tiles (n > 0) with the mode on -- PT_ERR_UNSUPPORTED; pt_render and pt_write_accum with the mode on --
+ * PT_ERR_STATE; pt_render_adaptive, pt_adaptive_stats_get, pt_read_adaptive, pt_write_adaptive with the mode off -- PT_ERR_STATE; pt_write_adaptive
+ * with counts that are not constant over a block, odd, or above max_samples -- PT_ERR_INVALID.  A refused call changes nothing. */
+typedef struct {
+    float threshold; /* a block stops when E_b < threshold; 0 = never by error (uniform sampling to max_samples) */
+    uint32_t min_samples; /* 0 = 64; even, >= 2: every pixel gets these before anything is judged */
+    uint32_t round_samples; /* 0 = 64; even, >= 2 */
+    uint32_t max_samples; /* 0 = 1024; even, >= min_samples, <= 1 << 20 */
+    uint32_t _reserved[4];
+} pt_adaptive_params; /* 32 bytes */
+typedef struct {
+    uint32_t rounds, blocks, active_blocks, nonfinite; /* rounds since pt_clear; of the last evaluation: blocks whose flag is set, pixels whose e was not finite */
+    uint32_t min_count, max_count; /* over the blocks; max_count == pt_samples_per_pixel */
+    uint64_t samples_total; /* sum of counts */
+    float max_block_error;
+    uint32_t _reserved[5];
+} pt_adaptive_stats; /* 56 bytes */
+int pt_set_adaptive(pt_ctx* ctx, const pt_adaptive_params* params); /* NULL: off */
+int pt_adaptive(const pt_ctx* ctx); /* 1 / 0 */
+int pt_adaptive_params_get(const pt_ctx* ctx, pt_adaptive_params* out); /* the parameters in force, defaults resolved; PT_ERR_STATE with the mode off */
+int pt_render_adaptive(pt_ctx* ctx, uint32_t rounds); /* up to `rounds` rounds, 0 = until no block is active or S == max_samples; synchronous at round ends */
+int pt_adaptive_stats_get(pt_ctx* ctx, pt_adaptive_stats* out);
+int pt_read_adaptive(pt_ctx* ctx, float* A, float* B, uint32_t* counts, float* error, float* block_error); /* host; width*height*4, *4, *1, *1 and `blocks` entries; any may be NULL */
+int pt_write_adaptive(pt_ctx* ctx, const float* A, const float* B, const uint32_t* counts); /* checkpoint restore and tests: evaluates and publishes, S = max count */
+void* pt_adaptive_device_ptr(pt_ctx* ctx, int which); /* 0 A, 1 B, 2 counts, 3 error; NULL before allocation */
+/* Diagnostic (tools/adaptive_timing.py), sums since pt_create: out[0] device ms in the evaluate / publish launches, out[1] how many evaluations,
+ * out[2] host ms spent changing the pixel list inside pt_render_adaptive (the list, its upload, the queues re-made), out[3] how many changes. */
+int pt_debug_adaptive_timing(pt_ctx* ctx, double out[4]);
+
 /* ---- kernel-granular entry points (parity tests and micro-benchmarks) ------------------
  * Host SoA arrays in, host SoA arrays out; the scene must have been uploaded. */
 typedef struct {

@@ -408,6 +408,20 @@ struct pt_ctx {
     uint32_t fireflyRank = 0;
     float fireflyScale = 0; // pt_firefly_params, defaults resolved
 
+    // adaptive sampling (include/ptamd.h; pt_adaptive.h): the two half accumulators, the per-pixel counts and errors, one error and one flag per 8 x 8
+    // block, the counters of an evaluation and the pinned area the flags and counters are read back into (flags first) -- allocated at the first
+    // pt_render_adaptive / pt_write_adaptive, freed when the mode is turned off and by pt_destroy.  The mode changes only while there are no samples.
+    DevBuf<float4> adaptiveHalf[2];
+    DevBuf<uint32_t> adaptiveCounts, adaptiveFlags;
+    DevBuf<float> adaptiveError, adaptiveBlockError;
+    DevBuf<ptd::AdaptiveCounters> adaptiveCounters;
+    Pinned<uint32_t> adaptiveBack; // `blocks` flags, then one AdaptiveCounters
+    bool adaptiveSet = false;
+    pt_adaptive_params adaptivePrm {}; // defaults resolved
+    pt_adaptive_stats adaptiveStats {}; // of the last evaluation
+    Event adaptiveEvents[2]; // around an evaluation's launches
+    double adaptiveTiming[4] = {}; // pt_debug_adaptive_timing: device ms in evaluations, their number, host ms changing the pixel list, list changes
+
     // instance motion (include/ptamd.h): one record per instance of the ACTIVE dynamic state (indexed like its instance table, which is how the guide
     // pass meets a hit), and the two guide sums made from them -- (displacement.xyz, 0) and (normal then.xyz, 0), width * height float4 each, allocated at
     // the first pt_set_instance_motion / pt_write_motion_guides.  pt_frame_tick forgets the motion; pt_clear zeroes the sums and keeps it.

@@ -10,6 +10,7 @@
 #include "pt_team.h"
 #include "pt_denoise.h"
 #include "pt_temporal.h"
+#include "pt_adaptive.h"
 #ifndef PT_PACK_WIDE
 #define PT_PACK_WIDE 1
 #endif
@@ -904,12 +905,14 @@ int pt_set_camera(pt_ctx* c, const pt_camera* cam)
     return PT_OK;
 }
 
-int pt_set_tiles(pt_ctx* c, const pt_rect* rects, uint32_t n)
+} // extern "C"
+
+namespace {
+
+// The owned pixels of a context, from rects: pt_set_tiles' whole body, and how a round of pt_render_adaptive installs the pixels of its active blocks
+// and puts the whole frame back.  n == 0: the whole frame.
+int installPixelRects(pt_ctx* c, const pt_rect* rects, uint32_t n)
 {
-    return guarded(c, "pt_set_tiles", [&]() -> int {
-    if (!c)
-        return PT_ERR_INVALID;
-    HIPCHK(c, hipSetDevice(c->device));
     const uint32_t W = c->cfg.width, H = c->cfg.height;
     pt_rect whole { 0, 0, W, H };
     if (n == 0 || !rects) {
@@ -964,6 +967,111 @@ int pt_set_tiles(pt_ctx* c, const pt_rect* rects, uint32_t n)
     c->hostPixelList = std::move(list);
     c->queuesReady = false; // the ordinal of a pixel may have changed: queues and planes are re-made lazily (ensureQueues)
     return PT_OK;
+}
+
+// ---- adaptive sampling: the state and its one evaluation (pt_adaptive.h); the entry points stand behind the firefly clamp's
+
+inline uint32_t adaptiveBlocksX(const pt_ctx* c) { return (c->cfg.width + 7u) / 8u; }
+inline uint32_t adaptiveBlocks(const pt_ctx* c) { return adaptiveBlocksX(c) * ((c->cfg.height + 7u) / 8u); }
+constexpr size_t kAdaptiveCounterWords = kAdaptiveStripes * sizeof(AdaptiveCounters) / sizeof(uint32_t);
+
+// no samples: halves, counts and errors zero, every block active (a count of 0 is below any min_samples)
+int clearAdaptive(pt_ctx* c)
+{
+    for (DevBuf<float4>& half : c->adaptiveHalf)
+        HIPCHK(c, hipMemsetAsync(half.p, 0, half.n * sizeof(float4), c->stream));
+    HIPCHK(c, hipMemsetAsync(c->adaptiveCounts.p, 0, c->adaptiveCounts.n * sizeof(uint32_t), c->stream));
+    HIPCHK(c, hipMemsetAsync(c->adaptiveError.p, 0, c->adaptiveError.n * sizeof(float), c->stream));
+    HIPCHK(c, hipMemsetAsync(c->adaptiveBlockError.p, 0, c->adaptiveBlockError.n * sizeof(float), c->stream));
+    HIPCHK(c, hipMemsetAsync(c->adaptiveFlags.p, 0x01, c->adaptiveFlags.n * sizeof(uint32_t), c->stream)); // (any non-zero word is a set flag)
+    c->adaptiveStats = pt_adaptive_stats {};
+    c->adaptiveStats.blocks = c->adaptiveStats.active_blocks = adaptiveBlocks(c);
+    return PT_OK;
+}
+
+int ensureAdaptive(pt_ctx* c)
+{
+    if (c->adaptiveCounts.p)
+        return PT_OK;
+    const size_t n = (size_t)c->cfg.width * c->cfg.height, nB = adaptiveBlocks(c);
+    HIPCHK(c, c->adaptiveHalf[0].alloc(n));
+    HIPCHK(c, c->adaptiveHalf[1].alloc(n));
+    HIPCHK(c, c->adaptiveError.alloc(n));
+    HIPCHK(c, c->adaptiveBlockError.alloc(nB));
+    HIPCHK(c, c->adaptiveFlags.alloc(nB));
+    HIPCHK(c, c->adaptiveCounters.alloc(kAdaptiveStripes));
+    HIPCHK(c, c->adaptiveBack.alloc(nB + kAdaptiveCounterWords));
+    HIPCHK(c, c->adaptiveEvents[0].create(true));
+    HIPCHK(c, c->adaptiveEvents[1].create(true));
+    HIPCHK(c, c->adaptiveCounts.alloc(n)); // (last: its pointer says that the state is complete)
+    return clearAdaptive(c);
+}
+
+void releaseAdaptive(pt_ctx* c)
+{
+    c->adaptiveHalf[0].release(), c->adaptiveHalf[1].release(), c->adaptiveCounts.release(), c->adaptiveError.release();
+    c->adaptiveBlockError.release(), c->adaptiveFlags.release(), c->adaptiveCounters.release(), c->adaptiveBack.release();
+}
+
+// Steps 4 to 6 of a round: the blocks flagged on the device got `add` samples per pixel (0: judge the state as it stands); count, judge, publish the
+// accumulator for `spp` = the largest count, read the flags and counters back behind a synchronisation.  Fused: one launch does all of it
+// (EXPERIMENTS.md, "Adaptive sampling" has the two-launch form timed against it; PTAMD_ADAPTIVE_SPLIT selects that one, diagnostics).
+int evaluateAdaptive(pt_ctx* c, uint32_t add, uint32_t spp)
+{
+    static const bool split = getenv("PTAMD_ADAPTIVE_SPLIT") != nullptr;
+    const uint32_t W = c->cfg.width, H = c->cfg.height, nB = adaptiveBlocks(c);
+    HIPCHK(c, hipMemsetAsync(c->adaptiveCounters.p, 0, kAdaptiveStripes * sizeof(AdaptiveCounters), c->stream));
+    AdaptiveArgs a {};
+    a.A = c->adaptiveHalf[0].p, a.B = c->adaptiveHalf[1].p, a.counts = c->adaptiveCounts.p, a.error = c->adaptiveError.p;
+    a.blockError = c->adaptiveBlockError.p, a.flags = c->adaptiveFlags.p, a.counters = c->adaptiveCounters.p, a.accum = c->accum;
+    a.width = W, a.height = H, a.blocksX = adaptiveBlocksX(c), a.blocks = nB;
+    a.add = add, a.spp = spp;
+    a.minSamples = c->adaptivePrm.min_samples, a.maxSamples = c->adaptivePrm.max_samples, a.threshold = c->adaptivePrm.threshold;
+    HIPCHK(c, hipEventRecord(c->adaptiveEvents[0], c->stream));
+    if (split) {
+        hipLaunchKernelGGL(k_adaptive_eval<false>, dim3((nB + 3u) / 4u), dim3(256), 0, c->stream, a);
+        hipLaunchKernelGGL(k_adaptive_publish, dim3((W * H + 255u) / 256u), dim3(256), 0, c->stream, a.A, a.B, (const uint32_t*)a.counts, a.accum, W * H, spp);
+    } else {
+        hipLaunchKernelGGL(k_adaptive_eval<true>, dim3((nB + 3u) / 4u), dim3(256), 0, c->stream, a);
+    }
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipEventRecord(c->adaptiveEvents[1], c->stream));
+    c->spp = spp;
+    HIPCHK(c, hipMemcpyAsync(c->adaptiveBack.p, c->adaptiveFlags.p, nB * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->adaptiveBack.p + nB, c->adaptiveCounters.p, kAdaptiveStripes * sizeof(AdaptiveCounters), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    AdaptiveCounters k {};
+    for (uint32_t s = 0; s < kAdaptiveStripes; s++) { // (the stripes the blocks spread their atomics over)
+        AdaptiveCounters one;
+        std::memcpy(&one, c->adaptiveBack.p + nB + s * (sizeof(AdaptiveCounters) / sizeof(uint32_t)), sizeof(one));
+        k.active += one.active, k.nonfinite += one.nonfinite, k.total += one.total;
+        k.maxErrorBits = std::max(k.maxErrorBits, one.maxErrorBits), k.maxNotCount = std::max(k.maxNotCount, one.maxNotCount);
+    }
+    pt_adaptive_stats& st = c->adaptiveStats;
+    st.blocks = nB, st.active_blocks = k.active, st.nonfinite = k.nonfinite;
+    st.min_count = ~k.maxNotCount, st.max_count = spp, st.samples_total = k.total;
+    std::memcpy(&st.max_block_error, &k.maxErrorBits, sizeof(float));
+    float ms = 0;
+    if (hipEventElapsedTime(&ms, c->adaptiveEvents[0], c->adaptiveEvents[1]) == hipSuccess)
+        c->adaptiveTiming[0] += ms, c->adaptiveTiming[1] += 1.0;
+    else
+        (void)hipGetLastError();
+    return PT_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int pt_set_tiles(pt_ctx* c, const pt_rect* rects, uint32_t n)
+{
+    return guarded(c, "pt_set_tiles", [&]() -> int {
+    if (!c)
+        return PT_ERR_INVALID;
+    if (c->adaptiveSet && n != 0 && rects)
+        return fail(c, PT_ERR_UNSUPPORTED, "pt_set_tiles: adaptive sampling is on (pt_set_adaptive) -- it owns the pixel list; sharded adaptive sampling is not supported");
+    HIPCHK(c, hipSetDevice(c->device));
+    return installPixelRects(c, rects, n);
     });
 }
 
@@ -1003,18 +1111,19 @@ int pt_clear(pt_ctx* c)
     c->mergePending = false;
     if (parityMode(c) && c->queuesReady && (rc = resetStreams(c)))
         return rc;
+    if (c->adaptiveSet && c->adaptiveCounts.p && (rc = clearAdaptive(c))) // the halves, counts and errors belong to the image; the mode stays set
+        return rc;
     return PT_OK;
     });
 }
 
-int pt_render(pt_ctx* c, uint32_t spp)
+} // extern "C"
+
+namespace {
+
+// pt_render's body: `spp` more samples of every owned pixel into c->accum (pt_render_adaptive runs it twice per round, aimed at the two halves)
+int renderSamples(pt_ctx* c, uint32_t spp)
 {
-    return guarded(c, "pt_render", [&]() -> int {
-    if (!c)
-        return PT_ERR_INVALID;
-    if (!c->haveStatic || !c->haveDynamic || !c->haveCamera)
-        return fail(c, PT_ERR_STATE, "pt_render: scene (static + dynamic) and camera must be set first");
-    HIPCHK(c, hipSetDevice(c->device));
     int rc;
     if ((rc = checkOverflow(c)))
         return rc;
@@ -1088,6 +1197,23 @@ int pt_render(pt_ctx* c, uint32_t spp)
         c->msGen = fam[0], c->msIntersect = fam[1] + fam[4], c->msShade = fam[2], c->msShadow = fam[3], c->msPacket = fam[4];
     }
     return PT_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int pt_render(pt_ctx* c, uint32_t spp)
+{
+    return guarded(c, "pt_render", [&]() -> int {
+    if (!c)
+        return PT_ERR_INVALID;
+    if (c->adaptiveSet)
+        return fail(c, PT_ERR_STATE, "pt_render: adaptive sampling is on -- pt_render_adaptive renders, or pt_clear and pt_set_adaptive(NULL)");
+    if (!c->haveStatic || !c->haveDynamic || !c->haveCamera)
+        return fail(c, PT_ERR_STATE, "pt_render: scene (static + dynamic) and camera must be set first");
+    HIPCHK(c, hipSetDevice(c->device));
+    return renderSamples(c, spp);
     });
 }
 
@@ -1174,8 +1300,10 @@ int pt_write_accum(pt_ctx* c, const float* in, uint32_t spp)
 {
     if (!c || !in)
         return PT_ERR_INVALID;
+    if (c->adaptiveSet)
+        return fail(c, PT_ERR_STATE, "pt_write_accum: adaptive sampling is on -- the accumulator is made from the halves (pt_write_adaptive)");
     HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipMemcpyAsync(c->accum, in, (size_t)c->cfg.width * c->cfg.height * sizeof(float4), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->accum, in,(size_t)c->cfg.width * c->cfg.height * sizeof(float4), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->spp = spp;
     return PT_OK;
@@ -1955,6 +2083,205 @@ int pt_firefly_counts(pt_ctx* c, uint32_t counts[2])
 }
 
 void* pt_firefly_device_ptr(pt_ctx* c) { return c && c->fireflySet && c->fireflyEvaluated ? (void*)c->fireflyPlane.p : nullptr; }
+
+// ---- adaptive sampling (k_adaptive_eval; the helpers stand before pt_set_tiles) -------------------
+
+int pt_set_adaptive(pt_ctx* c, const pt_adaptive_params* prm)
+{
+    return guarded(c, "pt_set_adaptive", [&]() -> int {
+    if (!c)
+        return PT_ERR_INVALID;
+    if (const int rc = fixedScheduleOnly(c, "pt_set_adaptive"))
+        return rc;
+    pt_adaptive_params p {};
+    if (prm) {
+        p.threshold = prm->threshold;
+        p.min_samples = prm->min_samples ? prm->min_samples : 64u;
+        p.round_samples = prm->round_samples ? prm->round_samples : 64u;
+        p.max_samples = prm->max_samples ? prm->max_samples : 1024u;
+        if (!std::isfinite(p.threshold) || p.threshold < 0.0f)
+            return fail(c, PT_ERR_INVALID, "pt_set_adaptive: threshold = %g (finite, >= 0; 0 = never stop by error)", (double)prm->threshold);
+        if ((p.min_samples | p.round_samples | p.max_samples) & 1u)
+            return fail(c, PT_ERR_INVALID, "pt_set_adaptive: min_samples = %u, round_samples = %u, max_samples = %u must be even (a round is two equal halves)",
+                p.min_samples, p.round_samples, p.max_samples);
+        if (p.max_samples < p.min_samples || p.max_samples > (1u << 20))
+            return fail(c, PT_ERR_INVALID, "pt_set_adaptive: max_samples = %u (min_samples = %u .. %u)", p.max_samples, p.min_samples, 1u << 20);
+    }
+    const bool on = prm != nullptr;
+    if (on != c->adaptiveSet) {
+        if (on && tilesSet(c))
+            return fail(c, PT_ERR_UNSUPPORTED, "pt_set_adaptive: tiles are set -- adaptive sampling owns the pixel list of a whole-frame context");
+        if (c->spp != 0)
+            return fail(c, PT_ERR_STATE, "pt_set_adaptive: the mode changes only while there are no samples (pt_clear first)");
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    if (!on) {
+        if (c->adaptiveSet) {
+            HIPCHK(c, hipStreamSynchronize(c->stream));
+            releaseAdaptive(c);
+        }
+        c->adaptiveSet = false;
+        return PT_OK;
+    }
+    const bool was = c->adaptiveSet;
+    c->adaptiveSet = true;
+    c->adaptivePrm = p;
+    if (!was) {
+        c->adaptiveStats = pt_adaptive_stats {};
+        c->adaptiveStats.blocks = c->adaptiveStats.active_blocks = adaptiveBlocks(c);
+    } else if (c->spp > 0 && c->adaptiveCounts.p) { // the flags are a function of the state AND the parameters
+        return evaluateAdaptive(c, 0, c->spp);
+    }
+    return PT_OK;
+    });
+}
+
+int pt_adaptive(const pt_ctx* c) { return c && c->adaptiveSet ? 1 : 0; }
+
+int pt_adaptive_params_get(const pt_ctx* c, pt_adaptive_params* out)
+{
+    if (!c || !out)
+        return PT_ERR_INVALID;
+    if (!c->adaptiveSet)
+        return fail(const_cast<pt_ctx*>(c), PT_ERR_STATE, "pt_adaptive_params_get: adaptive sampling is off (pt_set_adaptive)");
+    *out = c->adaptivePrm;
+    return PT_OK;
+}
+
+int pt_render_adaptive(pt_ctx* c, uint32_t rounds)
+{
+    return guarded(c, "pt_render_adaptive", [&]() -> int {
+    if (!c)
+        return PT_ERR_INVALID;
+    if (!c->adaptiveSet)
+        return fail(c, PT_ERR_STATE, "pt_render_adaptive: adaptive sampling is off (pt_set_adaptive)");
+    if (!c->haveStatic || !c->haveDynamic || !c->haveCamera)
+        return fail(c, PT_ERR_STATE, "pt_render_adaptive: scene (static + dynamic) and camera must be set first");
+    HIPCHK(c, hipSetDevice(c->device));
+    int rc = ensureAdaptive(c);
+    if (rc)
+        return rc;
+    const pt_adaptive_params& prm = c->adaptivePrm;
+    const uint32_t W = c->cfg.width, H = c->cfg.height, bX = adaptiveBlocksX(c), nB = adaptiveBlocks(c);
+    float4* const accum = c->accum;
+    std::vector<pt_rect> rects;
+    for (uint32_t r = 0; (rounds == 0 || r < rounds) && c->spp < prm.max_samples; r++) {
+        const uint32_t S = c->spp;
+        rects.clear();
+        for (uint32_t b = 0; b < nB; b++) // (no samples yet: every block, whatever the read-back area holds)
+            if (S == 0 || c->adaptiveBack.p[b]) {
+                const uint32_t x = (b % bX) * 8u, y = (b / bX) * 8u;
+                rects.push_back({ x, y, std::min(x + 8u, W), std::min(y + 8u, H) });
+            }
+        if (rects.empty())
+            break;
+        const uint32_t h = std::min(S == 0 ? prm.min_samples : prm.round_samples, prm.max_samples - S) / 2u;
+        const auto t0 = std::chrono::steady_clock::now();
+        if ((rc = installPixelRects(c, rects.data(), (uint32_t)rects.size())))
+            break;
+        const bool changed = !c->queuesReady; // (the same list as the one installed costs nothing)
+        if ((rc = ensureQueues(c)))
+            break;
+        if (changed) {
+            c->adaptiveTiming[2] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+            c->adaptiveTiming[3] += 1.0;
+        }
+        for (int half = 0; half < 2 && !rc; half++) { // sample indices base + S .. + h - 1 into A, the next h into B
+            c->accum = c->adaptiveHalf[half].p;
+            rc = renderSamples(c, h);
+        }
+        c->accum = accum;
+        if (rc) { // (the halves hold part of a round: pt_clear and render again, as after any failed pt_render)
+            c->spp = S;
+            break;
+        }
+        if ((rc = evaluateAdaptive(c, 2u * h, S + 2u * h)))
+            break;
+        c->adaptiveStats.rounds++;
+    }
+    const int whole = installPixelRects(c, nullptr, 0); // the context owns the whole frame again: guides, denoiser and history see no tiles
+    return rc ? rc : whole;
+    });
+}
+
+int pt_adaptive_stats_get(pt_ctx* c, pt_adaptive_stats* out)
+{
+    if (!c || !out)
+        return PT_ERR_INVALID;
+    if (!c->adaptiveSet)
+        return fail(c, PT_ERR_STATE, "pt_adaptive_stats_get: adaptive sampling is off (pt_set_adaptive)");
+    *out = c->adaptiveStats;
+    return PT_OK;
+}
+
+int pt_read_adaptive(pt_ctx* c, float* A, float* B, uint32_t* counts, float* error, float* block_error)
+{
+    if (!c)
+        return PT_ERR_INVALID;
+    if (!c->adaptiveSet)
+        return fail(c, PT_ERR_STATE, "pt_read_adaptive: adaptive sampling is off (pt_set_adaptive)");
+    HIPCHK(c, hipSetDevice(c->device));
+    if (const int rc = ensureAdaptive(c))
+        return rc;
+    auto get = [&](void* out, const void* dev, size_t bytes) { return out ? hipMemcpyAsync(out, dev, bytes, hipMemcpyDeviceToHost, c->stream) : hipSuccess; };
+    HIPCHK(c, get(A, c->adaptiveHalf[0].p, c->adaptiveHalf[0].n * sizeof(float4)));
+    HIPCHK(c, get(B, c->adaptiveHalf[1].p, c->adaptiveHalf[1].n * sizeof(float4)));
+    HIPCHK(c, get(counts, c->adaptiveCounts.p, c->adaptiveCounts.n * sizeof(uint32_t)));
+    HIPCHK(c, get(error, c->adaptiveError.p, c->adaptiveError.n * sizeof(float)));
+    HIPCHK(c, get(block_error, c->adaptiveBlockError.p, c->adaptiveBlockError.n * sizeof(float)));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return PT_OK;
+}
+
+int pt_write_adaptive(pt_ctx* c, const float* A, const float* B, const uint32_t* counts)
+{
+    return guarded(c, "pt_write_adaptive", [&]() -> int {
+    if (!c || !A || !B || !counts)
+        return PT_ERR_INVALID;
+    if (!c->adaptiveSet)
+        return fail(c, PT_ERR_STATE, "pt_write_adaptive: adaptive sampling is off (pt_set_adaptive)");
+    const uint32_t W = c->cfg.width, H = c->cfg.height;
+    uint32_t most = 0;
+    for (uint32_t y = 0; y < H; y++)
+        for (uint32_t x = 0; x < W; x++) {
+            const uint32_t n = counts[(size_t)y * W + x];
+            if (n != counts[(size_t)(y & ~7u) * W + (x & ~7u)])
+                return fail(c, PT_ERR_INVALID, "pt_write_adaptive: counts differ within the 8 x 8 block of pixel (%u, %u)", x, y);
+            if ((n & 1u) || n > c->adaptivePrm.max_samples)
+                return fail(c, PT_ERR_INVALID, "pt_write_adaptive: count %u at pixel (%u, %u) (even, <= max_samples = %u)", n, x, y, c->adaptivePrm.max_samples);
+            most = std::max(most, n);
+        }
+    HIPCHK(c, hipSetDevice(c->device));
+    if (const int rc = ensureAdaptive(c))
+        return rc;
+    const size_t n = (size_t)W * H;
+    HIPCHK(c, hipMemcpyAsync(c->adaptiveHalf[0].p, A, n * sizeof(float4), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->adaptiveHalf[1].p, B, n * sizeof(float4), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->adaptiveCounts.p, counts, n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    return evaluateAdaptive(c, 0, most); // (synchronises: the caller's arrays are free again)
+    });
+}
+
+void* pt_adaptive_device_ptr(pt_ctx* c, int which)
+{
+    if (!c || !c->adaptiveCounts.p)
+        return nullptr;
+    switch (which) {
+    case 0: return c->adaptiveHalf[0].p;
+    case 1: return c->adaptiveHalf[1].p;
+    case 2: return c->adaptiveCounts.p;
+    case 3: return c->adaptiveError.p;
+    default: return nullptr;
+    }
+}
+
+int pt_debug_adaptive_timing(pt_ctx* c, double out[4])
+{
+    if (!c || !out)
+        return PT_ERR_INVALID;
+    std::memcpy(out, c->adaptiveTiming, sizeof(c->adaptiveTiming));
+    return PT_OK;
+}
 
 // ---- instance motion (k_guides<1>, k_temporal<true>) --------------------------------------------
 

@@ -296,6 +296,36 @@ void RayTracer::setFireflyClamp(bool on)
     check(pt_set_firefly_clamp(m_ctx, on ? &defaults : nullptr), "pt_set_firefly_clamp");
 }
 
+void RayTracer::setAdaptive(const pt_adaptive_params* params)
+{
+    if ((params != nullptr) != (pt_adaptive(m_ctx) != 0)) // the mode changes only while there are no samples
+        check(pt_clear(m_ctx), "pt_clear");
+    check(pt_set_adaptive(m_ctx, params), "pt_set_adaptive");
+}
+
+pt_adaptive_stats RayTracer::rayTraceAdaptive(const Camera& camera, unsigned rounds)
+{
+    const CameraData cam = camera.get_camera_data();
+    if (!m_haveCamera || std::memcmp(&cam, &m_prevCamera, sizeof(CameraData)) != 0) { // as rayTrace
+        m_prevCamera = cam;
+        m_haveCamera = true;
+        check(pt_set_camera(m_ctx, &cam), "pt_set_camera");
+        check(pt_clear(m_ctx), "pt_clear");
+    }
+    check(pt_render_adaptive(m_ctx, rounds), "pt_render_adaptive"); // (synchronous at the end of every round)
+    m_temporalDirty = true;
+    pt_adaptive_stats st {};
+    check(pt_adaptive_stats_get(m_ctx, &st), "pt_adaptive_stats_get");
+    return st;
+}
+
+std::vector<uint32_t> RayTracer::getAdaptiveCounts()
+{
+    std::vector<uint32_t> out((size_t)m_width * m_height);
+    check(pt_read_adaptive(m_ctx, nullptr, nullptr, out.data(), nullptr, nullptr), "pt_read_adaptive");
+    return out;
+}
+
 void RayTracer::setGuideChain(unsigned maxTransmissions)
 {
     check(pt_clear(m_ctx), "pt_clear"); // (the chain changes, and a motion is forgotten, only while no guide samples are in the sums)

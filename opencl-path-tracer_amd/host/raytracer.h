@@ -126,6 +126,13 @@ public:
     // and getDenoisedOutput (iterations > 0); getOutput and the accumulator are what they were.  Trades energy for variance: single-pixel highlights
     // and caustics lose light.  May change at any time, the history is kept.  Off by default.
     void setFireflyClamp(bool on);
+    // Adaptive sampling (include/ptamd.h, "adaptive sampling"): rayTraceAdaptive renders in rounds of params->round_samples and stops the 8 x 8 blocks
+    // whose two half images agree to within params->threshold; the accumulator then holds every pixel's mean times getSamplesPerPixel(), so getOutput,
+    // getDenoisedOutput and getAccumulator are used as ever.  Turning the mode on or off restarts the accumulation; null turns it off.  While it is on,
+    // rayTrace() is refused (std::runtime_error).  rayTraceAdaptive: up to `rounds` rounds, 0 = until every block has stopped or holds max_samples.
+    void setAdaptive(const pt_adaptive_params* params);
+    pt_adaptive_stats rayTraceAdaptive(const Camera& camera, unsigned rounds = 0);
+    std::vector<uint32_t> getAdaptiveCounts(); // width*height: the samples each pixel holds
     // Guide rays follow up to `maxTransmissions` refractions (0..PT_GUIDE_CHAIN_MAX; 0, the default: off) to the first surface that is not glass
     // (include/ptamd.h, "guide chain"): the filter and the history then see the edges and albedos behind a pane or inside a glass body.  Restarts the
     // accumulation (pt_clear: guide sums of two definitions must not mix).  While it is on no instance or vertex motion is handed to the device library

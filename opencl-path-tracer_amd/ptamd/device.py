@@ -103,6 +103,18 @@ class FireflyParams(C.Structure):
 
 FIREFLY_RADIUS, FIREFLY_MAX_RANK = 2, 4  # PT_FIREFLY_RADIUS, PT_FIREFLY_MAX_RANK
 
+
+class AdaptiveParams(C.Structure):
+    """pt_adaptive_params (32 bytes); a sample count of 0 selects the default documented in include/ptamd.h, threshold 0 never stops a block by its error"""
+    _fields_ = [("threshold", C.c_float), ("min_samples", C.c_uint32), ("round_samples", C.c_uint32), ("max_samples", C.c_uint32), ("_reserved", C.c_uint32 * 4)]
+
+
+class AdaptiveStats(C.Structure):
+    """pt_adaptive_stats (56 bytes)"""
+    _fields_ = [("rounds", C.c_uint32), ("blocks", C.c_uint32), ("active_blocks", C.c_uint32), ("nonfinite", C.c_uint32), ("min_count", C.c_uint32),
+                ("max_count", C.c_uint32), ("samples_total", C.c_uint64), ("max_block_error", C.c_float), ("_reserved", C.c_uint32 * 5)]
+
+
 EXPORTS = ["pt_create", "pt_destroy", "pt_last_error", "pt_set_stream", "pt_upload_static", "pt_upload_static_async", "pt_upload_dynamic",
            "pt_upload_dynamic_async", "pt_frame_tick", "pt_update_geometry", "pt_refit_vertices",
            "pt_upload_texture_array", "pt_set_camera", "pt_set_tiles", "pt_set_accum_buffer", "pt_clear", "pt_render",
@@ -118,6 +130,8 @@ EXPORTS = ["pt_create", "pt_destroy", "pt_last_error", "pt_set_stream", "pt_uplo
            "pt_read_temporal_variance", "pt_write_temporal_variance", "pt_temporal_variance_device_ptr",
            "pt_set_temporal_response", "pt_temporal_response", "pt_read_temporal_fast", "pt_write_temporal_fast", "pt_read_temporal_response",
            "pt_temporal_fast_device_ptr", "pt_set_firefly_clamp", "pt_firefly_clamp", "pt_read_firefly", "pt_firefly_counts", "pt_firefly_device_ptr",
+           "pt_set_adaptive", "pt_adaptive", "pt_adaptive_params_get", "pt_render_adaptive", "pt_adaptive_stats_get", "pt_read_adaptive", "pt_write_adaptive",
+           "pt_adaptive_device_ptr", "pt_debug_adaptive_timing",
            "pt_stats_get", "pt_stats_reset", "pt_profile_kernels", "pt_reduce_accum",
            "pt_intersect", "pt_gen_rays", "pt_primary_pass", "pt_shade_batch", "pt_debug_quantise_node", "pt_debug_convert", "pt_debug_copy_bandwidth", "pt_debug_math_probe", "pt_debug_rng_probe", "pt_debug_live_resources",
            "pt_version"]
@@ -229,6 +243,16 @@ def lib():
         l.pt_firefly_counts.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
         l.pt_firefly_device_ptr.restype = C.c_void_p
         l.pt_firefly_device_ptr.argtypes = [C.c_void_p]
+        l.pt_set_adaptive.argtypes = [C.c_void_p, C.POINTER(AdaptiveParams)]
+        l.pt_adaptive.argtypes = [C.c_void_p]
+        l.pt_adaptive_params_get.argtypes = [C.c_void_p, C.POINTER(AdaptiveParams)]
+        l.pt_render_adaptive.argtypes = [C.c_void_p, C.c_uint32]
+        l.pt_adaptive_stats_get.argtypes = [C.c_void_p, C.POINTER(AdaptiveStats)]
+        l.pt_read_adaptive.argtypes = [C.c_void_p] + [C.c_void_p] * 5
+        l.pt_write_adaptive.argtypes = [C.c_void_p] + [C.c_void_p] * 3
+        l.pt_adaptive_device_ptr.restype = C.c_void_p
+        l.pt_adaptive_device_ptr.argtypes = [C.c_void_p, C.c_int]
+        l.pt_debug_adaptive_timing.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
         l.pt_stats_get.argtypes = [C.c_void_p, C.POINTER(Stats)]
         l.pt_stats_reset.argtypes = [C.c_void_p]
         l.pt_profile_kernels.argtypes = [C.c_void_p, C.c_int]
@@ -664,6 +688,63 @@ class Context:
     def firefly_device_ptr(self):
         """Device address of the clamped plane (0 while the mode is off or before the first evaluation)."""
         return lib().pt_firefly_device_ptr(self._h) or 0
+
+    # ---- adaptive sampling
+    def set_adaptive(self, enable=True, threshold=0.0, min_samples=0, round_samples=0, max_samples=0):
+        """Converging renders in rounds that stop the 8 x 8 blocks whose two half images agree to within `threshold` (0: never by error -- uniform
+        sampling to max_samples).  The sample counts are even; 0 selects 64, 64 and 1024.  False turns the mode off.  The mode changes only right after
+        clear(); with the mode on the parameters may change at any time, which re-evaluates the flags."""
+        prm = AdaptiveParams(threshold, min_samples, round_samples, max_samples)
+        self._chk(lib().pt_set_adaptive(self._h, C.byref(prm) if enable else None), "pt_set_adaptive")
+
+    @property
+    def adaptive(self):
+        return bool(lib().pt_adaptive(self._h))
+
+    @property
+    def adaptive_params(self):
+        """(threshold, min_samples, round_samples, max_samples) in force, defaults resolved"""
+        prm = AdaptiveParams()
+        self._chk(lib().pt_adaptive_params_get(self._h, C.byref(prm)), "pt_adaptive_params_get")
+        return float(prm.threshold), int(prm.min_samples), int(prm.round_samples), int(prm.max_samples)
+
+    def render_adaptive(self, rounds=0):
+        """Up to `rounds` rounds (0: until no block is active or every pixel holds max_samples); returns adaptive_stats."""
+        self._chk(lib().pt_render_adaptive(self._h, rounds), "pt_render_adaptive")
+        return self.adaptive_stats
+
+    @property
+    def adaptive_stats(self):
+        st = AdaptiveStats()
+        self._chk(lib().pt_adaptive_stats_get(self._h, C.byref(st)), "pt_adaptive_stats_get")
+        return {k: getattr(st, k) for k, _ in AdaptiveStats._fields_ if not k.startswith("_")}
+
+    def read_adaptive(self):
+        """dict: A, B (width*height, 4) float32 sums; counts (width*height,) uint32; error (width*height,) float32; block_error (blocks,) float32"""
+        n, nb = self.width * self.height, ((self.width + 7) // 8) * ((self.height + 7) // 8)
+        out = {"A": np.zeros((n, 4), np.float32), "B": np.zeros((n, 4), np.float32), "counts": np.zeros(n, np.uint32),
+               "error": np.zeros(n, np.float32), "block_error": np.zeros(nb, np.float32)}
+        self._chk(lib().pt_read_adaptive(self._h, _p(out["A"]), _p(out["B"]), _p(out["counts"]), _p(out["error"]), _p(out["block_error"])), "pt_read_adaptive")
+        return out
+
+    def write_adaptive(self, A, B, counts):
+        """Restore the two halves and the counts (constant per 8 x 8 block, even, <= max_samples): evaluates and publishes; samples_per_pixel = max count."""
+        n = self.width * self.height
+        A = np.ascontiguousarray(A, np.float32).reshape(n, 4)
+        B = np.ascontiguousarray(B, np.float32).reshape(n, 4)
+        counts = np.ascontiguousarray(counts, np.uint32).reshape(n)
+        self._chk(lib().pt_write_adaptive(self._h, _p(A), _p(B), _p(counts)), "pt_write_adaptive")
+
+    def adaptive_device_ptr(self, which):
+        """Device address of A (0), B (1), counts (2), error (3); 0 before the state is allocated."""
+        return lib().pt_adaptive_device_ptr(self._h, which) or 0
+
+    @property
+    def adaptive_timing(self):
+        """pt_debug_adaptive_timing: (device ms in evaluations, evaluations, host ms changing the pixel list, list changes), sums since creation"""
+        out = (C.c_double * 4)()
+        self._chk(lib().pt_debug_adaptive_timing(self._h, out), "pt_debug_adaptive_timing")
+        return tuple(out)
 
     # ---- instance motion
     def set_instance_motion(self, prev):
