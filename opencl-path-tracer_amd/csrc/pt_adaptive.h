@@ -26,7 +26,7 @@ struct AdaptiveArgs {
     float* blockError; // per block: E_b
     uint32_t* flags; // per block: read as the set that was just rendered, written as the next round's
     AdaptiveCounters* counters; // kAdaptiveStripes of them
-    float4* accum; // the published accumulator (PUBLISH)
+    float4* accum; // the published accumulator
     uint32_t width, height, blocksX, blocks;
     uint32_t add; // 2h: what the round gave every pixel of a flagged block (0: evaluate the state as it stands)
     uint32_t spp; // S' = S + add: the largest count, pt_samples_per_pixel after the round
@@ -50,8 +50,7 @@ __device__ __forceinline__ float4 adaptivePublished(float4 a, float4 b, uint32_t
 // The count of a block is constant over its pixels (pt_render_adaptive keeps it so, pt_write_adaptive checks it), so the wave takes it from lane 0,
 // whose pixel is always inside.  E_b is the butterfly sum (__shfl_xor over 32, 16, ... 1: every lane ends with the same bits) divided by the number
 // of pixels inside.  One integer atomic per wave and counter, by lane 0; no float atomics, every plane and counter is bit-reproducible.
-// 32 B read + 4 B read and written (counts) + 4 B (e) + 16 B (accumulator) per pixel with PUBLISH: 60 B.
-template <bool PUBLISH>
+// 32 B read + 4 B read and written (counts) + 4 B (e) + 16 B (accumulator) per pixel: 60 B.
 __global__ void __launch_bounds__(256) k_adaptive_eval(AdaptiveArgs a)
 {
     const uint32_t lane = threadIdx.x & 63u;
@@ -85,8 +84,7 @@ __global__ void __launch_bounds__(256) k_adaptive_eval(AdaptiveArgs a)
     }
     if (inside) {
         a.error[p] = e;
-        if (PUBLISH)
-            a.accum[p] = adaptivePublished(A, B, n, a.spp);
+        a.accum[p] = adaptivePublished(A, B, n, a.spp);
     }
     float sum = e;
 #pragma unroll
@@ -109,15 +107,6 @@ __global__ void __launch_bounds__(256) k_adaptive_eval(AdaptiveArgs a)
         atomicMax(&k->maxNotCount, ~countB);
         atomicAdd(&k->total, (unsigned long long)countB * nB);
     }
-}
-
-// The second half of the fused kernel as a launch of its own (PTAMD_ADAPTIVE_SPLIT, diagnostics: EXPERIMENTS.md has both timed): one thread per pixel
-// of the frame, 36 B read and 16 B written, after k_adaptive_eval<false> has brought the counts up to date.
-__global__ void __launch_bounds__(256) k_adaptive_publish(const float4* A, const float4* B, const uint32_t* counts, float4* accum, uint32_t n, uint32_t spp)
-{
-    const uint32_t p = blockIdx.x * 256u + threadIdx.x;
-    if (p < n)
-        accum[p] = adaptivePublished(A[p], B[p], counts[p], spp);
 }
 
 } // namespace ptd

@@ -39,6 +39,29 @@ struct DevBuf {
         p = nullptr;
         n = 0;
     }
+    // The whole buffer on stream `s`: zeroed; allocated and zeroed if it is not there yet; to and from the host.  copyTo / copyFrom issue the
+    // asynchronous copy alone, for buffers that travel together behind one synchronisation; read / write are one copy and the synchronisation.  A null
+    // `host` is skipped on the way out (the entry points that allow one say so).
+    hipError_t zero(hipStream_t s) { return hipMemsetAsync(p, 0, n * sizeof(T), s); }
+    hipError_t ensureZeroed(size_t count, hipStream_t s)
+    {
+        if (p)
+            return hipSuccess;
+        const hipError_t e = alloc(count);
+        return e == hipSuccess ? zero(s) : e;
+    }
+    hipError_t copyTo(void* host, hipStream_t s) const { return host ? hipMemcpyAsync(host, p, n * sizeof(T), hipMemcpyDeviceToHost, s) : hipSuccess; }
+    hipError_t copyFrom(const void* host, hipStream_t s) { return hipMemcpyAsync(p, host, n * sizeof(T), hipMemcpyHostToDevice, s); }
+    hipError_t read(void* host, hipStream_t s) const
+    {
+        const hipError_t e = copyTo(host, s);
+        return e == hipSuccess ? hipStreamSynchronize(s) : e;
+    }
+    hipError_t write(const void* host, hipStream_t s)
+    {
+        const hipError_t e = copyFrom(host, s);
+        return e == hipSuccess ? hipStreamSynchronize(s) : e;
+    }
 };
 
 // `count` records of pinned host memory
@@ -386,68 +409,85 @@ struct pt_ctx {
 
     // temporal variance (include/ptamd.h): one more plane per history set, width * height floats -- the variance of the luminances the pixel's history
     // stands for --, allocated (zeroed) at the first temporal call with the mode on.  The mode changes only while there is no history.
-    DevBuf<float> temporalVariance[2];
-    bool varianceSet = false;
-    float sigmaVariance = 0, relativeFloor = 0, fullHistory = 0; // pt_variance_params, defaults resolved
+    struct Variance {
+        DevBuf<float> plane[2];
+        bool set = false;
+        float sigma = 0, relativeFloor = 0, fullHistory = 0; // pt_variance_params, defaults resolved
+    } variance;
 
     // temporal response (include/ptamd.h): one more float4 image per history set, the fast history (d_f.rgb, N_f), and two scratch planes -- the
     // luminance pairs k_temporal<., ., true> leaves for k_temporal_response, and the mix factor s of the last accumulate --, allocated (zeroed) at the
     // first temporal call with the mode on.  The mode changes only while there is no history.
-    DevBuf<float4> temporalFast[2];
-    DevBuf<float2> responseLuminance;
-    DevBuf<float> responseMix;
-    bool responseSet = false;
-    float fastHistory = 0, sigmaResponse = 0, responseFloor = 0; // pt_response_params, defaults resolved
+    struct Response {
+        DevBuf<float4> fast[2];
+        DevBuf<float2> luminance;
+        DevBuf<float> mix;
+        bool set = false;
+        float fastHistory = 0, sigma = 0, relativeFloor = 0; // pt_response_params, defaults resolved
+    } response;
 
     // firefly clamp (include/ptamd.h; pt_firefly.h): the clamped plane (d.rgb, s), width * height float4, and its two counters (clamped, nonfinite) --
     // allocated at the first evaluation with the mode on, made afresh by every call that consumes the plane.  The mode may change at any time.
-    DevBuf<float4> fireflyPlane;
-    DevBuf<uint32_t> fireflyCounts;
-    bool fireflySet = false;
-    bool fireflyEvaluated = false; // the plane and the counters hold an evaluation
-    uint32_t fireflyRank = 0;
-    float fireflyScale = 0; // pt_firefly_params, defaults resolved
+    struct Firefly {
+        DevBuf<float4> plane;
+        DevBuf<uint32_t> counts;
+        bool set = false;
+        bool evaluated = false; // the plane and the counters hold an evaluation
+        uint32_t rank = 0;
+        float scale = 0; // pt_firefly_params, defaults resolved
+    } firefly;
 
     // adaptive sampling (include/ptamd.h; pt_adaptive.h): the two half accumulators, the per-pixel counts and errors, one error and one flag per 8 x 8
-    // block, the counters of an evaluation and the pinned area the flags and counters are read back into (flags first) -- allocated at the first
+    // block, the counters of an evaluation and the pinned area the flags and counters are read back into (flags first) -- `buf`, made whole at the first
     // pt_render_adaptive / pt_write_adaptive, freed when the mode is turned off and by pt_destroy.  The mode changes only while there are no samples.
-    DevBuf<float4> adaptiveHalf[2];
-    DevBuf<uint32_t> adaptiveCounts, adaptiveFlags;
-    DevBuf<float> adaptiveError, adaptiveBlockError;
-    DevBuf<ptd::AdaptiveCounters> adaptiveCounters;
-    Pinned<uint32_t> adaptiveBack; // `blocks` flags, then one AdaptiveCounters
-    bool adaptiveSet = false;
-    pt_adaptive_params adaptivePrm {}; // defaults resolved
-    pt_adaptive_stats adaptiveStats {}; // of the last evaluation
-    Event adaptiveEvents[2]; // around an evaluation's launches
-    double adaptiveTiming[4] = {}; // pt_debug_adaptive_timing: device ms in evaluations, their number, host ms changing the pixel list, list changes
+    struct Adaptive {
+        struct Buffers {
+            DevBuf<float4> half[2];
+            DevBuf<uint32_t> counts, flags;
+            DevBuf<float> error, blockError;
+            DevBuf<ptd::AdaptiveCounters> counters;
+            Pinned<uint32_t> back; // `blocks` flags, then the AdaptiveCounters
+        };
+        std::unique_ptr<Buffers> buf;
+        bool set = false;
+        pt_adaptive_params prm {}; // defaults resolved
+        pt_adaptive_stats stats {}; // of the last evaluation
+        Event events[2]; // around an evaluation's launches
+        double timing[4] = {}; // pt_debug_adaptive_timing: device ms in evaluations, their number, host ms changing the pixel list, list changes
+    } adaptive;
 
     // instance motion (include/ptamd.h): one record per instance of the ACTIVE dynamic state (indexed like its instance table, which is how the guide
     // pass meets a hit), and the two guide sums made from them -- (displacement.xyz, 0) and (normal then.xyz, 0), width * height float4 each, allocated at
     // the first pt_set_instance_motion / pt_write_motion_guides.  pt_frame_tick forgets the motion; pt_clear zeroes the sums and keeps it.
-    DevBuf<MotionRecord> motionRecords;
-    std::vector<MotionRecord> motionHost;
-    bool motionSet = false;
-    uint32_t motionMoving = 0;
+    struct InstanceMotion {
+        DevBuf<MotionRecord> records;
+        std::vector<MotionRecord> host;
+        bool set = false;
+        uint32_t moving = 0;
+    } motion;
     PlanePair motionGuides; // [0] (displacement.xyz, 0), [1] (normal then.xyz, 0)
 
     // vertex motion (include/ptamd.h): a snapshot of the shading records the previous dynamic state held (numTris of them, taken on the render stream by
     // pt_set_vertex_motion: the guide pass never reads the inactive set, which the next upload may be overwriting), and three float4 rows per instance of
     // the active state -- the linear part of the world transform the instance had then.  Grow-only; pt_frame_tick forgets the motion.  While it is set
-    // without an instance motion, motionRecords holds identity records (A = t = 0, the current rows).
-    DevBuf<TriFat> fatThen;
-    DevBuf<float4> vertexRows;
-    std::vector<float4> vertexRowsHost;
-    bool vertexMotionSet = false;
-    bool vertexDeformed = false; // the previous state held another version of the static arrays: k_guides<2> runs
+    // without an instance motion, motion.records holds identity records (A = t = 0, the current rows).
+    struct VertexMotion {
+        DevBuf<TriFat> fatThen;
+        DevBuf<float4> rows;
+        std::vector<float4> rowsHost;
+        bool set = false; // forgetting the motion clears this alone: `deformed` and rebuiltMotion.set are written whenever it is set and read only while it is
+        bool deformed = false; // the previous state held another version of the static arrays: k_guides<2> runs
+    } vertexMotion;
 
     // rebuilt motion (include/ptamd.h): the second way to fill fatThen, for a state whose tree was rebuilt -- the caller's map (active triangle -> triangle
     // of the previous state) on the device, where k_gather_then reads it, and the pinned copy the asynchronous upload reads from (its event: created at the
     // first call, recorded on the render stream).  Grow-only.  Set: the vertex motion above (set, deformed) came from pt_set_rebuilt_motion.
-    DevBuf<uint32_t> rebuiltMap;
-    Staging rebuiltStage;
-    bool rebuiltMotionSet = false;
-    uint32_t rebuiltFollowed = 0;
+    struct RebuiltMotion {
+        DevBuf<uint32_t> map;
+        Staging stage;
+        bool set = false;
+        uint32_t followed = 0;
+    } rebuiltMotion;
 
     double msLastRender = 0, msIntersect = 0, msShade = 0, msShadow = 0, msGen = 0, msPacket = 0;
 };
@@ -533,28 +573,23 @@ int uploadVec(pt_ctx* c, DevBuf<T>& buf, const std::vector<T>& host)
 int PlanePair::zero(pt_ctx* c)
 {
     for (DevBuf<float4>& b : plane)
-        HIPCHK(c, hipMemsetAsync(b.p, 0, b.n * sizeof(float4), c->stream));
+        HIPCHK(c, b.zero(c->stream));
     return PT_OK;
 }
 
 int PlanePair::ensure(pt_ctx* c)
 {
-    if (plane[0].p)
-        return PT_OK;
     for (DevBuf<float4>& b : plane)
-        HIPCHK(c, b.alloc((size_t)c->cfg.width * c->cfg.height));
-    return zero(c);
+        HIPCHK(c, b.ensureZeroed((size_t)c->cfg.width * c->cfg.height, c->stream));
+    return PT_OK;
 }
 
 int PlanePair::read(pt_ctx* c, float* out0, float* out1)
 {
     if (const int rc = ensure(c))
         return rc;
-    float* const out[2] = { out0, out1 };
-    for (int k = 0; k < 2; k++)
-        if (out[k])
-            HIPCHK(c, hipMemcpyAsync(out[k], plane[k].p, plane[k].n * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, plane[0].copyTo(out0, c->stream));
+    HIPCHK(c, plane[1].read(out1, c->stream));
     return PT_OK;
 }
 
@@ -562,10 +597,8 @@ int PlanePair::write(pt_ctx* c, const float* in0, const float* in1)
 {
     if (const int rc = ensure(c))
         return rc;
-    const float* const in[2] = { in0, in1 };
-    for (int k = 0; k < 2; k++)
-        HIPCHK(c, hipMemcpyAsync(plane[k].p, in[k], plane[k].n * sizeof(float4), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, plane[0].copyFrom(in0, c->stream));
+    HIPCHK(c, plane[1].write(in1, c->stream));
     return PT_OK;
 }
 

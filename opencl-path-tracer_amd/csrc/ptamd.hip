@@ -27,6 +27,7 @@
 #include <cstdio>
 #include <cstring>
 #include <functional>
+#include <memory>
 #include <new>
 #include <stdexcept>
 #include <string>
@@ -229,6 +230,9 @@ int growTo(pt_ctx* c, DevBuf<T>& buf, size_t count)
     HIPCHK(c, buf.alloc(std::max<size_t>(count + count / 8, 1))); // some headroom: the number of world-space copies varies from state to state
     return PT_OK;
 }
+
+// the grid of a kernel whose workgroup is one tileW x tileH tile of the frame
+dim3 tileGrid(uint32_t W, uint32_t H, uint32_t tileW, uint32_t tileH) { return dim3((W + tileW - 1) / tileW, (H + tileH - 1) / tileH); }
 
 // pt_render_guides: the n hits of the guide pass's scratch queue into the guide sums; MOTION as k_guides knows it (pt_denoise.h)
 template <int MOTION>
@@ -839,9 +843,9 @@ int pt_frame_tick(pt_ctx* c)
     newEpoch(c); // (what a batch's first pass emits belongs to the scene state it was measured on)
     c->pending = -1;
     c->haveDynamic = true;
-    c->motionSet = false; // (its records are indexed by the state that was just replaced)
-    c->motionMoving = 0;
-    c->vertexMotionSet = c->vertexDeformed = c->rebuiltMotionSet = false; // (its "then" is the state before the one that was just replaced)
+    c->motion.set = false; // (its records are indexed by the state that was just replaced)
+    c->motion.moving = 0;
+    c->vertexMotion.set = false; // (its "then" is the state before the one that was just replaced)
     if (next.staticIndex != c->statCur) { // the state was built on a rebuilt scene (pt_upload_static_async): that scene is the current one from here on
         c->statCur = next.staticIndex;
         c->st = &c->stat[c->statCur];
@@ -978,82 +982,73 @@ constexpr size_t kAdaptiveCounterWords = kAdaptiveStripes * sizeof(AdaptiveCount
 // no samples: halves, counts and errors zero, every block active (a count of 0 is below any min_samples)
 int clearAdaptive(pt_ctx* c)
 {
-    for (DevBuf<float4>& half : c->adaptiveHalf)
-        HIPCHK(c, hipMemsetAsync(half.p, 0, half.n * sizeof(float4), c->stream));
-    HIPCHK(c, hipMemsetAsync(c->adaptiveCounts.p, 0, c->adaptiveCounts.n * sizeof(uint32_t), c->stream));
-    HIPCHK(c, hipMemsetAsync(c->adaptiveError.p, 0, c->adaptiveError.n * sizeof(float), c->stream));
-    HIPCHK(c, hipMemsetAsync(c->adaptiveBlockError.p, 0, c->adaptiveBlockError.n * sizeof(float), c->stream));
-    HIPCHK(c, hipMemsetAsync(c->adaptiveFlags.p, 0x01, c->adaptiveFlags.n * sizeof(uint32_t), c->stream)); // (any non-zero word is a set flag)
-    c->adaptiveStats = pt_adaptive_stats {};
-    c->adaptiveStats.blocks = c->adaptiveStats.active_blocks = adaptiveBlocks(c);
+    pt_ctx::Adaptive::Buffers& b = *c->adaptive.buf;
+    HIPCHK(c, b.half[0].zero(c->stream));
+    HIPCHK(c, b.half[1].zero(c->stream));
+    HIPCHK(c, b.counts.zero(c->stream));
+    HIPCHK(c, b.error.zero(c->stream));
+    HIPCHK(c, b.blockError.zero(c->stream));
+    HIPCHK(c, hipMemsetAsync(b.flags.p, 0x01, b.flags.n * sizeof(uint32_t), c->stream)); // (any non-zero word is a set flag)
+    c->adaptive.stats = pt_adaptive_stats {};
+    c->adaptive.stats.blocks = c->adaptive.stats.active_blocks = adaptiveBlocks(c);
     return PT_OK;
 }
 
 int ensureAdaptive(pt_ctx* c)
 {
-    if (c->adaptiveCounts.p)
+    if (c->adaptive.buf)
         return PT_OK;
     const size_t n = (size_t)c->cfg.width * c->cfg.height, nB = adaptiveBlocks(c);
-    HIPCHK(c, c->adaptiveHalf[0].alloc(n));
-    HIPCHK(c, c->adaptiveHalf[1].alloc(n));
-    HIPCHK(c, c->adaptiveError.alloc(n));
-    HIPCHK(c, c->adaptiveBlockError.alloc(nB));
-    HIPCHK(c, c->adaptiveFlags.alloc(nB));
-    HIPCHK(c, c->adaptiveCounters.alloc(kAdaptiveStripes));
-    HIPCHK(c, c->adaptiveBack.alloc(nB + kAdaptiveCounterWords));
-    HIPCHK(c, c->adaptiveEvents[0].create(true));
-    HIPCHK(c, c->adaptiveEvents[1].create(true));
-    HIPCHK(c, c->adaptiveCounts.alloc(n)); // (last: its pointer says that the state is complete)
+    auto b = std::make_unique<pt_ctx::Adaptive::Buffers>(); // (the context gets it whole: a failure on the way frees what there is)
+    HIPCHK(c, b->half[0].alloc(n));
+    HIPCHK(c, b->half[1].alloc(n));
+    HIPCHK(c, b->error.alloc(n));
+    HIPCHK(c, b->blockError.alloc(nB));
+    HIPCHK(c, b->flags.alloc(nB));
+    HIPCHK(c, b->counters.alloc(kAdaptiveStripes));
+    HIPCHK(c, b->back.alloc(nB + kAdaptiveCounterWords));
+    HIPCHK(c, c->adaptive.events[0].create(true));
+    HIPCHK(c, c->adaptive.events[1].create(true));
+    HIPCHK(c, b->counts.alloc(n));
+    c->adaptive.buf = std::move(b);
     return clearAdaptive(c);
 }
 
-void releaseAdaptive(pt_ctx* c)
-{
-    c->adaptiveHalf[0].release(), c->adaptiveHalf[1].release(), c->adaptiveCounts.release(), c->adaptiveError.release();
-    c->adaptiveBlockError.release(), c->adaptiveFlags.release(), c->adaptiveCounters.release(), c->adaptiveBack.release();
-}
-
 // Steps 4 to 6 of a round: the blocks flagged on the device got `add` samples per pixel (0: judge the state as it stands); count, judge, publish the
-// accumulator for `spp` = the largest count, read the flags and counters back behind a synchronisation.  Fused: one launch does all of it
-// (EXPERIMENTS.md, "Adaptive sampling" has the two-launch form timed against it; PTAMD_ADAPTIVE_SPLIT selects that one, diagnostics).
+// accumulator for `spp` = the largest count, read the flags and counters back behind a synchronisation.  One launch does all of it (DESIGN.md,
+// section 10, has the two-launch form it was timed against).
 int evaluateAdaptive(pt_ctx* c, uint32_t add, uint32_t spp)
 {
-    static const bool split = getenv("PTAMD_ADAPTIVE_SPLIT") != nullptr;
+    pt_ctx::Adaptive::Buffers& b = *c->adaptive.buf;
     const uint32_t W = c->cfg.width, H = c->cfg.height, nB = adaptiveBlocks(c);
-    HIPCHK(c, hipMemsetAsync(c->adaptiveCounters.p, 0, kAdaptiveStripes * sizeof(AdaptiveCounters), c->stream));
+    HIPCHK(c, b.counters.zero(c->stream));
     AdaptiveArgs a {};
-    a.A = c->adaptiveHalf[0].p, a.B = c->adaptiveHalf[1].p, a.counts = c->adaptiveCounts.p, a.error = c->adaptiveError.p;
-    a.blockError = c->adaptiveBlockError.p, a.flags = c->adaptiveFlags.p, a.counters = c->adaptiveCounters.p, a.accum = c->accum;
+    a.A = b.half[0].p, a.B = b.half[1].p, a.counts = b.counts.p, a.error = b.error.p;
+    a.blockError = b.blockError.p, a.flags = b.flags.p, a.counters = b.counters.p, a.accum = c->accum;
     a.width = W, a.height = H, a.blocksX = adaptiveBlocksX(c), a.blocks = nB;
     a.add = add, a.spp = spp;
-    a.minSamples = c->adaptivePrm.min_samples, a.maxSamples = c->adaptivePrm.max_samples, a.threshold = c->adaptivePrm.threshold;
-    HIPCHK(c, hipEventRecord(c->adaptiveEvents[0], c->stream));
-    if (split) {
-        hipLaunchKernelGGL(k_adaptive_eval<false>, dim3((nB + 3u) / 4u), dim3(256), 0, c->stream, a);
-        hipLaunchKernelGGL(k_adaptive_publish, dim3((W * H + 255u) / 256u), dim3(256), 0, c->stream, a.A, a.B, (const uint32_t*)a.counts, a.accum, W * H, spp);
-    } else {
-        hipLaunchKernelGGL(k_adaptive_eval<true>, dim3((nB + 3u) / 4u), dim3(256), 0, c->stream, a);
-    }
+    a.minSamples = c->adaptive.prm.min_samples, a.maxSamples = c->adaptive.prm.max_samples, a.threshold = c->adaptive.prm.threshold;
+    HIPCHK(c, hipEventRecord(c->adaptive.events[0], c->stream));
+    hipLaunchKernelGGL(k_adaptive_eval, dim3((nB + 3u) / 4u), dim3(256), 0, c->stream, a);
     HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipEventRecord(c->adaptiveEvents[1], c->stream));
+    HIPCHK(c, hipEventRecord(c->adaptive.events[1], c->stream));
     c->spp = spp;
-    HIPCHK(c, hipMemcpyAsync(c->adaptiveBack.p, c->adaptiveFlags.p, nB * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->adaptiveBack.p + nB, c->adaptiveCounters.p, kAdaptiveStripes * sizeof(AdaptiveCounters), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, b.flags.copyTo(b.back.p, c->stream));
+    HIPCHK(c, b.counters.read(b.back.p + nB, c->stream));
     AdaptiveCounters k {};
     for (uint32_t s = 0; s < kAdaptiveStripes; s++) { // (the stripes the blocks spread their atomics over)
         AdaptiveCounters one;
-        std::memcpy(&one, c->adaptiveBack.p + nB + s * (sizeof(AdaptiveCounters) / sizeof(uint32_t)), sizeof(one));
+        std::memcpy(&one, b.back.p + nB + s * (sizeof(AdaptiveCounters) / sizeof(uint32_t)), sizeof(one));
         k.active += one.active, k.nonfinite += one.nonfinite, k.total += one.total;
         k.maxErrorBits = std::max(k.maxErrorBits, one.maxErrorBits), k.maxNotCount = std::max(k.maxNotCount, one.maxNotCount);
     }
-    pt_adaptive_stats& st = c->adaptiveStats;
+    pt_adaptive_stats& st = c->adaptive.stats;
     st.blocks = nB, st.active_blocks = k.active, st.nonfinite = k.nonfinite;
     st.min_count = ~k.maxNotCount, st.max_count = spp, st.samples_total = k.total;
     std::memcpy(&st.max_block_error, &k.maxErrorBits, sizeof(float));
     float ms = 0;
-    if (hipEventElapsedTime(&ms, c->adaptiveEvents[0], c->adaptiveEvents[1]) == hipSuccess)
-        c->adaptiveTiming[0] += ms, c->adaptiveTiming[1] += 1.0;
+    if (hipEventElapsedTime(&ms, c->adaptive.events[0], c->adaptive.events[1]) == hipSuccess)
+        c->adaptive.timing[0] += ms, c->adaptive.timing[1] += 1.0;
     else
         (void)hipGetLastError();
     return PT_OK;
@@ -1068,7 +1063,7 @@ int pt_set_tiles(pt_ctx* c, const pt_rect* rects, uint32_t n)
     return guarded(c, "pt_set_tiles", [&]() -> int {
     if (!c)
         return PT_ERR_INVALID;
-    if (c->adaptiveSet && n != 0 && rects)
+    if (c->adaptive.set && n != 0 && rects)
         return fail(c, PT_ERR_UNSUPPORTED, "pt_set_tiles: adaptive sampling is on (pt_set_adaptive) -- it owns the pixel list; sharded adaptive sampling is not supported");
     HIPCHK(c, hipSetDevice(c->device));
     return installPixelRects(c, rects, n);
@@ -1111,7 +1106,7 @@ int pt_clear(pt_ctx* c)
     c->mergePending = false;
     if (parityMode(c) && c->queuesReady && (rc = resetStreams(c)))
         return rc;
-    if (c->adaptiveSet && c->adaptiveCounts.p && (rc = clearAdaptive(c))) // the halves, counts and errors belong to the image; the mode stays set
+    if (c->adaptive.set && c->adaptive.buf && (rc = clearAdaptive(c))) // the halves, counts and errors belong to the image; the mode stays set
         return rc;
     return PT_OK;
     });
@@ -1208,7 +1203,7 @@ int pt_render(pt_ctx* c, uint32_t spp)
     return guarded(c, "pt_render", [&]() -> int {
     if (!c)
         return PT_ERR_INVALID;
-    if (c->adaptiveSet)
+    if (c->adaptive.set)
         return fail(c, PT_ERR_STATE, "pt_render: adaptive sampling is on -- pt_render_adaptive renders, or pt_clear and pt_set_adaptive(NULL)");
     if (!c->haveStatic || !c->haveDynamic || !c->haveCamera)
         return fail(c, PT_ERR_STATE, "pt_render: scene (static + dynamic) and camera must be set first");
@@ -1259,8 +1254,7 @@ int pt_resolve(pt_ctx* c, float* rgba_out)
     if (const int rc = resolveTarget(c, nullptr, &image))
         return rc;
     launchResolve(c, image);
-    HIPCHK(c, hipMemcpyAsync(rgba_out, image, c->resolveTmp.n * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, c->resolveTmp.read(rgba_out, c->stream));
     return checkOverflow(c);
     });
 }
@@ -1291,7 +1285,7 @@ int pt_read_accum(pt_ctx* c, float* out)
     if (!c || !out)
         return PT_ERR_INVALID;
     HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipMemcpyAsync(out, c->accum, (size_t)c->cfg.width * c->cfg.height * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(out, c->accum, (size_t)c->cfg.width * c->cfg.height * sizeof(float4), hipMemcpyDeviceToHost, c->stream)); // (not a DevBuf: the caller's memory, perhaps -- pt_set_accum_buffer)
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return checkOverflow(c);
 }
@@ -1300,10 +1294,10 @@ int pt_write_accum(pt_ctx* c, const float* in, uint32_t spp)
 {
     if (!c || !in)
         return PT_ERR_INVALID;
-    if (c->adaptiveSet)
+    if (c->adaptive.set)
         return fail(c, PT_ERR_STATE, "pt_write_accum: adaptive sampling is on -- the accumulator is made from the halves (pt_write_adaptive)");
     HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipMemcpyAsync(c->accum, in,(size_t)c->cfg.width * c->cfg.height * sizeof(float4), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->accum, in, (size_t)c->cfg.width * c->cfg.height * sizeof(float4), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->spp = spp;
     return PT_OK;
@@ -1326,6 +1320,24 @@ int fixedScheduleOnly(pt_ctx* c, const char* who)
 }
 
 bool tilesSet(const pt_ctx* c) { return (uint64_t)c->numOwned != (uint64_t)c->cfg.width * c->cfg.height; }
+
+// What the frame stages (filter, history, clamp) refuse alike, in two parts because the history asks for its camera between them: a context that owns
+// part of the frame (`why`: what the stage needs the rest for, and what to do instead) ...
+int wholeFrameOnly(pt_ctx* c, const char* who, const char* why)
+{
+    if (tilesSet(c))
+        return fail(c, PT_ERR_UNSUPPORTED, "%s: tiles are set -- %s, on a context that owns the frame", who, why);
+    return PT_OK;
+}
+// ... and an image without colour or guide samples
+int samplesPresent(pt_ctx* c, const char* who)
+{
+    if (c->spp == 0)
+        return fail(c, PT_ERR_STATE, "%s: no colour samples yet (pt_render)", who);
+    if (c->guideSpp == 0)
+        return fail(c, PT_ERR_STATE, "%s: no guide samples yet (pt_render_guides)", who);
+    return PT_OK;
+}
 
 } // namespace
 
@@ -1411,10 +1423,10 @@ int pt_render_guides(pt_ctx* c, uint32_t spp)
             continue;
         }
         launchTrace(c, false, a);
-        if (c->vertexMotionSet && c->vertexDeformed) // (the snapshot, never the inactive set: the next state may be on its way into that)
-            launchGuides<2>(c, n, GuideMotionArgs { c->motionRecords.p, c->motionGuides[0], c->motionGuides[1], c->fatThen.p, c->vertexRows.p });
-        else if (c->motionSet || c->vertexMotionSet) // (vertex motion with nothing deformed: identity records, exact zeros and the bits of N)
-            launchGuides<1>(c, n, GuideMotionArgs { c->motionRecords.p, c->motionGuides[0], c->motionGuides[1], nullptr, nullptr });
+        if (c->vertexMotion.set && c->vertexMotion.deformed) // (the snapshot, never the inactive set: the next state may be on its way into that)
+            launchGuides<2>(c, n, GuideMotionArgs { c->motion.records.p, c->motionGuides[0], c->motionGuides[1], c->vertexMotion.fatThen.p, c->vertexMotion.rows.p });
+        else if (c->motion.set || c->vertexMotion.set) // (vertex motion with nothing deformed: identity records, exact zeros and the bits of N)
+            launchGuides<1>(c, n, GuideMotionArgs { c->motion.records.p, c->motionGuides[0], c->motionGuides[1], nullptr, nullptr });
         else
             launchGuides<0>(c, n, GuideMotionArgs {});
     }
@@ -1441,7 +1453,7 @@ int pt_set_guide_chain(pt_ctx* c, uint32_t maxTransmissions)
     if (maxTransmissions != 0u) {
         if (const int rc = fixedScheduleOnly(c, "pt_set_guide_chain"))
             return rc;
-        if (c->motionSet || c->vertexMotionSet)
+        if (c->motion.set || c->vertexMotion.set)
             return fail(c, PT_ERR_UNSUPPORTED, "pt_set_guide_chain: an instance or vertex motion is set -- motion deposits along a chain are not supported");
     }
     if (c->guideSpp != 0)
@@ -1503,8 +1515,7 @@ int pt_debug_read_guide_chain_terminals(pt_ctx* c, int32_t* out4)
     if (!c->guideChainTerminals.p)
         return fail(c, PT_ERR_STATE, "pt_debug_read_guide_chain_terminals: the records are not enabled (pt_debug_guide_chain_terminals)");
     HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipMemcpyAsync(out4, c->guideChainTerminals.p, c->guideChainTerminals.n * sizeof(int4), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, c->guideChainTerminals.read(out4, c->stream));
     return PT_OK;
     });
 }
@@ -1538,35 +1549,30 @@ void resolveGuideSigmas(float k_normal, float sigma_depth, float* kNormal, float
     *invSigmaDepth = 1.0f / (sigma_depth > 0.f ? sigma_depth : PT_DENOISE_DEFAULT_SIGMA_DEPTH);
 }
 
-// the run-time switches of a call to the instantiation that has them as template flags
+// the run-time switches of a call to the instantiation that has them as template flags: one table per kernel family, indexed by the switches as bits
 // (clamped: `source` is the firefly plane, PT_DENOISE_INPUT_ACCUM alone)
 void launchPrepare(pt_ctx* c, uint32_t input, bool clamped, const float4* source, const float* variance, uint32_t n)
 {
-    const auto k = input == PT_DENOISE_INPUT_ACCUM ? (clamped ? k_denoise_prepare<PT_DENOISE_INPUT_ACCUM, true> : k_denoise_prepare<PT_DENOISE_INPUT_ACCUM>)
-        : (input == PT_DENOISE_INPUT_TEMPORAL ? k_denoise_prepare<PT_DENOISE_INPUT_TEMPORAL> : k_denoise_prepare<PT_DENOISE_INPUT_TEMPORAL_VARIANCE>);
-    hipLaunchKernelGGL(k, dim3((n + 255u) / 256u), dim3(256), 0, c->stream, source, variance, c->guides[0], c->guides[1], c->denoiseColour[0].p,
+    static_assert(PT_DENOISE_INPUT_ACCUM == 0 && PT_DENOISE_INPUT_TEMPORAL == 1 && PT_DENOISE_INPUT_TEMPORAL_VARIANCE == 2, "the table below is indexed by the input");
+    static const decltype(&k_denoise_prepare<PT_DENOISE_INPUT_ACCUM>) table[4] = { k_denoise_prepare<PT_DENOISE_INPUT_ACCUM>, k_denoise_prepare<PT_DENOISE_INPUT_TEMPORAL>,
+        k_denoise_prepare<PT_DENOISE_INPUT_TEMPORAL_VARIANCE>, k_denoise_prepare<PT_DENOISE_INPUT_ACCUM, true> };
+    hipLaunchKernelGGL(table[clamped ? 3u : input], dim3((n + 255u) / 256u), dim3(256), 0, c->stream, source, variance, c->guides[0], c->guides[1], c->denoiseColour[0].p,
         c->denoiseGuide.p, n, (float)c->spp, (float)c->guideSpp);
 }
 void launchAtrous(hipStream_t stream, dim3 grid, dim3 block, bool inLds, bool guided, const AtrousArgs& a)
 {
-    hipLaunchKernelGGL(inLds ? (guided ? k_atrous<true, true> : k_atrous<true>) : (guided ? k_atrous<false, true> : k_atrous<false>), grid, block, 0, stream, a);
+    static const decltype(&k_atrous<false>) table[4] = { k_atrous<false>, k_atrous<true>, k_atrous<false, true>, k_atrous<true, true> };
+    hipLaunchKernelGGL(table[inLds | guided << 1], grid, block, 0, stream, a);
 }
 void launchTemporal(hipStream_t stream, dim3 grid, dim3 block, bool moved, bool variance, bool response, const TemporalArgs& a)
 {
-    if (a.firefly) { // (pt_set_firefly_clamp: d comes from the clamped plane)
-        if (response)
-            hipLaunchKernelGGL(moved ? (variance ? k_temporal<true, true, true, true> : k_temporal<true, false, true, true>)
-                                     : (variance ? k_temporal<false, true, true, true> : k_temporal<false, false, true, true>), grid, block, 0, stream, a);
-        else
-            hipLaunchKernelGGL(moved ? (variance ? k_temporal<true, true, false, true> : k_temporal<true, false, false, true>)
-                                     : (variance ? k_temporal<false, true, false, true> : k_temporal<false, false, false, true>), grid, block, 0, stream, a);
-        return;
-    }
-    if (response)
-        hipLaunchKernelGGL(moved ? (variance ? k_temporal<true, true, true> : k_temporal<true, false, true>)
-                                 : (variance ? k_temporal<false, true, true> : k_temporal<false, false, true>), grid, block, 0, stream, a);
-    else
-        hipLaunchKernelGGL(moved ? (variance ? k_temporal<true, true> : k_temporal<true>) : (variance ? k_temporal<false, true> : k_temporal<false>), grid, block, 0, stream, a);
+    static const decltype(&k_temporal<false>) table[16] = { // <moved, variance, response, firefly>
+        k_temporal<false, false, false, false>, k_temporal<true, false, false, false>, k_temporal<false, true, false, false>, k_temporal<true, true, false, false>,
+        k_temporal<false, false, true, false>, k_temporal<true, false, true, false>, k_temporal<false, true, true, false>, k_temporal<true, true, true, false>,
+        k_temporal<false, false, false, true>, k_temporal<true, false, false, true>, k_temporal<false, true, false, true>, k_temporal<true, true, false, true>,
+        k_temporal<false, false, true, true>, k_temporal<true, false, true, true>, k_temporal<false, true, true, true>, k_temporal<true, true, true, true> };
+    const bool firefly = a.firefly != nullptr; // (pt_set_firefly_clamp: d comes from the clamped plane)
+    hipLaunchKernelGGL(table[moved | variance << 1 | response << 2 | firefly << 3], grid, block, 0, stream, a);
 }
 
 // The firefly clamp's one launch (pt_firefly.h): the plane and the counters of the current accumulator and albedo sums, on the render stream.  The
@@ -1575,18 +1581,18 @@ int evaluateFirefly(pt_ctx* c)
 {
     const uint32_t W = c->cfg.width, H = c->cfg.height;
     const size_t n = (size_t)W * H;
-    if (c->fireflyPlane.n != n) {
-        HIPCHK(c, c->fireflyPlane.alloc(n));
-        HIPCHK(c, c->fireflyCounts.alloc(2));
+    if (c->firefly.plane.n != n) {
+        HIPCHK(c, c->firefly.plane.alloc(n));
+        HIPCHK(c, c->firefly.counts.alloc(2));
     }
-    HIPCHK(c, hipMemsetAsync(c->fireflyCounts.p, 0, 2 * sizeof(uint32_t), c->stream));
+    HIPCHK(c, c->firefly.counts.zero(c->stream));
     FireflyArgs f {};
-    f.accum = c->accum, f.albedoHits = c->guides[0], f.plane = c->fireflyPlane.p, f.counts = c->fireflyCounts.p;
+    f.accum = c->accum, f.albedoHits = c->guides[0], f.plane = c->firefly.plane.p, f.counts = c->firefly.counts.p;
     f.width = W, f.height = H, f.spp = (float)c->spp, f.gspp = (float)c->guideSpp;
-    f.rank = c->fireflyRank, f.scale = c->fireflyScale;
-    hipLaunchKernelGGL(k_firefly, dim3((W + kAtrousTileW - 1) / kAtrousTileW, (H + kAtrousTileH - 1) / kAtrousTileH), dim3(kAtrousTileW, kAtrousTileH), 0, c->stream, f);
+    f.rank = c->firefly.rank, f.scale = c->firefly.scale;
+    hipLaunchKernelGGL(k_firefly, tileGrid(W, H, kAtrousTileW, kAtrousTileH), dim3(kAtrousTileW, kAtrousTileH), 0, c->stream, f);
     HIPCHK(c, hipGetLastError());
-    c->fireflyEvaluated = true;
+    c->firefly.evaluated = true;
     return PT_OK;
 }
 
@@ -1603,17 +1609,14 @@ int pt_denoise_device(pt_ctx* c, const pt_denoise_params* prm, void* device_rgba
         return fail(c, PT_ERR_INVALID, "pt_denoise: output = %u (PT_DENOISE_TONEMAPPED or PT_DENOISE_HDR)", prm->output);
     if (prm->k_normal < 0.f || prm->sigma_depth < 0.f || prm->sigma_lum < 0.f)
         return fail(c, PT_ERR_INVALID, "pt_denoise: negative filter parameter");
-    if (tilesSet(c))
-        return fail(c, PT_ERR_UNSUPPORTED, "pt_denoise: tiles are set -- the filter needs every pixel's neighbours; denoise after the reduce, on a context that owns the frame");
-    if (c->spp == 0)
-        return fail(c, PT_ERR_STATE, "pt_denoise: no colour samples yet (pt_render)");
-    if (c->guideSpp == 0)
-        return fail(c, PT_ERR_STATE, "pt_denoise: no guide samples yet (pt_render_guides)");
+    int rc;
+    if ((rc = wholeFrameOnly(c, "pt_denoise", "the filter needs every pixel's neighbours; denoise after the reduce")) || (rc = samplesPresent(c, "pt_denoise")))
+        return rc;
     if (prm->input != PT_DENOISE_INPUT_ACCUM && prm->input != PT_DENOISE_INPUT_TEMPORAL && prm->input != PT_DENOISE_INPUT_TEMPORAL_VARIANCE)
         return fail(c, PT_ERR_INVALID, "pt_denoise: input = %u (PT_DENOISE_INPUT_ACCUM, PT_DENOISE_INPUT_TEMPORAL or PT_DENOISE_INPUT_TEMPORAL_VARIANCE)", prm->input);
     const bool guided = prm->input == PT_DENOISE_INPUT_TEMPORAL_VARIANCE; // the history, filtered under its variance
     const bool temporal = prm->input == PT_DENOISE_INPUT_TEMPORAL || guided;
-    if (guided && !c->varianceSet)
+    if (guided && !c->variance.set)
         return fail(c, PT_ERR_STATE, "pt_denoise: PT_DENOISE_INPUT_TEMPORAL_VARIANCE while the temporal variance is off (pt_set_temporal_variance)");
     if (temporal && c->temporalFrames == 0)
         return fail(c, PT_ERR_STATE, "pt_denoise: PT_DENOISE_INPUT_TEMPORAL%s without a history (pt_temporal_accumulate)", guided ? "_VARIANCE" : "");
@@ -1623,7 +1626,7 @@ int pt_denoise_device(pt_ctx* c, const pt_denoise_params* prm, void* device_rgba
     HIPCHK(c, hipSetDevice(c->device));
     const uint32_t W = c->cfg.width, H = c->cfg.height, n = W * H;
     float4* image;
-    if (const int rc = resolveTarget(c, device_rgba, &image))
+    if ((rc = resolveTarget(c, device_rgba, &image)))
         return rc;
     const PlanePair& history = c->temporal[c->temporalNewest];
     const dim3 lin((n + 255u) / 256u);
@@ -1643,11 +1646,10 @@ int pt_denoise_device(pt_ctx* c, const pt_denoise_params* prm, void* device_rgba
         HIPCHK(c, c->denoiseColour[1].alloc(n));
         HIPCHK(c, c->denoiseGuide.alloc(n));
     }
-    const bool clamped = c->fireflySet && !temporal; // d_0 is the clamped plane, made afresh (the history was fed clamped frames already)
-    if (clamped)
-        if (const int rc = evaluateFirefly(c))
-            return rc;
-    launchPrepare(c, prm->input, clamped, temporal ? history[0] : (clamped ? c->fireflyPlane.p : c->accum), guided ? c->temporalVariance[c->temporalNewest].p : nullptr, n);
+    const bool clamped = c->firefly.set && !temporal; // d_0 is the clamped plane, made afresh (the history was fed clamped frames already)
+    if (clamped && (rc = evaluateFirefly(c)))
+        return rc;
+    launchPrepare(c, prm->input, clamped, temporal ? history[0] : (clamped ? c->firefly.plane.p : c->accum), guided ? c->variance.plane[c->temporalNewest].p : nullptr, n);
     AtrousArgs a {};
     a.guide = c->denoiseGuide.p;
     a.albedoHits = c->guides[0];
@@ -1656,8 +1658,8 @@ int pt_denoise_device(pt_ctx* c, const pt_denoise_params* prm, void* device_rgba
     const float sigmaLum = prm->sigma_lum > 0.f ? prm->sigma_lum : PT_DENOISE_DEFAULT_SIGMA_LUM;
     a.gspp = (float)c->guideSpp;
     a.relativeAperture = c->camera.relativeAperture, a.shutterTime = c->camera.shutterTime, a.ISO = c->camera.ISO;
-    a.history = history[0], a.sigmaVariance = c->sigmaVariance, a.relativeFloor = c->relativeFloor, a.invFullHistory = 1.0f / (c->fullHistory - 1.0f); // (guided)
-    const dim3 grid((W + kAtrousTileW - 1) / kAtrousTileW, (H + kAtrousTileH - 1) / kAtrousTileH), block(kAtrousTileW, kAtrousTileH);
+    a.history = history[0], a.sigmaVariance = c->variance.sigma, a.relativeFloor = c->variance.relativeFloor, a.invFullHistory = 1.0f / (c->variance.fullHistory - 1.0f); // (guided)
+    const dim3 grid = tileGrid(W, H, kAtrousTileW, kAtrousTileH), block(kAtrousTileW, kAtrousTileH);
     for (uint32_t i = 0; i < prm->iterations; i++) {
         const bool last = i + 1u == prm->iterations;
         a.colour = c->denoiseColour[i & 1u].p;
@@ -1682,8 +1684,7 @@ int pt_denoise(pt_ctx* c, const pt_denoise_params* prm, float* rgba_out, float* 
     if (rc)
         return rc;
     HIPCHK(c, hipEventRecord(c->evDenoise[1], c->stream));
-    HIPCHK(c, hipMemcpyAsync(rgba_out, c->resolveTmp.p, (size_t)c->cfg.width * c->cfg.height * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, c->resolveTmp.read(rgba_out, c->stream));
     if (ms_out)
         HIPCHK(c, hipEventElapsedTime(ms_out, c->evDenoise[0], c->evDenoise[1]));
     return checkOverflow(c);
@@ -1711,23 +1712,43 @@ int ensureTemporal(pt_ctx* c)
     int rc;
     if ((rc = c->temporal[0].ensure(c)) || (rc = c->temporal[1].ensure(c)))
         return rc;
-    if (c->varianceSet && !c->temporalVariance[0].p)
-        for (DevBuf<float>& plane : c->temporalVariance) {
-            HIPCHK(c, plane.alloc((size_t)c->cfg.width * c->cfg.height));
-            HIPCHK(c, hipMemsetAsync(plane.p, 0, plane.n * sizeof(float), c->stream));
-        }
-    if (c->responseSet && !c->temporalFast[0].p) {
-        const size_t n = (size_t)c->cfg.width * c->cfg.height;
-        for (DevBuf<float4>& image : c->temporalFast) {
-            HIPCHK(c, image.alloc(n));
-            HIPCHK(c, hipMemsetAsync(image.p, 0, n * sizeof(float4), c->stream));
-        }
-        HIPCHK(c, c->responseLuminance.alloc(n));
-        HIPCHK(c, hipMemsetAsync(c->responseLuminance.p, 0, n * sizeof(float2), c->stream));
-        HIPCHK(c, c->responseMix.alloc(n));
-        HIPCHK(c, hipMemsetAsync(c->responseMix.p, 0, n * sizeof(float), c->stream));
+    const size_t n = (size_t)c->cfg.width * c->cfg.height;
+    if (c->variance.set)
+        for (DevBuf<float>& plane : c->variance.plane)
+            HIPCHK(c, plane.ensureZeroed(n, c->stream));
+    if (c->response.set) {
+        for (DevBuf<float4>& image : c->response.fast)
+            HIPCHK(c, image.ensureZeroed(n, c->stream));
+        HIPCHK(c, c->response.luminance.ensureZeroed(n, c->stream));
+        HIPCHK(c, c->response.mix.ensureZeroed(n, c->stream));
     }
     return PT_OK;
+}
+
+// What the setters of the two temporal modes share: no parameter negative or non-finite ...
+int nonNegativeFinite(pt_ctx* c, const char* who, std::initializer_list<float> given)
+{
+    for (const float f : given)
+        if (!(f >= 0.0f) || !std::isfinite(f))
+            return fail(c, PT_ERR_INVALID, "%s: negative or non-finite parameter", who);
+    return PT_OK;
+}
+// ... and a mode that changes only while there is no history
+int noHistoryOnly(pt_ctx* c, const char* who)
+{
+    if (c->temporalFrames != 0)
+        return fail(c, PT_ERR_STATE, "%s: a history of %u frames exists -- set or forget the mode right after pt_temporal_reset", who, c->temporalFrames);
+    return PT_OK;
+}
+// What the transfers of the two modes' planes share: PT_OK with the mode on (`set`; "variance" or "response"), a history there and the buffers allocated
+int temporalModeReady(pt_ctx* c, const char* who, bool set, const char* mode)
+{
+    if (!set)
+        return fail(c, PT_ERR_STATE, "%s: the temporal %s is off (pt_set_temporal_%s)", who, mode, mode);
+    if (c->temporalFrames == 0)
+        return fail(c, PT_ERR_STATE, "%s: no history (pt_temporal_accumulate, pt_write_temporal)", who);
+    HIPCHK(c, hipSetDevice(c->device));
+    return ensureTemporal(c);
 }
 
 struct D3 {
@@ -1748,17 +1769,15 @@ int pt_temporal_accumulate(pt_ctx* c, const pt_temporal_params* prm)
         return fail(c, PT_ERR_INVALID, "pt_temporal_accumulate: max_history = %u (1..4096; 0 = 32)", prm->max_history);
     if (!(prm->k_normal >= 0.f) || !(prm->sigma_depth >= 0.f))
         return fail(c, PT_ERR_INVALID, "pt_temporal_accumulate: negative or NaN k_normal / sigma_depth");
-    if (tilesSet(c))
-        return fail(c, PT_ERR_UNSUPPORTED, "pt_temporal_accumulate: tiles are set -- the history is reprojected across the whole frame; accumulate after the reduce, on a context that owns the frame");
+    int rc;
+    if ((rc = wholeFrameOnly(c, "pt_temporal_accumulate", "the history is reprojected across the whole frame; accumulate after the reduce")))
+        return rc;
     if (!c->haveCamera)
         return fail(c, PT_ERR_STATE, "pt_temporal_accumulate: no camera yet (pt_set_camera)");
-    if (c->spp == 0)
-        return fail(c, PT_ERR_STATE, "pt_temporal_accumulate: no colour samples yet (pt_render)");
-    if (c->guideSpp == 0)
-        return fail(c, PT_ERR_STATE, "pt_temporal_accumulate: no guide samples yet (pt_render_guides)");
+    if ((rc = samplesPresent(c, "pt_temporal_accumulate")))
+        return rc;
     HIPCHK(c, hipSetDevice(c->device));
-    int rc = ensureTemporal(c);
-    if (rc)
+    if ((rc = ensureTemporal(c)))
         return rc;
     const int from = c->temporalNewest, to = from ^ 1;
     TemporalArgs a {};
@@ -1782,28 +1801,28 @@ int pt_temporal_accumulate(pt_ctx* c, const pt_temporal_params* prm)
             a.rowLambda = scaledToV3(uv, 1.0 / det), a.rowAlpha = scaledToV3(vs, 1.0 / det), a.rowBeta = scaledToV3(su, 1.0 / det);
         }
     }
-    const dim3 grid((a.width + kTemporalTileW - 1) / kTemporalTileW, (a.height + kTemporalTileH - 1) / kTemporalTileH), block(kTemporalTileW, kTemporalTileH);
-    const bool moved = c->motionSet || c->vertexMotionSet; // the history is met where the surfaces were (the two sums are there: the setters made them)
+    const dim3 grid = tileGrid(a.width, a.height, kTemporalTileW, kTemporalTileH), block(kTemporalTileW, kTemporalTileH);
+    const bool moved = c->motion.set || c->vertexMotion.set; // the history is met where the surfaces were (the two sums are there: the setters made them)
     if (moved)
         a.motion = c->motionGuides[0], a.prevNormal = c->motionGuides[1];
-    a.histVariance = c->temporalVariance[from].p, a.outVariance = c->temporalVariance[to].p; // (varianceSet: the same arithmetic and one more plane)
-    a.histFast = c->temporalFast[from].p, a.outFast = c->temporalFast[to].p, a.outLuminance = c->responseLuminance.p, a.fastHistory = c->fastHistory; // (responseSet)
-    if (c->fireflySet) { // the current frame's d comes clamped, from a plane made afresh
+    a.histVariance = c->variance.plane[from].p, a.outVariance = c->variance.plane[to].p; // (varianceSet: the same arithmetic and one more plane)
+    a.histFast = c->response.fast[from].p, a.outFast = c->response.fast[to].p, a.outLuminance = c->response.luminance.p, a.fastHistory = c->response.fastHistory; // (responseSet)
+    if (c->firefly.set) { // the current frame's d comes clamped, from a plane made afresh
         if ((rc = evaluateFirefly(c)))
             return rc;
-        a.firefly = c->fireflyPlane.p;
+        a.firefly = c->firefly.plane.p;
     }
-    launchTemporal(c->stream, grid, block, moved, c->varianceSet, c->responseSet, a);
+    launchTemporal(c->stream, grid, block, moved, c->variance.set, c->response.set, a);
     HIPCHK(c, hipGetLastError());
-    if (c->responseSet) {
+    if (c->response.set) {
         if (a.histColour) { // the two histories of every pixel are there: mix them where the window says so
             ResponseArgs r {};
-            r.luminance = c->responseLuminance.p, r.colour = a.outColour, r.fast = a.outFast, r.mix = c->responseMix.p;
-            r.width = a.width, r.height = a.height, r.sigmaResponse = c->sigmaResponse, r.relativeFloor = c->responseFloor;
+            r.luminance = c->response.luminance.p, r.colour = a.outColour, r.fast = a.outFast, r.mix = c->response.mix.p;
+            r.width = a.width, r.height = a.height, r.sigmaResponse = c->response.sigma, r.relativeFloor = c->response.relativeFloor;
             hipLaunchKernelGGL(k_temporal_response, grid, block, 0, c->stream, r);
             HIPCHK(c, hipGetLastError());
         } else // no history: fast = (d, 1) = colour_count, nothing to mix
-            HIPCHK(c, hipMemsetAsync(c->responseMix.p, 0, c->responseMix.n * sizeof(float), c->stream));
+            HIPCHK(c, c->response.mix.zero(c->stream));
     }
     c->temporalCamera = c->camera;
     c->temporalNewest = to;
@@ -1840,14 +1859,10 @@ int pt_write_temporal(pt_ctx* c, const float* colour_count, const float* normal_
     int rc;
     if ((rc = ensureTemporal(c)) || (rc = c->temporal[c->temporalNewest].write(c, colour_count, normal_depth)))
         return rc;
-    if (c->varianceSet) { // nothing is known about these colours' spread: pt_write_temporal_variance restores it
-        DevBuf<float>& plane = c->temporalVariance[c->temporalNewest];
-        HIPCHK(c, hipMemsetAsync(plane.p, 0, plane.n * sizeof(float), c->stream));
-    }
-    if (c->responseSet) { // the fast history restarts from the current frame: pt_write_temporal_fast restores it
-        DevBuf<float4>& image = c->temporalFast[c->temporalNewest];
-        HIPCHK(c, hipMemsetAsync(image.p, 0, image.n * sizeof(float4), c->stream));
-    }
+    if (c->variance.set) // nothing is known about these colours' spread: pt_write_temporal_variance restores it
+        HIPCHK(c, c->variance.plane[c->temporalNewest].zero(c->stream));
+    if (c->response.set) // the fast history restarts from the current frame: pt_write_temporal_fast restores it
+        HIPCHK(c, c->response.fast[c->temporalNewest].zero(c->stream));
     auto f4 = [](const float* p) { return make_float4(p[0], p[1], p[2], 0.f); };
     c->temporalCamera = CameraDev {};
     c->temporalCamera.eye = f4(made_under->eyePoint), c->temporalCamera.screen = f4(made_under->screenPoint);
@@ -1866,56 +1881,34 @@ int pt_set_temporal_variance(pt_ctx* c, const pt_variance_params* prm)
         return PT_ERR_INVALID;
     if (const int rc = fixedScheduleOnly(c, "pt_set_temporal_variance"))
         return rc;
+    int rc;
     if (prm) {
-        const float given[3] = { prm->sigma_variance, prm->relative_floor, prm->full_history };
-        for (const float f : given)
-            if (!(f >= 0.0f) || !std::isfinite(f))
-                return fail(c, PT_ERR_INVALID, "pt_set_temporal_variance: negative or non-finite parameter");
+        if ((rc = nonNegativeFinite(c, "pt_set_temporal_variance", { prm->sigma_variance, prm->relative_floor, prm->full_history })))
+            return rc;
         if (prm->full_history != 0.0f && prm->full_history < 2.0f)
             return fail(c, PT_ERR_INVALID, "pt_set_temporal_variance: full_history = %g (at least 2; 0 = %g)", (double)prm->full_history,
                 (double)PT_VARIANCE_DEFAULT_FULL_HISTORY);
     }
-    if (c->temporalFrames != 0)
-        return fail(c, PT_ERR_STATE, "pt_set_temporal_variance: a history of %u frames exists -- set or forget the mode right after pt_temporal_reset",
-            c->temporalFrames);
-    c->varianceSet = prm != nullptr;
+    if ((rc = noHistoryOnly(c, "pt_set_temporal_variance")))
+        return rc;
+    c->variance.set = prm != nullptr;
     if (prm) {
-        c->sigmaVariance = prm->sigma_variance > 0.f ? prm->sigma_variance : PT_VARIANCE_DEFAULT_SIGMA_VARIANCE;
-        c->relativeFloor = prm->relative_floor > 0.f ? prm->relative_floor : PT_VARIANCE_DEFAULT_RELATIVE_FLOOR;
-        c->fullHistory = prm->full_history > 0.f ? prm->full_history : PT_VARIANCE_DEFAULT_FULL_HISTORY;
+        c->variance.sigma = prm->sigma_variance > 0.f ? prm->sigma_variance : PT_VARIANCE_DEFAULT_SIGMA_VARIANCE;
+        c->variance.relativeFloor = prm->relative_floor > 0.f ? prm->relative_floor : PT_VARIANCE_DEFAULT_RELATIVE_FLOOR;
+        c->variance.fullHistory = prm->full_history > 0.f ? prm->full_history : PT_VARIANCE_DEFAULT_FULL_HISTORY;
     }
     return PT_OK;
 }
 
-int pt_temporal_variance(const pt_ctx* c) { return c && c->varianceSet ? 1 : 0; }
-
-namespace {
-
-// what reading and writing the plane share: PT_OK with the newest set's plane in place
-int variancePlane(pt_ctx* c, const char* who, DevBuf<float>** plane)
-{
-    if (!c->varianceSet)
-        return fail(c, PT_ERR_STATE, "%s: the temporal variance is off (pt_set_temporal_variance)", who);
-    if (c->temporalFrames == 0)
-        return fail(c, PT_ERR_STATE, "%s: no history (pt_temporal_accumulate, pt_write_temporal)", who);
-    HIPCHK(c, hipSetDevice(c->device));
-    if (const int rc = ensureTemporal(c))
-        return rc;
-    *plane = &c->temporalVariance[c->temporalNewest];
-    return PT_OK;
-}
-
-} // namespace
+int pt_temporal_variance(const pt_ctx* c) { return c && c->variance.set ? 1 : 0; }
 
 int pt_read_temporal_variance(pt_ctx* c, float* out)
 {
     if (!c || !out)
         return PT_ERR_INVALID;
-    DevBuf<float>* plane;
-    if (const int rc = variancePlane(c, "pt_read_temporal_variance", &plane))
+    if (const int rc = temporalModeReady(c, "pt_read_temporal_variance", c->variance.set, "variance"))
         return rc;
-    HIPCHK(c, hipMemcpyAsync(out, plane->p, plane->n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, c->variance.plane[c->temporalNewest].read(out, c->stream));
     return PT_OK;
 }
 
@@ -1923,15 +1916,13 @@ int pt_write_temporal_variance(pt_ctx* c, const float* in)
 {
     if (!c || !in)
         return PT_ERR_INVALID;
-    DevBuf<float>* plane;
-    if (const int rc = variancePlane(c, "pt_write_temporal_variance", &plane))
+    if (const int rc = temporalModeReady(c, "pt_write_temporal_variance", c->variance.set, "variance"))
         return rc;
-    HIPCHK(c, hipMemcpyAsync(plane->p, in, plane->n * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, c->variance.plane[c->temporalNewest].write(in, c->stream));
     return PT_OK;
 }
 
-void* pt_temporal_variance_device_ptr(pt_ctx* c) { return c && c->varianceSet ? (void*)c->temporalVariance[c->temporalNewest].p : nullptr; }
+void* pt_temporal_variance_device_ptr(pt_ctx* c) { return c && c->variance.set ? (void*)c->variance.plane[c->temporalNewest].p : nullptr; }
 
 // ---- temporal response (k_temporal<., ., true>, k_temporal_response) ----------------------------
 
@@ -1944,49 +1935,29 @@ int pt_set_temporal_response(pt_ctx* c, const pt_response_params* prm)
     if (prm) {
         if (prm->fast_history > 4096u)
             return fail(c, PT_ERR_INVALID, "pt_set_temporal_response: fast_history = %u (1..4096; 0 = %u)", prm->fast_history, PT_RESPONSE_DEFAULT_FAST_HISTORY);
-        const float given[2] = { prm->sigma_response, prm->relative_floor };
-        for (const float f : given)
-            if (!(f >= 0.0f) || !std::isfinite(f))
-                return fail(c, PT_ERR_INVALID, "pt_set_temporal_response: negative or non-finite parameter");
+        if (const int rc = nonNegativeFinite(c, "pt_set_temporal_response", { prm->sigma_response, prm->relative_floor }))
+            return rc;
     }
-    if (c->temporalFrames != 0)
-        return fail(c, PT_ERR_STATE, "pt_set_temporal_response: a history of %u frames exists -- set or forget the mode right after pt_temporal_reset",
-            c->temporalFrames);
-    c->responseSet = prm != nullptr;
+    if (const int rc = noHistoryOnly(c, "pt_set_temporal_response"))
+        return rc;
+    c->response.set = prm != nullptr;
     if (prm) {
-        c->fastHistory = (float)(prm->fast_history ? prm->fast_history : PT_RESPONSE_DEFAULT_FAST_HISTORY);
-        c->sigmaResponse = prm->sigma_response > 0.f ? prm->sigma_response : PT_RESPONSE_DEFAULT_SIGMA_RESPONSE;
-        c->responseFloor = prm->relative_floor > 0.f ? prm->relative_floor : PT_RESPONSE_DEFAULT_RELATIVE_FLOOR;
+        c->response.fastHistory = (float)(prm->fast_history ? prm->fast_history : PT_RESPONSE_DEFAULT_FAST_HISTORY);
+        c->response.sigma = prm->sigma_response > 0.f ? prm->sigma_response : PT_RESPONSE_DEFAULT_SIGMA_RESPONSE;
+        c->response.relativeFloor = prm->relative_floor > 0.f ? prm->relative_floor : PT_RESPONSE_DEFAULT_RELATIVE_FLOOR;
     }
     return PT_OK;
 }
 
-int pt_temporal_response(const pt_ctx* c) { return c && c->responseSet ? 1 : 0; }
-
-namespace {
-
-// what the three transfers share: PT_OK with the mode on, a history there and the buffers allocated
-int responseReady(pt_ctx* c, const char* who)
-{
-    if (!c->responseSet)
-        return fail(c, PT_ERR_STATE, "%s: the temporal response is off (pt_set_temporal_response)", who);
-    if (c->temporalFrames == 0)
-        return fail(c, PT_ERR_STATE, "%s: no history (pt_temporal_accumulate, pt_write_temporal)", who);
-    HIPCHK(c, hipSetDevice(c->device));
-    return ensureTemporal(c);
-}
-
-} // namespace
+int pt_temporal_response(const pt_ctx* c) { return c && c->response.set ? 1 : 0; }
 
 int pt_read_temporal_fast(pt_ctx* c, float* colour_count)
 {
     if (!c || !colour_count)
         return PT_ERR_INVALID;
-    if (const int rc = responseReady(c, "pt_read_temporal_fast"))
+    if (const int rc = temporalModeReady(c, "pt_read_temporal_fast", c->response.set, "response"))
         return rc;
-    const DevBuf<float4>& image = c->temporalFast[c->temporalNewest];
-    HIPCHK(c, hipMemcpyAsync(colour_count, image.p, image.n * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, c->response.fast[c->temporalNewest].read(colour_count, c->stream));
     return PT_OK;
 }
 
@@ -1994,11 +1965,9 @@ int pt_write_temporal_fast(pt_ctx* c, const float* colour_count)
 {
     if (!c || !colour_count)
         return PT_ERR_INVALID;
-    if (const int rc = responseReady(c, "pt_write_temporal_fast"))
+    if (const int rc = temporalModeReady(c, "pt_write_temporal_fast", c->response.set, "response"))
         return rc;
-    const DevBuf<float4>& image = c->temporalFast[c->temporalNewest];
-    HIPCHK(c, hipMemcpyAsync(image.p, colour_count, image.n * sizeof(float4), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, c->response.fast[c->temporalNewest].write(colour_count, c->stream));
     return PT_OK;
 }
 
@@ -2006,14 +1975,13 @@ int pt_read_temporal_response(pt_ctx* c, float* s_out)
 {
     if (!c || !s_out)
         return PT_ERR_INVALID;
-    if (const int rc = responseReady(c, "pt_read_temporal_response"))
+    if (const int rc = temporalModeReady(c, "pt_read_temporal_response", c->response.set, "response"))
         return rc;
-    HIPCHK(c, hipMemcpyAsync(s_out, c->responseMix.p, c->responseMix.n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, c->response.mix.read(s_out, c->stream));
     return PT_OK;
 }
 
-void* pt_temporal_fast_device_ptr(pt_ctx* c) { return c && c->responseSet ? (void*)c->temporalFast[c->temporalNewest].p : nullptr; }
+void* pt_temporal_fast_device_ptr(pt_ctx* c) { return c && c->response.set ? (void*)c->response.fast[c->temporalNewest].p : nullptr; }
 
 // ---- firefly clamp (k_firefly, k_temporal<., ., ., true>, k_denoise_prepare<., true>) ------------
 
@@ -2029,26 +1997,23 @@ int pt_set_firefly_clamp(pt_ctx* c, const pt_firefly_params* prm)
         if (!std::isfinite(prm->scale) || prm->scale < 0.0f || (prm->scale > 0.0f && prm->scale < 1.0f))
             return fail(c, PT_ERR_INVALID, "pt_set_firefly_clamp: scale = %g (at least 1; 0 = %g)", (double)prm->scale, (double)PT_FIREFLY_DEFAULT_SCALE);
     }
-    c->fireflySet = prm != nullptr;
+    c->firefly.set = prm != nullptr;
     if (prm) {
-        c->fireflyRank = prm->rank ? prm->rank : PT_FIREFLY_DEFAULT_RANK;
-        c->fireflyScale = prm->scale > 0.f ? prm->scale : PT_FIREFLY_DEFAULT_SCALE;
+        c->firefly.rank = prm->rank ? prm->rank : PT_FIREFLY_DEFAULT_RANK;
+        c->firefly.scale = prm->scale > 0.f ? prm->scale : PT_FIREFLY_DEFAULT_SCALE;
     }
     return PT_OK;
 }
 
-int pt_firefly_clamp(const pt_ctx* c) { return c && c->fireflySet ? 1 : 0; }
+int pt_firefly_clamp(const pt_ctx* c) { return c && c->firefly.set ? 1 : 0; }
 
 namespace {
 
 // the plane and / or the counters of the last evaluation to the host, behind a synchronisation
 int readFirefly(pt_ctx* c, float* d_s, uint32_t counts[2])
 {
-    if (d_s)
-        HIPCHK(c, hipMemcpyAsync(d_s, c->fireflyPlane.p, c->fireflyPlane.n * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
-    if (counts)
-        HIPCHK(c, hipMemcpyAsync(counts, c->fireflyCounts.p, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, c->firefly.plane.copyTo(d_s, c->stream));
+    HIPCHK(c, c->firefly.counts.read(counts, c->stream));
     return PT_OK;
 }
 
@@ -2058,16 +2023,13 @@ int pt_read_firefly(pt_ctx* c, float* d_s, uint32_t counts[2])
 {
     if (!c)
         return PT_ERR_INVALID;
-    if (!c->fireflySet)
+    if (!c->firefly.set)
         return fail(c, PT_ERR_STATE, "pt_read_firefly: the firefly clamp is off (pt_set_firefly_clamp)");
-    if (tilesSet(c))
-        return fail(c, PT_ERR_UNSUPPORTED, "pt_read_firefly: tiles are set -- the clamp needs every pixel's neighbours; evaluate after the reduce, on a context that owns the frame");
-    if (c->spp == 0)
-        return fail(c, PT_ERR_STATE, "pt_read_firefly: no colour samples yet (pt_render)");
-    if (c->guideSpp == 0)
-        return fail(c, PT_ERR_STATE, "pt_read_firefly: no guide samples yet (pt_render_guides)");
+    int rc;
+    if ((rc = wholeFrameOnly(c, "pt_read_firefly", "the clamp needs every pixel's neighbours; evaluate after the reduce")) || (rc = samplesPresent(c, "pt_read_firefly")))
+        return rc;
     HIPCHK(c, hipSetDevice(c->device));
-    if (const int rc = evaluateFirefly(c))
+    if ((rc = evaluateFirefly(c)))
         return rc;
     return readFirefly(c, d_s, counts);
 }
@@ -2076,13 +2038,13 @@ int pt_firefly_counts(pt_ctx* c, uint32_t counts[2])
 {
     if (!c || !counts)
         return PT_ERR_INVALID;
-    if (!c->fireflyEvaluated)
+    if (!c->firefly.evaluated)
         return fail(c, PT_ERR_STATE, "pt_firefly_counts: the stage has not been evaluated yet (pt_temporal_accumulate, pt_denoise, pt_read_firefly with the mode on)");
     HIPCHK(c, hipSetDevice(c->device));
     return readFirefly(c, nullptr, counts);
 }
 
-void* pt_firefly_device_ptr(pt_ctx* c) { return c && c->fireflySet && c->fireflyEvaluated ? (void*)c->fireflyPlane.p : nullptr; }
+void* pt_firefly_device_ptr(pt_ctx* c) { return c && c->firefly.set && c->firefly.evaluated ? (void*)c->firefly.plane.p : nullptr; }
 
 // ---- adaptive sampling (k_adaptive_eval; the helpers stand before pt_set_tiles) -------------------
 
@@ -2108,7 +2070,7 @@ int pt_set_adaptive(pt_ctx* c, const pt_adaptive_params* prm)
             return fail(c, PT_ERR_INVALID, "pt_set_adaptive: max_samples = %u (min_samples = %u .. %u)", p.max_samples, p.min_samples, 1u << 20);
     }
     const bool on = prm != nullptr;
-    if (on != c->adaptiveSet) {
+    if (on != c->adaptive.set) {
         if (on && tilesSet(c))
             return fail(c, PT_ERR_UNSUPPORTED, "pt_set_adaptive: tiles are set -- adaptive sampling owns the pixel list of a whole-frame context");
         if (c->spp != 0)
@@ -2116,35 +2078,35 @@ int pt_set_adaptive(pt_ctx* c, const pt_adaptive_params* prm)
     }
     HIPCHK(c, hipSetDevice(c->device));
     if (!on) {
-        if (c->adaptiveSet) {
+        if (c->adaptive.set) {
             HIPCHK(c, hipStreamSynchronize(c->stream));
-            releaseAdaptive(c);
+            c->adaptive.buf.reset();
         }
-        c->adaptiveSet = false;
+        c->adaptive.set = false;
         return PT_OK;
     }
-    const bool was = c->adaptiveSet;
-    c->adaptiveSet = true;
-    c->adaptivePrm = p;
+    const bool was = c->adaptive.set;
+    c->adaptive.set = true;
+    c->adaptive.prm = p;
     if (!was) {
-        c->adaptiveStats = pt_adaptive_stats {};
-        c->adaptiveStats.blocks = c->adaptiveStats.active_blocks = adaptiveBlocks(c);
-    } else if (c->spp > 0 && c->adaptiveCounts.p) { // the flags are a function of the state AND the parameters
+        c->adaptive.stats = pt_adaptive_stats {};
+        c->adaptive.stats.blocks = c->adaptive.stats.active_blocks = adaptiveBlocks(c);
+    } else if (c->spp > 0 && c->adaptive.buf) { // the flags are a function of the state AND the parameters
         return evaluateAdaptive(c, 0, c->spp);
     }
     return PT_OK;
     });
 }
 
-int pt_adaptive(const pt_ctx* c) { return c && c->adaptiveSet ? 1 : 0; }
+int pt_adaptive(const pt_ctx* c) { return c && c->adaptive.set ? 1 : 0; }
 
 int pt_adaptive_params_get(const pt_ctx* c, pt_adaptive_params* out)
 {
     if (!c || !out)
         return PT_ERR_INVALID;
-    if (!c->adaptiveSet)
+    if (!c->adaptive.set)
         return fail(const_cast<pt_ctx*>(c), PT_ERR_STATE, "pt_adaptive_params_get: adaptive sampling is off (pt_set_adaptive)");
-    *out = c->adaptivePrm;
+    *out = c->adaptive.prm;
     return PT_OK;
 }
 
@@ -2153,7 +2115,7 @@ int pt_render_adaptive(pt_ctx* c, uint32_t rounds)
     return guarded(c, "pt_render_adaptive", [&]() -> int {
     if (!c)
         return PT_ERR_INVALID;
-    if (!c->adaptiveSet)
+    if (!c->adaptive.set)
         return fail(c, PT_ERR_STATE, "pt_render_adaptive: adaptive sampling is off (pt_set_adaptive)");
     if (!c->haveStatic || !c->haveDynamic || !c->haveCamera)
         return fail(c, PT_ERR_STATE, "pt_render_adaptive: scene (static + dynamic) and camera must be set first");
@@ -2161,7 +2123,7 @@ int pt_render_adaptive(pt_ctx* c, uint32_t rounds)
     int rc = ensureAdaptive(c);
     if (rc)
         return rc;
-    const pt_adaptive_params& prm = c->adaptivePrm;
+    const pt_adaptive_params& prm = c->adaptive.prm;
     const uint32_t W = c->cfg.width, H = c->cfg.height, bX = adaptiveBlocksX(c), nB = adaptiveBlocks(c);
     float4* const accum = c->accum;
     std::vector<pt_rect> rects;
@@ -2169,7 +2131,7 @@ int pt_render_adaptive(pt_ctx* c, uint32_t rounds)
         const uint32_t S = c->spp;
         rects.clear();
         for (uint32_t b = 0; b < nB; b++) // (no samples yet: every block, whatever the read-back area holds)
-            if (S == 0 || c->adaptiveBack.p[b]) {
+            if (S == 0 || c->adaptive.buf->back.p[b]) {
                 const uint32_t x = (b % bX) * 8u, y = (b / bX) * 8u;
                 rects.push_back({ x, y, std::min(x + 8u, W), std::min(y + 8u, H) });
             }
@@ -2183,11 +2145,11 @@ int pt_render_adaptive(pt_ctx* c, uint32_t rounds)
         if ((rc = ensureQueues(c)))
             break;
         if (changed) {
-            c->adaptiveTiming[2] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-            c->adaptiveTiming[3] += 1.0;
+            c->adaptive.timing[2] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+            c->adaptive.timing[3] += 1.0;
         }
         for (int half = 0; half < 2 && !rc; half++) { // sample indices base + S .. + h - 1 into A, the next h into B
-            c->accum = c->adaptiveHalf[half].p;
+            c->accum = c->adaptive.buf->half[half].p;
             rc = renderSamples(c, h);
         }
         c->accum = accum;
@@ -2197,7 +2159,7 @@ int pt_render_adaptive(pt_ctx* c, uint32_t rounds)
         }
         if ((rc = evaluateAdaptive(c, 2u * h, S + 2u * h)))
             break;
-        c->adaptiveStats.rounds++;
+        c->adaptive.stats.rounds++;
     }
     const int whole = installPixelRects(c, nullptr, 0); // the context owns the whole frame again: guides, denoiser and history see no tiles
     return rc ? rc : whole;
@@ -2208,9 +2170,9 @@ int pt_adaptive_stats_get(pt_ctx* c, pt_adaptive_stats* out)
 {
     if (!c || !out)
         return PT_ERR_INVALID;
-    if (!c->adaptiveSet)
+    if (!c->adaptive.set)
         return fail(c, PT_ERR_STATE, "pt_adaptive_stats_get: adaptive sampling is off (pt_set_adaptive)");
-    *out = c->adaptiveStats;
+    *out = c->adaptive.stats;
     return PT_OK;
 }
 
@@ -2218,18 +2180,17 @@ int pt_read_adaptive(pt_ctx* c, float* A, float* B, uint32_t* counts, float* err
 {
     if (!c)
         return PT_ERR_INVALID;
-    if (!c->adaptiveSet)
+    if (!c->adaptive.set)
         return fail(c, PT_ERR_STATE, "pt_read_adaptive: adaptive sampling is off (pt_set_adaptive)");
     HIPCHK(c, hipSetDevice(c->device));
     if (const int rc = ensureAdaptive(c))
         return rc;
-    auto get = [&](void* out, const void* dev, size_t bytes) { return out ? hipMemcpyAsync(out, dev, bytes, hipMemcpyDeviceToHost, c->stream) : hipSuccess; };
-    HIPCHK(c, get(A, c->adaptiveHalf[0].p, c->adaptiveHalf[0].n * sizeof(float4)));
-    HIPCHK(c, get(B, c->adaptiveHalf[1].p, c->adaptiveHalf[1].n * sizeof(float4)));
-    HIPCHK(c, get(counts, c->adaptiveCounts.p, c->adaptiveCounts.n * sizeof(uint32_t)));
-    HIPCHK(c, get(error, c->adaptiveError.p, c->adaptiveError.n * sizeof(float)));
-    HIPCHK(c, get(block_error, c->adaptiveBlockError.p, c->adaptiveBlockError.n * sizeof(float)));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const pt_ctx::Adaptive::Buffers& b = *c->adaptive.buf;
+    HIPCHK(c, b.half[0].copyTo(A, c->stream));
+    HIPCHK(c, b.half[1].copyTo(B, c->stream));
+    HIPCHK(c, b.counts.copyTo(counts, c->stream));
+    HIPCHK(c, b.error.copyTo(error, c->stream));
+    HIPCHK(c, b.blockError.read(block_error, c->stream));
     return PT_OK;
 }
 
@@ -2238,7 +2199,7 @@ int pt_write_adaptive(pt_ctx* c, const float* A, const float* B, const uint32_t*
     return guarded(c, "pt_write_adaptive", [&]() -> int {
     if (!c || !A || !B || !counts)
         return PT_ERR_INVALID;
-    if (!c->adaptiveSet)
+    if (!c->adaptive.set)
         return fail(c, PT_ERR_STATE, "pt_write_adaptive: adaptive sampling is off (pt_set_adaptive)");
     const uint32_t W = c->cfg.width, H = c->cfg.height;
     uint32_t most = 0;
@@ -2247,30 +2208,30 @@ int pt_write_adaptive(pt_ctx* c, const float* A, const float* B, const uint32_t*
             const uint32_t n = counts[(size_t)y * W + x];
             if (n != counts[(size_t)(y & ~7u) * W + (x & ~7u)])
                 return fail(c, PT_ERR_INVALID, "pt_write_adaptive: counts differ within the 8 x 8 block of pixel (%u, %u)", x, y);
-            if ((n & 1u) || n > c->adaptivePrm.max_samples)
-                return fail(c, PT_ERR_INVALID, "pt_write_adaptive: count %u at pixel (%u, %u) (even, <= max_samples = %u)", n, x, y, c->adaptivePrm.max_samples);
+            if ((n & 1u) || n > c->adaptive.prm.max_samples)
+                return fail(c, PT_ERR_INVALID, "pt_write_adaptive: count %u at pixel (%u, %u) (even, <= max_samples = %u)", n, x, y, c->adaptive.prm.max_samples);
             most = std::max(most, n);
         }
     HIPCHK(c, hipSetDevice(c->device));
     if (const int rc = ensureAdaptive(c))
         return rc;
-    const size_t n = (size_t)W * H;
-    HIPCHK(c, hipMemcpyAsync(c->adaptiveHalf[0].p, A, n * sizeof(float4), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->adaptiveHalf[1].p, B, n * sizeof(float4), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->adaptiveCounts.p, counts, n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    pt_ctx::Adaptive::Buffers& b = *c->adaptive.buf;
+    HIPCHK(c, b.half[0].copyFrom(A, c->stream));
+    HIPCHK(c, b.half[1].copyFrom(B, c->stream));
+    HIPCHK(c, b.counts.copyFrom(counts, c->stream));
     return evaluateAdaptive(c, 0, most); // (synchronises: the caller's arrays are free again)
     });
 }
 
 void* pt_adaptive_device_ptr(pt_ctx* c, int which)
 {
-    if (!c || !c->adaptiveCounts.p)
+    if (!c || !c->adaptive.buf)
         return nullptr;
     switch (which) {
-    case 0: return c->adaptiveHalf[0].p;
-    case 1: return c->adaptiveHalf[1].p;
-    case 2: return c->adaptiveCounts.p;
-    case 3: return c->adaptiveError.p;
+    case 0: return c->adaptive.buf->half[0].p;
+    case 1: return c->adaptive.buf->half[1].p;
+    case 2: return c->adaptive.buf->counts.p;
+    case 3: return c->adaptive.buf->error.p;
     default: return nullptr;
     }
 }
@@ -2279,7 +2240,7 @@ int pt_debug_adaptive_timing(pt_ctx* c, double out[4])
 {
     if (!c || !out)
         return PT_ERR_INVALID;
-    std::memcpy(out, c->adaptiveTiming, sizeof(c->adaptiveTiming));
+    std::memcpy(out, c->adaptive.timing, sizeof(c->adaptive.timing));
     return PT_OK;
 }
 
@@ -2291,13 +2252,13 @@ namespace {
 // synchronisation: a guide pass may still read the old one).  The host copy stays with the context.
 int uploadMotionRecords(pt_ctx* c, std::vector<MotionRecord>& records, size_t capacity, size_t count)
 {
-    if (c->motionRecords.n < capacity) {
+    if (c->motion.records.n < capacity) {
         HIPCHK(c, hipStreamSynchronize(c->stream));
-        HIPCHK(c, c->motionRecords.alloc(capacity));
+        HIPCHK(c, c->motion.records.alloc(capacity));
     }
-    c->motionHost = std::move(records);
+    c->motion.host = std::move(records);
     if (count)
-        HIPCHK(c, hipMemcpyAsync(c->motionRecords.p, c->motionHost.data(), count * sizeof(MotionRecord), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(c->motion.records.p, c->motion.host.data(), count * sizeof(MotionRecord), hipMemcpyHostToDevice, c->stream));
     return PT_OK;
 }
 
@@ -2336,12 +2297,46 @@ int commitVertexTables(pt_ctx* c, bool withMotion, std::vector<MotionRecord>& re
     int rc;
     if (!withMotion && (rc = uploadMotionRecords(c, records, std::max<size_t>(std::max<size_t>(d.numTopNodes, records.size()), 1), records.size())))
         return rc;
-    if (c->vertexRows.n < rows.size()) {
+    if (c->vertexMotion.rows.n < rows.size()) {
         HIPCHK(c, hipStreamSynchronize(c->stream));
-        HIPCHK(c, c->vertexRows.alloc(rows.size() + rows.size() / 8));
+        HIPCHK(c, c->vertexMotion.rows.alloc(rows.size() + rows.size() / 8));
     }
-    c->vertexRowsHost = std::move(rows);
-    HIPCHK(c, hipMemcpyAsync(c->vertexRows.p, c->vertexRowsHost.data(), c->vertexRowsHost.size() * sizeof(float4), hipMemcpyHostToDevice, c->stream));
+    c->vertexMotion.rowsHost = std::move(rows);
+    HIPCHK(c, hipMemcpyAsync(c->vertexMotion.rows.p, c->vertexMotion.rowsHost.data(), c->vertexMotion.rowsHost.size() * sizeof(float4), hipMemcpyHostToDevice, c->stream));
+    return PT_OK;
+}
+
+// What pt_set_vertex_motion and pt_set_rebuilt_motion make before they touch the device: the tables over the instance motion's records where one is
+// set, and the two motion sums
+int prepareVertexTables(pt_ctx* c, std::vector<MotionRecord>& records, std::vector<float4>& rows, const char* who)
+{
+    if (c->motion.set)
+        records = c->motion.host;
+    const int rc = makeVertexTables(c, c->motion.set, records, rows, who);
+    return rc ? rc : c->motionGuides.ensure(c);
+}
+
+// What the three motion setters refuse alike, in the order they refuse it; `forget`: the call takes a motion away, which a guide chain does not mind
+int motionSetterReady(pt_ctx* c, const char* who, bool forget)
+{
+    if (const int rc = fixedScheduleOnly(c, who))
+        return rc;
+    if (!c->haveDynamic)
+        return fail(c, PT_ERR_STATE, "%s: no dynamic state is active yet (pt_upload_dynamic)", who);
+    if (c->guideSpp != 0)
+        return fail(c, PT_ERR_STATE, "%s: %u guide samples are in the sums already -- set or forget the motion right after pt_clear", who, c->guideSpp);
+    if (!forget && c->guideChain)
+        return fail(c, PT_ERR_UNSUPPORTED, "%s: a guide chain is set (pt_set_guide_chain) -- motion deposits along a chain are not supported", who);
+    return PT_OK;
+}
+
+// ... and the two that need the previous state: it is still whole in the inactive set
+int previousStateThere(pt_ctx* c, const char* who)
+{
+    if (c->pending >= 0)
+        return fail(c, PT_ERR_STATE, "%s: an upload is pending (pt_upload_dynamic_async without its pt_frame_tick): it is overwriting the set that held the previous state", who);
+    if (!c->dyn[1 - c->active].used)
+        return fail(c, PT_ERR_STATE, "%s: there is no previous state (one pt_frame_tick adopted the only state so far)", who);
     return PT_OK;
 }
 
@@ -2352,27 +2347,22 @@ int pt_set_instance_motion(pt_ctx* c, const float* prevInv, uint32_t nTop)
     return guarded(c, "pt_set_instance_motion", [&]() -> int {
     if (!c)
         return PT_ERR_INVALID;
-    if (const int rc = fixedScheduleOnly(c, "pt_set_instance_motion"))
+    const bool forget = !prevInv || nTop == 0;
+    int rc;
+    if ((rc = motionSetterReady(c, "pt_set_instance_motion", forget)))
         return rc;
-    if (!c->haveDynamic)
-        return fail(c, PT_ERR_STATE, "pt_set_instance_motion: no dynamic state is active yet (pt_upload_dynamic)");
-    if (c->guideSpp != 0)
-        return fail(c, PT_ERR_STATE, "pt_set_instance_motion: %u guide samples are in the sums already -- set or forget the motion right after pt_clear", c->guideSpp);
-    if (!prevInv || nTop == 0) {
-        if (c->vertexMotionSet) { // only the instance part goes: the vertex motion goes on from the current transforms
+    if (forget) {
+        if (c->vertexMotion.set) { // only the instance part goes: the vertex motion goes on from the current transforms
             HIPCHK(c, hipSetDevice(c->device));
             std::vector<MotionRecord> ident;
             std::vector<float4> rows;
-            int rc = makeVertexTables(c, false, ident, rows, "pt_set_instance_motion");
-            if (rc || (rc = commitVertexTables(c, false, ident, rows)))
+            if ((rc = makeVertexTables(c, false, ident, rows, "pt_set_instance_motion")) || (rc = commitVertexTables(c, false, ident, rows)))
                 return rc;
         }
-        c->motionSet = false;
-        c->motionMoving = 0;
+        c->motion.set = false;
+        c->motion.moving = 0;
         return PT_OK;
     }
-    if (c->guideChain)
-        return fail(c, PT_ERR_UNSUPPORTED, "pt_set_instance_motion: a guide chain is set (pt_set_guide_chain) -- motion deposits along a chain are not supported");
     const pt_ctx::DynamicSet& d = c->dyn[c->active];
     if (nTop != d.numTopNodes)
         return fail(c, PT_ERR_INVALID, "pt_set_instance_motion: %u previous transforms for an active state of %u top-level nodes", nTop, d.numTopNodes);
@@ -2394,17 +2384,16 @@ int pt_set_instance_motion(pt_ctx* c, const float* prevInv, uint32_t nTop)
     std::vector<MotionRecord> records(std::max<size_t>(nInst, 1));
     uint32_t moving = 0;
     std::string why;
-    int rc = ptconv::motionRecords(prev.data(), cur.data(), (uint32_t)nInst, nullptr, records.data(), &moving, why);
-    if (rc)
+    if ((rc = ptconv::motionRecords(prev.data(), cur.data(), (uint32_t)nInst, nullptr, records.data(), &moving, why)))
         return fail(c, rc, "pt_set_instance_motion: %s (entries count the state's instances, in the order of its top-level leaves)", why.c_str());
     std::vector<float4> rows;
-    if (c->vertexMotionSet && (rc = makeVertexTables(c, true, records, rows, "pt_set_instance_motion")))
+    if (c->vertexMotion.set && (rc = makeVertexTables(c, true, records, rows, "pt_set_instance_motion")))
         return rc;
     if ((rc = c->motionGuides.ensure(c)) || (rc = uploadMotionRecords(c, records, std::max<size_t>(nTop, 1), nInst))) // n_top entries: never fewer than the state has instances
         return rc;
-    c->motionSet = true;
-    c->motionMoving = moving;
-    if (c->vertexMotionSet && (rc = commitVertexTables(c, true, c->motionHost, rows)))
+    c->motion.set = true;
+    c->motion.moving = moving;
+    if (c->vertexMotion.set && (rc = commitVertexTables(c, true, c->motion.host, rows)))
         return rc;
     return PT_OK;
     });
@@ -2413,8 +2402,8 @@ int pt_set_instance_motion(pt_ctx* c, const float* prevInv, uint32_t nTop)
 int pt_instance_motion(const pt_ctx* c, uint32_t* movingOut)
 {
     if (movingOut)
-        *movingOut = c && c->motionSet ? c->motionMoving : 0u;
-    return c && c->motionSet ? 1 : 0;
+        *movingOut = c && c->motion.set ? c->motion.moving : 0u;
+    return c && c->motion.set ? 1 : 0;
 }
 
 // ---- vertex motion (k_guides<2>) ------------------------------------------------------------------
@@ -2423,23 +2412,16 @@ int pt_set_vertex_motion(pt_ctx* c, int enable)
     return guarded(c, "pt_set_vertex_motion", [&]() -> int {
     if (!c)
         return PT_ERR_INVALID;
-    if (const int rc = fixedScheduleOnly(c, "pt_set_vertex_motion"))
+    int rc;
+    if ((rc = motionSetterReady(c, "pt_set_vertex_motion", !enable)))
         return rc;
-    if (!c->haveDynamic)
-        return fail(c, PT_ERR_STATE, "pt_set_vertex_motion: no dynamic state is active yet (pt_upload_dynamic)");
-    if (c->guideSpp != 0)
-        return fail(c, PT_ERR_STATE, "pt_set_vertex_motion: %u guide samples are in the sums already -- set or forget the motion right after pt_clear", c->guideSpp);
     if (!enable) {
-        c->vertexMotionSet = c->vertexDeformed = c->rebuiltMotionSet = false;
+        c->vertexMotion.set = false;
         return PT_OK;
     }
-    if (c->guideChain)
-        return fail(c, PT_ERR_UNSUPPORTED, "pt_set_vertex_motion: a guide chain is set (pt_set_guide_chain) -- motion deposits along a chain are not supported");
-    if (c->pending >= 0)
-        return fail(c, PT_ERR_STATE, "pt_set_vertex_motion: an upload is pending (pt_upload_dynamic_async without its pt_frame_tick): it is overwriting the set that held the previous state");
+    if ((rc = previousStateThere(c, "pt_set_vertex_motion")))
+        return rc;
     pt_ctx::DynamicSet &cur = c->dyn[c->active], &old = c->dyn[1 - c->active];
-    if (!old.used)
-        return fail(c, PT_ERR_STATE, "pt_set_vertex_motion: there is no previous state (one pt_frame_tick adopted the only state so far)");
     if (old.staticIndex != cur.staticIndex)
         return fail(c, PT_ERR_UNSUPPORTED, "pt_set_vertex_motion: the previous state was built on another static scene (pt_upload_static_async): a rebuilt tree numbers its triangles anew -- hand the correspondence to pt_set_rebuilt_motion");
     if (old.numTris != cur.numTris)
@@ -2450,26 +2432,23 @@ int pt_set_vertex_motion(pt_ctx* c, int enable)
         return fail(c, PT_ERR_STATE, "pt_set_vertex_motion: the states hold no shading records for %u triangles", cur.numTris);
     std::vector<MotionRecord> records;
     std::vector<float4> rows;
-    if (c->motionSet)
-        records = c->motionHost;
-    int rc = makeVertexTables(c, c->motionSet, records, rows, "pt_set_vertex_motion");
-    if (rc || (rc = c->motionGuides.ensure(c)))
+    if ((rc = prepareVertexTables(c, records, rows, "pt_set_vertex_motion")))
         return rc;
     if (deformed) {
-        if (c->fatThen.n < cur.numTris) {
+        if (c->vertexMotion.fatThen.n < cur.numTris) {
             HIPCHK(c, hipStreamSynchronize(c->stream)); // (growing frees what an earlier guide pass may still read)
-            HIPCHK(c, c->fatThen.alloc(cur.numTris));
+            HIPCHK(c, c->vertexMotion.fatThen.alloc(cur.numTris));
         }
         // "then": the inactive set still holds the previous state's records.  Taken on the render stream, which has waited for that set's upload at its tick;
         // the next pt_upload_dynamic_async writes the set on the copy stream after the set's lastUse event, which therefore moves behind this copy.
-        HIPCHK(c, hipMemcpyAsync(c->fatThen.p, old.fat.p, (size_t)cur.numTris * sizeof(TriFat), hipMemcpyDeviceToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(c->vertexMotion.fatThen.p, old.fat.p, (size_t)cur.numTris * sizeof(TriFat), hipMemcpyDeviceToDevice, c->stream));
         HIPCHK(c, hipEventRecord(old.lastUse, c->stream));
     }
-    if ((rc = commitVertexTables(c, c->motionSet, records, rows)))
+    if ((rc = commitVertexTables(c, c->motion.set, records, rows)))
         return rc;
-    c->vertexMotionSet = true;
-    c->vertexDeformed = deformed;
-    c->rebuiltMotionSet = false;
+    c->vertexMotion.set = true;
+    c->vertexMotion.deformed = deformed;
+    c->rebuiltMotion.set = false;
     return PT_OK;
     });
 }
@@ -2477,8 +2456,8 @@ int pt_set_vertex_motion(pt_ctx* c, int enable)
 int pt_vertex_motion(const pt_ctx* c, uint32_t* deformedOut)
 {
     if (deformedOut)
-        *deformedOut = c && c->vertexMotionSet && c->vertexDeformed ? 1u : 0u;
-    return c && c->vertexMotionSet ? 1 : 0;
+        *deformedOut = c && c->vertexMotion.set && c->vertexMotion.deformed ? 1u : 0u;
+    return c && c->vertexMotion.set ? 1 : 0;
 }
 
 // test hook, no device needed: the rows pt_set_vertex_motion makes of n invTransforms (12 floats each)
@@ -2512,23 +2491,17 @@ int pt_set_rebuilt_motion(pt_ctx* c, const uint32_t* prevTriangle, uint32_t nTri
     return guarded(c, "pt_set_rebuilt_motion", [&]() -> int {
     if (!c)
         return PT_ERR_INVALID;
-    if (const int rc = fixedScheduleOnly(c, "pt_set_rebuilt_motion"))
+    const bool forget = !prevTriangle || nTris == 0;
+    int rc;
+    if ((rc = motionSetterReady(c, "pt_set_rebuilt_motion", forget)))
         return rc;
-    if (!c->haveDynamic)
-        return fail(c, PT_ERR_STATE, "pt_set_rebuilt_motion: no dynamic state is active yet (pt_upload_dynamic)");
-    if (c->guideSpp != 0)
-        return fail(c, PT_ERR_STATE, "pt_set_rebuilt_motion: %u guide samples are in the sums already -- set or forget the motion right after pt_clear", c->guideSpp);
-    if (!prevTriangle || nTris == 0) {
-        c->vertexMotionSet = c->vertexDeformed = c->rebuiltMotionSet = false;
+    if (forget) {
+        c->vertexMotion.set = false;
         return PT_OK;
     }
-    if (c->guideChain)
-        return fail(c, PT_ERR_UNSUPPORTED, "pt_set_rebuilt_motion: a guide chain is set (pt_set_guide_chain) -- motion deposits along a chain are not supported");
-    if (c->pending >= 0)
-        return fail(c, PT_ERR_STATE, "pt_set_rebuilt_motion: an upload is pending (pt_upload_dynamic_async without its pt_frame_tick): it is overwriting the set that held the previous state");
+    if ((rc = previousStateThere(c, "pt_set_rebuilt_motion")))
+        return rc;
     pt_ctx::DynamicSet &cur = c->dyn[c->active], &old = c->dyn[1 - c->active];
-    if (!old.used)
-        return fail(c, PT_ERR_STATE, "pt_set_rebuilt_motion: there is no previous state (one pt_frame_tick adopted the only state so far)");
     if (old.fat.n < old.numTris || cur.fat.n < cur.numTris)
         return fail(c, PT_ERR_STATE, "pt_set_rebuilt_motion: the states hold no shading records for their %u and %u triangles", old.numTris, cur.numTris);
     if (nTris != cur.numTris)
@@ -2536,10 +2509,10 @@ int pt_set_rebuilt_motion(pt_ctx* c, const uint32_t* prevTriangle, uint32_t nTri
     HIPCHK(c, hipSetDevice(c->device));
     // the one pass over the map: validated, counted and copied into pinned memory of the context's own, which the asynchronous upload reads (the caller's
     // array is free again when the call returns; the previous call's upload out of that memory has long been read)
-    HIPCHK(c, c->rebuiltStage.read.create());
-    HIPCHK(c, c->rebuiltStage.wait());
-    HIPCHK(c, c->rebuiltStage.reserve((size_t)nTris * sizeof(uint32_t), ((size_t)nTris + nTris / 8) * sizeof(uint32_t)));
-    uint32_t* const map = (uint32_t*)c->rebuiltStage.mem.p;
+    HIPCHK(c, c->rebuiltMotion.stage.read.create());
+    HIPCHK(c, c->rebuiltMotion.stage.wait());
+    HIPCHK(c, c->rebuiltMotion.stage.reserve((size_t)nTris * sizeof(uint32_t), ((size_t)nTris + nTris / 8) * sizeof(uint32_t)));
+    uint32_t* const map = (uint32_t*)c->rebuiltMotion.stage.mem.p;
     uint32_t followed = 0;
     for (uint32_t i = 0; i < nTris; i++) {
         const uint32_t j = prevTriangle[i];
@@ -2552,39 +2525,36 @@ int pt_set_rebuilt_motion(pt_ctx* c, const uint32_t* prevTriangle, uint32_t nTri
     }
     std::vector<MotionRecord> records;
     std::vector<float4> rows;
-    if (c->motionSet)
-        records = c->motionHost;
-    int rc = makeVertexTables(c, c->motionSet, records, rows, "pt_set_rebuilt_motion");
-    if (rc || (rc = c->motionGuides.ensure(c)))
+    if ((rc = prepareVertexTables(c, records, rows, "pt_set_rebuilt_motion")))
         return rc;
-    if (c->fatThen.n < nTris || c->rebuiltMap.n < nTris) {
+    if (c->vertexMotion.fatThen.n < nTris || c->rebuiltMotion.map.n < nTris) {
         HIPCHK(c, hipStreamSynchronize(c->stream)); // (growing frees what an earlier guide pass or gather may still read)
-        if (c->fatThen.n < nTris)
-            HIPCHK(c, c->fatThen.alloc(nTris));
-        if (c->rebuiltMap.n < nTris)
-            HIPCHK(c, c->rebuiltMap.alloc(nTris));
+        if (c->vertexMotion.fatThen.n < nTris)
+            HIPCHK(c, c->vertexMotion.fatThen.alloc(nTris));
+        if (c->rebuiltMotion.map.n < nTris)
+            HIPCHK(c, c->rebuiltMotion.map.alloc(nTris));
     }
     // "then", through the map: the inactive set still holds the previous state's records, the active set the current ones.  On the render stream, which has
     // waited for both sets' uploads at their ticks and on which every earlier gather has read the map; the inactive set's lastUse moves behind the
     // gather as it moves behind pt_set_vertex_motion's copy, so the next upload into that set may be started at once.
-    HIPCHK(c, hipMemcpyAsync(c->rebuiltMap.p, map, (size_t)nTris * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, c->rebuiltStage.recordRead(c->stream));
-    launchGatherThen(c->stream, old.fat.p, old.numTris, cur.fat.p, c->rebuiltMap.p, c->fatThen.p, nTris);
+    HIPCHK(c, hipMemcpyAsync(c->rebuiltMotion.map.p, map, (size_t)nTris * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, c->rebuiltMotion.stage.recordRead(c->stream));
+    launchGatherThen(c->stream, old.fat.p, old.numTris, cur.fat.p, c->rebuiltMotion.map.p, c->vertexMotion.fatThen.p, nTris);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipEventRecord(old.lastUse, c->stream));
-    if ((rc = commitVertexTables(c, c->motionSet, records, rows)))
+    if ((rc = commitVertexTables(c, c->motion.set, records, rows)))
         return rc;
-    c->vertexMotionSet = c->vertexDeformed = c->rebuiltMotionSet = true;
-    c->rebuiltFollowed = followed;
+    c->vertexMotion.set = c->vertexMotion.deformed = c->rebuiltMotion.set = true;
+    c->rebuiltMotion.followed = followed;
     return PT_OK;
     });
 }
 
 int pt_rebuilt_motion(const pt_ctx* c, uint32_t* followedOut)
 {
-    const bool set = c && c->vertexMotionSet && c->rebuiltMotionSet;
+    const bool set = c && c->vertexMotion.set && c->rebuiltMotion.set;
     if (followedOut)
-        *followedOut = set ? c->rebuiltFollowed : 0u;
+        *followedOut = set ? c->rebuiltMotion.followed : 0u;
     return set ? 1 : 0;
 }
 

@@ -5,9 +5,8 @@
 
 Per scene and size: `uniform`, pt_render(max) -- wall ms, the device ms pt_stats reports for the call, rays (extension + shadow) from pt_stats; per threshold
 pt_render_adaptive(0) -- wall ms, rays, samples_total, rounds, blocks still active, and from pt_debug_adaptive_timing the device ms inside the evaluate /
-publish launches (with the bytes they must move: 60 per pixel fused, 96 in two launches, against pt_debug_copy_bandwidth) and the host ms spent changing the
-pixel list (the list, its upload, every queue released and allocated again), with how often.  PTAMD_ADAPTIVE_SPLIT=1 in the environment times the
-two-launch form.  With --reference N > 0: the tone-mapped RMSE against N samples per pixel of other random numbers, pooled over the quarter of 8 x 8 blocks
+publish launch (with the bytes it must move: 60 per pixel, against pt_debug_copy_bandwidth) and the host ms spent changing the
+pixel list (the list, its upload, every queue released and allocated again), with how often.  With --reference N > 0: the tone-mapped RMSE against N samples per pixel of other random numbers, pooled over the quarter of 8 x 8 blocks
 whose reference halves differ most, for the uniform render and every adaptive one, and `uniform_ms_at_equal_error`: the uniform wall time scaled by
 (uniform error / adaptive error)^2 -- an extrapolation along error ~ 1 / sqrt(spp), not a measurement."""
 import argparse
@@ -41,8 +40,7 @@ def main():
     from ptamd import device as D, scenes
     import adaptive_ref as R
 
-    out = {"max_samples": args.max, "min_samples": args.min, "round_samples": args.round, "reference_spp": args.reference,
-           "split": "PTAMD_ADAPTIVE_SPLIT" in os.environ, "runs": {}}
+    out = {"max_samples": args.max, "min_samples": args.min, "round_samples": args.round, "reference_spp": args.reference, "runs": {}}
     for scene in args.scenes.split(","):
         for size in args.sizes.split(","):
             width, height = (int(v) for v in size.split("x"))
@@ -102,7 +100,7 @@ def main():
                 wall = (time.perf_counter() - t0) * 1e3
                 eval_ms, evals, list_ms, lists = ctx.adaptive_timing
                 per_eval = eval_ms / max(evals, 1)
-                moved = (96 if out["split"] else 60) * width * height
+                moved = 60 * width * height
                 a = {"wall_ms": round(wall, 2), "rays": rays(ctx) - r0, "samples_total": int(st["samples_total"]), "rounds": int(st["rounds"]),
                      "share_of_uniform": round(st["samples_total"] / (width * height * args.max), 4), "active_blocks": int(st["active_blocks"]),
                      "eval_ms_total": round(eval_ms, 4), "eval_ms_per_round": round(per_eval, 4), "eval_bytes": moved,
